@@ -26,13 +26,23 @@ to rank i % N, every rank walks its pairs in batches of ``--pairs`` (ragged last
 over the split, scaling is "strong".  Scenes repeat with period ``--pool`` (generating 545 distinct scenes would
 take minutes of host time; the device work does not depend on which scene it is).
 
-The JSON line carries, besides the driver's contract fields,
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON line: the headline (``metric``, ``value``,
+``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``) and what the timed steps' own results give (success rate,
+registration errors, the run's configuration).  ``--dump-outputs DIR`` also writes what the last timed step returned
+(per pair: the pose and the RANSAC statistics of ``RegistrationResult``) as ``DIR/<name>.npy``, float64, in global pair
+order; the inputs are seeded, so two builds can be compared output for output.
+
+``--full`` adds everything that takes runs or timers of its own:
   roofline      the sparse-convolution kernels (22 launches per forward) summed: algorithmic FLOP (SURVEY.md 8d,
-                from the realised rulebooks) over their hipEvent durations inside the timed steps;
+                from the realised rulebooks) over their hipEvent durations (per-launch events inside the timed steps
+                and a one-stream pass behind them);
   hbm_gather    the same launches as algorithmic gather bytes / time against 8 TB/s, with the compulsory bytes
                 and, when profiles/ holds a PMC pass of this workload, traffic / compulsory;
+  extras        single-pair latency, batch 8, fp32 arithmetic, the 545-pair split, voxeliser, training step, RANSAC
+                sweep over inlier ratios, SC2-PCR back-end, nuScenes-shaped pairs (one GPU; ``--no-extras`` drops them);
   cpu_baseline  the CPU oracle (a port of the reference algorithms; the reference's own sparse conv and RANSAC
-                live in MinkowskiEngine / Open3D, which cannot run here): median over 5 pairs after a warm-up.
+                live in MinkowskiEngine / Open3D, which cannot run here): median over 5 pairs after a warm-up
+                (``--no-cpu-baseline`` drops it).
 """
 import argparse
 import json
@@ -75,9 +85,13 @@ def parse_args(argv=None):
                          "this is configs[4] on one GPU) - what profiles/r5_sc2pcr_* were taken on")
     ap.add_argument("--math", choices=["auto", "fp32", "split16"], default="auto",
                     help="arithmetic of the sparse convolutions (auto: split16 for batches that fill the chip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-layer timers, roofline, extras and CPU baseline (see the module docstring); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64, global pair order)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baseline")
     ap.add_argument("--no-extras", "--no-latency-probe", dest="no_extras", action="store_true",
-                    help="only the timed steps (profiling passes: keeps the kernel statistics to the timed region)")
+                    help="(--full) only the timed steps and their roofline (profiling passes: keeps the kernel statistics to the timed region)")
     ap.add_argument("--dry-run", action="store_true",
                     help="(tests) no GPU work: a stub step exercises launch / sharding / timing / gather on CPU over gloo")
     ap.add_argument("--overlap-maps", action=argparse.BooleanOptionalAction, default=True,
@@ -236,6 +250,7 @@ class StubPipeline:
     class _R:
         def __init__(self, T):
             self.transformation, self.inliers, self.survivors = T.astype(np.float64), 0, 0
+            self.fitness, self.inlier_rmse, self.best_hypothesis = 0.0, 0.0, -1
 
     def register(self, batch, seed=0):
         return [self._R(T) for T in batch.T_gt]
@@ -253,6 +268,26 @@ def records_of(results, batch, rank, cfg):
         rec[p, :16] = r.transformation.astype(np.float32).reshape(16)
         rec[p, 16:] = (rte, np.rad2deg(rre), float(ok), float(rank))
     return rec
+
+
+OUT_FIELDS = ("fitness", "inlier_rmse", "inliers", "best_hypothesis", "survivors")     # RegistrationResult, besides the pose
+
+
+def outputs_of(results):
+    """``f64 [P, 16 + 5]``: what a caller of the timed path receives per pair (--dump-outputs)."""
+    out = np.zeros((len(results), 16 + len(OUT_FIELDS)), np.float64)
+    for p, r in enumerate(results):
+        out[p, :16] = np.asarray(r.transformation, np.float64).reshape(16)
+        out[p, 16:] = [float(getattr(r, f)) for f in OUT_FIELDS]
+    return out
+
+
+def dump_outputs(directory, allout):
+    """``DIR/transformation.npy`` ``[P, 4, 4]`` and one ``[P]`` array per field of ``OUT_FIELDS``, float64 (168 bytes per pair)."""
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "transformation.npy"), allout[:, :16].reshape(-1, 4, 4))
+    for i, name in enumerate(OUT_FIELDS):
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(allout[:, 16 + i]))
 
 
 def csrc_sha16():
@@ -412,7 +447,7 @@ def worker(args):
         made = make_pairs(scenes, args.nuscenes, workers=scene_workers(local_world, len(scenes)))
         gen = dict(zip(scenes, made))
         nus_pairs = None
-        if world == 1 and not total_mode and not args.no_extras and not args.nuscenes:
+        if args.full and world == 1 and not total_mode and not args.no_extras and not args.nuscenes:
             nus_pairs = make_pairs(list(range(5000, 5016)), True)   # configs[4] leg of the extras (needs the fork too)
     log(f"{len(scenes)} scenes generated for {len(mine)} pairs")
 
@@ -468,7 +503,8 @@ def worker(args):
         torch.cuda.synchronize()
     log(f"inputs resident: {sum(b.voxels for _, b in batches)} voxels in {len(batches)} batch(es)")
 
-    if model is not None:
+    timing = args.full and model is not None         # per-launch / per-stage events: the roofline's, not the headline's
+    if timing:
         model.set_timing(True)
         pipe.timing = True
     passes = args.steps
@@ -492,7 +528,7 @@ def worker(args):
         else:                               # SC2-PCR path: the record is the pose
             Th = host.numpy().astype(np.float64)
             acc.last[s_ % len(batches_)] = [eyoc_amd.registration.RegistrationResult(Th[p], 0.0, 0.0) for p in range(batch_.P)]
-        if model is not None:
+        if timing:
             model.timing_slot(slot_)
             ms = np.array(model.layer_ms())
             acc.layer_ms = ms if acc.layer_ms is None else acc.layer_ms + ms
@@ -596,12 +632,12 @@ def worker(args):
     # step's map build, and an event-bracketed layer time then holds whatever else ran in between.  A short one-stream pass (maps
     # behind the forward, nothing beside the forward's kernels) gives the kernels' own durations for the roofline
     alone = None
-    if model is not None and not dry and two:
+    if timing and not dry and two:
         alone = Acc()
         run_steps(2, Acc(), two_=False, maps_after="feat")
         run_steps(max(4, min(10, steps_timed)), alone, two_=False, maps_after="feat")
         torch.cuda.synchronize()
-    if model is not None:
+    if timing:
         model.set_timing(False)
         pipe.timing = False
     log(f"timed region: {elapsed:.3f} s")
@@ -612,6 +648,12 @@ def worker(args):
     n_global = args.total_pairs if total_mode else args.pairs * world
     allrec = (edist.gather_records_ragged(rec_t, n_global) if total_mode else edist.gather_records(rec_t)).cpu().numpy()
     ranks_seen = sorted({int(r) for r in allrec[:, 19] if not np.isnan(r)})
+    if args.dump_outputs:
+        o = np.concatenate([outputs_of(last[b]) for b in sorted(last)]) if last else np.zeros((0, 16 + len(OUT_FIELDS)))
+        o_t = torch.from_numpy(o).to(device)
+        allout = (edist.gather_records_ragged(o_t, n_global) if total_mode else edist.gather_records(o_t)).cpu().numpy()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, allout)
 
     if rank != 0:
         return
@@ -658,6 +700,12 @@ def worker(args):
         out["config"]["total_pairs"] = args.total_pairs
         out["config"]["batches_per_rank"] = [len(ids) for ids, _ in batches]
         out["pose_tx_first8"] = allrec[:8, 3].tolist()        # x translation of the first records (global pair order)
+    math_mode = model.last_spconv_math
+    if math_mode == "split16":
+        out["dtype"] = "f32 (split16 products: fp32 storage/accumulation, 3 fp16 MFMAs on hi/lo-split operands per product)"
+    if not args.full:
+        print(json.dumps(out))
+        return
     # ---- algorithmic work of one forward on the first batch's geometry
     x = eyoc_amd.SparseTensor(b0.feats, coordinates=b0.coords)
     work = model.layer_work(x)
@@ -680,7 +728,6 @@ def worker(args):
                   f"{w['gather_bytes'] / ms_i / 1e6:10.1f} {w['pairs']:10d}", file=sys.stderr)
     achieved_tf = flops / (conv_ms * 1e-3) / 1e12
     achieved_gbs = gather / (conv_ms * 1e-3) / 1e9
-    math_mode = model.last_spconv_math
     kernel = ("spconv_st_asm_kernel<64, 2, 1, 4, 256, .> (10 of the launches: stride-1 layers with 64 / 128 channels, the last one with the 1x1 tail "
               "in its epilogue; + <.., 128> on 128-row tiles: the three strided layers and the two 256-channel ones, <32, 1, 18, 4> the two 32-channel "
               "layers, spconv_upc_kernel the three transposed ones)" if math_mode == "split16" else "spconv_wave_kernel<...>") + " - the sparse-conv launches of one forward, summed"
@@ -690,7 +737,6 @@ def worker(args):
         # re-uses gathered rows in LDS, so SURVEY 8(d)'s gather bytes mostly never reach HBM): the roofline is priced
         # against the dense fp16 MFMA peak with the USEFUL products (3 x algorithmic flop; zero blocks the dense offset
         # sweep also multiplies are not counted).  The survey's HBM-side gather figure stays in `hbm_gather`.
-        out["dtype"] = "f32 (split16 products: fp32 storage/accumulation, 3 fp16 MFMAs on hi/lo-split operands per product)"
         out["roofline"] = {"bound": "mfma", "pipe": "fp16 matrix pipe (v_mfma_f32_16x16x32_f16), useful split16 products",
                            "achieved": 3 * achieved_tf, "peak": MFMA_F16_PEAK_TF, "unit": "TFLOP/s",
                            "frac": 3 * achieved_tf / MFMA_F16_PEAK_TF, "traffic": None, "traffic_measured_in_run": False,
@@ -925,8 +971,18 @@ def worker(args):
     print(json.dumps(out))
 
 
+def run(args):
+    """``worker`` and then, in a multi-rank job, the end of the process group: a rank whose process exits with the group's
+    threads still running can die in ``std::terminate`` (SIGABRT) after its work is done."""
+    try:
+        worker(args)
+    finally:
+        if torch.distributed.is_initialized():
+            torch.distributed.destroy_process_group()
+
+
 def _spawned(rank, world, argv):
-    worker(parse_args(argv))
+    run(parse_args(argv))
 
 
 def main(argv=None):
@@ -936,7 +992,7 @@ def main(argv=None):
         # no launcher: start the ranks ourselves (one per GPU, RCCL over 127.0.0.1)
         edist.spawn_ranks(_spawned, args.gpus, (list(argv),))
         return
-    worker(args)
+    run(args)
 
 
 if __name__ == "__main__":

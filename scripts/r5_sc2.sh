@@ -7,7 +7,7 @@ python -m pytest tests/test_gpu_sc2pcr.py -x -q 2>&1 | tail -3
 PAIRS=16 python scripts/bench_sc2pcr.py
 export EYOC_BENCH_PAIR_CACHE=/tmp/eyoc_bench_pairs_nus.pkl
 for f in 1 2; do
-python bench.py --sc2pcr --nuscenes --pairs 16 --steps 10 --warmup 2 --no-cpu-baseline --no-extras --in-flight $f 2>gpurun_out/sc2_err_$f.log | python -c "
+python bench.py --sc2pcr --nuscenes --pairs 16 --steps 10 --warmup 2 --no-cpu-baseline --no-extras --full --in-flight $f 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('in-flight $f', round(d['value'],1),'pairs/s', round(d['ms_per_step'],2),'ms', d['stage_ms_per_step'], d['success_rate'])"
 done

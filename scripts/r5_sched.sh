@@ -2,7 +2,7 @@
 # round 5: one stream per step against two steps in flight (alternating runs on one box)
 cd $GRAFT_REPO_ROOT
 export EYOC_BENCH_PAIR_CACHE=/tmp/eyoc_bench_pairs.pkl
-B="python bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-extras"
+B="python bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-extras --full"
 f() { python -c "
 import json,sys
 for l in open('$1'):

@@ -48,6 +48,24 @@ def loss_case(seed, n0, n1, n_pairs, c=32, noise=0.25):
     return _rownorm(F0).astype(np.float32), _rownorm(F1).astype(np.float32), np.stack([i0, i1], 1)
 
 
+def loss_helper_case(seed):
+    """Inputs of the loss helpers (``pdist`` / ``pair_hash``): two row sets that are not unit-norm and 300 index pairs below 5000."""
+    A = _normal(seed, 50, 32).astype(np.float32)
+    B = _normal(seed + 1, 70, 32).astype(np.float32)
+    pairs = (_u(seed + 2, 300, 2) * 5000).astype(np.int64)
+    return A, B, pairs
+
+
+def exact_rows_case(seed):
+    """Rows ``64 + k / 16`` (|k| <= 32): every difference, square and 32-term sum of ``(a - b)^2`` is exact in fp32 whatever the
+    summation order, so the squared distances are bit-reproducible on any machine - while ``|a|^2 + |b|^2 - 2ab`` (~2^17, 1/256
+    steps) is not.  The first 5 rows of both sets are the same (distance 0: only the L2 form's epsilon is left)."""
+    k = lambda s, n: np.floor(_u(s, n, 32) * 65.0) - 32.0
+    A, B = (64.0 + k(seed, 50) / 16.0).astype(np.float32), (64.0 + k(seed + 1, 70) / 16.0).astype(np.float32)
+    B[:5] = A[:5]
+    return A, B
+
+
 def rot_zyx(rx, ry, rz):
     cx, sx, cy, sy, cz, sz = np.cos(rx), np.sin(rx), np.cos(ry), np.sin(ry), np.cos(rz), np.sin(rz)
     Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
@@ -106,7 +124,7 @@ def label_batch_case(seed, sizes=((1500, 1300), (800, 2000), (1000, 1000))):
 
 def dist_sim_table(seed=0):
     """A similarity table of the reference's shape family (config/dist_sim_plot/*.npz: six float64 slices [gap cells, distance
-    cells]) - synthetic data; the reference's own tables stay with the reference."""
+    cells]) - synthetic data; of the reference's own tables only the KITTI one is stored (g11_host.npz)."""
     rng = np.random.default_rng(seed)
     out = {}
     for i, shape in enumerate([(12, 16), (18, 16), (20, 18), (20, 18), (20, 18), (20, 18)]):

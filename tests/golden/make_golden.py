@@ -18,6 +18,9 @@ reference's numeric outputs only.
   g8_labels.npz  lib.trainer.CorrespondenceExtensionTrainer.calculate_ratio_test / get_topk_matches (lib/trainer.py:993-1016)
   g10_match_filter.npz  lib.trainer.CorrespondenceExtensionTrainer.match_and_filter_corr (lib/trainer.py:1025-1151) with STORED K = 2 neighbours
   g9_eval.npz    scripts.test_kitti.find_corr / random_sample / apply_transform / evaluate_nn_dist (scripts/test_kitti.py:28-73)
+  g11_host.npz   host-side data of the reference: lib.metrics.pdist / util.misc._hash outputs, the SC2-PCR constants of
+                 scripts/SC2_PCR/config_json/config_KITTI.json, the KITTI similarity table (config/dist_sim_plot/kitti_distSimPlot.npz)
+                 and the ``o3d.<...>`` attribute chains of scripts/test_kitti.py:162-177 and util/pointcloud.py:9-21 (names only)
 ``lib.trainer`` and ``scripts.test_kitti`` import through ``_refimport.install()`` (codec alias + EMPTY stand-ins for the
 absent libraries; no arithmetic is stubbed).
 """
@@ -334,7 +337,43 @@ def g10():
     np.savez_compressed(os.path.join(HERE, "g10_match_filter.npz"), **out)
 
 
+def _o3d_chains(path, lo, hi):
+    """Every ``o3d.<a>.<b>...`` attribute chain in lines ``lo..hi`` of a reference file."""
+    import ast
+    import textwrap
+    body = "\n".join(open(path, encoding="utf-8").read().split("\n")[lo - 1:hi])
+    out = set()
+    for node in ast.walk(ast.parse(textwrap.dedent(body))):
+        if isinstance(node, ast.Attribute):
+            parts, cur = [], node
+            while isinstance(cur, ast.Attribute):
+                parts.append(cur.attr)
+                cur = cur.value
+            if isinstance(cur, ast.Name) and cur.id == "o3d":
+                out.add(tuple(reversed(parts)))
+    return out
+
+
+def g11():
+    from util.misc import _hash
+    out = {}
+    A, B, pairs = gi.loss_helper_case(31)
+    E0, E1 = gi.exact_rows_case(34)
+    for t in ("L2", "SquareL2"):
+        out[f"pdist_{t}"] = pdist(torch.from_numpy(A), torch.from_numpy(B), t).numpy()
+        out[f"pdist_exact_{t}"] = pdist(torch.from_numpy(E0), torch.from_numpy(E1), t).numpy()
+    out["hash_array"] = _hash(pairs, 5000)
+    out["hash_list"] = _hash([pairs[:, 0], pairs[:, 1]], 5000)
+    out["config_kitti"] = np.array(json.dumps(json.load(open(os.path.join(REF, "scripts/SC2_PCR/config_json/config_KITTI.json")))))
+    maps = np.load(os.path.join(REF, "config/dist_sim_plot/kitti_distSimPlot.npz"), allow_pickle=True)["res"].tolist()
+    for i in range(6):
+        out[f"dist_sim_kitti_{i}"] = np.asarray(maps[i], np.float64)
+    used = _o3d_chains(os.path.join(REF, "scripts/test_kitti.py"), 162, 177) | _o3d_chains(os.path.join(REF, "util/pointcloud.py"), 9, 21)
+    out["o3d_chains"] = np.array(json.dumps(sorted(used)))
+    np.savez_compressed(os.path.join(HERE, "g11_host.npz"), **out)
+
+
 if __name__ == "__main__":
-    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10):
+    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11):
         fn()
         print("wrote", fn.__name__)

@@ -80,3 +80,22 @@ def test_scene_workers_are_divided_by_the_ranks_of_the_node():
     assert bench.scene_workers(8, 64) == max(1, min(8, cores // 8, 64))
     assert bench.scene_workers(1, 64) == max(1, min(8, cores, 64))
     assert bench.scene_workers(8, 1) == 1
+
+
+def test_dump_outputs_hold_the_last_step_in_global_pair_order(tmp_path):
+    """``--dump-outputs DIR``: what the last timed step returned per pair (pose + RANSAC statistics), float64, gathered over the
+    ranks in global pair order - weak scaling and a ragged fixed split; ``--full`` leaves the headline and the outputs alone."""
+    out = _run("--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "3", "--dump-outputs", str(tmp_path / "weak"))
+    T = np.load(tmp_path / "weak" / "transformation.npy")
+    assert T.dtype == np.float64 and T.shape == (6, 4, 4)
+    assert T[:, 0, 3].tolist() == out["pose_tx"] == [float(i) for i in range(6)]
+    for name in ("fitness", "inlier_rmse", "inliers", "best_hypothesis", "survivors"):
+        a = np.load(tmp_path / "weak" / f"{name}.npy")
+        assert a.dtype == np.float64 and a.shape == (6,)
+    full = _run("--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "3", "--full", "--dump-outputs", str(tmp_path / "full"))
+    assert full["steps"] == out["steps"] == 2 and full["pose_tx"] == out["pose_tx"]
+    np.testing.assert_array_equal(np.load(tmp_path / "full" / "transformation.npy"), T)
+    out = _run("--gpus", "2", "--steps", "1", "--warmup", "0", "--pairs", "4", "--total-pairs", "11", "--pool", "3",
+               "--dump-outputs", str(tmp_path / "split"))
+    T = np.load(tmp_path / "split" / "transformation.npy")
+    assert T.shape == (11, 4, 4) and T[:, 0, 3].tolist() == out["pose_tx"]

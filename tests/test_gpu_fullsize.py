@@ -148,7 +148,7 @@ def test_bench_geometry_forward_rows_vs_oracle(big_batch):
     assert float((a - b).abs().max()) < 2e-5
 
 
-def test_bench_total_pairs_split_runs_on_the_gpu():
+def test_bench_total_pairs_split_runs_on_the_gpu(tmp_path):
     """configs[3]'s code path (``bench.py --total-pairs``: fixed split, ragged last batch, records gathered in global
     pair order) on one GPU: 21 pairs in batches of 8 / 8 / 5 from a pool of 4 scenes.  Run as its own process - bench.py
     forks its scene generators before it touches the GPU."""
@@ -158,7 +158,7 @@ def test_bench_total_pairs_split_runs_on_the_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--total-pairs", "21", "--pairs", "8",
-                        "--pool", "4", "--steps", "1", "--warmup", "1", "--no-extras", "--no-cpu-baseline"],
+                        "--pool", "4", "--steps", "1", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
                        capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -169,3 +169,8 @@ def test_bench_total_pairs_split_runs_on_the_gpu():
     # global pair order: pair i is scene i % 4 of rank 0's pool, and a registered pair's pose is that scene's T_gt
     tx = line["pose_tx_first8"]
     assert len(tx) == 8 and np.allclose(tx[:4], tx[4:8], atol=0.5) and len({round(v, 1) for v in tx[:4]}) > 1
+    # --dump-outputs: the last pass's RegistrationResults in the same global pair order
+    T = np.load(tmp_path / "transformation.npy")
+    assert T.dtype == np.float64 and T.shape == (21, 4, 4) and T[:8, 0, 3].tolist() == tx
+    inl = np.load(tmp_path / "inliers.npy")
+    assert inl.shape == (21,) and inl.max() > 0 and np.array_equal(np.load(tmp_path / "fitness.npy"), inl / 5000)

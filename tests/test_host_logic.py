@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 
-def test_load_config_reads_the_reference_run_configuration(tmp_path):
+def test_load_config_reads_the_reference_run_configuration(tmp_path, golden_dir):
     from eyoc_amd.harness import load_config, RegistrationConfig
     cfg = {"model": "ResUNetBN2C", "model_n_out": 32, "conv1_kernel_size": 5, "normalize_feature": True, "bn_momentum": 0.05,
            "voxel_size": 0.3, "batch_size": 4, "lr": 0.1, "dataset": "KITTINMPairDataset", "optimizer": "SGD"}
@@ -21,11 +21,11 @@ def test_load_config_reads_the_reference_run_configuration(tmp_path):
     c2 = load_config(cfg, sc, use_RANSAC=False, rte_thresh=1.0, rre_thresh=2.5)
     assert not c2.use_RANSAC and c2.rte_thresh == 1.0 and c2.rre_thresh == 2.5
     assert c2.sc2pcr["num_node"] == 8000 and c2.sc2pcr["nms_radius"] == 0.6 and "downsample" not in c2.sc2pcr
-    # the reference's own SC2-PCR constants, when its tree is around
-    ref = "/root/reference/scripts/SC2_PCR/config_json/config_KITTI.json"
-    if os.path.exists(ref):
-        c3 = load_config(cfg, ref, use_RANSAC=False)
-        assert c3.sc2pcr == RegistrationConfig().sc2pcr          # the defaults ARE config_KITTI.json
+    # the reference's own SC2-PCR constants (scripts/SC2_PCR/config_json/config_KITTI.json, stored in tests/golden/g11_host.npz)
+    ref = tmp_path / "config_KITTI.json"
+    ref.write_text(str(np.load(os.path.join(golden_dir, "g11_host.npz"))["config_kitti"]))
+    c3 = load_config(cfg, str(ref), use_RANSAC=False)
+    assert c3.sc2pcr == RegistrationConfig().sc2pcr          # the defaults ARE config_KITTI.json
 
 
 def test_planted_correspondences_have_the_stated_inlier_ratio():
@@ -78,34 +78,12 @@ def test_generated_staged_loop_is_what_the_generator_writes(tmp_path):
     assert min(regs) >= 64 and max(regs) <= 252                                   # v0 - v63 stay with the compiler
 
 
-def test_o3d_shim_covers_every_open3d_name_the_reference_call_site_uses():
+def test_o3d_shim_covers_every_open3d_name_the_reference_call_site_uses(golden_dir):
     """``import eyoc_amd.o3d as o3d`` must let scripts/test_kitti.py:159-177 and util/pointcloud.py:9-21 run unchanged: every
-    ``o3d.<...>`` attribute chain in those line ranges (read from the reference tree at run time - this container only) resolves
-    in the shim.  The call itself runs in tests/test_gpu_pose.py."""
-    import ast
-    import os
-    import pytest
-    ref = "/root/reference"
-    if not os.path.isdir(ref):
-        pytest.skip("reference tree not present")
+    ``o3d.<...>`` attribute chain in those line ranges (read from the reference tree by tests/golden/make_golden.py and stored in
+    g11_host.npz) resolves in the shim.  The call itself runs in tests/test_gpu_pose.py."""
     import eyoc_amd.o3d as shim
-
-    def chains(path, lo, hi, encoding="utf-8"):
-        src = open(path, encoding=encoding).read().split("\n")
-        body = "\n".join(src[lo - 1:hi])
-        import textwrap
-        tree = ast.parse(textwrap.dedent(body))
-        out = set()
-        for node in ast.walk(tree):
-            if isinstance(node, ast.Attribute):
-                parts, cur = [], node
-                while isinstance(cur, ast.Attribute):
-                    parts.append(cur.attr)
-                    cur = cur.value
-                if isinstance(cur, ast.Name) and cur.id == "o3d":
-                    out.add(tuple(reversed(parts)))
-        return out
-    used = chains(f"{ref}/scripts/test_kitti.py", 162, 177) | chains(f"{ref}/util/pointcloud.py", 9, 21)
+    used = {tuple(c) for c in json.loads(str(np.load(os.path.join(golden_dir, "g11_host.npz"))["o3d_chains"]))}
     assert ("pipelines", "registration", "registration_ransac_based_on_feature_matching") in used and len(used) >= 8
     for chain in used:
         obj = shim

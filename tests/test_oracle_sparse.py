@@ -168,21 +168,17 @@ def test_label_oracle_properties():
     assert len(out) == 100
 
 
-def test_similarity_mask_against_an_independent_torch_formulation():
+def test_similarity_mask_against_an_independent_torch_formulation(golden_dir):
     """oracle.labels.similarity_mask (numpy) against the same rule written with torch tensor ops (norm, integer cast,
-    clamping by masked assignment, 2-D indexing) on the reference's real KITTI table when the reference tree is around
-    (this container), else on a synthetic table of the same shapes.  lib/trainer.py itself cannot be imported
-    (MinkowskiEngine / pytorch3d / open3d at module scope), so this is as close to a pin as the filter gets."""
+    clamping by masked assignment, 2-D indexing) on the reference's real KITTI table (config/dist_sim_plot/kitti_distSimPlot.npz,
+    stored in tests/golden/g11_host.npz).  lib/trainer.py itself cannot be imported (MinkowskiEngine / pytorch3d / open3d at module
+    scope), so this is as close to a pin as the filter gets."""
     import os
     import torch
     from oracle import labels as ol
-    path = "/root/reference/config/dist_sim_plot/kitti_distSimPlot.npz"
+    g = np.load(os.path.join(golden_dir, "g11_host.npz"))
+    table = {i: g[f"dist_sim_kitti_{i}"] for i in range(6)}
     rng = np.random.default_rng(3)
-    if os.path.exists(path):
-        maps = np.load(path, allow_pickle=True)["res"].tolist()
-        table = {i: np.asarray(maps[i], np.float64) for i in range(6)}
-    else:
-        table = {i: rng.uniform(0, 1, sh) for i, sh in enumerate([(12, 16), (18, 16), (20, 18), (20, 18), (20, 18), (20, 18)])}
     C0 = (rng.uniform(-1, 1, (2000, 3)) * rng.choice([5, 40, 150], (2000, 1))).astype(np.float32)
     C1 = (rng.uniform(-1, 1, (2000, 3)) * rng.choice([5, 40, 150], (2000, 1))).astype(np.float32)
     a, b = rng.integers(0, 2000, 3000), rng.integers(0, 2000, 3000)
