@@ -17,7 +17,7 @@ from .transform_estimation import (est_quad_linear_robust, estimate_transform, p
 from .registration import (Matcher, registration_ransac_based_on_feature_matching,  # noqa: F401
                            ransac_from_correspondences, ransac_batched_from_correspondences, RegistrationResult)
 from .metrics import registration_errors, apply_transform, evaluate_nn_dist  # noqa: F401
-from .voxelize import sparse_quantize, voxelize, extract_features  # noqa: F401
+from .voxelize import sparse_quantize, sparse_quantize_batch, voxelize, extract_features  # noqa: F401
 from .labels import (knn2_segmented, lowe_topk, spherical_filter, similarity_filter, load_dist_sim_map,  # noqa: F401
                      match_and_filter_corr, correspondences_under_pose)
 from .autograd import sparse_conv, contrastive_hardest_negative_loss  # noqa: F401,E402

@@ -57,6 +57,43 @@ __global__ void k_insert(const int32_t* __restrict__ coords, int n, int ts2, Has
   if (slot_out) slot_out[i] = (int)s;
 }
 
+// the voxeliser's insert: consecutive points of a sweep often share a voxel, so within a wave only the first point of every run of equal
+// keys probes the table (CAS + atomicMin: it is also the run's smallest index) and the others take its slot - the same table, slots
+// and values as k_insert(ts2 = 1)
+__global__ __launch_bounds__(256) void k_insert_runs(const int32_t* __restrict__ coords, int n, HashTable t, int* __restrict__ slot_out,
+                                                     int* __restrict__ err) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
+  constexpr int LIM = COORD_BIAS - 16;
+  bool ok = false;
+  unsigned long long key = KEY_EMPTY;      // no valid key is KEY_EMPTY (batch < 1024)
+  if (i < n) {
+    const int4 c = reinterpret_cast<const int4*>(coords)[i];
+    ok = !(c.x < 0 || c.x >= 1024 || c.y < -LIM || c.y >= LIM || c.z < -LIM || c.z >= LIM || c.w < -LIM || c.w >= LIM);
+    if (ok) {
+      key = pack_key(c.x, c.y, c.z, c.w);
+    } else {
+      atomicAdd(&err[0], 1);
+      slot_out[i] = 0;
+    }
+  }
+  const unsigned long long prev = __shfl_up(key, 1, 64);
+  const bool lead = ok && (lane == 0 || prev != key);
+  int s = 0;
+  if (lead) {
+    s = (int)(hash_key(key) & t.mask);
+    while (true) {
+      const unsigned long long old = atomicCAS(&t.keys[s], KEY_EMPTY, key);
+      if (old == KEY_EMPTY || old == key) break;
+      s = (int)((s + 1) & t.mask);
+    }
+    atomicMin(&t.vals[s], i);
+  }
+  const unsigned long long below = __ballot(lead) & (lane == 63 ? ~0ull : (2ull << lane) - 1);   // leaders at or below this lane
+  const int src = below ? 63 - __clzll((long long)below) : lane;
+  const int from_lead = __shfl(s, src, 64);
+  if (ok) slot_out[i] = from_lead;
+}
+
 // flag[i] = 1 iff row i is the first row of its slot; for ts2 == 1 any 0 flag is a duplicate row
 __global__ void k_flag(const int* __restrict__ slot, const int* __restrict__ vals, int n, int* __restrict__ flag,
                        int* __restrict__ dup) {
@@ -115,10 +152,16 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_top(int* __restrict__ parti
 }
 
 // compaction: first rows write their coarse coordinate at pos and re-label their slot with it
+// kPoints (the voxeliser): rows are raw points of packed clouds (batch index batch_base + cloud); sel_out gets the index of the
+// point within its cloud (pt_off: the clouds' point offsets; not read for one cloud) and xyz_out, unless NULL, its xyz
+template <bool kPoints>
 __global__ __launch_bounds__(SCAN_BLOCK) void k_compact(const int* __restrict__ flag, const int* __restrict__ partial,
                                                         const int* __restrict__ slot, const int32_t* __restrict__ coords,
                                                         int n, int ts2, int32_t* __restrict__ coords_out,
-                                                        int* __restrict__ vals, int32_t* __restrict__ sel_out) {
+                                                        int* __restrict__ vals, int32_t* __restrict__ sel_out,
+                                                        const int64_t* __restrict__ pt_off = nullptr, int n_clouds = 1,
+                                                        int batch_base = 0, const float* __restrict__ xyz = nullptr,
+                                                        int stride = 0, float* __restrict__ xyz_out = nullptr) {
   const int base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
   int f[SCAN_ITEMS];
   int s = 0;
@@ -138,7 +181,17 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_compact(const int* __restrict__ 
       int4 c = make_int4(b, x, y, z);
       reinterpret_cast<int4*>(coords_out)[pos] = c;
       vals[slot[i]] = pos;
-      if (sel_out) sel_out[pos] = i;
+      if constexpr (kPoints) {
+        sel_out[pos] = n_clouds == 1 ? i : i - (int)pt_off[b - batch_base];
+        if (xyz_out) {
+          const float* p = xyz + (size_t)i * stride;
+          xyz_out[3 * (size_t)pos] = p[0];
+          xyz_out[3 * (size_t)pos + 1] = p[1];
+          xyz_out[3 * (size_t)pos + 2] = p[2];
+        }
+      } else if (sel_out) {
+        sel_out[pos] = i;
+      }
       ++pos;
     }
   }
@@ -462,13 +515,58 @@ __global__ void k_iota(int32_t* __restrict__ out, int n) {
 }
 
 // voxel coordinates of raw points: floor(x / voxel) in fp32 (IEEE division, like torch / numpy on fp32 input)
-__global__ void k_quantize(const float* __restrict__ xyz, int n, int stride, float voxel, int batch,
-                           int32_t* __restrict__ coords) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
+// Packed clouds: point i of cloud b (pt_off[b] <= i < pt_off[b+1]; not read for one cloud) gets batch index batch_base + b, so equal
+// voxels of different clouds never share a key.  The cloud of the workgroup's first point by one binary search, every point's by a
+// forward walk from there (empty clouds only lengthen the walk).  bad (atomicMax of n_clouds - b): the first cloud that holds a point
+// outside the key range k_insert accepts.
+__global__ void k_quantize(const float* __restrict__ xyz, int n, int stride, float voxel, const int64_t* __restrict__ pt_off,
+                           int n_clouds, int batch_base, int32_t* __restrict__ coords, int* __restrict__ bad) {
+  __shared__ int cloud0;
+  const int i0 = blockIdx.x * blockDim.x;
+  if (n_clouds > 1) {
+    if (threadIdx.x == 0) {    // the last cloud that starts at or before i0 (pt_off[0] = 0, pt_off[n_clouds] = n > i0)
+      int lo = 0, hi = n_clouds - 1;
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (pt_off[mid] <= i0) lo = mid; else hi = mid - 1;
+      }
+      cloud0 = lo;
+    }
+    __syncthreads();
+  }
+  const int i = i0 + threadIdx.x;
   if (i >= n) return;
+  int b = 0;
+  if (n_clouds > 1) {
+    b = cloud0;
+    while (pt_off[b + 1] <= i) ++b;
+  }
   const float* p = xyz + (size_t)i * stride;
-  int4 c = make_int4(batch, (int)floorf(p[0] / voxel), (int)floorf(p[1] / voxel), (int)floorf(p[2] / voxel));
+  int4 c = make_int4(batch_base + b, (int)floorf(p[0] / voxel), (int)floorf(p[1] / voxel), (int)floorf(p[2] / voxel));
   reinterpret_cast<int4*>(coords)[i] = c;
+  constexpr int LIM = COORD_BIAS - 16;   // k_insert's test
+  if (c.y < -LIM || c.y >= LIM || c.z < -LIM || c.z >= LIM || c.w < -LIM || c.w >= LIM) atomicMax(bad, n_clouds - b);
+}
+
+// the clouds' row offsets in the compacted output: the exclusive scan of the flags at a cloud's first point is the scanned partial sum
+// of its tile plus the flags from the tile's start to that point (deterministic, no atomics).  One wave per boundary pt_off[j],
+// j <= n_clouds; a boundary at n (empty clouds at the end, and pt_off[n_clouds]) is the total.
+__global__ __launch_bounds__(256) void k_cloud_offsets(const int* __restrict__ flag, const int* __restrict__ partial,
+                                                       const int* __restrict__ total, int n, const int64_t* __restrict__ pt_off,
+                                                       int n_clouds, int* __restrict__ vox_off) {
+  const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (j > n_clouds) return;
+  const int p = (int)pt_off[j];
+  if (p >= n) {
+    if (lane == 0) vox_off[j] = *total;
+    return;
+  }
+  const int tile = p / SCAN_TILE;
+  int s = 0;
+  for (int k = tile * SCAN_TILE + lane; k < p; k += 64) s += flag[k];
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+  if (lane == 0) vox_off[j] = partial[tile] + s;
 }
 
 // octree links for the rows of level l (tensor stride 1 << sh): slot[] / vals still describe where each
@@ -832,7 +930,7 @@ int eyoc_maps_build_ordered(eyoc_ctx* ctx, const int32_t* coords_dev, int n, voi
       }
       continue;
     }
-    hipLaunchKernelGGL(k_compact, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, partial, slot, src, n_src, ts2,
+    hipLaunchKernelGGL(k_compact<false>, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, partial, slot, src, n_src, ts2,
                        m->coords[l], t.vals, (int32_t*)nullptr);
     // octree links fine (l-1) <-> coarse (l); same stream, so k_compact's re-labelling is visible
     hipLaunchKernelGGL(k_children, dim3(cdiv(n_src, 256)), dim3(256), 0, st, slot, t.vals, src, n_src, l - 1,
@@ -1040,18 +1138,24 @@ size_t eyoc_voxelize_workspace_bytes(int n_points) {
          align_up((n / SCAN_TILE + 2) * 4) + 4096 + 16 * 256;
 }
 
-int eyoc_voxelize(eyoc_ctx* ctx, const float* xyz_dev, int n, int stride, float voxel_size, int batch_index,
-                  int32_t* sel_dev, int32_t* coords_dev, int* n_out, void* ws, size_t ws_bytes, void* stream) {
-  EYOC_REQUIRE(ctx && xyz_dev && sel_dev && coords_dev && n_out && ws, EYOC_ERR_INVALID, "eyoc_voxelize: NULL argument");
-  EYOC_REQUIRE(n > 0 && stride >= 3 && voxel_size > 0.0f, EYOC_ERR_INVALID, "eyoc_voxelize: n %d stride %d voxel %g", n,
-               stride, voxel_size);
-  EYOC_REQUIRE(batch_index >= 0 && batch_index < 1024, EYOC_ERR_RANGE, "eyoc_voxelize: batch index %d", batch_index);
-  EYOC_REQUIRE(((uintptr_t)ws & 255) == 0 && ws_bytes >= eyoc_voxelize_workspace_bytes(n), EYOC_ERR_WORKSPACE,
-               "eyoc_voxelize: workspace %zu < required %zu bytes (256-byte aligned)", ws_bytes,
-               eyoc_voxelize_workspace_bytes(n));
-  hipStream_t st = (hipStream_t)stream;
+size_t eyoc_voxelize_batched_workspace_bytes(int n_points_total, int n_clouds) {
+  if (n_points_total < 0 || n_clouds < 1) return 0;
+  return eyoc_voxelize_workspace_bytes(n_points_total) + align_up((size_t)(n_clouds + 1) * 8) + align_up((size_t)(n_clouds + 1) * 4);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The voxeliser of eyoc_voxelize (one cloud) and eyoc_voxelize_batched (n_clouds packed clouds): quantise, hash-grid insert, flag,
+// scan, per-cloud row offsets, compact, and one read-back.  Arguments validated by the callers; n > 0.  pt_off_host: [n_clouds + 1]
+// (uploaded through the ctx's pinned staging; one cloud needs none), vox_off_host: [n_clouds + 1] out.
+int voxelize_run(eyoc_ctx* ctx, const char* who, const float* xyz_dev, int n, int stride, const int64_t* pt_off_host,
+                 int n_clouds, float voxel_size, int batch_base, int32_t* sel_dev, int32_t* coords_dev, float* xyz_out_dev,
+                 int64_t* vox_off_host, void* ws, size_t ws_bytes, hipStream_t st) {
   Carver cv(ws, ws_bytes);
-  int* counters = cv.take<int>(64);
+  int* counters = cv.take<int>(64 + n_clouds + 1);   // [0] range errors, [1] first bad cloud (n_clouds - b), [2] total, [64..] row offsets
+  int64_t* pt_off = cv.take<int64_t>(n_clouds + 1);
   int32_t* raw = cv.take<int32_t>((size_t)n * 4);
   int* slot = cv.take<int>(n);
   int* flag = cv.take<int>(n);
@@ -1061,23 +1165,101 @@ int eyoc_voxelize(eyoc_ctx* ctx, const float* xyz_dev, int n, int stride, float 
   t.keys = cv.take<unsigned long long>(cap);
   t.vals = cv.take<int>(cap);
   t.mask = cap - 1;
+  EYOC_REQUIRE(cv.ok(), EYOC_ERR_WORKSPACE, "%s: internal workspace accounting error (%zu > %zu)", who, cv.off, cv.cap);
+  // pinned staging: the point offsets up at 0, the counters and row offsets back behind them
+  const size_t up_bytes = n_clouds > 1 ? align_up((size_t)(n_clouds + 1) * 8) : 0;
+  const int back = n_clouds > 1 ? 64 + n_clouds + 1 : 4;
+  EYOC_REQUIRE(up_bytes + (size_t)back * 4 <= ctx->pinned_bytes, EYOC_ERR_INVALID, "%s: %d clouds exceed the pinned staging", who,
+               n_clouds);
+  int64_t* up = (int64_t*)ctx->pinned;
+  int* host = (int*)((char*)ctx->pinned + up_bytes);
+  if (n_clouds > 1) {
+    memcpy(up, pt_off_host, (size_t)(n_clouds + 1) * 8);
+    EYOC_CHECK_HIP(hipMemcpyAsync(pt_off, up, (size_t)(n_clouds + 1) * 8, hipMemcpyHostToDevice, st));
+  }
   EYOC_CHECK_HIP(hipMemsetAsync(counters, 0, 64 * sizeof(int), st));
   EYOC_CHECK_HIP(hipMemsetAsync(t.keys, 0xFF, (size_t)cap * 8, st));
   EYOC_CHECK_HIP(hipMemsetAsync(t.vals, 0x7F, (size_t)cap * 4, st));
-  hipLaunchKernelGGL(k_quantize, dim3(cdiv(n, 256)), dim3(256), 0, st, xyz_dev, n, stride, voxel_size, batch_index, raw);
-  hipLaunchKernelGGL(k_insert, dim3(cdiv(n, 256)), dim3(256), 0, st, raw, n, 1, t, slot, counters);
+  hipLaunchKernelGGL(k_quantize, dim3(cdiv(n, 256)), dim3(256), 0, st, xyz_dev, n, stride, voxel_size, (const int64_t*)pt_off,
+                     n_clouds, batch_base, raw, counters + 1);
+  hipLaunchKernelGGL(k_insert_runs, dim3(cdiv(n, 256)), dim3(256), 0, st, (const int32_t*)raw, n, t, slot, counters);
   hipLaunchKernelGGL(k_flag, dim3(cdiv(n, 256)), dim3(256), 0, st, slot, t.vals, n, flag, (int*)nullptr);
   const int nb = cdiv(n, SCAN_TILE);
   hipLaunchKernelGGL(k_scan_partials, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, n, partial);
   hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(SCAN_BLOCK), 0, st, partial, nb, counters + 2);
-  hipLaunchKernelGGL(k_compact, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, partial, slot, raw, n, 1, coords_dev, t.vals,
-                     sel_dev);
-  int* host = (int*)ctx->pinned;
-  EYOC_CHECK_HIP(hipMemcpyAsync(host, counters, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (n_clouds > 1)
+    hipLaunchKernelGGL(k_cloud_offsets, dim3(cdiv(n_clouds + 1, 4)), dim3(256), 0, st, (const int*)flag, (const int*)partial,
+                       (const int*)(counters + 2), n, (const int64_t*)pt_off, n_clouds, counters + 64);
+  hipLaunchKernelGGL(k_compact<true>, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, partial, slot, raw, n, 1, coords_dev, t.vals,
+                     sel_dev, (const int64_t*)pt_off, n_clouds, batch_base, xyz_dev, stride, xyz_out_dev);
+  EYOC_CHECK_HIP(hipGetLastError());
+  EYOC_CHECK_HIP(hipMemcpyAsync(host, counters, (size_t)back * sizeof(int), hipMemcpyDeviceToHost, st));
   EYOC_CHECK_HIP(hipStreamSynchronize(st));
-  EYOC_REQUIRE(host[0] == 0, EYOC_ERR_RANGE, "eyoc_voxelize: %d points fall outside the key range (|c| < 2^17 - 16)", host[0]);
-  *n_out = host[2];
+  if (host[0] != 0) {
+    if (n_clouds > 1)
+      EYOC_REQUIRE(false, EYOC_ERR_RANGE, "%s: %d points fall outside the key range (|c| < 2^17 - 16), the first of them in cloud %d",
+                   who, host[0], n_clouds - host[1]);
+    EYOC_REQUIRE(false, EYOC_ERR_RANGE, "%s: %d points fall outside the key range (|c| < 2^17 - 16)", who, host[0]);
+  }
+  vox_off_host[0] = 0;
+  if (n_clouds == 1) {
+    vox_off_host[1] = host[2];
+  } else {
+    for (int b = 1; b <= n_clouds; ++b) vox_off_host[b] = host[64 + b];
+  }
   return EYOC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int eyoc_voxelize(eyoc_ctx* ctx, const float* xyz_dev, int n, int stride, float voxel_size, int batch_index,
+                  int32_t* sel_dev, int32_t* coords_dev, int* n_out, void* ws, size_t ws_bytes, void* stream) {
+  EYOC_REQUIRE(ctx && xyz_dev && sel_dev && coords_dev && n_out && ws, EYOC_ERR_INVALID, "eyoc_voxelize: NULL argument");
+  EYOC_REQUIRE(n > 0 && stride >= 3 && voxel_size > 0.0f, EYOC_ERR_INVALID, "eyoc_voxelize: n %d stride %d voxel %g", n,
+               stride, voxel_size);
+  EYOC_REQUIRE(batch_index >= 0 && batch_index < 1024, EYOC_ERR_RANGE, "eyoc_voxelize: batch index %d", batch_index);
+  EYOC_REQUIRE(((uintptr_t)ws & 255) == 0 && ws_bytes >= eyoc_voxelize_workspace_bytes(n), EYOC_ERR_WORKSPACE,
+               "eyoc_voxelize: workspace %zu < required %zu bytes (256-byte aligned)", ws_bytes,
+               eyoc_voxelize_workspace_bytes(n));
+  const int64_t pt_off[2] = {0, n};
+  int64_t vox_off[2];
+  if (int rc = voxelize_run(ctx, "eyoc_voxelize", xyz_dev, n, stride, pt_off, 1, voxel_size, batch_index, sel_dev, coords_dev,
+                            nullptr, vox_off, ws, ws_bytes, (hipStream_t)stream))
+    return rc;
+  *n_out = (int)vox_off[1];
+  return EYOC_OK;
+}
+
+int eyoc_voxelize_batched(eyoc_ctx* ctx, const float* xyz_dev, int stride, const int64_t* point_offsets, int n_clouds,
+                          int n_points, float voxel_size, int batch_base, int32_t* sel_dev, int32_t* coords_dev,
+                          float* xyz_out_dev, int64_t* voxel_offsets, void* ws, size_t ws_bytes, void* stream) {
+  EYOC_REQUIRE(ctx && point_offsets && voxel_offsets, EYOC_ERR_INVALID, "eyoc_voxelize_batched: NULL argument");
+  EYOC_REQUIRE(n_clouds >= 1 && n_clouds <= 1024, EYOC_ERR_INVALID, "eyoc_voxelize_batched: %d clouds (1 .. 1024)", n_clouds);
+  EYOC_REQUIRE(n_points >= 0 && n_points <= (1 << 30), EYOC_ERR_INVALID, "eyoc_voxelize_batched: %d points in all (0 .. 2^30)",
+               n_points);
+  EYOC_REQUIRE(stride >= 3 && voxel_size > 0.0f, EYOC_ERR_INVALID, "eyoc_voxelize_batched: stride %d voxel %g", stride, voxel_size);
+  EYOC_REQUIRE(batch_base >= 0 && batch_base + n_clouds <= 1024, EYOC_ERR_RANGE,
+               "eyoc_voxelize_batched: batch indices %d .. %d (< 1024)", batch_base, batch_base + n_clouds - 1);
+  EYOC_REQUIRE(point_offsets[0] == 0, EYOC_ERR_INVALID, "eyoc_voxelize_batched: point_offsets[0] = %lld", (long long)point_offsets[0]);
+  for (int b = 0; b < n_clouds; ++b)
+    EYOC_REQUIRE(point_offsets[b + 1] >= point_offsets[b], EYOC_ERR_INVALID,
+                 "eyoc_voxelize_batched: point offsets decrease at cloud %d (%lld -> %lld)", b, (long long)point_offsets[b],
+                 (long long)point_offsets[b + 1]);
+  EYOC_REQUIRE(point_offsets[n_clouds] == n_points, EYOC_ERR_INVALID,
+               "eyoc_voxelize_batched: point_offsets[%d] = %lld, not the total %d", n_clouds, (long long)point_offsets[n_clouds],
+               n_points);
+  if (n_points == 0) {          // every cloud empty: nothing to launch
+    for (int b = 0; b <= n_clouds; ++b) voxel_offsets[b] = 0;
+    return EYOC_OK;
+  }
+  EYOC_REQUIRE(xyz_dev && sel_dev && coords_dev && ws, EYOC_ERR_INVALID, "eyoc_voxelize_batched: NULL argument");
+  const size_t need = eyoc_voxelize_batched_workspace_bytes(n_points, n_clouds);
+  EYOC_REQUIRE(((uintptr_t)ws & 255) == 0 && ws_bytes >= need, EYOC_ERR_WORKSPACE,
+               "eyoc_voxelize_batched: workspace %zu < required %zu bytes (256-byte aligned)", ws_bytes, need);
+  return voxelize_run(ctx, "eyoc_voxelize_batched", xyz_dev, n_points, stride, point_offsets, n_clouds, voxel_size, batch_base,
+                      sel_dev, coords_dev, xyz_out_dev, voxel_offsets, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int eyoc_maps_free(eyoc_maps* maps) {

@@ -66,6 +66,14 @@ def load_config(config, sc2pcr_config=None, use_RANSAC=True, rte_thresh=2.0, rre
     return out
 
 
+def sample_indices(seed, i, n, n_points):
+    """``random_sample`` of scripts/test_kitti.py:159-160 for cloud ``i`` (0 source, 1 target) of the pair with ``seed``: ``n_points``
+    of the ``n`` voxels, without replacement when there are enough of them, with replacement otherwise."""
+    if n >= n_points:
+        return subsample_indices(seed * 2 + i, n, n_points)
+    return np.random.default_rng(seed * 2 + i + 10**6).choice(n, n_points)
+
+
 class DeviceBatch:
     """``P`` pairs resident in HBM: batched coordinates/features for the 2P clouds, the voxel centres'
     points, and the (seeded) sample indices of ``random_sample`` (scripts/test_kitti.py:159-160).
@@ -100,12 +108,7 @@ class DeviceBatch:
                 G0.append(planted["G0"]); G1.append(planted["G1"]); self.planted.append(planted["planted"])
             for i, (sel, xyz) in enumerate(((sel0, xyz0), (sel1, xyz1))):
                 n = self.sizes[2 * j + i]
-                if planted is not None:
-                    idx = planted[f"sel{i}"]
-                elif n >= n_points:
-                    idx = subsample_indices(seed * 2 + i, n, n_points)
-                else:                        # random_sample with replacement when the cloud is small
-                    idx = np.random.default_rng(seed * 2 + i + 10**6).choice(n, n_points)
+                idx = planted[f"sel{i}"] if planted is not None else sample_indices(seed, i, n, n_points)
                 sel.append(idx + self.offsets[2 * j + i])
                 xyz.append(p[f"xyz{i}"][idx])
             self.counts.append(n_points)
@@ -117,6 +120,43 @@ class DeviceBatch:
         self.xyz1 = torch.from_numpy(np.stack(xyz1)).to(device)
         self.seg = np.arange(self.P + 1) * n_points
         self.n_points = n_points
+
+    @classmethod
+    def from_scans(cls, scans, T_gt, seeds, device, voxel_size=0.3, n_points=5000, descriptor=None):
+        """The same batch from RAW scans: ``scans`` = ``[(src, tgt), ...]`` unvoxelised ``[N,3]`` / ``[N,4]`` float32 clouds (numpy or
+        torch), voxelised and collated on the GPU by ONE ``sparse_quantize_batch`` call (one read-back: the clouds' voxel counts) -
+        lib/data_loaders.py:936-979 per cloud and ``collate_pair_fn`` (:31-85) for the batch.  The sample draws are ``__init__``'s
+        (``sample_indices`` on the counts); the sampled points are gathered on the device.  Equal, attribute for attribute, to
+        ``DeviceBatch(pairs, seeds, device, n_points)`` of the pairs these scans voxelise to.  The descriptor mode plants its
+        correspondences on the host and is not available here."""
+        from .voxelize import sparse_quantize_batch
+        if descriptor:
+            raise ValueError("DeviceBatch.from_scans: the descriptor mode (plant_correspondences) needs host-voxelised pairs")
+        if not len(scans) == len(T_gt) == len(seeds):
+            raise ValueError(f"DeviceBatch.from_scans: {len(scans)} scan pairs, {len(T_gt)} poses, {len(seeds)} seeds")
+        device = torch.device(device)
+        self = cls.__new__(cls)
+        self.P = len(scans)
+        self.descriptor, self.beta = None, 0.0
+        clouds = [c for pair in scans for c in pair]
+        self.coords, _, kept_xyz, self.offsets = sparse_quantize_batch(clouds, voxel_size, 0, device=device)
+        self.sizes = [int(v) for v in np.diff(self.offsets)]
+        self.feats = torch.ones((len(self.coords), 1), dtype=torch.float32, device=self.coords.device)
+        self.T_gt = [np.asarray(T, np.float32) for T in T_gt]
+        sel = ([], [])
+        for j, seed in enumerate(seeds):
+            for i in (0, 1):
+                sel[i].append(sample_indices(seed, i, self.sizes[2 * j + i], n_points) + self.offsets[2 * j + i])
+        self.counts = [n_points] * self.P
+        self.G0 = self.G1 = None
+        self.planted = []
+        self.sel0 = torch.from_numpy(np.concatenate(sel[0])).to(self.coords.device)
+        self.sel1 = torch.from_numpy(np.concatenate(sel[1])).to(self.coords.device)
+        self.xyz0 = kept_xyz[self.sel0].reshape(self.P, n_points, 3)
+        self.xyz1 = kept_xyz[self.sel1].reshape(self.P, n_points, 3)
+        self.seg = np.arange(self.P + 1) * n_points
+        self.n_points = n_points
+        return self
 
     @property
     def voxels(self):

@@ -262,11 +262,12 @@ def _pose(x, y, yaw):
 
 
 def make_pair(seed, voxel_size=0.3, dist_range=(5.0, 20.0), beams=64, azimuths=2000,
-              band=(28500, 31500), max_yaw_deg=10.0, max_range=80.0, elev=(2.0, -24.8)):
+              band=(28500, 31500), max_yaw_deg=10.0, max_range=80.0, elev=(2.0, -24.8), keep_raw=False):
     """One synthetic registration pair.
 
     Returns a dict with ``xyz0/xyz1 f32 [N,3]`` (voxelised points), ``coords0/coords1 i32 [N,3]``,
-    ``feats0/feats1 f32 [N,1]`` (ones) and ``T_gt f32 [4,4]`` with ``xyz1 ~ R xyz0 + t``.
+    ``feats0/feats1 f32 [N,1]`` (ones) and ``T_gt f32 [4,4]`` with ``xyz1 ~ R xyz0 + t``; with ``keep_raw`` also
+    ``raw0/raw1 f32 [M,3]``, the unvoxelised sweeps the voxelised clouds were taken from (same draws either way).
     The brush-layer level is bisected (deterministically) until the mean voxel count of the two
     clouds falls in ``band``; ``stats`` reports what was realised.
     """
@@ -297,7 +298,7 @@ def make_pair(seed, voxel_size=0.3, dist_range=(5.0, 20.0), beams=64, azimuths=2
         level = 0.5 * (lo + hi)
     (p0, sel0, c0), (p1, sel1, c1) = clouds
     T_gt = (np.linalg.inv(poses[1]) @ poses[0]).astype(np.float32)
-    return {
+    out = {
         "xyz0": p0[sel0], "xyz1": p1[sel1],
         "coords0": c0, "coords1": c1,
         "feats0": np.ones((len(sel0), 1), np.float32), "feats1": np.ones((len(sel1), 1), np.float32),
@@ -305,6 +306,9 @@ def make_pair(seed, voxel_size=0.3, dist_range=(5.0, 20.0), beams=64, azimuths=2
         "stats": {"raw0": len(p0), "raw1": len(p1), "n0": len(sel0), "n1": len(sel1),
                   "brush_level": level, "dist": float(d), "yaw_deg": float(np.rad2deg(yaw))},
     }
+    if keep_raw:
+        out["raw0"], out["raw1"] = p0, p1
+    return out
 
 
 def batch_coords(coords_list):

@@ -45,6 +45,78 @@ def sparse_quantize(xyz, voxel_size: float, batch_index: int = 0):
     return coords[:m], sel[:m].long()
 
 
+MAX_BATCH = 1024          # batch indices of the coordinate keys (include/eyoc_hip.h)
+MAX_POINTS = 1 << 30      # points of one batched call
+
+
+def _batch_layout(clouds, voxel_size, batch_base):
+    """Host-side checks of ``sparse_quantize_batch`` (before anything touches the device) -> (row width, point offsets int64 [B+1])."""
+    B = len(clouds)
+    if B == 0:
+        raise ValueError("sparse_quantize_batch: no clouds")
+    if not float(voxel_size) > 0.0:
+        raise ValueError(f"sparse_quantize_batch: voxel_size must be > 0, got {voxel_size}")
+    if int(batch_base) < 0 or int(batch_base) + B > MAX_BATCH:
+        raise ValueError(f"sparse_quantize_batch: batch indices {batch_base} .. {int(batch_base) + B - 1} outside 0 .. {MAX_BATCH - 1}")
+    shapes = [tuple(c.shape) for c in clouds]
+    if any(len(s) != 2 or s[1] not in (3, 4) for s in shapes):
+        raise ValueError("sparse_quantize_batch: every cloud must be [N,3] or [N,4]")
+    widths = {s[1] for s in shapes}
+    if len(widths) != 1:
+        raise ValueError(f"sparse_quantize_batch: mixed row widths {sorted(widths)} (all [N,3] or all [N,4])")
+    offsets = np.zeros(B + 1, np.int64)
+    np.cumsum([s[0] for s in shapes], out=offsets[1:])
+    if offsets[-1] > MAX_POINTS:
+        raise ValueError(f"sparse_quantize_batch: {offsets[-1]} points in all (at most 2^30 per call)")
+    return widths.pop(), offsets
+
+
+def sparse_quantize_batch(clouds, voxel_size: float, batch_base: int = 0, device=None):
+    """``sparse_quantize`` of B raw clouds and their ``sparse_collate`` in one call with one stream synchronisation
+    (lib/data_loaders.py:940-943,969-979 per cloud, then :31-85).
+
+    ``clouds``: ``[N_b,3]`` or ``[N_b,4]`` float32 arrays (numpy or torch, host or device; one width for all, empty clouds allowed).
+    Host clouds are packed into one pinned buffer and uploaded with one copy.  ``device``: where host-only input goes (default: the
+    current device).  Returns device tensors ``(coords int32 [M,4] = (batch_base + b, floor(p / voxel)), sel int64 [M] = index of the
+    kept point within its cloud, xyz f32 [M,3] = the kept points)`` and the clouds' row ranges ``offsets np.int64 [B+1]`` - bit for bit
+    the concatenation of ``sparse_quantize(clouds[b], voxel_size, batch_base + b)``."""
+    clouds = list(clouds)
+    width, pt_off = _batch_layout(clouds, voxel_size, batch_base)
+    B, n = len(clouds), int(pt_off[-1])
+    if not torch.cuda.is_available():
+        raise _lib.EyocError("no GPU visible: the EYOC hot path runs on MI355X only (no CPU fallback)")
+    on_dev = [c for c in clouds if isinstance(c, torch.Tensor) and c.is_cuda]
+    dev = torch.device(device) if device is not None else on_dev[0].device if on_dev else torch.device("cuda")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if n == 0:
+        return (torch.empty((0, 4), dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+                torch.empty((0, 3), dtype=torch.float32, device=dev), np.zeros(B + 1, np.int64))
+    lib = _lib.load()
+    vox_off = np.zeros(B + 1, np.int64)
+    i64 = C.POINTER(C.c_int64)
+    with torch.cuda.device(dev):
+        if on_dev:
+            packed = torch.cat([(c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c, np.float32)))
+                                .to(dev, torch.float32) for c in clouds], 0).contiguous()
+        else:
+            host = torch.empty((n, width), dtype=torch.float32, pin_memory=True)
+            h = host.numpy()
+            for b, c in enumerate(clouds):
+                h[pt_off[b]:pt_off[b + 1]] = c.detach().numpy() if isinstance(c, torch.Tensor) else np.asarray(c)
+            packed = host.to(dev, non_blocking=True)   # on the library's stream, which the call synchronises
+        sel = torch.empty(n, dtype=torch.int32, device=dev)
+        coords = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        xyz = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        ws = _lib.workspace(lib.eyoc_voxelize_batched_workspace_bytes(n, B), dev)
+        _lib.check(lib.eyoc_voxelize_batched(_lib.ctx(dev.index), _lib.ptr(packed), width, pt_off.ctypes.data_as(i64), B, n,
+                                             float(voxel_size), int(batch_base), _lib.ptr(sel), _lib.ptr(coords), _lib.ptr(xyz),
+                                             vox_off.ctypes.data_as(i64), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   "eyoc_voxelize_batched")
+    m = int(vox_off[-1])
+    return coords[:m], sel[:m].long(), xyz[:m], vox_off
+
+
 def voxelize(xyz, voxel_size: float, batch_index: int = 0):
     """``(xyz[sel], coords, feats = ones [M,1])`` - the per-cloud part of lib/data_loaders.py:936-979."""
     t = xyz if isinstance(xyz, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(xyz, np.float32))

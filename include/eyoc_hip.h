@@ -160,6 +160,28 @@ int eyoc_voxelize(eyoc_ctx* ctx, const float* xyz_dev, int n_points, int stride,
                   void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * batched voxeliser + collation (SURVEY.md 8f "next": batched voxelise + collate)
+ *   replaces: the per-cloud ME.utils.sparse_quantize(xyz / voxel_size, return_index=True) +
+ *             floor(xyz[sel] / voxel_size).int() of lib/data_loaders.py:940-943,969-979 for a whole batch,
+ *             and the ME.utils.sparse_collate of collate_pair_fn (lib/data_loaders.py:31-85)
+ *   xyz_dev: n_clouds clouds packed back to back, rows of `stride` floats (3 = xyz, 4 = KITTI xyzr);
+ *   point_offsets (HOST, int64 [n_clouds+1]): cloud b is rows point_offsets[b] .. point_offsets[b+1]; monotone,
+ *   point_offsets[0] = 0, point_offsets[n_clouds] = n_points <= 2^30; empty clouds allowed anywhere.
+ *   1 <= n_clouds, batch_base + n_clouds <= 1024.
+ *   Output: bit for bit the concatenation, in cloud order, of eyoc_voxelize(cloud b, voxel_size, batch_base + b):
+ *   sel int32 = index of the kept point WITHIN its cloud (ascending per cloud), coords int32 [.,4] =
+ *   (batch_base + b, floor(p / v)), xyz_out f32 [.,3] = the kept points' xyz (or NULL: not written);
+ *   voxel_offsets (HOST out, int64 [n_clouds+1]) = the clouds' row ranges of the outputs.  Outputs need room for
+ *   n_points rows.  A point outside the key range fails the call (EYOC_ERR_RANGE; the message names the first cloud
+ *   holding one).  Synchronises `stream` once per call; n_points = 0 launches nothing.
+ * --------------------------------------------------------------------------------------------- */
+size_t eyoc_voxelize_batched_workspace_bytes(int n_points_total, int n_clouds);
+int eyoc_voxelize_batched(eyoc_ctx* ctx, const float* xyz_dev, int stride, const int64_t* point_offsets, int n_clouds,
+                          int n_points, float voxel_size, int batch_base, int32_t* sel_dev, int32_t* coords_dev,
+                          float* xyz_out_dev, int64_t* voxel_offsets, void* workspace_dev, size_t workspace_bytes,
+                          void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * one sparse convolution layer (unit tests, profiling)
  *   replaces: one MinkowskiConvolution / MinkowskiConvolutionTranspose forward with the batch norm
  *             that follows it folded in, plus the residual add / ReLU / concat write around it
