@@ -202,14 +202,28 @@ struct eyoc_maps {
   // from the octree (spconv_st.hip build_local_rulebook_derived) / from the compact [8][n] table up8[l] (derive.h) and leaves the
   // [27][n] tables UNWRITTEN (their memory stays reserved).  eyoc::maps_ensure_table fills one on first use: the accessors
   // (eyoc_maps_table, _copy_table, _info), a forward whose layer falls back to a gathering kernel, a build whose records overflowed.
+  // Set only by maps_ensure_table, next to the record of s1_ev / up_ev below.
   bool s1_ready[EYOC_MAX_LEVELS] = {true, true, true, true};
   bool up_ready[EYOC_MAX_LEVELS] = {true, true, true, true};
   int32_t* up8[EYOC_MAX_LEVELS] = {nullptr, nullptr, nullptr, nullptr};
+  // Cross-stream order of the items filled on demand (S1 level 0, UP per level, table[0]): the fill goes out on whichever stream asked
+  // first, so each item gets an event, created and recorded by its fill.  Every reader goes through maps_ensure_table /
+  // maps_build_table0, which make the reader's stream wait for that event; a build that fills nothing creates none.  The ready flags
+  // above and table0_built are only set there, next to the event record.  The destructor waits for pending fills (eyoc_maps_free).
+  hipEvent_t s1_ev[EYOC_MAX_LEVELS] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t up_ev[EYOC_MAX_LEVELS] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t table0_ev = nullptr;
+  eyoc_maps() = default;
+  eyoc_maps(const eyoc_maps&) = delete;
+  eyoc_maps& operator=(const eyoc_maps&) = delete;
+  ~eyoc_maps();
 };
 
 namespace eyoc {
+// builds table[0] on `st` on first use; afterwards makes `st` wait for that build
 int maps_build_table0(eyoc_maps* maps, hipStream_t st);
-// fills a lazily skipped [27][n] table (kind: EYOC_MAP_S1 / EYOC_MAP_UP; anything else is always there) on `st`; no-op when ready
+// fills a lazily skipped [27][n] table (kind: EYOC_MAP_S1 / EYOC_MAP_UP; anything else is always there) on `st`; when it was filled
+// before, `st` waits for that fill instead.  Every reader of nbr_s1[0], nbr_up[l] comes through here.
 int maps_ensure_table(eyoc_maps* maps, int kind, int level, hipStream_t st);
 size_t sort_rows64_tmp_bytes(int n);
 int sort_rows_by_key64(void* tmp, size_t tmp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out, const int* vals_in,

@@ -718,6 +718,25 @@ unsigned int table_capacity(int n) {
   return cap;
 }
 
+// a table's device array without any fill or wait (NULL: no such table)
+const int32_t* table_ptr(const eyoc_maps* maps, int kind, int level) {
+  if (!maps || level < 0 || level >= maps->n_levels) return nullptr;
+  switch (kind) {
+    case EYOC_MAP_S1: return maps->nbr_s1[level];
+    case EYOC_MAP_DOWN: return level + 1 < maps->n_levels ? maps->nbr_down[level] : nullptr;
+    case EYOC_MAP_UP: return level + 1 < maps->n_levels ? maps->nbr_up[level] : nullptr;
+    default: return nullptr;
+  }
+}
+
+// the fill event of a [27][n] table that may be filled on demand (S1 / UP below the coarsest level); NULL for every other table
+hipEvent_t* fill_event(eyoc_maps* m, int kind, int level) {
+  if (!m || level < 0 || level + 1 >= m->n_levels) return nullptr;      // the coarsest level's table is always built
+  if (kind == EYOC_MAP_S1) return &m->s1_ev[level];
+  if (kind == EYOC_MAP_UP) return &m->up_ev[level];
+  return nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1263,7 +1282,7 @@ int eyoc_voxelize_batched(eyoc_ctx* ctx, const float* xyz_dev, int stride, const
 }
 
 int eyoc_maps_free(eyoc_maps* maps) {
-  delete maps;
+  delete maps;   // (~eyoc_maps waits for fills still pending on other streams)
   return EYOC_OK;
 }
 
@@ -1278,21 +1297,18 @@ const int32_t* eyoc_maps_coords(const eyoc_maps* maps, int level) {
 }
 
 const int32_t* eyoc_maps_table(const eyoc_maps* maps, int kind, int level) {
-  if (!maps || level < 0 || level >= maps->n_levels) return nullptr;
-  // a table the build skipped (lazy tables) is filled now and waited for: the pointer is valid for any stream.  On the NULL stream -
-  // eyoc_maps_build synchronised its own stream before it returned, so everything the fill reads is complete, and the stream the
-  // maps were built on may be gone by now (a torch side stream)
-  if ((kind == EYOC_MAP_S1 && !maps->s1_ready[level]) || (kind == EYOC_MAP_UP && level + 1 < maps->n_levels && !maps->up_ready[level])) {
-    eyoc_maps* mm = const_cast<eyoc_maps*>(maps);
-    if (maps_ensure_table(mm, kind, level, (hipStream_t)nullptr) != EYOC_OK) return nullptr;
-    if (hipStreamSynchronize((hipStream_t)nullptr) != hipSuccess) return nullptr;
+  const int32_t* t = table_ptr(maps, kind, level);
+  if (!t) return nullptr;
+  // a raw pointer is read on any stream, later: a table filled on demand - now (a table the build skipped) or earlier, on whatever stream
+  // asked first - is waited for on the host.  A fill that happens here goes on the NULL stream: eyoc_maps_build synchronised its own
+  // stream after everything the fill reads, and the stream the maps were built on may be gone by now (a torch side stream)
+  eyoc_maps* mm = const_cast<eyoc_maps*>(maps);
+  if (hipEvent_t* ev = fill_event(mm, kind, level)) {
+    if ((kind == EYOC_MAP_S1 ? !maps->s1_ready[level] : !maps->up_ready[level]) && maps_ensure_table(mm, kind, level, (hipStream_t)nullptr) != EYOC_OK)
+      return nullptr;
+    if (*ev && hipEventSynchronize(*ev) != hipSuccess) return nullptr;
   }
-  switch (kind) {
-    case EYOC_MAP_S1: return maps->nbr_s1[level];
-    case EYOC_MAP_DOWN: return level + 1 < maps->n_levels ? maps->nbr_down[level] : nullptr;
-    case EYOC_MAP_UP: return level + 1 < maps->n_levels ? maps->nbr_up[level] : nullptr;
-    default: return nullptr;
-  }
+  return t;
 }
 
 int eyoc_maps_copy_coords(const eyoc_maps* maps, int level, int32_t* out_dev, void* stream) {
@@ -1303,8 +1319,10 @@ int eyoc_maps_copy_coords(const eyoc_maps* maps, int level, int32_t* out_dev, vo
 }
 
 int eyoc_maps_copy_table(const eyoc_maps* maps, int kind, int level, int32_t* out_dev, void* stream) {
-  const int32_t* src = eyoc_maps_table(maps, kind, level);
+  const int32_t* src = table_ptr(maps, kind, level);
   EYOC_REQUIRE(src && out_dev, EYOC_ERR_INVALID, "eyoc_maps_copy_table: bad kind %d / level %d or NULL output", kind, level);
+  // stream-ordered: a table filled on demand is filled on `stream` now, or `stream` waits for its earlier fill
+  if (int rc = maps_ensure_table(const_cast<eyoc_maps*>(maps), kind, level, (hipStream_t)stream)) return rc;
   const int n_out = kind == EYOC_MAP_DOWN ? maps->rows[level + 1] : maps->rows[level];
   EYOC_CHECK_HIP(hipMemcpyAsync(out_dev, src, (size_t)n_out * 27 * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return EYOC_OK;
@@ -1312,13 +1330,24 @@ int eyoc_maps_copy_table(const eyoc_maps* maps, int kind, int level, int32_t* ou
 
 }  // extern "C"
 
+// the event of an item filled on demand: created on its first fill and recorded right after it, on the stream that filled it
+static int publish_fill(hipEvent_t& ev, hipStream_t st) {
+  if (!ev) EYOC_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  EYOC_CHECK_HIP(hipEventRecord(ev, st));
+  return EYOC_OK;
+}
+
 int eyoc::maps_ensure_table(eyoc_maps* m, int kind, int level, hipStream_t st) {
-  if (!m || level < 0 || level + 1 >= m->n_levels) return EYOC_OK;      // the coarsest level's table is always built
-  const bool s1 = kind == EYOC_MAP_S1 && !m->s1_ready[level], up = kind == EYOC_MAP_UP && !m->up_ready[level];
-  if (!s1 && !up) return EYOC_OK;
+  hipEvent_t* ev = fill_event(m, kind, level);
+  if (!ev) return EYOC_OK;                                              // built by eyoc_maps_build: nothing to order
+  bool& ready = (kind == EYOC_MAP_S1 ? m->s1_ready : m->up_ready)[level];
+  if (ready) {                                                          // filled before, maybe on another stream
+    if (*ev) EYOC_CHECK_HIP(hipStreamWaitEvent(st, *ev, 0));
+    return EYOC_OK;
+  }
   const int nl = m->rows[level], nc = m->rows[level + 1];
   if (nl > 0) {
-    if (s1)
+    if (kind == EYOC_MAP_S1)
       hipLaunchKernelGGL((k_derive_fine<true, 0>), dim3(cdiv(nl, 256)), dim3(256), 0, st, m->coords[level], nl, level, m->parent[level],
                          m->children[level], m->nbr_s1[level + 1], nc, m->nbr_s1[level], (int32_t*)nullptr, (unsigned int*)nullptr,
                          (int*)nullptr, 0u, -1);
@@ -1328,13 +1357,17 @@ int eyoc::maps_ensure_table(eyoc_maps* m, int kind, int level, hipStream_t st) {
                          (int*)nullptr, 0u, -1);
     EYOC_CHECK_HIP(hipGetLastError());
   }
-  (s1 ? m->s1_ready : m->up_ready)[level] = true;
+  if (int rc = publish_fill(*ev, st)) return rc;
+  ready = true;
   return EYOC_OK;
 }
 
-// level-0 hash table on demand (only the hash-probing first-convolution fallback reads it)
+// level-0 hash table on demand (only the hash-probing first-convolution fallback, the window gather and eyoc_maps_info read it)
 int eyoc::maps_build_table0(eyoc_maps* m, hipStream_t st) {
-  if (m->table0_built) return EYOC_OK;
+  if (m->table0_built) {                                                // built before, maybe on another stream
+    if (m->table0_ev) EYOC_CHECK_HIP(hipStreamWaitEvent(st, m->table0_ev, 0));
+    return EYOC_OK;
+  }
   HashTable& t = m->table[0];
   const size_t cap = (size_t)t.mask + 1;
   EYOC_CHECK_HIP(hipMemsetAsync(t.keys, 0xFF, cap * 8, st));
@@ -1342,8 +1375,18 @@ int eyoc::maps_build_table0(eyoc_maps* m, hipStream_t st) {
   hipLaunchKernelGGL(k_insert, dim3(cdiv(m->rows[0], 256)), dim3(256), 0, st, m->coords[0], m->rows[0], 1, t, (int*)nullptr,
                      (int*)nullptr /* no range errors: the rows passed eyoc_maps_build */);
   EYOC_CHECK_HIP(hipGetLastError());
+  if (int rc = publish_fill(m->table0_ev, st)) return rc;
   m->table0_built = true;
   return EYOC_OK;
+}
+
+eyoc_maps::~eyoc_maps() {
+  // a fill still pending on some stream writes into the workspace, which the caller may reuse once the maps are freed
+  for (hipEvent_t* ev : {&table0_ev, s1_ev + 0, s1_ev + 1, s1_ev + 2, s1_ev + 3, up_ev + 0, up_ev + 1, up_ev + 2, up_ev + 3})
+    if (*ev) {
+      (void)hipEventSynchronize(*ev);
+      (void)hipEventDestroy(*ev);
+    }
 }
 
 extern "C" {

@@ -242,7 +242,8 @@ class RegistrationPipeline:
         """Build the coordinate maps of ``batch`` NOW, on a side stream: they only depend on the coordinates, so a
         serving loop builds the next batch's maps (hash / sort / rulebook kernels, latency- and atomics-bound) while the
         previous batch is still in its RANSAC (VALU-bound) on the main stream.  Returns the handle ``register(...,
-        maps=)`` takes; keep it alive until that step's results were read.  ``after``: an event the side stream waits for
+        maps=)`` takes; it may be dropped right after the step was enqueued (the maps' workspace is recorded on every stream that
+        reads it, ``CoordinateManager._reading``).  ``after``: an event the side stream waits for
         first - ``self.matched`` (recorded by ``register`` when its forward and matching are enqueued) puts the build
         beside that step's RANSAC instead of beside whatever the main stream happens to run at enqueue time (the forward:
         both want LDS and the atomics path, and the forward's kernels slow down by ~10 %)."""

@@ -273,6 +273,7 @@ class ResUNet2(nn.Module):
         lib = _lib.load()
         cm = x.coordinate_manager
         maps = cm.maps(-1)        # automatic internal order (Z-order from 8192 rows); in and out stay in the caller's rows
+        cm._reading()             # the forward reads the maps on this stream
         out = torch.empty((len(x), self.out_channels), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             ws = _lib.workspace(lib.eyoc_model_workspace_bytes(self._handle, maps), dev)

@@ -38,6 +38,7 @@ class CoordinateManager:
         self._ws = None
         self._maps_caller = None      # a second set in the caller's row order, built only if an accessor needs one
         self._ws_caller = None
+        self._readers = set()         # raw handles of the streams recorded on the workspaces (``_reading``)
 
     @property
     def device(self):
@@ -53,6 +54,23 @@ class CoordinateManager:
                                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), int(order),
                                                    C.byref(h)), "eyoc_maps_build")
         return h, ws
+
+    def _reading(self):
+        """Ties the maps' workspaces to the current stream before work that reads the maps is enqueued on it (``record_stream``): the
+        caching allocator then hands a workspace out again only after that stream's work at the time of this manager's death has
+        finished - a build on the stream the maps were built on (``prepare_maps``' side stream) may otherwise get the block while a
+        forward or a fill on another stream still reads or writes it.  Once per stream and manager (a set lookup after the first)."""
+        try:
+            h = torch._C._cuda_getCurrentRawStream(self.device.index)
+        except AttributeError:                         # (a torch without the raw getter)
+            h = torch.cuda.current_stream(self.device).cuda_stream
+        if h in self._readers:
+            return
+        s = torch.cuda.current_stream(self.device)
+        for ws in (self._ws, self._ws_caller):
+            if ws is not None:
+                ws.record_stream(s)
+        self._readers.add(h)
 
     def maps(self, order: int = 0):
         """The device-side maps, built on first use.  ``order``: internal row order of a build that happens now -
@@ -71,6 +89,7 @@ class CoordinateManager:
             return self._maps
         if self._maps_caller is None:
             self._maps_caller, self._ws_caller = self._build(0)
+            self._readers.clear()                      # the streams recorded so far are not on this workspace yet
         return self._maps_caller
 
     def rows(self, level: int) -> int:
@@ -82,6 +101,7 @@ class CoordinateManager:
         m = self.maps() if internal else self._caller_maps()
         n = self.rows(level)
         out = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+        self._reading()
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().eyoc_maps_copy_coords(m, level, _lib.ptr(out), _lib.stream_ptr()), "eyoc_maps_copy_coords")
         return out
@@ -92,6 +112,7 @@ class CoordinateManager:
         m = self.maps() if internal else self._caller_maps()
         n_out = {0: self.rows(level), 1: self.rows(level + 1), 2: self.rows(level)}[kind]
         out = torch.empty((27, n_out), dtype=torch.int32, device=self.device)
+        self._reading()
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().eyoc_maps_copy_table(m, kind, level, _lib.ptr(out), _lib.stream_ptr()), "eyoc_maps_copy_table")
         return out
@@ -105,6 +126,7 @@ class CoordinateManager:
         ptr = _lib.load().eyoc_maps_table(m, kind, level)
         if not ptr or n_out == 0:
             return self.table(kind, level, internal)
+        self._reading()                                # the view is read on the current stream
         return torch.as_tensor(_DeviceArray(int(ptr), (27, n_out), self), device=self.device)
 
     def row_order(self) -> torch.Tensor | None:
@@ -115,6 +137,7 @@ class CoordinateManager:
         if not lib.eyoc_maps_row_order(self.maps()):
             return None
         out = torch.empty((self.rows(0),), dtype=torch.int32, device=self.device)
+        self._reading()
         with torch.cuda.device(self.device):
             _lib.check(lib.eyoc_maps_copy_row_order(self.maps(), _lib.ptr(out), _lib.stream_ptr()), "eyoc_maps_copy_row_order")
         return out
@@ -123,14 +146,17 @@ class CoordinateManager:
         """Copy of the row order ``int32 [rows(level)]`` the transposed convolutions tile their outputs in."""
         m = self.maps() if internal else self._caller_maps()
         out = torch.empty((self.rows(level),), dtype=torch.int32, device=self.device)
+        self._reading()
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().eyoc_maps_copy_up_order(m, level, _lib.ptr(out), _lib.stream_ptr()), "eyoc_maps_copy_up_order")
         return out
 
     def info(self, conv1_kernel_size: int = 0) -> dict:
         info = _lib.MapsInfo()
+        m = self.maps()
+        self._reading()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().eyoc_maps_info(_lib.ctx(self.device.index), self.maps(), conv1_kernel_size,
+            _lib.check(_lib.load().eyoc_maps_info(_lib.ctx(self.device.index), m, conv1_kernel_size,
                                                   _lib.stream_ptr(), C.byref(info)), "eyoc_maps_info")
         L = info.n_levels
         return {"rows": list(info.rows[:L]), "pairs_s1": list(info.pairs_s1[:L]),

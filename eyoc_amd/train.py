@@ -169,12 +169,14 @@ def gather_window(cm, feats: torch.Tensor, ks: int, internal: bool = False) -> t
     n, cin = feats.shape
     out = torch.empty((n, ks ** 3 * cin), dtype=torch.float32, device=feats.device)
     lib = _lib.load()
+    m = cm.maps() if internal else cm._caller_maps()
+    cm._reading()
     with _lib.on_device(feats.device):
         if internal:
-            _lib.check(lib.eyoc_maps_gather_window_internal(_lib.ctx(feats.device.index), cm.maps(), int(ks), _lib.ptr(feats.contiguous()), cin,
+            _lib.check(lib.eyoc_maps_gather_window_internal(_lib.ctx(feats.device.index), m, int(ks), _lib.ptr(feats.contiguous()), cin,
                                                             _lib.ptr(out), _lib.stream_ptr()), "eyoc_maps_gather_window_internal")
         else:
-            _lib.check(lib.eyoc_maps_gather_window(_lib.ctx(feats.device.index), cm._caller_maps(), int(ks), _lib.ptr(feats.contiguous()), cin,
+            _lib.check(lib.eyoc_maps_gather_window(_lib.ctx(feats.device.index), m, int(ks), _lib.ptr(feats.contiguous()), cin,
                                                    _lib.ptr(out), _lib.stream_ptr()), "eyoc_maps_gather_window")
     return out
 

@@ -136,10 +136,20 @@ const int32_t* eyoc_maps_row_order(const eyoc_maps* maps);
 /* stream-ordered copy of the same array (the identity when the caller's order was kept); out_dev: int32 [rows[0]] */
 int eyoc_maps_copy_row_order(const eyoc_maps* maps, int32_t* out_dev, void* stream);
 int eyoc_maps_rows(const eyoc_maps* maps, int level);
+/* Streams.  A maps object may be read on any stream, not only the one it was built on: everything the build writes is complete when
+ * eyoc_maps_build returns, and what is filled later on demand (lazy tables, the level-0 hash table) is filled on the stream of the
+ * first call that needs it, which records an event; every later reader - eyoc_maps_table / _copy_table / _info, a forward, a window
+ * gather - waits for that event, on the host (eyoc_maps_table) or on its own stream (everything else).  The maps' workspace is the
+ * caller's: it must not be reused before the work of every stream that read the maps has finished (torch callers: record_stream).
+ * eyoc_maps_free waits for fills still pending and may be called while readers are in flight.  Like its ctx, a maps object is
+ * single-threaded: one host thread at a time. */
 /* device pointers into the workspace; valid while the maps object lives */
 const int32_t* eyoc_maps_coords(const eyoc_maps* maps, int level);             /* [rows,4]        */
-const int32_t* eyoc_maps_table(const eyoc_maps* maps, int kind, int level);    /* [27][n_out]; a lazily skipped table is filled first (NULL stream, waited for) */
-/* stream-ordered device-to-device copies of the same arrays into caller-owned buffers */
+/* [27][n_out]; a table filled on demand is filled first if need be (NULL stream) and waited for on the host: the pointer is valid for
+ * any stream */
+const int32_t* eyoc_maps_table(const eyoc_maps* maps, int kind, int level);
+/* stream-ordered device-to-device copies of the same arrays into caller-owned buffers (a table filled on demand: filled on `stream`, or
+ * `stream` waits for its earlier fill) */
 int eyoc_maps_copy_coords(const eyoc_maps* maps, int level, int32_t* out_dev, void* stream);
 int eyoc_maps_copy_table(const eyoc_maps* maps, int kind, int level, int32_t* out_dev, void* stream);
 /* counts valid pairs (one reduction per table + a sync); conv1_kernel_size 0 skips pairs_conv1 */
