@@ -62,6 +62,7 @@ PROTOTYPES = {
     "eyoc_maps_build": (_i, [_vp, _vp, _i, _vp, _sz, _vp, C.POINTER(_vp)]),
     "eyoc_maps_build_ordered": (_i, [_vp, _vp, _i, _vp, _sz, _vp, _i, C.POINTER(_vp)]),
     "eyoc_maps_free": (_i, [_vp]),
+    "eyoc_maps_last_fault_batches": (_i, [_vp, _vp, _vp]),
     "eyoc_maps_internal_order": (_i, [_vp, _i]),
     "eyoc_maps_lazy_tables": (_i, [_vp, _i]),
     "eyoc_maps_fused_levels": (_i, [_vp, _i]),
@@ -149,6 +150,7 @@ PROTOTYPES = {
     "eyoc_ransac": (_i, [_vp, _vp, _vp, _vp, _i, C.POINTER(RansacParams), _vp, _vp]),
     "eyoc_maps_select_orders": (_i, [_vp, _i, _i]),
     "eyoc_ransac_select_pruning": (_i, [_vp, _i]),
+    "eyoc_registration_accept_degenerate": (_i, [_vp, _i]),
     "eyoc_ransac_transform_store": (_i, [_vp, _i]),
     "eyoc_ransac_workspace_bytes": (_sz, [_vp, _i, _i, _i, _sz]),
     "eyoc_ransac_batched_ws": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
@@ -234,6 +236,21 @@ def knob(name: str, *values, device=None) -> int:
     if isinstance(device, torch.device):
         device = device.index
     return getattr(load(), name)(ctx(device), *values)
+
+
+def fault_batches(device=None):
+    """``(dup, range)``: the sorted batch indices that made the last map build of the device's ctx fail - duplicate rows after an
+    EYOC_ERR_DUPLICATE, rows out of the key range after an EYOC_ERR_RANGE, both empty otherwise (``eyoc_maps_last_fault_batches``)."""
+    import numpy as np
+    import torch
+    if isinstance(device, torch.device):
+        device = device.index
+    dup, rng = np.zeros(32, np.uint32), np.zeros(32, np.uint32)
+    check(load().eyoc_maps_last_fault_batches(ctx(device), dup.ctypes.data, rng.ctypes.data), "eyoc_maps_last_fault_batches")
+
+    def bits(w):
+        return [int(b) for b in np.flatnonzero(np.unpackbits(w.view(np.uint8), bitorder="little"))]
+    return bits(dup), bits(rng)
 
 
 def stream_ptr():

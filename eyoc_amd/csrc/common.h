@@ -84,6 +84,8 @@ struct eyoc_ctx {
   // SC2-PCR diagnostics (eyoc_sc2pcr_set_shortlist_cap / eyoc_sc2pcr_set_dense_threshold): per ctx, not per process
   int sc2_list_cap = 1024, sc2_dense_x = 0;
   int sc2_legacy = 0;      // eyoc_sc2pcr_select_kernels (sc2pcr.hip): bits select the round-5 forms of three kernels, for A/B tests
+  // eyoc_maps_last_fault_batches: bit b of word b >> 5 = batch index b held a duplicate / out-of-range row in the last build that failed
+  uint32_t fault_dup[32] = {}, fault_range[32] = {};
   // kernel-selection and tiling switches (tests, diagnostics, bench flags).  Per ctx since round 5: they were file-scope statics, so two
   // models in one process - or a test that forgot to restore one - shared kernel selection.  Every entry point reads them from the
   // ctx it was given; the setters (eyoc_spconv_select_*, eyoc_maps_*, eyoc_knn_prefilter, eyoc_ransac_*, eyoc_model_fuse_tail) take the ctx
@@ -110,6 +112,7 @@ struct eyoc_ctx {
     int st_ksplit = 1;                 // eyoc_spconv_st_ksplit
     int ransac_store = 1 << 20;        // eyoc_ransac_transform_store
     int ransac_prune = 2;              // eyoc_ransac_select_pruning: 0 full sweeps, 1 reference pruning, 2 + survivors stop counting once they cannot reach the largest count (round 6)
+    int accept_degenerate = 0;         // eyoc_registration_accept_degenerate: batched RANSAC / SC2-PCR give pairs below their minimum a failed record
   } knobs;
 };
 // the switches of a call: the ctx's, or the defaults where an internal launcher was handed no ctx

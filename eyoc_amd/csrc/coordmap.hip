@@ -33,9 +33,10 @@ __device__ inline void coarse_coord(const int32_t* c, int ts2, int& b, int& x, i
   b = c[0]; x = c[1] & m; y = c[2] & m; z = c[3] & m;
 }
 
-// ts2 == 1: keys of the rows themselves.  err[0] counts out-of-range coordinates.
+// ts2 == 1: keys of the rows themselves.  err[0] counts out-of-range coordinates; range_mask (if any) gets bit b of every batch index
+// b < 1024 that holds one (eyoc_maps_last_fault_batches)
 __global__ void k_insert(const int32_t* __restrict__ coords, int n, int ts2, HashTable t, int* __restrict__ slot_out,
-                         int* __restrict__ err) {
+                         int* __restrict__ err, unsigned int* __restrict__ range_mask = nullptr) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   int b, x, y, z;
@@ -43,6 +44,7 @@ __global__ void k_insert(const int32_t* __restrict__ coords, int n, int ts2, Has
   constexpr int LIM = COORD_BIAS - 16;  // margin: neighbour probes reach +-8 voxels at tensor stride 8
   if (b < 0 || b >= 1024 || x < -LIM || x >= LIM || y < -LIM || y >= LIM || z < -LIM || z >= LIM) {
     if (err) atomicAdd(&err[0], 1);
+    if (range_mask && b >= 0 && b < 1024) atomicOr(&range_mask[b >> 5], 1u << (b & 31));
     if (slot_out) slot_out[i] = 0;
     return;
   }
@@ -226,8 +228,10 @@ __global__ void k_flag_sorted(const int32_t* __restrict__ coords, int n, int ts2
 // adjacent rows at every level), so that eyoc_maps_build reads them with ONE synchronisation instead of one per level
 // counts[0]: rows that do not fit the speculated key width (+-2^kbits, batch < 2^bbits); counts[EYOC_MAX_LEVELS + 2 / + 3]: the
 // largest |coordinate| / batch index (the next build's speculation)
+// masks [32] + [32] behind the counts: bit b = batch index b < 1024 holds a duplicate / an out-of-range row (set by faulty rows only)
 __global__ __launch_bounds__(256) void k_count_levels(const int32_t* __restrict__ coords, int n, int kbits, int bbits,
-                                                      int* __restrict__ counts /* [EYOC_MAX_LEVELS + 4] */) {
+                                                      int* __restrict__ counts /* [EYOC_MAX_LEVELS + 4] */,
+                                                      unsigned int* __restrict__ masks /* dup [32], range [32] */) {
   // grid-stride: a few thousand atomics on the counters in all (one per level and workgroup), not one per wave of 64 rows -
   // 180 k atomics on three words cost 2 ms on the 3.8 M-row batch
   __shared__ int part[EYOC_MAX_LEVELS + 2];
@@ -244,8 +248,15 @@ __global__ __launch_bounds__(256) void k_count_levels(const int32_t* __restrict_
     amax = max(amax, max(max(c.y < 0 ? ~c.y : c.y, c.z < 0 ? ~c.z : c.z), c.w < 0 ? ~c.w : c.w));   // v fits iff -2^k <= v < 2^k iff (v < 0 ? ~v : v) < 2^k
     bmax = max(bmax, c.x);
     // validation here too: the build must not run its table kernels on keys outside the supported range
-    if (c.x < 0 || c.x >= 1024 || c.y < -LIM || c.y >= LIM || c.z < -LIM || c.z >= LIM || c.w < -LIM || c.w >= LIM) ++cnt[EYOC_MAX_LEVELS];
-    if (i > 0 && c.x == q.x && c.y == q.y && c.z == q.z && c.w == q.w) ++cnt[EYOC_MAX_LEVELS + 1];
+    const bool fits = c.x >= 0 && c.x < 1024;
+    if (!fits || c.y < -LIM || c.y >= LIM || c.z < -LIM || c.z >= LIM || c.w < -LIM || c.w >= LIM) {
+      ++cnt[EYOC_MAX_LEVELS];
+      if (fits) atomicOr(&masks[32 + (c.x >> 5)], 1u << (c.x & 31));
+    }
+    if (i > 0 && c.x == q.x && c.y == q.y && c.z == q.z && c.w == q.w) {
+      ++cnt[EYOC_MAX_LEVELS + 1];
+      if (fits) atomicOr(&masks[c.x >> 5], 1u << (c.x & 31));
+    }
 #pragma unroll
     for (int l = 1; l < EYOC_MAX_LEVELS; ++l) {
       const int m = ~((1 << l) - 1);
@@ -574,7 +585,8 @@ __global__ __launch_bounds__(256) void k_cloud_offsets(const int* __restrict__ f
 // Two rows landing in the same child slot of the same block have identical coordinates: `dup` (level 0 only) counts
 // them - the duplicate check of the input needs no hash table of its own.
 __global__ void k_children(const int* __restrict__ slot, const int* __restrict__ vals, const int32_t* __restrict__ coords,
-                           int n, int sh, int32_t* __restrict__ parent, int32_t* __restrict__ children, int* __restrict__ dup) {
+                           int n, int sh, int32_t* __restrict__ parent, int32_t* __restrict__ children, int* __restrict__ dup,
+                           unsigned int* __restrict__ dup_mask = nullptr) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int4 c = reinterpret_cast<const int4*>(coords)[i];
@@ -582,7 +594,10 @@ __global__ void k_children(const int* __restrict__ slot, const int* __restrict__
   const int cs = ((c.y >> sh) & 1) | (((c.z >> sh) & 1) << 1) | (((c.w >> sh) & 1) << 2);
   parent[i] = p;
   if (dup) {
-    if (atomicCAS(&children[(size_t)p * 8 + cs], -1, i) != -1) atomicAdd(dup, 1);
+    if (atomicCAS(&children[(size_t)p * 8 + cs], -1, i) != -1) {
+      atomicAdd(dup, 1);
+      if (dup_mask) atomicOr(&dup_mask[c.x >> 5], 1u << (c.x & 31));   // in range: the level's k_insert passed
+    }
   } else {
     children[(size_t)p * 8 + cs] = i;
   }
@@ -737,6 +752,13 @@ hipEvent_t* fill_event(eyoc_maps* m, int kind, int level) {
   return nullptr;
 }
 
+// a failed build's fault masks (dup [32], range [32], read back with its error counts) -> the ctx, for eyoc_maps_last_fault_batches:
+// the mask of the kind the build fails with, only (the caller-order path stops at the range check before it looks for duplicates)
+void keep_fault_masks(eyoc_ctx* ctx, const int* h, int code) {
+  if (code == EYOC_ERR_DUPLICATE) memcpy(ctx->fault_dup, h, 32 * sizeof(uint32_t));
+  if (code == EYOC_ERR_RANGE) memcpy(ctx->fault_range, h + 32, 32 * sizeof(uint32_t));
+}
+
 }  // namespace
 
 extern "C" {
@@ -770,6 +792,10 @@ int eyoc_maps_build(eyoc_ctx* ctx, const int32_t* coords_dev, int n, void* ws, s
 
 int eyoc_maps_build_ordered(eyoc_ctx* ctx, const int32_t* coords_dev, int n, void* ws, size_t ws_bytes, void* stream,
                             int order, eyoc_maps** out) {
+  if (ctx) {                    // eyoc_maps_last_fault_batches: this build's masks, whatever it returns
+    memset(ctx->fault_dup, 0, sizeof(ctx->fault_dup));
+    memset(ctx->fault_range, 0, sizeof(ctx->fault_range));
+  }
   EYOC_REQUIRE(ctx && out && ws, EYOC_ERR_INVALID, "eyoc_maps_build: NULL argument");
   EYOC_REQUIRE(order >= -1 && order <= 1, EYOC_ERR_INVALID, "eyoc_maps_build_ordered: order %d", order);
   EYOC_REQUIRE(n > 0 && coords_dev, EYOC_ERR_INVALID, "eyoc_maps_build: empty coordinate set (n=%d)", n);
@@ -780,7 +806,8 @@ int eyoc_maps_build_ordered(eyoc_ctx* ctx, const int32_t* coords_dev, int n, voi
   Carver cv(ws, ws_bytes);
   eyoc_maps* m = new eyoc_maps();
   m->n_levels = EYOC_MAX_LEVELS;
-  int* counters = cv.take<int>(64);       // [0] range errors, [1] duplicates, [2+l] coarse totals
+  int* counters = cv.take<int>(128);      // [0] range errors, [1] duplicates, [2+l] coarse totals; [64, 128): the fault masks
+  unsigned int* fault_masks = (unsigned int*)(counters + 64);   // dup [32], range [32] (eyoc_maps_last_fault_batches)
   int* slot = cv.take<int>(n);
   int* flag = cv.take<int>(n);
   int* partial = cv.take<int>(n / SCAN_TILE + 2);
@@ -795,7 +822,7 @@ int eyoc_maps_build_ordered(eyoc_ctx* ctx, const int32_t* coords_dev, int n, voi
     }                                                                                        \
   } while (0)
 
-  FAIL_HIP(hipMemsetAsync(counters, 0, 64 * sizeof(int), st));
+  FAIL_HIP(hipMemsetAsync(counters, 0, 128 * sizeof(int), st));
   // ---- level 0: the caller's rows, in the caller's order
   m->rows[0] = n;
   m->coords[0] = cv.take<int32_t>((size_t)n * 4);
@@ -820,8 +847,9 @@ int eyoc_maps_build_ordered(eyoc_ctx* ctx, const int32_t* coords_dev, int n, voi
       hipLaunchKernelGGL(k_gather_coords, dim3(cdiv(n, 256)), dim3(256), 0, st, coords_dev, m->row_perm, n, m->coords[0]);
       // every level's row count - and the validation - now, with one read-back
       hipLaunchKernelGGL(k_count_levels, dim3(cdiv(n, 256) < 1024 ? cdiv(n, 256) : 1024), dim3(256), 0, st, m->coords[0], n, kbits, bbits,
-                         counters + 16);
-      FAIL_HIP(hipMemcpyAsync(host + 16, counters + 16, (EYOC_MAX_LEVELS + 4) * sizeof(int), hipMemcpyDeviceToHost, st));
+                         counters + 16, fault_masks);
+      // (the fault masks ride along: host[64, 128))
+      FAIL_HIP(hipMemcpyAsync(host + 16, counters + 16, (128 - 16) * sizeof(int), hipMemcpyDeviceToHost, st));
       FAIL_HIP(hipStreamSynchronize(st));
       if (host[16] == 0) break;                                         // every row fitted the speculated width
       kbits = 17; bbits = 10;
@@ -837,11 +865,13 @@ int eyoc_maps_build_ordered(eyoc_ctx* ctx, const int32_t* coords_dev, int n, voi
     if (host[16 + EYOC_MAX_LEVELS] != 0) {
       set_error("eyoc_maps_build: %d coordinate rows outside the supported key range (|c| < 2^17 - 16, 0 <= batch < 1024)",
                 host[16 + EYOC_MAX_LEVELS]);
+      keep_fault_masks(ctx, host + 64, EYOC_ERR_RANGE);
       delete m;
       return EYOC_ERR_RANGE;
     }
     if (host[16 + EYOC_MAX_LEVELS + 1] != 0) {
       set_error("eyoc_maps_build: %d duplicate coordinate rows (a sparse tensor needs unique coordinates)", host[16 + EYOC_MAX_LEVELS + 1]);
+      keep_fault_masks(ctx, host + 64, EYOC_ERR_DUPLICATE);
       delete m;
       return EYOC_ERR_DUPLICATE;
     }
@@ -909,7 +939,8 @@ int eyoc_maps_build_ordered(eyoc_ctx* ctx, const int32_t* coords_dev, int n, voi
       t.mask = cap - 1;
       FAIL_HIP(hipMemsetAsync(t.keys, 0xFF, (size_t)cap * 8, st));
       FAIL_HIP(hipMemsetAsync(t.vals, 0x7F, (size_t)cap * 4, st));
-      hipLaunchKernelGGL(k_insert, dim3(cdiv(n_src, 256)), dim3(256), 0, st, src, n_src, ts2, t, slot, counters);
+      hipLaunchKernelGGL(k_insert, dim3(cdiv(n_src, 256)), dim3(256), 0, st, src, n_src, ts2, t, slot, counters,
+                         l == 1 ? fault_masks + 32 : (unsigned int*)nullptr);
       hipLaunchKernelGGL(k_flag, dim3(cdiv(n_src, 256)), dim3(256), 0, st, slot, t.vals, n_src, flag, (int*)nullptr);
     }
     hipLaunchKernelGGL(k_scan_partials, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, n_src, partial);
@@ -917,16 +948,23 @@ int eyoc_maps_build_ordered(eyoc_ctx* ctx, const int32_t* coords_dev, int n, voi
     if (zorder) {
       m->rows[l] = pre_rows[l];
     } else {
-    FAIL_HIP(hipMemcpyAsync(host, counters + 2 + l, sizeof(int), hipMemcpyDeviceToHost, st));
-    if (l == 1) FAIL_HIP(hipMemcpyAsync(host + 1, counters, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    FAIL_HIP(hipStreamSynchronize(st));
+    if (l == 1) {   // the level's total, the error counts and the fault masks in one copy (host[128, 256))
+      FAIL_HIP(hipMemcpyAsync(host + 128, counters, 128 * sizeof(int), hipMemcpyDeviceToHost, st));
+      FAIL_HIP(hipStreamSynchronize(st));
+      host[0] = host[128 + 2 + l]; host[1] = host[128]; host[2] = host[128 + 1];
+    } else {
+      FAIL_HIP(hipMemcpyAsync(host, counters + 2 + l, sizeof(int), hipMemcpyDeviceToHost, st));
+      FAIL_HIP(hipStreamSynchronize(st));
+    }
     if (l == 1 && host[1] != 0) {
       set_error("eyoc_maps_build: %d coordinate rows outside the supported key range (|c| < 2^17 - 16, 0 <= batch < 1024)", host[1]);
+      keep_fault_masks(ctx, host + 128 + 64, EYOC_ERR_RANGE);
       delete m;
       return EYOC_ERR_RANGE;
     }
     if (l == 1 && sorted_level && host[2] != 0) {
       set_error("eyoc_maps_build: %d duplicate coordinate rows (a sparse tensor needs unique coordinates)", host[2]);
+      keep_fault_masks(ctx, host + 128 + 64, EYOC_ERR_DUPLICATE);
       delete m;
       return EYOC_ERR_DUPLICATE;
     }
@@ -953,12 +991,15 @@ int eyoc_maps_build_ordered(eyoc_ctx* ctx, const int32_t* coords_dev, int n, voi
                        m->coords[l], t.vals, (int32_t*)nullptr);
     // octree links fine (l-1) <-> coarse (l); same stream, so k_compact's re-labelling is visible
     hipLaunchKernelGGL(k_children, dim3(cdiv(n_src, 256)), dim3(256), 0, st, slot, t.vals, src, n_src, l - 1,
-                       m->parent[l - 1], m->children[l - 1], l == 1 ? counters + 1 : (int*)nullptr);
-    if (l == 1) {
-      FAIL_HIP(hipMemcpyAsync(host, counters + 1, sizeof(int), hipMemcpyDeviceToHost, st));
+                       m->parent[l - 1], m->children[l - 1], l == 1 ? counters + 1 : (int*)nullptr,
+                       l == 1 ? fault_masks : (unsigned int*)nullptr);
+    if (l == 1) {   // the duplicate count and the fault masks in one copy
+      FAIL_HIP(hipMemcpyAsync(host + 128, counters, 128 * sizeof(int), hipMemcpyDeviceToHost, st));
       FAIL_HIP(hipStreamSynchronize(st));
+      host[0] = host[128 + 1];
       if (host[0] != 0) {
         set_error("eyoc_maps_build: %d duplicate coordinate rows (a sparse tensor needs unique coordinates)", host[0]);
+        keep_fault_masks(ctx, host + 128 + 64, EYOC_ERR_DUPLICATE);
         delete m;
         return EYOC_ERR_DUPLICATE;
       }
@@ -1108,11 +1149,13 @@ int eyoc_maps_build_ordered(eyoc_ctx* ctx, const int32_t* coords_dev, int n, voi
     FAIL_HIP(hipStreamSynchronize(st));
     if (host[32] != 0) {
       set_error("eyoc_maps_build: %d coordinate rows outside the supported key range (|c| < 2^17 - 16, 0 <= batch < 1024)", host[32]);
+      keep_fault_masks(ctx, host + 64, EYOC_ERR_RANGE);     // k_count_levels' masks, read back with the level counts
       delete m;
       return EYOC_ERR_RANGE;
     }
     if (host[33] != 0) {
       set_error("eyoc_maps_build: %d duplicate coordinate rows (a sparse tensor needs unique coordinates)", host[33]);
+      keep_fault_masks(ctx, host + 64, EYOC_ERR_DUPLICATE);
       delete m;
       return EYOC_ERR_DUPLICATE;
     }
@@ -1390,6 +1433,13 @@ eyoc_maps::~eyoc_maps() {
 }
 
 extern "C" {
+
+int eyoc_maps_last_fault_batches(const eyoc_ctx* ctx, uint32_t* dup, uint32_t* range) {
+  EYOC_REQUIRE(ctx && dup && range, EYOC_ERR_INVALID, "eyoc_maps_last_fault_batches: NULL argument");
+  memcpy(dup, ctx->fault_dup, sizeof(ctx->fault_dup));
+  memcpy(range, ctx->fault_range, sizeof(ctx->fault_range));
+  return EYOC_OK;
+}
 
 int eyoc_maps_internal_order(eyoc_ctx* ctx, int mode) {
   if (!ctx) return -1;

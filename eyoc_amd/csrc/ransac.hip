@@ -889,7 +889,68 @@ int ransac_validate(const float* src_dev, const float* tgt_dev, const int64_t* c
   return EYOC_OK;
 }
 
+// degenerate pairs (eyoc_registration_accept_degenerate): their records, written by the call instead of the pipeline of launches
+struct FailedPairs {
+  int n;
+  int idx[64];
+};
+__global__ void k_failed_records(eyoc_ransac_result* __restrict__ results, FailedPairs f) {
+  eyoc_ransac_result* r = results + f.idx[blockIdx.x];
+  const int t = threadIdx.x;
+  if (t < 16) r->T[t] = __builtin_nanf("");
+  if (t == 0) {
+    r->inliers = 0;
+    r->best_hypothesis = -1;
+    r->survivors = 0;
+    r->inlier_rmse = 0.0f;
+  }
+}
+
+// A batch with degenerate pairs (fewer than 4 correspondences, none at all included): every maximal run of the other pairs goes through
+// `run` as a batch of its own with seed + the run's first pair - pair b still samples with seed + b, and the records do not depend on how
+// the pairs are chunked -, the degenerate pairs get the failed record; their rows are never read.  Returns 1 when there is nothing to split.
+template <class Run>
+int ransac_split(eyoc_ctx* ctx, const int32_t* seg_src_host, const int32_t* seg_tgt_host, int n_pairs, const eyoc_ransac_params* p,
+                 eyoc_ransac_result* results_dev, hipStream_t st, Run run) {
+  if (!ctx || !ctx->knobs.accept_degenerate || !seg_src_host || !seg_tgt_host || !p || !results_dev || n_pairs < 1) return 1;
+  bool any = false;
+  for (int b = 0; b < n_pairs; ++b) {
+    const int n = seg_src_host[b + 1] - seg_src_host[b];
+    any |= n >= 0 && n < 4;
+  }
+  if (!any) return 1;
+  FailedPairs f;
+  f.n = 0;
+  for (int b = 0; b < n_pairs;) {
+    const int n = seg_src_host[b + 1] - seg_src_host[b];
+    if (n >= 0 && n < 4) {
+      f.idx[f.n++] = b++;
+      if (f.n == 64) {
+        hipLaunchKernelGGL(k_failed_records, dim3(f.n), dim3(64), 0, st, results_dev, f);
+        f.n = 0;
+      }
+      continue;
+    }
+    int e = b + 1;
+    while (e < n_pairs && !(seg_src_host[e + 1] - seg_src_host[e] >= 0 && seg_src_host[e + 1] - seg_src_host[e] < 4)) ++e;
+    eyoc_ransac_params q = *p;
+    q.seed = p->seed + (unsigned)b;
+    if (int rc = run(seg_src_host + b, seg_tgt_host + b, e - b, &q, results_dev + b)) return rc;
+    b = e;
+  }
+  if (f.n) hipLaunchKernelGGL(k_failed_records, dim3(f.n), dim3(64), 0, st, results_dev, f);
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
 }  // namespace
+
+extern "C" int eyoc_registration_accept_degenerate(eyoc_ctx* ctx, int on) {
+  if (!ctx) return -1;
+  const int prev = ctx->knobs.accept_degenerate;
+  if (on == 0 || on == 1) ctx->knobs.accept_degenerate = on;
+  return prev;
+}
 
 extern "C" int eyoc_ransac_transform_store(eyoc_ctx* ctx, int survivors) {
   if (!ctx) return -1;
@@ -918,8 +979,14 @@ extern "C" int eyoc_ransac_batched_ws(eyoc_ctx* ctx, const float* src_dev, const
                                       size_t workspace_bytes, void* stream) {
   EYOC_REQUIRE(ctx && workspace_dev, EYOC_ERR_INVALID, "eyoc_ransac_batched_ws: NULL argument");
   EYOC_REQUIRE(((uintptr_t)workspace_dev & 255) == 0, EYOC_ERR_INVALID, "eyoc_ransac_batched_ws: workspace must be 256-byte aligned");
+  int rc = ransac_split(ctx, seg_src_host, seg_tgt_host, n_pairs, p, results_dev, (hipStream_t)stream,
+                        [&](const int32_t* ss, const int32_t* stt, int np, const eyoc_ransac_params* q, eyoc_ransac_result* r) {
+                          return eyoc_ransac_batched_ws(ctx, src_dev, tgt_dev, corr_tgt_dev, ss, stt, np, q, r, workspace_dev,
+                                                        workspace_bytes, stream);
+                        });
+  if (rc <= 0) return rc;
   int max_n = 0;
-  int rc = ransac_validate(src_dev, tgt_dev, corr_tgt_dev, seg_src_host, seg_tgt_host, n_pairs, p, results_dev, &max_n);
+  rc = ransac_validate(src_dev, tgt_dev, corr_tgt_dev, seg_src_host, seg_tgt_host, n_pairs, p, results_dev, &max_n);
   if (rc) return rc;
   const int total = seg_src_host[n_pairs];
   const int store = ctx->knobs.ransac_store;
@@ -938,8 +1005,13 @@ extern "C" int eyoc_ransac_batched(eyoc_ctx* ctx, const float* src_dev, const fl
                                    const int32_t* seg_src_host, const int32_t* seg_tgt_host, int n_pairs,
                                    const eyoc_ransac_params* p, eyoc_ransac_result* results_dev, void* stream) {
   EYOC_REQUIRE(ctx, EYOC_ERR_INVALID, "eyoc_ransac_batched: NULL argument");
+  int rc = ransac_split(ctx, seg_src_host, seg_tgt_host, n_pairs, p, results_dev, (hipStream_t)stream,
+                        [&](const int32_t* ss, const int32_t* stt, int np, const eyoc_ransac_params* q, eyoc_ransac_result* r) {
+                          return eyoc_ransac_batched(ctx, src_dev, tgt_dev, corr_tgt_dev, ss, stt, np, q, r, stream);
+                        });
+  if (rc <= 0) return rc;
   int max_n = 0;
-  int rc = ransac_validate(src_dev, tgt_dev, corr_tgt_dev, seg_src_host, seg_tgt_host, n_pairs, p, results_dev, &max_n);
+  rc = ransac_validate(src_dev, tgt_dev, corr_tgt_dev, seg_src_host, seg_tgt_host, n_pairs, p, results_dev, &max_n);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int total = seg_src_host[n_pairs];

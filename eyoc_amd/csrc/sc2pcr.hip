@@ -356,7 +356,7 @@ __device__ __forceinline__ void d_sc_spmv(const float* __restrict__ src, const f
 #pragma unroll
       for (int u = 0; u < SPMV_AHEAD; ++u) {
         const int kc = max(min(k[r] + 64 * u, e[r] - 1), 0);   // inside the row (an empty row reads a neighbour's entry; nothing is added)
-        c[r][u] = col_h[kc];
+        c[r][u] = min((int)col_h[kc], n - 1);              // an empty matrix: col_h[0] was never written - keep the gather inside x
         v[r][u] = val_h[kc];
       }
 #pragma unroll
@@ -1250,6 +1250,17 @@ Plan make_plan(int n, const eyoc_sc2pcr_params* p) {
   return pl;
 }
 
+// degenerate pairs (eyoc_registration_accept_degenerate): T = NaN, seedwise fitness 0, written by the call; their rows are never read
+struct FailedPairs {
+  int n;
+  int idx[64];
+};
+__global__ void k_failed_pairs(float* __restrict__ T, float* __restrict__ fitness, int fitness_stride, FailedPairs f) {
+  const int b = f.idx[blockIdx.x];
+  if (threadIdx.x < 16) T[16 * (size_t)b + threadIdx.x] = __builtin_nanf("");
+  for (int k = threadIdx.x; k < fitness_stride; k += blockDim.x) fitness[(size_t)b * fitness_stride + k] = 0.0f;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1409,6 +1420,34 @@ int eyoc_sc2pcr_batched(eyoc_ctx* ctx, const float* src_dev, const float* tgt_de
   EYOC_REQUIRE(ctx && src_dev && tgt_dev && seg_host && params && T_dev && fitness_dev && ws, EYOC_ERR_INVALID,
                "eyoc_sc2pcr_batched: NULL argument");
   EYOC_REQUIRE(n_pairs >= 1, EYOC_ERR_INVALID, "eyoc_sc2pcr_batched: n_pairs %d", n_pairs);
+  const auto degenerate = [&](int b) { const int n = seg_host[b + 1] - seg_host[b]; return n >= 0 && n < 8; };
+  bool any = false;
+  for (int b = 0; b < n_pairs && ctx->knobs.accept_degenerate; ++b) any |= degenerate(b);
+  if (any) {
+    // every maximal run of the other pairs as a call of its own (the results are per pair), the degenerate pairs their failed output
+    hipStream_t st = (hipStream_t)stream;
+    FailedPairs f;
+    f.n = 0;
+    for (int b = 0; b < n_pairs;) {
+      if (degenerate(b)) {
+        f.idx[f.n++] = b++;
+        if (f.n == 64) {
+          hipLaunchKernelGGL(k_failed_pairs, dim3(f.n), dim3(64), 0, st, T_dev, fitness_dev, fitness_stride, f);
+          f.n = 0;
+        }
+        continue;
+      }
+      int e = b + 1;
+      while (e < n_pairs && !degenerate(e)) ++e;
+      int rc = eyoc_sc2pcr_batched(ctx, src_dev, tgt_dev, seg_host + b, e - b, params + b, T_dev + 16 * (size_t)b,
+                                   fitness_dev + (size_t)b * fitness_stride, fitness_stride, ws, ws_bytes, stream);
+      if (rc) return rc;
+      b = e;
+    }
+    if (f.n) hipLaunchKernelGGL(k_failed_pairs, dim3(f.n), dim3(64), 0, st, T_dev, fitness_dev, fitness_stride, f);
+    EYOC_CHECK_HIP(hipGetLastError());
+    return EYOC_OK;
+  }
   size_t slice = 0;
   for (int b = 0; b < n_pairs; ++b) {
     const int n = seg_host[b + 1] - seg_host[b];

@@ -39,6 +39,15 @@ class RegistrationConfig:
     sc2pcr: dict = field(default_factory=lambda: dict(
         inlier_threshold=0.6, num_node=8000, use_mutual=False, d_thre=0.1, num_iterations=20, ratio=0.2,
         nms_radius=0.6, max_points=8000, k1=30, k2=20))   # scripts/SC2_PCR/config_json/config_KITTI.json
+    # what a split16 overflow of the pipeline costs (automatic arithmetic only): False - the model switches to fp32 MFMAs for good and
+    # the step runs again (a third of the throughput from then on); True - that step alone runs again in fp32, its pairs carry
+    # RETRIED_FP32 in ``status``, and the next step is split16 again
+    fp32_retry_per_step: bool = False
+
+
+# ``RegistrationResult.status`` / ``PendingStep.status`` bit: the pair's step overflowed split16 and was registered again in fp32
+# (``fp32_retry_per_step``); the records are those of the fp32 run
+RETRIED_FP32 = 1 << 4
 
 
 _SC2_KEYS = ("inlier_threshold", "num_node", "use_mutual", "d_thre", "num_iterations", "ratio", "nms_radius", "max_points",
@@ -166,16 +175,26 @@ class DeviceBatch:
 class PendingStep:
     """A step whose read-back was enqueued with it (``RegistrationPipeline.enqueue``)."""
 
-    def __init__(self, host, words, done, device_result, keep=None):
+    def __init__(self, host, words, done, device_result, keep=None, retry=None):
         self.host, self.words, self.done, self.device_result = host, words, done, device_result
         self.keep = keep          # tensors another stream still reads (the features under ``tail_stream``): released by ``wait``
+        self.retry = retry        # fp32_retry_per_step: (pipeline, batch, seed, maps, slot) to run the step again in fp32 after an overflow
+        self.status = None        # per-pair status bits (int64 [P]), set by ``wait``
 
     def wait(self):
         """-> (result records ``uint8 [P, 84]`` in pinned host memory - valid until the slot is enqueued again -, whether this
-        step's split16 forward overflowed).  Waits for this step only."""
+        step's split16 forward overflowed).  Waits for this step only.  Sets ``status``; under ``fp32_retry_per_step`` an overflowed step
+        is run again in fp32 right here (its records replace the split16 ones, every pair is flagged RETRIED_FP32)."""
         self.done.synchronize()
         self.keep = None
-        return self.host, bool(int(self.words[0]) != 0)
+        overflow = bool(int(self.words[0]) != 0)
+        self.status = np.zeros(self.host.shape[0], np.int64)
+        if overflow and self.retry is not None:
+            pipe, batch, seed, maps, slot = self.retry
+            self.host.copy_(pipe._retry_fp32(batch, seed, maps, True, slot).cpu())
+            self.status[:] = RETRIED_FP32
+        self.retry = None
+        return self.host, overflow
 
 
 class RegistrationPipeline:
@@ -189,6 +208,7 @@ class RegistrationPipeline:
         self.timing = False
         self.slot = 0          # which of two event sets the next ``register`` records into (see ``stage_ms``)
         self._ev = None
+        self.fp32_retries = 0  # fp32_retry_per_step: steps run again in fp32 after a split16 overflow
 
     def _mark(self, i):
         if self.timing:
@@ -232,10 +252,40 @@ class RegistrationPipeline:
         except _lib.EyocError as e:
             if e.code != _lib.ERR_RANGE or self.model.spconv_math != "auto":
                 raise
+            if self.cfg.fp32_retry_per_step:
+                res = self._retry_fp32(batch, seed, maps, False, self.slot)
+                for r in res:
+                    r.status |= RETRIED_FP32
+                return res
             import logging
             logging.warning("eyoc_amd: split16 overflow in the registration pipeline; switching the model to fp32 MFMAs")
             self.model.spconv_math = "fp32"
             return self.register(batch, seed, False, maps)
+
+    @torch.no_grad()
+    def _retry_fp32(self, batch, seed, maps, return_device, slot):
+        """fp32_retry_per_step: this step again with fp32 MFMAs, and back to the model's own arithmetic for the next one.  The re-run
+        uses the overflowed step's own buffer set ``slot`` (the SC2-PCR index staging of the other slot may still feed a step in flight)
+        and, for a pipelined step, leaves what the pipeline keeps about the LAST enqueued step - ``slot``, ``featured`` / ``matched`` (``prepare_maps(after=)``),
+        ``last_nn_idx``, the stage timers - as it was."""
+        from . import _lib
+        self.fp32_retries += 1
+        if return_device:     # a pipelined step knew of its overflow from its own words: clear the sticky flag the guard still holds
+            try:
+                self.model.check_range()
+            except _lib.EyocError as e:
+                if e.code != _lib.ERR_RANGE:
+                    raise
+        # (``register``'s own retry IS the last step: what it leaves behind stays)
+        kept = {k: self.__dict__[k] for k in ("slot", "featured", "matched", "last_nn_idx", "timing") if k in self.__dict__} if return_device else {}
+        math, self.model.spconv_math = self.model.spconv_math, "fp32"
+        if return_device:
+            self.slot, self.timing = slot, False
+        try:
+            return self.register(batch, seed, return_device, maps)
+        finally:
+            self.model.spconv_math = math
+            self.__dict__.update(kept)
 
     @torch.no_grad()
     def prepare_maps(self, batch: DeviceBatch, after=None):
@@ -279,7 +329,7 @@ class RegistrationPipeline:
             self.model.range_snapshot(words)
             done = torch.cuda.Event()
             done.record()
-            return PendingStep(host, words, done, res)
+            return PendingStep(host, words, done, res, retry=self._retry_args(batch, seed, maps, slot))
         main = torch.cuda.current_stream()
         if getattr(self, "_tail", None) is None:
             self._tail = torch.cuda.Stream(device=batch.coords.device)
@@ -299,7 +349,10 @@ class RegistrationPipeline:
             done = torch.cuda.Event()
             done.record(self._tail)
         # F was allocated on the caller's stream and is read on the tail stream: it stays referenced until wait()
-        return PendingStep(host, words, done, res, keep=(F,))
+        return PendingStep(host, words, done, res, keep=(F,), retry=self._retry_args(batch, seed, maps, slot))
+
+    def _retry_args(self, batch, seed, maps, slot):
+        return (self, batch, seed, maps, slot) if self.cfg.fp32_retry_per_step and self.model.spconv_math == "auto" else None
 
     def _pinned_stage(self, count):
         """Pinned int64 staging for the index upload of the SC2-PCR path; one buffer per event slot (``self.slot``: a slot's previous

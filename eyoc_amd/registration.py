@@ -30,6 +30,7 @@ class RegistrationResult:
     inliers: int = 0
     best_hypothesis: int = -1
     survivors: int = 0
+    status: int = 0                 # harness.RETRIED_FP32 when the step was registered again in fp32 (fp32_retry_per_step)
 
 
 def ransac_from_correspondences(src, tgt, corr_tgt, max_correspondence_distance, max_iteration=4000000, seed=0,
@@ -131,7 +132,7 @@ class Matcher:
         # the library takes int(ratio * n) seeds; hand it a ratio that floors to exactly Python's
         # int(num_corr * self.ratio) whatever fp32 does to the literal
         n_seed = int(n * self.ratio)
-        return _lib.Sc2pcrParams(float(self.inlier_threshold), float(self.d_thre), (n_seed + 0.5) / n,
+        return _lib.Sc2pcrParams(float(self.inlier_threshold), float(self.d_thre), (n_seed + 0.5) / max(n, 1),
                                  float(self.nms_radius), int(self.num_iterations), int(self.max_points),
                                  int(self.k1), int(self.k2)), n_seed
 

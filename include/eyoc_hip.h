@@ -42,6 +42,8 @@ typedef enum {
 
 #define EYOC_MAX_LEVELS 4
 /* 111 (round 6): eyoc_model_desc ends with `expanded` (ResUNetExpanded / ResUNetExpBN2C run through eyoc_model_forward too).
+ *     Later libraries of 111 add two entry points and change nothing else: eyoc_maps_last_fault_batches and
+ *     eyoc_registration_accept_degenerate (a binding checks for the symbols).
  * 110 (round 6): the kernel-selection setters and eyoc_ransac_workspace_bytes take the ctx first (round 5), eyoc_maps_gather_window
  * refuses Z-ordered maps again and eyoc_maps_gather_window_internal exists, eyoc_model_workspace_bytes depends on the maps' size class */
 #define EYOC_VERSION 111
@@ -94,6 +96,13 @@ int eyoc_maps_build(eyoc_ctx* ctx, const int32_t* coords_dev, int n_rows, void* 
  * are then in the caller's rows), 1 Z-order.  eyoc_maps_internal_order(ctx, 0 / 1) overrides it for every build of that ctx. */
 int eyoc_maps_build_ordered(eyoc_ctx* ctx, const int32_t* coords_dev, int n_rows, void* workspace_dev,
                             size_t workspace_bytes, void* stream, int order, eyoc_maps** out);
+/* Which batch indices made the ctx's LAST build fail (eyoc_maps_build / _ordered): dup / range (host arrays of 32 words) get bit b of
+ * word b >> 5 for every batch index b < 1024 that holds a duplicate row / a row outside the key range (a row whose own batch index is
+ * outside [0, 1024) sets no bit).  Every build clears both masks first; a build that fails with EYOC_ERR_RANGE fills the range mask
+ * only, one that fails with EYOC_ERR_DUPLICATE the dup mask only (the range check comes first: with rows out of range the caller-order
+ * path does not look for duplicates at all), and any other return leaves both 0.  The build's kernels set the bits from the faulty
+ * rows only and the masks come back with the read-back that detects the fault; return codes and messages are unchanged. */
+int eyoc_maps_last_fault_batches(const eyoc_ctx* ctx, uint32_t* dup, uint32_t* range);
 int eyoc_maps_free(eyoc_maps* maps);
 /* Row order the transposed convolutions tile their outputs in: the rows of `level` (a fine level, 0 <= level <
  * n_levels-1) sorted, stably, by the pattern of coarse blocks their transposed map reaches.  Purely a
@@ -582,6 +591,12 @@ int eyoc_ransac_batched(eyoc_ctx* ctx, const float* src_dev, const float* tgt_de
  * cannot win stay partial; it is applied to launch chunks of >= 32 pairs (every wave polls one word per pair: on fewer words the
  * polling costs more than the skipped work).  Other values only query.  Returns the previous state.  Per ctx; for tests / profiling. */
 int eyoc_ransac_select_pruning(eyoc_ctx* ctx, int on);
+/* Per-pair failure isolation of the batched back-ends (default 0).  With 1, eyoc_ransac_batched(_ws) accepts pairs with 0..3
+ * correspondences and eyoc_sc2pcr_batched pairs with 0..7 rows (empty segments included) instead of failing the call: such a pair
+ * gets a defined failed output - RANSAC: T all NaN, best_hypothesis -1, survivors 0, inliers 0, inlier_rmse 0; SC2-PCR: T all NaN,
+ * its fitness row 0 -, and its rows are never read.  The other pairs run as they would without it (pair b still samples with
+ * seed + b) and give the same bytes.  Other values only query; returns the previous state.  Per ctx. */
+int eyoc_registration_accept_degenerate(eyoc_ctx* ctx, int on);
 /* How many survivor transforms per pair are stored for the scorer (default 2^20 = 96 MB per pair; survivors beyond it are
  * re-derived from their hypothesis number by k_count_overflow - same counts, more work).  survivors >= 1 sets, anything else
  * only queries; returns the previous value.  Per ctx; tests set it tiny to drive every survivor through the overflow path. */
