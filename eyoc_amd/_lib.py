@@ -83,6 +83,12 @@ PROTOTYPES = {
     "eyoc_voxelize_batched_workspace_bytes": (_sz, [_i, _i]),
     "eyoc_voxelize_batched": (_i, [_vp, _vp, _i, C.POINTER(C.c_int64), _i, _i, C.c_float, _i, _vp, _vp, _vp,
                                    C.POINTER(C.c_int64), _vp, _sz, _vp]),
+    "eyoc_voxelize_batched_isolating_workspace_bytes": (_sz, [_i, _i]),
+    "eyoc_voxelize_batched_isolating": (_i, [_vp, _vp, _i, C.POINTER(C.c_int64), _i, _i, C.c_float, _i, _vp, _vp, _vp,
+                                             C.POINTER(C.c_int64), _vp, _sz, _vp, _vp]),
+    "eyoc_batch_drop_workspace_bytes": (_sz, [_i]),
+    "eyoc_batch_drop": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, C.POINTER(C.c_int), _vp, _vp, _sz, _vp]),
+    "eyoc_remap_rows": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "eyoc_gather_rows": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, C.c_float, _vp, _vp]),
     "eyoc_dotmax": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _vp, _vp, _vp]),
     "eyoc_knn2": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _vp, _vp, _vp, _vp]),

@@ -58,7 +58,7 @@ int eyoc_create(int device, eyoc_ctx** out) {
                "eyoc_create: device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
   eyoc_ctx* ctx = new eyoc_ctx();
   ctx->device = device;
-  ctx->pinned_bytes = 16384;   // eyoc_voxelize_batched at 1024 clouds: 8.2 KB of point offsets up, 4.4 KB of counters + row offsets back
+  ctx->pinned_bytes = 32768;   // eyoc_voxelize_batched(_isolating) at 1024 clouds: 8.2 KB of point offsets up, 4.4 KB of counters + row offsets (+ 8 KB of fault counts) back
   hipError_t e = hipHostMalloc(&ctx->pinned, ctx->pinned_bytes, hipHostMallocDefault);
   if (e != hipSuccess) {
     delete ctx;

@@ -19,14 +19,11 @@
 
 #include "spconv.h"
 #include "derive.h"
+#include "scan.h"
 
 using namespace eyoc;
 
 namespace {
-
-constexpr int SCAN_ITEMS = 8;
-constexpr int SCAN_BLOCK = 256;
-constexpr int SCAN_TILE = SCAN_ITEMS * SCAN_BLOCK;  // 2048 flags per block
 
 __device__ inline void coarse_coord(const int32_t* c, int ts2, int& b, int& x, int& y, int& z) {
   const int m = ~(ts2 - 1);  // ts2 is a power of two: floor to a multiple of ts2, also for negatives
@@ -62,8 +59,13 @@ __global__ void k_insert(const int32_t* __restrict__ coords, int n, int ts2, Has
 // the voxeliser's insert: consecutive points of a sweep often share a voxel, so within a wave only the first point of every run of equal
 // keys probes the table (CAS + atomicMin: it is also the run's smallest index) and the others take its slot - the same table, slots
 // and values as k_insert(ts2 = 1)
+// kIsolate (eyoc_voxelize_batched_isolating): a point whose cloud has a fault count (faults[cloud][2], complete: k_quantize is a launch
+// of its own) is skipped BEFORE the runs are formed - it has no key, leads no run and stands in for nobody -, counts no error and
+// takes slot 0, whose value is never its index: k_flag gives it 0
+template <bool kIsolate>
 __global__ __launch_bounds__(256) void k_insert_runs(const int32_t* __restrict__ coords, int n, HashTable t, int* __restrict__ slot_out,
-                                                     int* __restrict__ err) {
+                                                     int* __restrict__ err, const int* __restrict__ faults = nullptr,
+                                                     int batch_base = 0) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
   constexpr int LIM = COORD_BIAS - 16;
   bool ok = false;
@@ -71,10 +73,16 @@ __global__ __launch_bounds__(256) void k_insert_runs(const int32_t* __restrict__
   if (i < n) {
     const int4 c = reinterpret_cast<const int4*>(coords)[i];
     ok = !(c.x < 0 || c.x >= 1024 || c.y < -LIM || c.y >= LIM || c.z < -LIM || c.z >= LIM || c.w < -LIM || c.w >= LIM);
+    bool skip = false;
+    if constexpr (kIsolate) {
+      const int2 f = reinterpret_cast<const int2*>(faults)[c.x - batch_base];   // c.x = batch_base + cloud: k_quantize wrote it
+      skip = (f.x | f.y) != 0;
+      ok = ok && !skip;
+    }
     if (ok) {
       key = pack_key(c.x, c.y, c.z, c.w);
     } else {
-      atomicAdd(&err[0], 1);
+      if (!skip) atomicAdd(&err[0], 1);
       slot_out[i] = 0;
     }
   }
@@ -104,53 +112,6 @@ __global__ void k_flag(const int* __restrict__ slot, const int* __restrict__ val
   int f = vals[slot[i]] == i;
   flag[i] = f;
   if (dup && !f) atomicAdd(dup, 1);
-}
-
-__device__ inline int block_exclusive_scan(int v, int* total) {
-  __shared__ int wave_sum[SCAN_BLOCK / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    int o = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += o;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < SCAN_BLOCK / 64; ++w) {
-    int s = wave_sum[w];
-    if (w < wave) base += s;
-    tot += s;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + incl - v;
-}
-
-__global__ __launch_bounds__(SCAN_BLOCK) void k_scan_partials(const int* __restrict__ flag, int n, int* __restrict__ partial) {
-  const int base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-  int s = 0;
-#pragma unroll
-  for (int j = 0; j < SCAN_ITEMS; ++j) s += (base + j < n) ? flag[base + j] : 0;
-  int tot;
-  block_exclusive_scan(s, &tot);
-  if (threadIdx.x == 0) partial[blockIdx.x] = tot;
-}
-
-// single block: exclusive scan of partial[0..nb) in place, total -> *total
-__global__ __launch_bounds__(SCAN_BLOCK) void k_scan_top(int* __restrict__ partial, int nb, int* __restrict__ total) {
-  int carry = 0;
-  for (int b0 = 0; b0 < nb; b0 += SCAN_BLOCK) {
-    int i = b0 + threadIdx.x;
-    int v = i < nb ? partial[i] : 0;
-    int tot;
-    int ex = block_exclusive_scan(v, &tot);
-    if (i < nb) partial[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) *total = carry;
 }
 
 // compaction: first rows write their coarse coordinate at pos and re-label their slot with it
@@ -530,8 +491,12 @@ __global__ void k_iota(int32_t* __restrict__ out, int n) {
 // voxels of different clouds never share a key.  The cloud of the workgroup's first point by one binary search, every point's by a
 // forward walk from there (empty clouds only lengthen the walk).  bad (atomicMax of n_clouds - b): the first cloud that holds a point
 // outside the key range k_insert accepts.
+// kIsolate: instead, faults[b][0] counts cloud b's finite points outside the key range and faults[b][1] its points with a NaN / inf in
+// x, y or z (atomics from faulty points only); such a point's row holds its cloud and zeros.
+template <bool kIsolate>
 __global__ void k_quantize(const float* __restrict__ xyz, int n, int stride, float voxel, const int64_t* __restrict__ pt_off,
-                           int n_clouds, int batch_base, int32_t* __restrict__ coords, int* __restrict__ bad) {
+                           int n_clouds, int batch_base, int32_t* __restrict__ coords, int* __restrict__ bad,
+                           int* __restrict__ faults = nullptr) {
   __shared__ int cloud0;
   const int i0 = blockIdx.x * blockDim.x;
   if (n_clouds > 1) {
@@ -554,9 +519,19 @@ __global__ void k_quantize(const float* __restrict__ xyz, int n, int stride, flo
   }
   const float* p = xyz + (size_t)i * stride;
   int4 c = make_int4(batch_base + b, (int)floorf(p[0] / voxel), (int)floorf(p[1] / voxel), (int)floorf(p[2] / voxel));
-  reinterpret_cast<int4*>(coords)[i] = c;
   constexpr int LIM = COORD_BIAS - 16;   // k_insert's test
-  if (c.y < -LIM || c.y >= LIM || c.z < -LIM || c.z >= LIM || c.w < -LIM || c.w >= LIM) atomicMax(bad, n_clouds - b);
+  const bool out = c.y < -LIM || c.y >= LIM || c.z < -LIM || c.z >= LIM || c.w < -LIM || c.w >= LIM;
+  if constexpr (kIsolate) {
+    const bool finite = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
+    if (!finite || out) {
+      atomicAdd(&faults[2 * b + (finite ? 0 : 1)], 1);
+      c = make_int4(batch_base + b, 0, 0, 0);
+    }
+    reinterpret_cast<int4*>(coords)[i] = c;
+  } else {
+    reinterpret_cast<int4*>(coords)[i] = c;
+    if (out) atomicMax(bad, n_clouds - b);
+  }
 }
 
 // the clouds' row offsets in the compacted output: the exclusive scan of the flags at a cloud's first point is the scanned partial sum
@@ -1205,6 +1180,11 @@ size_t eyoc_voxelize_batched_workspace_bytes(int n_points_total, int n_clouds) {
   return eyoc_voxelize_workspace_bytes(n_points_total) + align_up((size_t)(n_clouds + 1) * 8) + align_up((size_t)(n_clouds + 1) * 4);
 }
 
+size_t eyoc_voxelize_batched_isolating_workspace_bytes(int n_points_total, int n_clouds) {
+  if (n_points_total < 0 || n_clouds < 1) return 0;
+  return eyoc_voxelize_batched_workspace_bytes(n_points_total, n_clouds) + align_up((size_t)n_clouds * 8 + 8);
+}
+
 }  // extern "C"
 
 namespace {
@@ -1212,11 +1192,17 @@ namespace {
 // The voxeliser of eyoc_voxelize (one cloud) and eyoc_voxelize_batched (n_clouds packed clouds): quantise, hash-grid insert, flag,
 // scan, per-cloud row offsets, compact, and one read-back.  Arguments validated by the callers; n > 0.  pt_off_host: [n_clouds + 1]
 // (uploaded through the ctx's pinned staging; one cloud needs none), vox_off_host: [n_clouds + 1] out.
+// faults_host ([n_clouds][2] out, or NULL): the isolating variant - per-cloud fault counts instead of an error, faulty clouds skipped;
+// the counts sit behind the row offsets and come back in the same copy.
 int voxelize_run(eyoc_ctx* ctx, const char* who, const float* xyz_dev, int n, int stride, const int64_t* pt_off_host,
                  int n_clouds, float voxel_size, int batch_base, int32_t* sel_dev, int32_t* coords_dev, float* xyz_out_dev,
-                 int64_t* vox_off_host, void* ws, size_t ws_bytes, hipStream_t st) {
+                 int64_t* vox_off_host, void* ws, size_t ws_bytes, hipStream_t st, int32_t* faults_host = nullptr) {
   Carver cv(ws, ws_bytes);
-  int* counters = cv.take<int>(64 + n_clouds + 1);   // [0] range errors, [1] first bad cloud (n_clouds - b), [2] total, [64..] row offsets
+  const bool iso = faults_host != nullptr;
+  // [0] range errors, [1] first bad cloud (n_clouds - b), [2] total, [64..] row offsets, isolating: [fo ..] fault counts (8-byte aligned)
+  const int fo = 64 + ((n_clouds + 2) & ~1);
+  int* counters = cv.take<int>(iso ? fo + 2 * n_clouds : 64 + n_clouds + 1);
+  int* faults = counters + fo;
   int64_t* pt_off = cv.take<int64_t>(n_clouds + 1);
   int32_t* raw = cv.take<int32_t>((size_t)n * 4);
   int* slot = cv.take<int>(n);
@@ -1230,7 +1216,7 @@ int voxelize_run(eyoc_ctx* ctx, const char* who, const float* xyz_dev, int n, in
   EYOC_REQUIRE(cv.ok(), EYOC_ERR_WORKSPACE, "%s: internal workspace accounting error (%zu > %zu)", who, cv.off, cv.cap);
   // pinned staging: the point offsets up at 0, the counters and row offsets back behind them
   const size_t up_bytes = n_clouds > 1 ? align_up((size_t)(n_clouds + 1) * 8) : 0;
-  const int back = n_clouds > 1 ? 64 + n_clouds + 1 : 4;
+  const int back = iso ? fo + 2 * n_clouds : n_clouds > 1 ? 64 + n_clouds + 1 : 4;
   EYOC_REQUIRE(up_bytes + (size_t)back * 4 <= ctx->pinned_bytes, EYOC_ERR_INVALID, "%s: %d clouds exceed the pinned staging", who,
                n_clouds);
   int64_t* up = (int64_t*)ctx->pinned;
@@ -1240,11 +1226,20 @@ int voxelize_run(eyoc_ctx* ctx, const char* who, const float* xyz_dev, int n, in
     EYOC_CHECK_HIP(hipMemcpyAsync(pt_off, up, (size_t)(n_clouds + 1) * 8, hipMemcpyHostToDevice, st));
   }
   EYOC_CHECK_HIP(hipMemsetAsync(counters, 0, 64 * sizeof(int), st));
+  if (iso) EYOC_CHECK_HIP(hipMemsetAsync(faults, 0, (size_t)n_clouds * 2 * sizeof(int), st));
   EYOC_CHECK_HIP(hipMemsetAsync(t.keys, 0xFF, (size_t)cap * 8, st));
   EYOC_CHECK_HIP(hipMemsetAsync(t.vals, 0x7F, (size_t)cap * 4, st));
-  hipLaunchKernelGGL(k_quantize, dim3(cdiv(n, 256)), dim3(256), 0, st, xyz_dev, n, stride, voxel_size, (const int64_t*)pt_off,
-                     n_clouds, batch_base, raw, counters + 1);
-  hipLaunchKernelGGL(k_insert_runs, dim3(cdiv(n, 256)), dim3(256), 0, st, (const int32_t*)raw, n, t, slot, counters);
+  if (iso) {
+    hipLaunchKernelGGL(k_quantize<true>, dim3(cdiv(n, 256)), dim3(256), 0, st, xyz_dev, n, stride, voxel_size, (const int64_t*)pt_off,
+                       n_clouds, batch_base, raw, counters + 1, faults);
+    hipLaunchKernelGGL(k_insert_runs<true>, dim3(cdiv(n, 256)), dim3(256), 0, st, (const int32_t*)raw, n, t, slot, counters,
+                       (const int*)faults, batch_base);
+  } else {
+    hipLaunchKernelGGL(k_quantize<false>, dim3(cdiv(n, 256)), dim3(256), 0, st, xyz_dev, n, stride, voxel_size, (const int64_t*)pt_off,
+                       n_clouds, batch_base, raw, counters + 1, (int*)nullptr);
+    hipLaunchKernelGGL(k_insert_runs<false>, dim3(cdiv(n, 256)), dim3(256), 0, st, (const int32_t*)raw, n, t, slot, counters,
+                       (const int*)nullptr, 0);
+  }
   hipLaunchKernelGGL(k_flag, dim3(cdiv(n, 256)), dim3(256), 0, st, slot, t.vals, n, flag, (int*)nullptr);
   const int nb = cdiv(n, SCAN_TILE);
   hipLaunchKernelGGL(k_scan_partials, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, n, partial);
@@ -1263,6 +1258,7 @@ int voxelize_run(eyoc_ctx* ctx, const char* who, const float* xyz_dev, int n, in
                    who, host[0], n_clouds - host[1]);
     EYOC_REQUIRE(false, EYOC_ERR_RANGE, "%s: %d points fall outside the key range (|c| < 2^17 - 16)", who, host[0]);
   }
+  if (iso) memcpy(faults_host, host + fo, (size_t)n_clouds * 2 * sizeof(int));
   vox_off_host[0] = 0;
   if (n_clouds == 1) {
     vox_off_host[1] = host[2];
@@ -1294,34 +1290,53 @@ int eyoc_voxelize(eyoc_ctx* ctx, const float* xyz_dev, int n, int stride, float 
   return EYOC_OK;
 }
 
-int eyoc_voxelize_batched(eyoc_ctx* ctx, const float* xyz_dev, int stride, const int64_t* point_offsets, int n_clouds,
-                          int n_points, float voxel_size, int batch_base, int32_t* sel_dev, int32_t* coords_dev,
-                          float* xyz_out_dev, int64_t* voxel_offsets, void* ws, size_t ws_bytes, void* stream) {
-  EYOC_REQUIRE(ctx && point_offsets && voxel_offsets, EYOC_ERR_INVALID, "eyoc_voxelize_batched: NULL argument");
-  EYOC_REQUIRE(n_clouds >= 1 && n_clouds <= 1024, EYOC_ERR_INVALID, "eyoc_voxelize_batched: %d clouds (1 .. 1024)", n_clouds);
-  EYOC_REQUIRE(n_points >= 0 && n_points <= (1 << 30), EYOC_ERR_INVALID, "eyoc_voxelize_batched: %d points in all (0 .. 2^30)",
+// eyoc_voxelize_batched and its isolating variant: the same checks, messages under the caller's name
+static int voxelize_batched(const char* who, bool isolating, eyoc_ctx* ctx, const float* xyz_dev, int stride,
+                            const int64_t* point_offsets, int n_clouds, int n_points, float voxel_size, int batch_base,
+                            int32_t* sel_dev, int32_t* coords_dev, float* xyz_out_dev, int64_t* voxel_offsets, void* ws,
+                            size_t ws_bytes, void* stream, int32_t* cloud_faults) {
+  EYOC_REQUIRE(ctx && point_offsets && voxel_offsets && (!isolating || cloud_faults), EYOC_ERR_INVALID, "%s: NULL argument", who);
+  EYOC_REQUIRE(n_clouds >= 1 && n_clouds <= 1024, EYOC_ERR_INVALID, "%s: %d clouds (1 .. 1024)", who, n_clouds);
+  EYOC_REQUIRE(n_points >= 0 && n_points <= (1 << 30), EYOC_ERR_INVALID, "%s: %d points in all (0 .. 2^30)", who,
                n_points);
-  EYOC_REQUIRE(stride >= 3 && voxel_size > 0.0f, EYOC_ERR_INVALID, "eyoc_voxelize_batched: stride %d voxel %g", stride, voxel_size);
+  EYOC_REQUIRE(stride >= 3 && voxel_size > 0.0f, EYOC_ERR_INVALID, "%s: stride %d voxel %g", who, stride, voxel_size);
   EYOC_REQUIRE(batch_base >= 0 && batch_base + n_clouds <= 1024, EYOC_ERR_RANGE,
-               "eyoc_voxelize_batched: batch indices %d .. %d (< 1024)", batch_base, batch_base + n_clouds - 1);
-  EYOC_REQUIRE(point_offsets[0] == 0, EYOC_ERR_INVALID, "eyoc_voxelize_batched: point_offsets[0] = %lld", (long long)point_offsets[0]);
+               "%s: batch indices %d .. %d (< 1024)", who, batch_base, batch_base + n_clouds - 1);
+  EYOC_REQUIRE(point_offsets[0] == 0, EYOC_ERR_INVALID, "%s: point_offsets[0] = %lld", who, (long long)point_offsets[0]);
   for (int b = 0; b < n_clouds; ++b)
     EYOC_REQUIRE(point_offsets[b + 1] >= point_offsets[b], EYOC_ERR_INVALID,
-                 "eyoc_voxelize_batched: point offsets decrease at cloud %d (%lld -> %lld)", b, (long long)point_offsets[b],
+                 "%s: point offsets decrease at cloud %d (%lld -> %lld)", who, b, (long long)point_offsets[b],
                  (long long)point_offsets[b + 1]);
   EYOC_REQUIRE(point_offsets[n_clouds] == n_points, EYOC_ERR_INVALID,
-               "eyoc_voxelize_batched: point_offsets[%d] = %lld, not the total %d", n_clouds, (long long)point_offsets[n_clouds],
+               "%s: point_offsets[%d] = %lld, not the total %d", who, n_clouds, (long long)point_offsets[n_clouds],
                n_points);
+  if (isolating) memset(cloud_faults, 0, (size_t)n_clouds * 2 * sizeof(int32_t));
   if (n_points == 0) {          // every cloud empty: nothing to launch
     for (int b = 0; b <= n_clouds; ++b) voxel_offsets[b] = 0;
     return EYOC_OK;
   }
-  EYOC_REQUIRE(xyz_dev && sel_dev && coords_dev && ws, EYOC_ERR_INVALID, "eyoc_voxelize_batched: NULL argument");
-  const size_t need = eyoc_voxelize_batched_workspace_bytes(n_points, n_clouds);
+  EYOC_REQUIRE(xyz_dev && sel_dev && coords_dev && ws, EYOC_ERR_INVALID, "%s: NULL argument", who);
+  const size_t need = isolating ? eyoc_voxelize_batched_isolating_workspace_bytes(n_points, n_clouds)
+                                 : eyoc_voxelize_batched_workspace_bytes(n_points, n_clouds);
   EYOC_REQUIRE(((uintptr_t)ws & 255) == 0 && ws_bytes >= need, EYOC_ERR_WORKSPACE,
-               "eyoc_voxelize_batched: workspace %zu < required %zu bytes (256-byte aligned)", ws_bytes, need);
-  return voxelize_run(ctx, "eyoc_voxelize_batched", xyz_dev, n_points, stride, point_offsets, n_clouds, voxel_size, batch_base,
-                      sel_dev, coords_dev, xyz_out_dev, voxel_offsets, ws, ws_bytes, (hipStream_t)stream);
+               "%s: workspace %zu < required %zu bytes (256-byte aligned)", who, ws_bytes, need);
+  return voxelize_run(ctx, who, xyz_dev, n_points, stride, point_offsets, n_clouds, voxel_size, batch_base,
+                      sel_dev, coords_dev, xyz_out_dev, voxel_offsets, ws, ws_bytes, (hipStream_t)stream, cloud_faults);
+}
+
+int eyoc_voxelize_batched(eyoc_ctx* ctx, const float* xyz_dev, int stride, const int64_t* point_offsets, int n_clouds,
+                          int n_points, float voxel_size, int batch_base, int32_t* sel_dev, int32_t* coords_dev,
+                          float* xyz_out_dev, int64_t* voxel_offsets, void* ws, size_t ws_bytes, void* stream) {
+  return voxelize_batched("eyoc_voxelize_batched", false, ctx, xyz_dev, stride, point_offsets, n_clouds, n_points, voxel_size,
+                          batch_base, sel_dev, coords_dev, xyz_out_dev, voxel_offsets, ws, ws_bytes, stream, nullptr);
+}
+
+int eyoc_voxelize_batched_isolating(eyoc_ctx* ctx, const float* xyz_dev, int stride, const int64_t* point_offsets, int n_clouds,
+                                    int n_points, float voxel_size, int batch_base, int32_t* sel_dev, int32_t* coords_dev,
+                                    float* xyz_out_dev, int64_t* voxel_offsets, void* ws, size_t ws_bytes, void* stream,
+                                    int32_t* cloud_faults) {
+  return voxelize_batched("eyoc_voxelize_batched_isolating", true, ctx, xyz_dev, stride, point_offsets, n_clouds, n_points,
+                          voxel_size, batch_base, sel_dev, coords_dev, xyz_out_dev, voxel_offsets, ws, ws_bytes, stream, cloud_faults);
 }
 
 int eyoc_maps_free(eyoc_maps* maps) {

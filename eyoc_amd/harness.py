@@ -43,11 +43,75 @@ class RegistrationConfig:
     # the step runs again (a third of the throughput from then on); True - that step alone runs again in fp32, its pairs carry
     # RETRIED_FP32 in ``status``, and the next step is split16 again
     fp32_retry_per_step: bool = False
+    # per-pair failure isolation (the reference's loops skip a bad pair and go on, lib/trainer.py:1306-1310,1596-1604): a pair whose cloud
+    # fails the map build (duplicate rows, rows outside the key range) is dropped from the batch and gets a failed record with its
+    # DROPPED_* bits in ``status``; the other pairs of the step are registered as without it
+    isolate_failures: bool = False
 
 
 # ``RegistrationResult.status`` / ``PendingStep.status`` bit: the pair's step overflowed split16 and was registered again in fp32
 # (``fp32_retry_per_step``); the records are those of the fp32 run
 RETRIED_FP32 = 1 << 4
+# why a pair was dropped from its batch (``isolate_failures`` / ``DeviceBatch.without_pairs``): a cloud of it held duplicate rows, rows
+# (points) outside the key range, no voxels at all, or NaN / inf points.  A dropped pair's record: T all NaN, fitness 0, inliers 0.
+DROPPED_DUPLICATE = 1 << 0
+DROPPED_RANGE = 1 << 1
+DROPPED_EMPTY = 1 << 2
+DROPPED_NONFINITE = 1 << 3
+DROPPED = DROPPED_DUPLICATE | DROPPED_RANGE | DROPPED_EMPTY | DROPPED_NONFINITE
+MAX_REBUILDS = 2     # per step: the range check of a map build runs before its duplicate check, so a second fault of the other kind can follow
+
+
+def pairs_of_clouds(clouds, offsets, P):
+    """Collated clouds (= their batch indices) -> pairs.  ``offsets`` lists the clouds in the order ``DeviceBatch`` collates them - source
+    and target of pair 0, of pair 1, ... -, so there are ``2 P`` of them and cloud ``c`` belongs to pair ``c // 2``."""
+    n_clouds = len(offsets) - 1
+    if n_clouds != 2 * P:
+        raise ValueError(f"{n_clouds} clouds for {P} pairs")
+    clouds = np.asarray(list(clouds), np.int64)
+    if clouds.size and (clouds.min() < 0 or clouds.max() >= n_clouds):
+        raise ValueError(f"cloud {int(clouds.max() if clouds.max() >= n_clouds else clouds.min())} is not one of the batch's {n_clouds}")
+    return clouds // 2
+
+
+def fault_bits(dup, rng, offsets, P):
+    """The batch indices a failed map build reports (``_lib.fault_batches``) -> ``int64 [P]`` of DROPPED_* bits."""
+    bits = np.zeros(P, np.int64)
+    np.bitwise_or.at(bits, pairs_of_clouds(dup, offsets, P), DROPPED_DUPLICATE)
+    np.bitwise_or.at(bits, pairs_of_clouds(rng, offsets, P), DROPPED_RANGE)
+    return bits
+
+
+def live_segments(dropped, n_points):
+    """``seg int64 [P+1]`` of the per-pair sample sets when only the live pairs' rows are stored: ``n_points`` rows for a live pair, an
+    EMPTY segment for a dropped one - pair ``b`` keeps slot ``b`` (and with it its seed ``seed + b``) in the batched back-ends."""
+    return np.concatenate([[0], np.cumsum(np.where(np.asarray(dropped) == 0, int(n_points), 0))]).astype(np.int64)
+
+
+def build_with_isolation(batch, build, fault_batches):
+    """``build(batch)`` with a failed map build answered by dropping the faulty pairs: -> ``(what build returned, the batch it was built
+    for)``.  An EYOC_ERR_DUPLICATE / EYOC_ERR_RANGE is looked up in ``fault_batches() -> (dup, range)`` batch indices, their pairs are
+    taken out (``batch.without_pairs``: a new batch, the caller's is not modified) and the build runs again - at most MAX_REBUILDS
+    times, then the ORIGINAL error is raised.  An error that names no batch index (a row whose own index is outside [0, 1024)) is raised
+    as it is."""
+    from . import _lib
+    first = None
+    for attempt in range(MAX_REBUILDS + 1):
+        try:
+            return build(batch), batch
+        except _lib.EyocError as e:
+            if e.code not in (_lib.ERR_DUPLICATE, _lib.ERR_RANGE):
+                raise
+            # kept as a copy without its traceback: the traceback's frames hold the failed build's workspace (gigabytes on a large
+            # batch) and, through this frame, the exception itself - a cycle only the garbage collector would free
+            first = first or _lib.EyocError(str(e), e.code)
+            if attempt == MAX_REBUILDS:
+                raise first
+            dup, rng = fault_batches()
+            bits = fault_bits(dup, rng, batch.offsets, batch.P)
+            if not bits[batch.dropped == 0].any():      # no live pair named: nothing to drop
+                raise first
+            batch = batch.without_pairs(bits)
 
 
 _SC2_KEYS = ("inlier_threshold", "num_node", "use_mutual", "d_thre", "num_iterations", "ratio", "nms_radius", "max_points",
@@ -93,7 +157,9 @@ class DeviceBatch:
     (``eyoc_gather_rows``), so that the matcher sees a stated inlier ratio instead of the zero signal of
     random-init weights."""
 
-    def __init__(self, pairs, seeds, device, n_points=5000, descriptor=None):
+    def __init__(self, pairs, seeds, device, n_points=5000, descriptor=None, isolate=False):
+        """``isolate=True``: a pair with a cloud of 0 voxels is dropped at construction (DROPPED_EMPTY in ``dropped``) instead of
+        failing the sample draw; see ``without_pairs`` for what a dropped pair leaves behind."""
         self.P = len(pairs)
         self.descriptor = dict(descriptor) if descriptor else None
         self.beta = float(self.descriptor.get("beta", 8.0)) if self.descriptor else 0.0
@@ -109,8 +175,15 @@ class DeviceBatch:
         self.T_gt = [np.asarray(p["T_gt"], np.float32) for p in pairs]
         sel0, sel1, xyz0, xyz1, self.counts = [], [], [], [], []
         G0, G1, self.planted = [], [], []
+        self.dropped = np.zeros(self.P, np.int64)     # DROPPED_* bits per pair (0: the pair is live)
         for j, (p, seed) in enumerate(zip(pairs, seeds)):
             planted = None
+            if isolate and min(self.sizes[2 * j:2 * j + 2]) == 0:
+                self.dropped[j] = DROPPED_EMPTY
+                if self.descriptor:
+                    self.planted.append(None)
+                self.counts.append(n_points)
+                continue
             if self.descriptor:
                 planted = plant_correspondences(p, seed, n_points, self.descriptor.get("inlier_ratio", 0.3),
                                                 self.descriptor.get("plant_radius", 0.3), self.descriptor.get("feat_dim", 32))
@@ -123,21 +196,30 @@ class DeviceBatch:
             self.counts.append(n_points)
         self.G0 = torch.from_numpy(np.concatenate(G0)).to(device) if G0 else None
         self.G1 = torch.from_numpy(np.concatenate(G1)).to(device) if G1 else None
-        self.sel0 = torch.from_numpy(np.concatenate(sel0)).to(device)
-        self.sel1 = torch.from_numpy(np.concatenate(sel1)).to(device)
-        self.xyz0 = torch.from_numpy(np.stack(xyz0)).to(device)      # [P, n_points, 3]
-        self.xyz1 = torch.from_numpy(np.stack(xyz1)).to(device)
+        self.sel0 = torch.from_numpy(np.concatenate(sel0) if sel0 else np.zeros(0, np.int64)).to(device)
+        self.sel1 = torch.from_numpy(np.concatenate(sel1) if sel1 else np.zeros(0, np.int64)).to(device)
+        # [P, n_points, 3] (the live pairs only, like sel / G, once pairs were dropped)
+        self.xyz0 = torch.from_numpy(np.stack(xyz0) if xyz0 else np.zeros((0, n_points, 3), np.float32)).to(device)
+        self.xyz1 = torch.from_numpy(np.stack(xyz1) if xyz1 else np.zeros((0, n_points, 3), np.float32)).to(device)
         self.seg = np.arange(self.P + 1) * n_points
         self.n_points = n_points
+        if self.dropped.any():
+            self.seg = live_segments(self.dropped, n_points)
+            self._remove_clouds(np.flatnonzero(self.dropped))      # the partner clouds of the empty ones
 
     @classmethod
-    def from_scans(cls, scans, T_gt, seeds, device, voxel_size=0.3, n_points=5000, descriptor=None):
+    def from_scans(cls, scans, T_gt, seeds, device, voxel_size=0.3, n_points=5000, descriptor=None, isolate=False):
         """The same batch from RAW scans: ``scans`` = ``[(src, tgt), ...]`` unvoxelised ``[N,3]`` / ``[N,4]`` float32 clouds (numpy or
         torch), voxelised and collated on the GPU by ONE ``sparse_quantize_batch`` call (one read-back: the clouds' voxel counts) -
         lib/data_loaders.py:936-979 per cloud and ``collate_pair_fn`` (:31-85) for the batch.  The sample draws are ``__init__``'s
         (``sample_indices`` on the counts); the sampled points are gathered on the device.  Equal, attribute for attribute, to
         ``DeviceBatch(pairs, seeds, device, n_points)`` of the pairs these scans voxelise to.  The descriptor mode plants its
-        correspondences on the host and is not available here."""
+        correspondences on the host and is not available here.
+
+        ``isolate=True``: the isolating voxeliser (``sparse_quantize_batch(isolate=True)``); a pair with a cloud that holds a point
+        outside the key range or a NaN / inf point, or that has no voxels at all, is dropped at construction (DROPPED_RANGE /
+        DROPPED_NONFINITE / DROPPED_EMPTY in ``dropped``, see ``without_pairs``) instead of failing the call.  The live pairs' draws
+        are seeded per pair and do not change."""
         from .voxelize import sparse_quantize_batch
         if descriptor:
             raise ValueError("DeviceBatch.from_scans: the descriptor mode (plant_correspondences) needs host-voxelised pairs")
@@ -148,12 +230,21 @@ class DeviceBatch:
         self.P = len(scans)
         self.descriptor, self.beta = None, 0.0
         clouds = [c for pair in scans for c in pair]
-        self.coords, _, kept_xyz, self.offsets = sparse_quantize_batch(clouds, voxel_size, 0, device=device)
+        self.dropped = np.zeros(self.P, np.int64)
+        if isolate:
+            self.coords, _, kept_xyz, self.offsets, faults = sparse_quantize_batch(clouds, voxel_size, 0, device=device, isolate=True)
+            per_cloud = (np.where(faults[:, 0] > 0, DROPPED_RANGE, 0) | np.where(faults[:, 1] > 0, DROPPED_NONFINITE, 0)).astype(np.int64)
+            per_cloud[(per_cloud == 0) & (np.diff(self.offsets) == 0)] = DROPPED_EMPTY
+            self.dropped = per_cloud[0::2] | per_cloud[1::2]
+        else:
+            self.coords, _, kept_xyz, self.offsets = sparse_quantize_batch(clouds, voxel_size, 0, device=device)
         self.sizes = [int(v) for v in np.diff(self.offsets)]
         self.feats = torch.ones((len(self.coords), 1), dtype=torch.float32, device=self.coords.device)
         self.T_gt = [np.asarray(T, np.float32) for T in T_gt]
-        sel = ([], [])
+        sel = ([np.zeros(0, np.int64)], [np.zeros(0, np.int64)])
         for j, seed in enumerate(seeds):
+            if self.dropped[j]:
+                continue
             for i in (0, 1):
                 sel[i].append(sample_indices(seed, i, self.sizes[2 * j + i], n_points) + self.offsets[2 * j + i])
         self.counts = [n_points] * self.P
@@ -161,11 +252,68 @@ class DeviceBatch:
         self.planted = []
         self.sel0 = torch.from_numpy(np.concatenate(sel[0])).to(self.coords.device)
         self.sel1 = torch.from_numpy(np.concatenate(sel[1])).to(self.coords.device)
-        self.xyz0 = kept_xyz[self.sel0].reshape(self.P, n_points, 3)
-        self.xyz1 = kept_xyz[self.sel1].reshape(self.P, n_points, 3)
+        self.xyz0 = kept_xyz[self.sel0].reshape(-1, n_points, 3)
+        self.xyz1 = kept_xyz[self.sel1].reshape(-1, n_points, 3)
         self.seg = np.arange(self.P + 1) * n_points
         self.n_points = n_points
+        if self.dropped.any():
+            self.seg = live_segments(self.dropped, n_points)
+            self._remove_clouds(np.flatnonzero(self.dropped))      # a faulty cloud is empty already: its partner's rows go too
         return self
+
+    def _remove_clouds(self, pairs):
+        """Takes the rows of both clouds of ``pairs`` out of ``coords / feats`` (``eyoc_batch_drop``: the other rows keep their order and
+        their batch indices), sends ``sel0 / sel1`` - which hold the live pairs only by now - through the row map on the device and
+        updates ``sizes / offsets``.  In place: for a batch under construction."""
+        from .isolate import batch_drop, remap_rows
+        clouds = [2 * int(p) + i for p in pairs for i in (0, 1)]
+        self.coords, self.feats, row_map, kept = batch_drop(self.coords, self.feats, clouds)
+        self.sel0, self.sel1 = remap_rows(self.sel0, row_map), remap_rows(self.sel1, row_map)
+        self.sizes = [int(v) for v in kept[:2 * self.P]]
+        self.offsets = np.concatenate([[0], np.cumsum(self.sizes)])
+
+    def without_pairs(self, bits_by_pair):
+        """A new batch without the clouds of some pairs; this one is not modified.  ``bits_by_pair``: DROPPED_* bits per pair (``[P]``, 0 =
+        keep; or a ``{pair: bits}`` dict).  ``P``, ``T_gt``, ``n_points`` and every pair's slot stay: the dropped pairs' rows are removed
+        from ``coords / feats`` on the device (batch indices unchanged), ``sel0 / sel1 / xyz0 / xyz1 / G0 / G1`` hold the live pairs only,
+        back to back, ``seg`` gives a dropped pair an EMPTY segment - pair ``b`` still samples with ``seed + b`` in the batched
+        back-ends, which answer an empty segment with a failed record (``eyoc_registration_accept_degenerate``) -, ``sizes / offsets``
+        are those of the remaining rows and ``dropped`` carries the bits."""
+        import copy
+        if isinstance(bits_by_pair, dict):
+            bits = np.zeros(self.P, np.int64)
+            for p, b in bits_by_pair.items():
+                bits[int(p)] = int(b)
+        else:
+            bits = np.asarray(bits_by_pair, np.int64)
+        if bits.shape != (self.P,) or (bits & ~DROPPED).any():
+            raise ValueError(f"without_pairs: DROPPED_* bits for each of the {self.P} pairs")
+        out = copy.copy(self)
+        out.T_gt, out.counts, out.planted, out.sizes = list(self.T_gt), list(self.counts), list(self.planted), list(self.sizes)
+        out.dropped = self.dropped | bits
+        new = (bits != 0) & (self.dropped == 0)
+        if not new.any():
+            return out
+        # the per-pair arrays hold the pairs that were live so far: keep those that still are
+        stay = torch.from_numpy(np.flatnonzero(~new[self.dropped == 0])).to(self.sel0.device)
+        n = self.n_points
+        out.sel0 = self.sel0.reshape(-1, n).index_select(0, stay).reshape(-1)
+        out.sel1 = self.sel1.reshape(-1, n).index_select(0, stay).reshape(-1)
+        out.xyz0, out.xyz1 = self.xyz0.index_select(0, stay), self.xyz1.index_select(0, stay)
+        if self.G0 is not None:
+            c = self.G0.shape[1]
+            out.G0 = self.G0.reshape(-1, n, c).index_select(0, stay).reshape(-1, c)
+            out.G1 = self.G1.reshape(-1, n, c).index_select(0, stay).reshape(-1, c)
+        out.seg = live_segments(out.dropped, n)
+        out._remove_clouds(np.flatnonzero(new))
+        return out
+
+    def record_stream(self, stream):
+        """A batch made on one stream (``prepare_maps``' side stream drops pairs there) and read on another: ties its device tensors to
+        the reading stream, so that the caching allocator reuses their memory only after that stream's work."""
+        for t in (self.coords, self.feats, self.sel0, self.sel1, self.xyz0, self.xyz1, self.G0, self.G1):
+            if t is not None:
+                t.record_stream(stream)
 
     @property
     def voxels(self):
@@ -175,8 +323,9 @@ class DeviceBatch:
 class PendingStep:
     """A step whose read-back was enqueued with it (``RegistrationPipeline.enqueue``)."""
 
-    def __init__(self, host, words, done, device_result, keep=None, retry=None):
+    def __init__(self, host, words, done, device_result, keep=None, retry=None, dropped=None):
         self.host, self.words, self.done, self.device_result = host, words, done, device_result
+        self.dropped = dropped    # isolate_failures: the step's DROPPED_* bits per pair (their records are the back-end's failed ones)
         self.keep = keep          # tensors another stream still reads (the features under ``tail_stream``): released by ``wait``
         self.retry = retry        # fp32_retry_per_step: (pipeline, batch, seed, maps, slot) to run the step again in fp32 after an overflow
         self.status = None        # per-pair status bits (int64 [P]), set by ``wait``
@@ -188,11 +337,11 @@ class PendingStep:
         self.done.synchronize()
         self.keep = None
         overflow = bool(int(self.words[0]) != 0)
-        self.status = np.zeros(self.host.shape[0], np.int64)
+        self.status = np.zeros(self.host.shape[0], np.int64) if self.dropped is None else np.array(self.dropped, np.int64)
         if overflow and self.retry is not None:
             pipe, batch, seed, maps, slot = self.retry
             self.host.copy_(pipe._retry_fp32(batch, seed, maps, True, slot).cpu())
-            self.status[:] = RETRIED_FP32
+            self.status |= RETRIED_FP32
         self.retry = None
         return self.host, overflow
 
@@ -209,6 +358,8 @@ class RegistrationPipeline:
         self.slot = 0          # which of two event sets the next ``register`` records into (see ``stage_ms``)
         self._ev = None
         self.fp32_retries = 0  # fp32_retry_per_step: steps run again in fp32 after a split16 overflow
+        self.dropped_pairs = 0  # isolate_failures: pairs that got a failed record because their batch was registered without them
+        self.registered_batch = None   # isolate_failures: the batch the last step actually ran on (the caller's, or it without the dropped pairs)
 
     def _mark(self, i):
         if self.timing:
@@ -229,15 +380,42 @@ class RegistrationPipeline:
         """scripts/test_kitti.py:141-150 for all 2P clouds at once (the maps are rebuilt per call, like
         the reference rebuilds its coordinate manager for every SparseTensor - or taken from ``prepare_maps``)."""
         # the split16 range check is deferred to where ``register`` synchronises anyway (no host wait after the forward)
+        return self._features(batch, maps)[0]
+
+    def _features(self, batch, maps):
+        """``features`` -> (the features, the batch they belong to): under ``isolate_failures`` that is ``batch`` without the pairs a
+        failed map build named - dropped here, or by ``prepare_maps``, whose handle then carries the reduced batch as a third element."""
         check, self.model.range_check = self.model.range_check, False
         try:
             if maps is not None:
-                cm, ready = maps
+                cm, ready = maps[:2]
                 torch.cuda.current_stream().wait_event(ready)
-                return self.model(SparseTensor(batch.feats, coordinate_manager=cm))
-            return self.model(SparseTensor(batch.feats, coordinates=batch.coords))
+                if self.cfg.isolate_failures and len(maps) > 2 and maps[2] is not batch:
+                    batch = maps[2]
+                    batch.record_stream(torch.cuda.current_stream())     # made on the side stream, read on this one
+                return self.model(SparseTensor(batch.feats, coordinate_manager=cm)), batch
+            if self.cfg.isolate_failures:
+                cm, batch = self._build_isolated(batch)
+                return self.model(SparseTensor(batch.feats, coordinate_manager=cm)), batch
+            return self.model(SparseTensor(batch.feats, coordinates=batch.coords)), batch
         finally:
             self.model.range_check = check
+
+    def _build_isolated(self, batch):
+        """The maps of ``batch`` on the current stream, faulty pairs dropped -> ``(coordinate manager, the batch it describes)``."""
+        from . import _lib
+        from .sparse_tensor import CoordinateManager
+
+        def build(b):
+            cm = CoordinateManager(b.coords)
+            cm.maps(-1)
+            return cm
+        return build_with_isolation(batch, build, lambda: _lib.fault_batches(batch.coords.device))
+
+    def _degenerate(self, device, on):
+        """isolate_failures: the back-ends' switch for pairs below their minimum (``eyoc_registration_accept_degenerate``) -> previous value."""
+        from . import _lib
+        return _lib.knob("eyoc_registration_accept_degenerate", int(on), device=device)
 
     def _checked(self, batch, seed, maps, words=None):
         """After the results were read back: raise on a split16 overflow - or, in automatic mode, switch the model to
@@ -278,6 +456,7 @@ class RegistrationPipeline:
                     raise
         # (``register``'s own retry IS the last step: what it leaves behind stays)
         kept = {k: self.__dict__[k] for k in ("slot", "featured", "matched", "last_nn_idx", "timing") if k in self.__dict__} if return_device else {}
+        kept["dropped_pairs"] = self.dropped_pairs      # the step's dropped pairs were counted when it ran first
         math, self.model.spconv_math = self.model.spconv_math, "fp32"
         if return_device:
             self.slot, self.timing = slot, False
@@ -293,7 +472,8 @@ class RegistrationPipeline:
         serving loop builds the next batch's maps (hash / sort / rulebook kernels, latency- and atomics-bound) while the
         previous batch is still in its RANSAC (VALU-bound) on the main stream.  Returns the handle ``register(...,
         maps=)`` takes; it may be dropped right after the step was enqueued (the maps' workspace is recorded on every stream that
-        reads it, ``CoordinateManager._reading``).  ``after``: an event the side stream waits for
+        reads it, ``CoordinateManager._reading``).  Under ``isolate_failures`` the handle is ``(cm, ready, batch')``: ``batch'`` is ``batch``
+        without the pairs whose clouds failed the build (``batch`` itself if none did), and ``register`` / ``enqueue`` run on it.  ``after``: an event the side stream waits for
         first - ``self.matched`` (recorded by ``register`` when its forward and matching are enqueued) puts the build
         beside that step's RANSAC instead of beside whatever the main stream happens to run at enqueue time (the forward:
         both want LDS and the atomics path, and the forward's kernels slow down by ~10 %)."""
@@ -303,6 +483,12 @@ class RegistrationPipeline:
         if after is not None:
             self._side.wait_event(after)
         with torch.cuda.stream(self._side):
+            if self.cfg.isolate_failures:
+                # a failed build has synchronised the side stream and raised: stream and ctx are free for the drop and the rebuild
+                cm, reduced = self._build_isolated(batch)
+                ready = torch.cuda.Event()
+                ready.record(self._side)
+                return cm, ready, reduced
             cm = CoordinateManager(batch.coords)
             cm.maps(-1)
             ready = torch.cuda.Event()
@@ -329,12 +515,18 @@ class RegistrationPipeline:
             self.model.range_snapshot(words)
             done = torch.cuda.Event()
             done.record()
-            return PendingStep(host, words, done, res, retry=self._retry_args(batch, seed, maps, slot))
+            if self.cfg.isolate_failures:
+                batch, maps = self.registered_batch, None      # what a retry runs on: the reduced batch builds cleanly
+            return PendingStep(host, words, done, res, retry=self._retry_args(batch, seed, maps, slot), dropped=self._dropped(batch))
         main = torch.cuda.current_stream()
         if getattr(self, "_tail", None) is None:
             self._tail = torch.cuda.Stream(device=batch.coords.device)
         self._mark(0)
-        F = self.features(batch, maps).F
+        F, batch = self._features(batch, maps)
+        F = F.F
+        if self.cfg.isolate_failures:
+            self.registered_batch, maps = batch, None
+            self.dropped_pairs += int((batch.dropped != 0).sum())
         self._mark(1)
         # the guard's words are this forward's own only until the next forward starts: snapshot them on the forward's stream
         words = self._pinned_words(slot)
@@ -343,13 +535,18 @@ class RegistrationPipeline:
         self.featured.record(main)
         self._tail.wait_event(self.featured)
         with torch.cuda.stream(self._tail):
+            if self.cfg.isolate_failures and batch.dropped.any():
+                batch.record_stream(self._tail)
             res = self._match_and_register(batch, F, seed) if self.cfg.use_RANSAC else self._match_and_register_sc2(batch, F, seed)
             host, _ = self._pinned_set(slot, res)
             host.copy_(res, non_blocking=True)
             done = torch.cuda.Event()
             done.record(self._tail)
         # F was allocated on the caller's stream and is read on the tail stream: it stays referenced until wait()
-        return PendingStep(host, words, done, res, keep=(F,), retry=self._retry_args(batch, seed, maps, slot))
+        return PendingStep(host, words, done, res, keep=(F,), retry=self._retry_args(batch, seed, maps, slot), dropped=self._dropped(batch))
+
+    def _dropped(self, batch):
+        return batch.dropped.copy() if self.cfg.isolate_failures else None
 
     def _retry_args(self, batch, seed, maps, slot):
         return (self, batch, seed, maps, slot) if self.cfg.fp32_retry_per_step and self.model.spconv_math == "auto" else None
@@ -381,6 +578,9 @@ class RegistrationPipeline:
         ``[P, 84]`` result records on the device."""
         F0 = gather_rows(F, batch.sel0, batch.G0, batch.beta)     # the sampled rows (+ descriptor blend, if any)
         F1 = gather_rows(F, batch.sel1, batch.G1, batch.beta)
+        # isolate_failures: a dropped pair is an empty segment - for the neighbour search, which gives the live rows what the live
+        # segments alone give (tests/test_gpu_isolate_batch.py), and for the back-end, where it keeps the pair's slot and every seed
+        iso = self.cfg.isolate_failures
         nn_idx = knn1_segmented(F0, F1, batch.seg, batch.seg, "SquareL2", return_distance=False)
         self.last_nn_idx = nn_idx
         self._mark(2)
@@ -391,10 +591,15 @@ class RegistrationPipeline:
         # size gives the same records)
         if getattr(self, "_ransac_budget", None) is None:
             self._ransac_budget = reg._ransac_budget(F.device)
-        res = reg.ransac_batched_from_correspondences(
-            batch.xyz0.reshape(-1, 3), batch.xyz1.reshape(-1, 3), nn_idx, batch.seg, batch.seg,
-            self.cfg.voxel_size * 1.0, self.cfg.ransac_max_iteration, seed=seed,
-            workspace_budget=self._ransac_budget)                                  # [P, 84] bytes on the device
+        prev = self._degenerate(F.device, 1) if iso else None
+        try:
+            res = reg.ransac_batched_from_correspondences(
+                batch.xyz0.reshape(-1, 3), batch.xyz1.reshape(-1, 3), nn_idx, batch.seg, batch.seg,
+                self.cfg.voxel_size * 1.0, self.cfg.ransac_max_iteration, seed=seed,
+                workspace_budget=self._ransac_budget)                                  # [P, 84] bytes on the device
+        finally:
+            if iso:
+                self._degenerate(F.device, prev)
         self._mark(3)
         return res
 
@@ -402,7 +607,11 @@ class RegistrationPipeline:
     def register(self, batch: DeviceBatch, seed: int = 0, return_device=False, maps=None):
         """One pass of the hot path over ``P`` pairs -> ``T f32 [P,4,4]`` (host) and per-pair stats."""
         self._mark(0)
-        F = self.features(batch, maps).F
+        F, batch = self._features(batch, maps)   # isolate_failures: the batch without the pairs that failed the map build
+        F = F.F
+        if self.cfg.isolate_failures:
+            self.registered_batch, maps = batch, None
+            self.dropped_pairs += int((batch.dropped != 0).sum())
         self._mark(1)
         self.featured = torch.cuda.Event()       # the forward is enqueued: what `prepare_maps(after=)` of the NEXT batch may wait for
         self.featured.record()
@@ -413,13 +622,21 @@ class RegistrationPipeline:
                 return res                # the caller reads back later - and calls model.check_range() then
             words = self._range_snapshot()
             host = res.cpu()
-            return self._checked(batch, seed, maps, words) or [reg.decode_ransac_result(host[p], n) for p in range(batch.P)]
+            return self._checked(batch, seed, maps, words) or self._flagged(batch, [reg.decode_ransac_result(host[p], n) for p in range(batch.P)])
         T = self._match_and_register_sc2(batch, F, seed)
         if return_device:
             return T
         words = self._range_snapshot()
         Th = T.cpu().numpy().astype(np.float64)
-        return self._checked(batch, seed, maps, words) or [reg.RegistrationResult(Th[p], 0.0, 0.0) for p in range(batch.P)]
+        return self._checked(batch, seed, maps, words) or self._flagged(batch, [reg.RegistrationResult(Th[p], 0.0, 0.0) for p in range(batch.P)])
+
+    def _flagged(self, batch, results):
+        """isolate_failures: a dropped pair's result - the failed record (T all NaN, fitness 0, no inliers, best_hypothesis -1) with the
+        pair's DROPPED_* bits in ``status``."""
+        if self.cfg.isolate_failures:
+            for p in np.flatnonzero(batch.dropped):
+                results[p] = reg.RegistrationResult(np.full((4, 4), np.nan), 0.0, 0.0, status=int(batch.dropped[p]))
+        return results
 
     def _range_snapshot(self):
         """The range guard's words on their way to pinned memory, enqueued IN FRONT of the result read-back: the read-back's own
@@ -451,10 +668,15 @@ class RegistrationPipeline:
         m = self.matcher
         P = batch.P
         dev = F.device
+        # isolate_failures: the per-pair arrays hold the live pairs only, back to back (``L`` of them; live pair ``p`` is block ``q``);
+        # the draws are still made for all P, so that a live pair's do not depend on who was dropped, and the back-end gets an empty
+        # segment for a dropped pair.  Without dropped pairs ``q == p`` and ``L == P``.
+        live = np.flatnonzero(batch.dropped == 0)
+        L = len(live)
         if m.num_node == 'all':
             nn_pts = n
             src_k, tgt_k = batch.xyz0.reshape(-1, 3), batch.xyz1.reshape(-1, 3)
-            seg = np.arange(P + 1) * nn_pts
+            seg = np.arange(L + 1) * nn_pts
             nn = knn1_segmented(F0, F1, seg, seg, "GemmL2", return_distance=False)      # match_pair's own formula
             self._mark(2)
             self.matched = torch.cuda.Event()
@@ -466,7 +688,7 @@ class RegistrationPipeline:
             draws = rng.randint(0, n, (P, 2, nn_pts)).astype(np.int64, copy=False)
             us, ut, inv, first, seg_a, seg_b = [], [], [], [], [0], [0]
             pos = np.arange(nn_pts, dtype=np.int64)
-            for p in range(P):
+            for q, p in enumerate(live):
                 d0, d1 = draws[p, 0], draws[p, 1]
                 present = np.zeros(n, bool)
                 present[d0] = True
@@ -476,12 +698,16 @@ class RegistrationPipeline:
                 np.minimum.at(fst, d1, pos)                                     # first draw of every target row
                 f1 = np.flatnonzero(fst[d1] == pos)                             # the first draws, ascending: distinct targets in that order
                 u1 = d1[f1]
-                us.append(u0 + p * n); inv.append(i0 + seg_a[-1])
-                ut.append(u1 + p * n); first.append(f1 + p * nn_pts)
+                us.append(u0 + q * n); inv.append(i0 + seg_a[-1])
+                ut.append(u1 + q * n); first.append(f1 + q * nn_pts)
                 seg_a.append(seg_a[-1] + len(u0)); seg_b.append(seg_b[-1] + len(u1))
-            draws += (np.arange(P, dtype=np.int64) * n)[:, None, None]
+            if L < P:
+                draws = draws[live]                       # the dropped pairs' draws stay out of the upload
+            draws += (np.arange(L, dtype=np.int64) * n)[:, None, None]
             gsi, gti = draws[:, 0].reshape(-1), draws[:, 1].reshape(-1)
             base_u = np.repeat(np.asarray(seg_b[:-1], np.int64), np.diff(seg_a))     # distinct source row -> first distinct target of its pair
+            if L == 0:
+                inv = us = ut = first = [np.zeros(0, np.int64)]
             parts = [gsi, gti, np.concatenate(inv), np.concatenate(us), np.concatenate(ut), np.concatenate(first), base_u]
             cuts = np.cumsum([0] + [len(a) for a in parts])
             # ONE upload, from pinned memory: a copy from pageable memory blocks the host until everything enqueued on this stream
@@ -501,36 +727,50 @@ class RegistrationPipeline:
             nn = first_d.index_select(0, nn_u + base_d).index_select(0, inv_d)
         keep = min(nn_pts, int(m.max_points))                                            # SC2_PCR.py:318-319 truncation
         if m.num_node == 'all':
-            base = torch.arange(P, device=dev).repeat_interleave(nn_pts) * nn_pts       # local -> packed target row
+            base = torch.arange(L, device=dev).repeat_interleave(nn_pts) * nn_pts       # local -> packed target row
             nn = nn + base
         tgt_m = tgt_k.index_select(0, nn)
         if keep < nn_pts:
-            src_k = src_k.reshape(P, nn_pts, 3)[:, :keep].reshape(-1, 3)
-            tgt_m = tgt_m.reshape(P, nn_pts, 3)[:, :keep].reshape(-1, 3)
-        T, _, _ = m.SC2_PCR_packed(src_k.contiguous(), tgt_m.contiguous(), np.arange(P + 1) * keep)
+            src_k = src_k.reshape(L, nn_pts, 3)[:, :keep].reshape(-1, 3)
+            tgt_m = tgt_m.reshape(L, nn_pts, 3)[:, :keep].reshape(-1, 3)
+        iso = self.cfg.isolate_failures
+        prev = self._degenerate(dev, 1) if iso else None
+        try:
+            T, _, _ = m.SC2_PCR_packed(src_k.contiguous(), tgt_m.contiguous(), live_segments(batch.dropped, keep))
+        finally:
+            if iso:
+                self._degenerate(dev, prev)
         self._mark(3)
         return T
 
     def correspondence_inlier_ratio(self, batch: DeviceBatch, nn_idx=None, thresh=None):
         """Diagnostic (outside the timed path): per pair, the fraction of the feature correspondences of the last
         RANSAC-path ``register`` whose ground-truth residual ``|T_gt x0 - x1|`` is below ``thresh`` (default: the
-        RANSAC distance threshold)."""
+        RANSAC distance threshold).  Under ``isolate_failures`` pass the batch the step ran on (``registered_batch``); a dropped
+        pair's ratio is NaN."""
         nn_idx = self.last_nn_idx if nn_idx is None else nn_idx
         thresh = self.cfg.voxel_size if thresh is None else thresh
         n = batch.n_points
-        nn = nn_idx.cpu().numpy().reshape(batch.P, n)
+        nn = nn_idx.cpu().numpy().reshape(-1, n)                     # the live pairs' rows, back to back
         x0, x1 = batch.xyz0.cpu().numpy(), batch.xyz1.cpu().numpy()
-        out = []
+        out, q = [], 0
         for p in range(batch.P):
+            if batch.dropped[p]:                                     # a dropped pair has no correspondences
+                out.append(float("nan"))
+                continue
             T = batch.T_gt[p].astype(np.float64)
-            r = x0[p].astype(np.float64) @ T[:3, :3].T + T[:3, 3] - x1[p][nn[p]]
+            r = x0[q].astype(np.float64) @ T[:3, :3].T + T[:3, 3] - x1[q][nn[q]]
             out.append(float((np.linalg.norm(r, axis=1) < thresh).mean()))
+            q += 1
         return out
 
     def evaluate(self, batch: DeviceBatch, results):
         """RTE / RRE / success per pair (scripts/test_kitti.py:187-211)."""
         rows = []
         for p, r in enumerate(results):
+            if r.status & DROPPED:                                   # a dropped pair: a failure, and no errors to compute on NaN
+                rows.append({"rte": float("nan"), "rre_deg": float("nan"), "success": False})
+                continue
             rte, rre, ok = registration_errors(r.transformation.astype(np.float32), batch.T_gt[p],
                                                self.cfg.rte_thresh, self.cfg.rre_thresh)
             rows.append({"rte": rte, "rre_deg": float(np.rad2deg(rre)), "success": ok})

@@ -30,7 +30,8 @@ class RegistrationResult:
     inliers: int = 0
     best_hypothesis: int = -1
     survivors: int = 0
-    status: int = 0                 # harness.RETRIED_FP32 when the step was registered again in fp32 (fp32_retry_per_step)
+    status: int = 0                 # harness.RETRIED_FP32 when the step was registered again in fp32 (fp32_retry_per_step);
+                                    # harness.DROPPED_* when the pair was dropped from its batch (isolate_failures)
 
 
 def ransac_from_correspondences(src, tgt, corr_tgt, max_correspondence_distance, max_iteration=4000000, seed=0,

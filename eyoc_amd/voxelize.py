@@ -71,7 +71,7 @@ def _batch_layout(clouds, voxel_size, batch_base):
     return widths.pop(), offsets
 
 
-def sparse_quantize_batch(clouds, voxel_size: float, batch_base: int = 0, device=None):
+def sparse_quantize_batch(clouds, voxel_size: float, batch_base: int = 0, device=None, isolate: bool = False):
     """``sparse_quantize`` of B raw clouds and their ``sparse_collate`` in one call with one stream synchronisation
     (lib/data_loaders.py:940-943,969-979 per cloud, then :31-85).
 
@@ -79,7 +79,11 @@ def sparse_quantize_batch(clouds, voxel_size: float, batch_base: int = 0, device
     Host clouds are packed into one pinned buffer and uploaded with one copy.  ``device``: where host-only input goes (default: the
     current device).  Returns device tensors ``(coords int32 [M,4] = (batch_base + b, floor(p / voxel)), sel int64 [M] = index of the
     kept point within its cloud, xyz f32 [M,3] = the kept points)`` and the clouds' row ranges ``offsets np.int64 [B+1]`` - bit for bit
-    the concatenation of ``sparse_quantize(clouds[b], voxel_size, batch_base + b)``."""
+    the concatenation of ``sparse_quantize(clouds[b], voxel_size, batch_base + b)``.
+
+    ``isolate=True`` (``eyoc_voxelize_batched_isolating``): a point outside the key range or with a NaN / inf coordinate no longer fails
+    the call; a fifth value comes back, ``faults np.int32 [B,2]`` = per cloud the finite points out of range and the non-finite points,
+    and a cloud with a count has an empty row range.  The other clouds' rows are those of the plain call."""
     clouds = list(clouds)
     width, pt_off = _batch_layout(clouds, voxel_size, batch_base)
     B, n = len(clouds), int(pt_off[-1])
@@ -89,9 +93,11 @@ def sparse_quantize_batch(clouds, voxel_size: float, batch_base: int = 0, device
     dev = torch.device(device) if device is not None else on_dev[0].device if on_dev else torch.device("cuda")
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
+    faults = np.zeros((B, 2), np.int32)
     if n == 0:
-        return (torch.empty((0, 4), dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
-                torch.empty((0, 3), dtype=torch.float32, device=dev), np.zeros(B + 1, np.int64))
+        empty = (torch.empty((0, 4), dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+                 torch.empty((0, 3), dtype=torch.float32, device=dev), np.zeros(B + 1, np.int64))
+        return empty + (faults,) if isolate else empty
     lib = _lib.load()
     vox_off = np.zeros(B + 1, np.int64)
     i64 = C.POINTER(C.c_int64)
@@ -108,13 +114,19 @@ def sparse_quantize_batch(clouds, voxel_size: float, batch_base: int = 0, device
         sel = torch.empty(n, dtype=torch.int32, device=dev)
         coords = torch.empty((n, 4), dtype=torch.int32, device=dev)
         xyz = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        ws = _lib.workspace(lib.eyoc_voxelize_batched_workspace_bytes(n, B), dev)
-        _lib.check(lib.eyoc_voxelize_batched(_lib.ctx(dev.index), _lib.ptr(packed), width, pt_off.ctypes.data_as(i64), B, n,
-                                             float(voxel_size), int(batch_base), _lib.ptr(sel), _lib.ptr(coords), _lib.ptr(xyz),
-                                             vox_off.ctypes.data_as(i64), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
-                   "eyoc_voxelize_batched")
+        args = (_lib.ptr(packed), width, pt_off.ctypes.data_as(i64), B, n, float(voxel_size), int(batch_base), _lib.ptr(sel),
+                _lib.ptr(coords), _lib.ptr(xyz), vox_off.ctypes.data_as(i64))
+        if isolate:
+            ws = _lib.workspace(lib.eyoc_voxelize_batched_isolating_workspace_bytes(n, B), dev)
+            _lib.check(lib.eyoc_voxelize_batched_isolating(_lib.ctx(dev.index), *args, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(),
+                                                           faults.ctypes.data), "eyoc_voxelize_batched_isolating")
+        else:
+            ws = _lib.workspace(lib.eyoc_voxelize_batched_workspace_bytes(n, B), dev)
+            _lib.check(lib.eyoc_voxelize_batched(_lib.ctx(dev.index), *args, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                       "eyoc_voxelize_batched")
     m = int(vox_off[-1])
-    return coords[:m], sel[:m].long(), xyz[:m], vox_off
+    out = coords[:m], sel[:m].long(), xyz[:m], vox_off
+    return out + (faults,) if isolate else out
 
 
 def voxelize(xyz, voxel_size: float, batch_index: int = 0):

@@ -44,6 +44,8 @@ typedef enum {
 /* 111 (round 6): eyoc_model_desc ends with `expanded` (ResUNetExpanded / ResUNetExpBN2C run through eyoc_model_forward too).
  *     Later libraries of 111 add two entry points and change nothing else: eyoc_maps_last_fault_batches and
  *     eyoc_registration_accept_degenerate (a binding checks for the symbols).
+ *     Later still, per-pair failure isolation adds eyoc_batch_drop(_workspace_bytes), eyoc_remap_rows and
+ *     eyoc_voxelize_batched_isolating(_workspace_bytes), again found by symbol; nothing that existed changes.
  * 110 (round 6): the kernel-selection setters and eyoc_ransac_workspace_bytes take the ctx first (round 5), eyoc_maps_gather_window
  * refuses Z-ordered maps again and eyoc_maps_gather_window_internal exists, eyoc_model_workspace_bytes depends on the maps' size class */
 #define EYOC_VERSION 111
@@ -199,6 +201,33 @@ int eyoc_voxelize_batched(eyoc_ctx* ctx, const float* xyz_dev, int stride, const
                           int n_points, float voxel_size, int batch_base, int32_t* sel_dev, int32_t* coords_dev,
                           float* xyz_out_dev, int64_t* voxel_offsets, void* workspace_dev, size_t workspace_bytes,
                           void* stream);
+/* The same call for a caller that isolates failures: instead of failing on a bad point it counts, per cloud, the finite points
+ * outside the key range (cloud_faults[b][0]) and the points with a NaN / +-inf in x, y or z (cloud_faults[b][1]; HOST out, int32
+ * [n_clouds][2]) and returns EYOC_OK.  A cloud with a non-zero count contributes NO voxels (its range in voxel_offsets is empty);
+ * every other cloud's rows are bit for bit those of eyoc_voxelize_batched, at the same batch index.  The counts come back with the
+ * call's one read-back.  The workspace holds two more counters per cloud. */
+size_t eyoc_voxelize_batched_isolating_workspace_bytes(int n_points_total, int n_clouds);
+int eyoc_voxelize_batched_isolating(eyoc_ctx* ctx, const float* xyz_dev, int stride, const int64_t* point_offsets, int n_clouds,
+                                    int n_points, float voxel_size, int batch_base, int32_t* sel_dev, int32_t* coords_dev,
+                                    float* xyz_out_dev, int64_t* voxel_offsets, void* workspace_dev, size_t workspace_bytes,
+                                    void* stream, int32_t* cloud_faults);
+
+/* ------------------------------------------------------------------------------------------------
+ * per-pair failure isolation: drop clouds from a collated batch
+ *   coords_dev int32 [n,4] (batch, x, y, z), feats_dev f32 [n,c] or NULL, rows in any order (clouds may interleave).
+ *   drop_mask (HOST, 32 words, the layout of eyoc_maps_last_fault_batches): bit b set = every row of batch index b goes; rows whose
+ *   batch index is outside [0, 1024) stay.  Outputs (room for n rows each; not in place): the kept rows' coordinates and features
+ *   in input order with their batch indices UNCHANGED (a map build accepts gaps), row_map int32 [n] = old row -> new row, -1 for a
+ *   dropped row.  n_kept (HOST out): the kept rows; kept_per_batch (HOST out, int32 [1024], or NULL): the kept rows of every batch
+ *   index.  Deterministic (no atomics on the data path).  Stream-ordered on `stream`, which it synchronises once (the counts);
+ *   n = 0 launches nothing.  eyoc_remap_rows: out[k] = row_map[idx[k]] (-1 for an index outside [0, n)); out == idx is allowed.
+ * --------------------------------------------------------------------------------------------- */
+size_t eyoc_batch_drop_workspace_bytes(int n_rows);
+int eyoc_batch_drop(eyoc_ctx* ctx, const int32_t* coords_dev, const float* feats_dev, int n_rows, int c, const uint32_t* drop_mask,
+                    int32_t* coords_out_dev, float* feats_out_dev, int32_t* row_map_dev, int* n_kept, int32_t* kept_per_batch,
+                    void* workspace_dev, size_t workspace_bytes, void* stream);
+int eyoc_remap_rows(eyoc_ctx* ctx, const int64_t* idx_dev, int m, const int32_t* row_map_dev, int n_rows, int64_t* out_dev,
+                    void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * one sparse convolution layer (unit tests, profiling)
