@@ -51,6 +51,16 @@ class Sc2pcrParams(C.Structure):
                 ("k1", C.c_int32), ("k2", C.c_int32)]
 
 
+class IcpParams(C.Structure):
+    _fields_ = [("max_distance", C.c_double), ("relative_fitness", C.c_double), ("relative_rmse", C.c_double),
+                ("max_iteration", C.c_int32), ("flags", C.c_int32)]
+
+
+class IcpResult(C.Structure):
+    _fields_ = [("T", C.c_double * 16), ("fitness", C.c_double), ("inlier_rmse", C.c_double), ("correspondences", C.c_int32),
+                ("iterations", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 # name -> (restype, argtypes); every symbol include/eyoc_hip.h declares
 PROTOTYPES = {
@@ -172,6 +182,11 @@ PROTOTYPES = {
     "eyoc_sc2pcr_select_kernels": (_i, [_vp, _i]),
     "eyoc_sc2pcr_batched": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(Sc2pcrParams), _vp, _vp, _i, _vp, _sz,
                                  _vp]),
+    "eyoc_icp_workspace_bytes": (_sz, [_i, _i, _i]),
+    "eyoc_icp_batched": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _vp, C.POINTER(IcpParams), _vp, _vp,
+                              _vp, _sz, _vp]),
+    "eyoc_icp_correspondences": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _vp, C.c_double, _vp, _vp,
+                                      _vp, _vp, _sz, _vp]),
 }
 
 

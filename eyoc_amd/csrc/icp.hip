@@ -1,0 +1,438 @@
+// Batched point-to-point ICP on a device-side cell grid (include/eyoc_hip.h, "ICP refinement").
+//
+// One call = one grid build + (max_iteration + 1) evaluations, nothing read back in between:
+//   k_icp_init   one thread per pair: T = init, BAD_INIT / empty-segment (FEW) pairs are finished here
+//   k_icp_keys   one thread per target / source row: cell key (pair << 54 | biased cell), RANGE for non-finite points and target
+//                cells outside the key range; the source key is the cell of the point under the initial pose
+//   2 x rocPRIM radix sort (stable, pair index in the top key bits: a pair's order never depends on its neighbours)
+//   k_icp_build  target points into sorted order (x, y, z, row local to the pair) + open-addressing table key -> (first row, count), 16 bytes per slot;
+//                integer atomics only - which slot a key lands in may differ from run to run, what a lookup returns does not
+//   k_icp_eval   256 sorted source rows of one pair per workgroup, lane = row: pose in fp64, probe the 27 cells, reduce the 17 sums
+//                lane -> wave -> workgroup in a fixed order, ONE partial record per workgroup (no floating-point atomics)
+//   k_icp_solve  one wave per pair: partials in a fixed order (lane l takes workgroups l, l + 64, ..., then the shuffle tree), fitness / rmse, convergence, Kabsch, T = U T, done flag
+// The evaluation's arithmetic is the contract's expression evaluated in fp64 without contraction (no FMA), so d2 does not depend on
+// how the compiler schedules it.
+#include <cmath>
+
+#include "common.h"
+#include "pose_math.h"
+
+namespace eyoc {
+namespace {
+
+constexpr int ICP_BLOCK = 256;
+constexpr int ICP_CHUNK = 64;      // pairs per set of launches: their segments travel as kernel arguments
+constexpr int ICP_SUMS = 17;       // count, sum d2, sum p (3), sum q (3), sum p q^T (9)
+constexpr double CELL_LIMIT = 131072.0;   // |cell| < 2^17 (COORD_BIAS)
+
+struct IcpSegs {
+  int n_pairs;
+  int src[ICP_CHUNK + 1], tgt[ICP_CHUNK + 1];
+  int wg[ICP_CHUNK + 1];     // first evaluation workgroup of every pair
+};
+
+__device__ inline int pair_of(const int* seg, int n_pairs, int row) {   // seg ascending, row < seg[n_pairs]
+  int b = 0;
+  while (b + 1 < n_pairs && seg[b + 1] <= row) ++b;
+  return b;
+}
+
+// cell of one fp64 coordinate: false when it is not finite or outside the key range (nothing is cast then)
+__device__ inline bool cell_of(double v, double edge, int* c) {
+  const double f = floor(v / edge);
+  if (!(f >= -CELL_LIMIT && f < CELL_LIMIT)) return false;   // NaN fails both comparisons
+  *c = (int)f;
+  return true;
+}
+
+__global__ void k_icp_init(IcpSegs s, const double* __restrict__ init, eyoc_icp_result* __restrict__ res, int* __restrict__ done) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= s.n_pairs) return;
+  eyoc_icp_result r;
+  bool finite = true;
+  for (int k = 0; k < 16; ++k) {
+    r.T[k] = init ? init[(size_t)b * 16 + k] : (k % 5 == 0 ? 1.0 : 0.0);
+    finite = finite && isfinite(r.T[k]);
+  }
+  r.fitness = 0.0; r.inlier_rmse = 0.0;
+  r.correspondences = 0; r.iterations = 0; r.reserved = 0;
+  r.status = 0;
+  if (!finite) r.status = EYOC_ICP_BAD_INIT;
+  else if (s.src[b + 1] == s.src[b] || s.tgt[b + 1] == s.tgt[b]) r.status = EYOC_ICP_FEW;
+  res[b] = r;
+  done[b] = r.status != 0;
+}
+
+__global__ __launch_bounds__(ICP_BLOCK) void k_icp_keys(IcpSegs s, const float* __restrict__ src, const float* __restrict__ tgt, double edge,
+                                                        eyoc_icp_result* __restrict__ res, int* __restrict__ done,
+                                                        unsigned long long* __restrict__ tkey, int* __restrict__ trow,
+                                                        unsigned long long* __restrict__ skey, int* __restrict__ srow,
+                                                        int32_t* __restrict__ corr, double* __restrict__ d2) {
+  const int n_tgt = s.tgt[s.n_pairs], n_src = s.src[s.n_pairs];
+  int i = blockIdx.x * ICP_BLOCK + threadIdx.x;
+  if (i < n_tgt) {
+    const int b = pair_of(s.tgt, s.n_pairs, i);
+    trow[i] = i;
+    unsigned long long key = pack_key(b, -COORD_BIAS, -COORD_BIAS, -COORD_BIAS);
+    if (!(res[b].status & EYOC_ICP_BAD_INIT)) {       // a pair with a bad init has nothing else read
+      int c[3];
+      bool ok = true;
+      for (int k = 0; k < 3; ++k) {
+        const float v = tgt[(size_t)i * 3 + k];
+        ok = ok && isfinite(v) && cell_of((double)v, edge, &c[k]);
+      }
+      if (ok) key = pack_key(b, c[0], c[1], c[2]);
+      else { atomicOr(&res[b].status, EYOC_ICP_RANGE); done[b] = 1; }
+    }
+    tkey[i] = key;
+    return;
+  }
+  i -= n_tgt;
+  if (i >= n_src) return;
+  const int b = pair_of(s.src, s.n_pairs, i);
+  srow[i] = i;
+  if (corr) corr[i] = -1;
+  if (d2) d2[i] = INFINITY;
+  unsigned long long key = pack_key(b, -COORD_BIAS, -COORD_BIAS, -COORD_BIAS);
+  if (!(res[b].status & EYOC_ICP_BAD_INIT)) {
+    const double x = src[(size_t)i * 3], y = src[(size_t)i * 3 + 1], z = src[(size_t)i * 3 + 2];
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) {
+      atomicOr(&res[b].status, EYOC_ICP_RANGE);
+      done[b] = 1;
+    } else {
+      // the order of the source rows only decides which lanes share a wave: a posed point outside the key range keeps the lowest key
+      const double* T = res[b].T;
+      int c[3];
+      bool ok = true;
+      for (int k = 0; k < 3; ++k) ok = ok && cell_of(T[4 * k] * x + T[4 * k + 1] * y + T[4 * k + 2] * z + T[4 * k + 3], edge, &c[k]);
+      if (ok) key = pack_key(b, c[0], c[1], c[2]);
+    }
+  }
+  skey[i] = key;
+}
+
+// one slot of the open-addressing table: 16 bytes, so that a probe is ONE load.  The table is filled with 0xFF bytes: key = KEY_EMPTY
+// and more = -1, i.e. the slot's run holds more + 1 rows starting at sorted row first.
+struct __align__(16) IcpCell {
+  unsigned long long key;
+  int first, more;
+};
+
+struct IcpGrid {
+  const IcpCell* cells;
+  unsigned int mask;
+  const float4* pts;     // sorted target points: x, y, z, row local to the pair (int bits)
+};
+
+__device__ inline IcpCell load_cell(const IcpCell* cells, unsigned int slot) {
+  const uint4 v = *reinterpret_cast<const uint4*>(cells + slot);
+  IcpCell c;
+  c.key = (unsigned long long)v.x | ((unsigned long long)v.y << 32);
+  c.first = (int)v.z; c.more = (int)v.w;
+  return c;
+}
+
+__global__ __launch_bounds__(ICP_BLOCK) void k_icp_build(IcpSegs s, const float* __restrict__ tgt, const unsigned long long* __restrict__ key_sorted,
+                                                         const int* __restrict__ row_sorted, const int* __restrict__ done, float4* __restrict__ pts,
+                                                         IcpCell* __restrict__ cells, unsigned int mask) {
+  const int i = blockIdx.x * ICP_BLOCK + threadIdx.x;
+  if (i >= s.tgt[s.n_pairs]) return;
+  const unsigned long long key = key_sorted[i];
+  const int b = (int)(key >> 54), row = row_sorted[i];
+  pts[i] = make_float4(tgt[(size_t)row * 3], tgt[(size_t)row * 3 + 1], tgt[(size_t)row * 3 + 2], __int_as_float(row - s.tgt[b]));
+  if (done[b]) return;      // never searched (and a RANGE pair's keys mean nothing)
+  unsigned int slot = hash_key(key) & mask;
+  for (unsigned int probes = 0; probes <= mask; ++probes) {     // bounded: capacity >= 2 x rows
+    const unsigned long long seen = atomicCAS(&cells[slot].key, KEY_EMPTY, key);
+    if (seen == KEY_EMPTY || seen == key) {
+      atomicAdd(&cells[slot].more, 1);
+      if (i == 0 || key_sorted[i - 1] != key) cells[slot].first = i;
+      return;
+    }
+    slot = (slot + 1) & mask;
+  }
+}
+
+#pragma clang fp contract(off)
+__global__ __launch_bounds__(ICP_BLOCK) void k_icp_eval(IcpSegs s, const float* __restrict__ src, const int* __restrict__ srow_sorted, IcpGrid g,
+                                                        double edge, double r2, const eyoc_icp_result* __restrict__ res,
+                                                        const int* __restrict__ done, double* __restrict__ partial,
+                                                        int32_t* __restrict__ corr, double* __restrict__ d2_out) {
+  __shared__ int sb;
+  __shared__ double red[ICP_BLOCK / 64][ICP_SUMS];
+  if (threadIdx.x == 0) sb = pair_of(s.wg, s.n_pairs, blockIdx.x);
+  __syncthreads();
+  const int b = sb;
+  if (done[b]) return;                                   // uniform per workgroup
+  const int local = (blockIdx.x - s.wg[b]) * ICP_BLOCK + threadIdx.x;   // counted from the pair's own first row
+  const bool live = local < s.src[b + 1] - s.src[b];
+  double v[ICP_SUMS];
+#pragma unroll
+  for (int k = 0; k < ICP_SUMS; ++k) v[k] = 0.0;
+  if (live) {
+    const int row = srow_sorted[s.src[b] + local];
+    const double* T = res[b].T;
+    const double x = src[(size_t)row * 3], y = src[(size_t)row * 3 + 1], z = src[(size_t)row * 3 + 2];
+    double p[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = T[4 * k] * x + T[4 * k + 1] * y + T[4 * k + 2] * z + T[4 * k + 3];
+    int c[3];
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ok = ok && cell_of(p[k], edge, &c[k]);
+    double best = INFINITY;
+    int best_row = -1;
+    float4 best_q = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ok) {
+      for (int ox = -1; ox <= 1; ++ox) {
+        // the first probes of a plane's 9 cells are independent loads: issued together, then resolved one by one
+        unsigned long long key[9];
+        unsigned int slot[9];
+        IcpCell cell[9];
+        const int cx = c[0] + ox;
+#pragma unroll
+        for (int o = 0; o < 9; ++o) {
+          const int cy = c[1] + o / 3 - 1, cz = c[2] + o % 3 - 1;
+          const bool inside = cx >= -COORD_BIAS && cx < COORD_BIAS && cy >= -COORD_BIAS && cy < COORD_BIAS && cz >= -COORD_BIAS && cz < COORD_BIAS;
+          key[o] = inside ? pack_key(b, cx, cy, cz) : KEY_EMPTY;      // KEY_EMPTY is no cell's key (the pair bits are never all ones)
+          slot[o] = hash_key(key[o]) & g.mask;
+          cell[o] = load_cell(g.cells, slot[o]);
+        }
+#pragma unroll
+        for (int o = 0; o < 9; ++o) {
+          if (key[o] == KEY_EMPTY) continue;
+          IcpCell e = cell[o];
+          unsigned int sl = slot[o];
+          for (unsigned int probes = 0; e.key != key[o] && e.key != KEY_EMPTY && probes < g.mask; ++probes) {   // bounded: never full
+            sl = (sl + 1) & g.mask;
+            e = load_cell(g.cells, sl);
+          }
+          if (e.key != key[o]) continue;
+          // the run's points four at a time: the loads of a group are issued together (the index is clamped inside the run, a
+          // repeated point is not evaluated twice)
+          const int n = e.more + 1;
+          for (int j = 0; j < n; j += 4) {
+            float4 q4[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) q4[u] = g.pts[e.first + (j + u < n ? j + u : n - 1)];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              if (j + u >= n) break;
+              const float4 q = q4[u];
+              const double dx = p[0] - (double)q.x, dy = p[1] - (double)q.y, dz = p[2] - (double)q.z;
+              const double d = dx * dx + dy * dy + dz * dz;
+              const int qrow = __float_as_int(q.w);
+              if (d < best || (d == best && qrow < best_row)) { best = d; best_row = qrow; best_q = q; }
+            }
+          }
+        }
+      }
+    }
+    const bool hit = best_row >= 0 && best < r2;
+    if (corr) corr[row] = hit ? best_row : -1;
+    if (d2_out) d2_out[row] = hit ? best : INFINITY;
+    if (hit) {
+      const double q[3] = {(double)best_q.x, (double)best_q.y, (double)best_q.z};
+      v[0] = 1.0; v[1] = best;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        v[2 + k] = p[k]; v[5 + k] = q[k];
+#pragma unroll
+        for (int l = 0; l < 3; ++l) v[8 + 3 * k + l] = p[k] * q[l];
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < ICP_SUMS; ++k) {
+    const double w = wave_sum(v[k]);
+    if (lane == 0) red[wave][k] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < ICP_SUMS) {
+    double t = red[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < ICP_BLOCK / 64; ++w) t += red[w][threadIdx.x];
+    partial[(size_t)blockIdx.x * ICP_SUMS + threadIdx.x] = t;
+  }
+}
+
+// evaluation `e` (0 = the one under the initial pose) of every pair that is still running
+__global__ __launch_bounds__(64) void k_icp_solve(IcpSegs s, const double* __restrict__ partial, eyoc_icp_result* __restrict__ res,
+                                                  int* __restrict__ done, int e, int max_iteration, double rel_fitness, double rel_rmse) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (done[b]) return;
+  // a fixed order that only depends on the pair's own workgroup count: lane l adds workgroups l, l + 64, ... in that order, then the
+  // wave's shuffle tree adds the lanes
+  double S[ICP_SUMS];
+#pragma unroll
+  for (int k = 0; k < ICP_SUMS; ++k) S[k] = 0.0;
+  for (int w = s.wg[b] + lane; w < s.wg[b + 1]; w += 64)
+#pragma unroll
+    for (int k = 0; k < ICP_SUMS; ++k) S[k] += partial[(size_t)w * ICP_SUMS + k];
+#pragma unroll
+  for (int k = 0; k < ICP_SUMS; ++k) S[k] = wave_sum(S[k]);
+  if (lane != 0) return;
+  eyoc_icp_result& r = res[b];
+  const double n = S[0];
+  const double fitness = n / (double)(s.src[b + 1] - s.src[b]);
+  const double rmse = n > 0.0 ? sqrt(S[1] / n) : 0.0;
+  const bool converged = e > 0 && fabs(r.fitness - fitness) < rel_fitness && fabs(r.inlier_rmse - rmse) < rel_rmse;
+  r.fitness = fitness; r.inlier_rmse = rmse;
+  r.correspondences = (int)n; r.iterations = e;
+  int status = r.status;
+  if (converged) status |= EYOC_ICP_CONVERGED;
+  if (n < 3.0) status |= EYOC_ICP_FEW;
+  r.status = status;
+  if (converged || n < 3.0 || e >= max_iteration) { done[b] = 1; return; }
+  double cp[3], cq[3], H[3][3], R[3][3];
+  for (int k = 0; k < 3; ++k) { cp[k] = S[2 + k] / n; cq[k] = S[5 + k] / n; }
+  for (int k = 0; k < 3; ++k)
+    for (int l = 0; l < 3; ++l) H[k][l] = S[8 + 3 * k + l] - n * cp[k] * cq[l];
+  kabsch_rotation(H, R);
+  double t[3], Tn[12];
+  for (int k = 0; k < 3; ++k) t[k] = cq[k] - (R[k][0] * cp[0] + R[k][1] * cp[1] + R[k][2] * cp[2]);
+  for (int k = 0; k < 3; ++k) {
+    for (int l = 0; l < 4; ++l) Tn[4 * k + l] = R[k][0] * r.T[l] + R[k][1] * r.T[4 + l] + R[k][2] * r.T[8 + l];
+    Tn[4 * k + 3] += t[k];
+  }
+  for (int k = 0; k < 12; ++k) r.T[k] = Tn[k];
+}
+
+unsigned int table_capacity(int total_tgt) {
+  unsigned int cap = 64;
+  while (cap < 2u * (unsigned)total_tgt) cap <<= 1;
+  return cap;
+}
+
+struct IcpWorkspace {
+  unsigned long long *tkey, *tkey_sorted, *skey, *skey_sorted;
+  IcpCell* cells;
+  int *trow, *trow_sorted, *srow, *srow_sorted, *done;
+  float4* pts;
+  double* partial;
+  void* sort_tmp;
+  size_t sort_bytes;
+  unsigned int cap;
+};
+
+// the layout for the LARGEST chunk a call with these totals can hold (every chunk reuses it)
+size_t carve(void* base, size_t bytes, int n_pairs, int total_src, int total_tgt, IcpWorkspace* w) {
+  Carver c(base, bytes);
+  const int chunk = n_pairs < ICP_CHUNK ? n_pairs : ICP_CHUNK;
+  w->cap = table_capacity(total_tgt);
+  w->tkey = c.take<unsigned long long>(total_tgt);
+  w->tkey_sorted = c.take<unsigned long long>(total_tgt);
+  w->skey = c.take<unsigned long long>(total_src);
+  w->skey_sorted = c.take<unsigned long long>(total_src);
+  w->cells = c.take<IcpCell>(w->cap);
+  w->trow = c.take<int>(total_tgt);
+  w->trow_sorted = c.take<int>(total_tgt);
+  w->srow = c.take<int>(total_src);
+  w->srow_sorted = c.take<int>(total_src);
+  w->done = c.take<int>(chunk > 0 ? chunk : 1);
+  w->pts = c.take<float4>(total_tgt);
+  w->partial = c.take<double>(((size_t)cdiv(total_src, ICP_BLOCK) + chunk + 1) * ICP_SUMS);
+  const size_t a = sort_rows64_tmp_bytes(total_tgt > 0 ? total_tgt : 1), b = sort_rows64_tmp_bytes(total_src > 0 ? total_src : 1);
+  w->sort_bytes = a > b ? a : b;
+  w->sort_tmp = c.take<char>(w->sort_bytes);
+  return align_up(c.off);
+}
+
+// one chunk of <= ICP_CHUNK pairs; every pointer is already that of the chunk's first row
+int run_chunk(const float* src, const float* tgt, const int32_t* seg_src, const int32_t* seg_tgt, int n_pairs, const double* init,
+              const eyoc_icp_params& p, eyoc_icp_result* res, int32_t* corr, double* d2, const IcpWorkspace& w, hipStream_t st) {
+  IcpSegs s;
+  s.n_pairs = n_pairs;
+  for (int b = 0; b <= n_pairs; ++b) {
+    s.src[b] = seg_src[b] - seg_src[0];
+    s.tgt[b] = seg_tgt[b] - seg_tgt[0];
+  }
+  s.wg[0] = 0;
+  for (int b = 0; b < n_pairs; ++b) s.wg[b + 1] = s.wg[b] + cdiv(s.src[b + 1] - s.src[b], ICP_BLOCK);
+  const int n_src = s.src[n_pairs], n_tgt = s.tgt[n_pairs], n_wg = s.wg[n_pairs];
+  const double edge = p.max_distance, r2 = p.max_distance * p.max_distance;
+  hipLaunchKernelGGL(k_icp_init, dim3(cdiv(n_pairs, 64)), dim3(64), 0, st, s, init, res, w.done);
+  if (n_src + n_tgt > 0)
+    hipLaunchKernelGGL(k_icp_keys, dim3(cdiv((long long)n_src + n_tgt, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, s, src, tgt, edge, res, w.done, w.tkey,
+                       w.trow, w.skey, w.srow, corr, d2);
+  if (n_src == 0 || n_tgt == 0) {       // every pair has an empty segment: k_icp_init finished them all
+    EYOC_CHECK_HIP(hipGetLastError());
+    return EYOC_OK;
+  }
+  int rc = sort_rows_by_key64(w.sort_tmp, w.sort_bytes, w.tkey, w.tkey_sorted, w.trow, w.trow_sorted, n_tgt, 60, st);
+  if (rc != EYOC_OK) return rc;
+  rc = sort_rows_by_key64(w.sort_tmp, w.sort_bytes, w.skey, w.skey_sorted, w.srow, w.srow_sorted, n_src, 60, st);
+  if (rc != EYOC_OK) return rc;
+  EYOC_CHECK_HIP(hipMemsetAsync(w.cells, 0xFF, (size_t)w.cap * sizeof(IcpCell), st));
+  hipLaunchKernelGGL(k_icp_build, dim3(cdiv(n_tgt, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, s, tgt, w.tkey_sorted, w.trow_sorted, w.done, w.pts,
+                     w.cells, w.cap - 1);
+  const IcpGrid g{w.cells, w.cap - 1, w.pts};
+  for (int e = 0; e <= p.max_iteration; ++e) {
+    hipLaunchKernelGGL(k_icp_eval, dim3(n_wg), dim3(ICP_BLOCK), 0, st, s, src, w.srow_sorted, g, edge, r2, res, w.done, w.partial, corr, d2);
+    hipLaunchKernelGGL(k_icp_solve, dim3(n_pairs), dim3(64), 0, st, s, w.partial, res, w.done, e, p.max_iteration, p.relative_fitness,
+                       p.relative_rmse);
+  }
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
+int run(const char* what, eyoc_ctx* ctx, const float* src, const float* tgt, const int32_t* seg_src, const int32_t* seg_tgt, int n_pairs,
+        const double* init, const eyoc_icp_params& p, eyoc_icp_result* res, int32_t* corr, double* d2, void* ws, size_t ws_bytes, void* stream) {
+  EYOC_REQUIRE(ctx && seg_src && seg_tgt && res && ws, EYOC_ERR_INVALID, "%s: NULL argument", what);
+  EYOC_REQUIRE(n_pairs >= 1 && n_pairs <= 1024, EYOC_ERR_INVALID, "%s: n_pairs = %d is outside [1, 1024]", what, n_pairs);
+  EYOC_REQUIRE(((uintptr_t)ws & 255) == 0, EYOC_ERR_INVALID, "%s: workspace must be 256-byte aligned", what);
+  EYOC_REQUIRE(std::isfinite(p.max_distance) && p.max_distance > 0.0, EYOC_ERR_INVALID, "%s: max_distance must be positive and finite", what);
+  EYOC_REQUIRE(p.max_iteration >= 0 && p.max_iteration <= 100000, EYOC_ERR_INVALID, "%s: max_iteration = %d is outside [0, 100000]", what,
+               p.max_iteration);
+  EYOC_REQUIRE(seg_src[0] == 0 && seg_tgt[0] == 0, EYOC_ERR_INVALID, "%s: segments must start at 0", what);
+  for (int b = 0; b < n_pairs; ++b)
+    EYOC_REQUIRE(seg_src[b + 1] >= seg_src[b] && seg_tgt[b + 1] >= seg_tgt[b], EYOC_ERR_INVALID, "%s: segment offsets must not decrease (pair %d)",
+                 what, b);
+  EYOC_REQUIRE((seg_src[n_pairs] == 0 || src) && (seg_tgt[n_pairs] == 0 || tgt), EYOC_ERR_INVALID, "%s: NULL cloud", what);
+  IcpWorkspace w;
+  const size_t need = carve(ws, ws_bytes, n_pairs, seg_src[n_pairs], seg_tgt[n_pairs], &w);
+  EYOC_REQUIRE(ws_bytes >= need, EYOC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (eyoc_icp_workspace_bytes)", what, ws_bytes, need);
+  EYOC_CHECK_HIP(hipSetDevice(ctx->device));
+  for (int b0 = 0; b0 < n_pairs; b0 += ICP_CHUNK) {
+    const int np = n_pairs - b0 < ICP_CHUNK ? n_pairs - b0 : ICP_CHUNK;
+    const size_t so = (size_t)seg_src[b0], to = (size_t)seg_tgt[b0];
+    const int rc = run_chunk(src ? src + 3 * so : nullptr, tgt ? tgt + 3 * to : nullptr, seg_src + b0, seg_tgt + b0, np,
+                             init ? init + 16 * (size_t)b0 : nullptr, p, res + b0, corr ? corr + so : nullptr, d2 ? d2 + so : nullptr, w,
+                             (hipStream_t)stream);
+    if (rc != EYOC_OK) return rc;
+  }
+  return EYOC_OK;
+}
+
+}  // namespace
+}  // namespace eyoc
+
+extern "C" size_t eyoc_icp_workspace_bytes(int n_pairs, int total_src, int total_tgt) {
+  if (n_pairs < 1 || total_src < 0 || total_tgt < 0) return 0;
+  eyoc::IcpWorkspace w;
+  return eyoc::carve(nullptr, 0, n_pairs, total_src, total_tgt, &w);
+}
+
+extern "C" int eyoc_icp_batched(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int32_t* seg_src_host,
+                                const int32_t* seg_tgt_host, int n_pairs, const double* init_dev, const eyoc_icp_params* params,
+                                eyoc_icp_result* results_dev, int32_t* corr_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  EYOC_REQUIRE(params, EYOC_ERR_INVALID, "eyoc_icp_batched: NULL params");
+  EYOC_REQUIRE(std::isfinite(params->relative_fitness) && std::isfinite(params->relative_rmse), EYOC_ERR_INVALID,
+               "eyoc_icp_batched: the convergence thresholds must be finite");
+  return eyoc::run("eyoc_icp_batched", ctx, src_dev, tgt_dev, seg_src_host, seg_tgt_host, n_pairs, init_dev, *params, results_dev, corr_dev,
+                   nullptr, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int eyoc_icp_correspondences(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int32_t* seg_src_host,
+                                        const int32_t* seg_tgt_host, int n_pairs, const double* T_dev, double max_distance, int32_t* corr_dev,
+                                        double* d2_dev, eyoc_icp_result* results_dev, void* workspace_dev, size_t workspace_bytes,
+                                        void* stream) {
+  eyoc_icp_params p;
+  p.max_distance = max_distance;
+  p.relative_fitness = p.relative_rmse = 0.0;
+  p.max_iteration = 0;
+  p.flags = 0;
+  return eyoc::run("eyoc_icp_correspondences", ctx, src_dev, tgt_dev, seg_src_host, seg_tgt_host, n_pairs, T_dev, p, results_dev, corr_dev,
+                   d2_dev, workspace_dev, workspace_bytes, stream);
+}

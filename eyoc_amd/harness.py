@@ -47,6 +47,12 @@ class RegistrationConfig:
     # fails the map build (duplicate rows, rows outside the key range) is dropped from the batch and gets a failed record with its
     # DROPPED_* bits in ``status``; the other pairs of the step are registered as without it
     isolate_failures: bool = False
+    # point-to-point ICP on the pairs' sample sets right after the back-end, started from its poses on the device (eyoc_amd.icp; the
+    # reference refines with Open3D on the CPU, scripts/SC2_PCR/benchmark_utils.py:40-56 behind --use_icp).  The gate defaults to
+    # 2 x voxel_size: the samples are ~one voxel apart, one voxel finds a fifth of them a partner, two voxels 56-67 %
+    icp_refine: bool = False
+    icp_max_correspondence_distance: float | None = None
+    icp_max_iteration: int = 30
 
 
 # ``RegistrationResult.status`` / ``PendingStep.status`` bit: the pair's step overflowed split16 and was registered again in fp32
@@ -323,8 +329,9 @@ class DeviceBatch:
 class PendingStep:
     """A step whose read-back was enqueued with it (``RegistrationPipeline.enqueue``)."""
 
-    def __init__(self, host, words, done, device_result, keep=None, retry=None, dropped=None):
+    def __init__(self, host, words, done, device_result, keep=None, retry=None, dropped=None, icp=None):
         self.host, self.words, self.done, self.device_result = host, words, done, device_result
+        self.icp = icp            # icp_refine: the step's ``eyoc_icp_result`` records, ``uint8 [P, 160]`` in pinned host memory (valid like ``host``)
         self.dropped = dropped    # isolate_failures: the step's DROPPED_* bits per pair (their records are the back-end's failed ones)
         self.keep = keep          # tensors another stream still reads (the features under ``tail_stream``): released by ``wait``
         self.retry = retry        # fp32_retry_per_step: (pipeline, batch, seed, maps, slot) to run the step again in fp32 after an overflow
@@ -341,6 +348,8 @@ class PendingStep:
         if overflow and self.retry is not None:
             pipe, batch, seed, maps, slot = self.retry
             self.host.copy_(pipe._retry_fp32(batch, seed, maps, True, slot).cpu())
+            if self.icp is not None:
+                self.icp.copy_(pipe._icp_dev.cpu())
             self.status |= RETRIED_FP32
         self.retry = None
         return self.host, overflow
@@ -360,6 +369,8 @@ class RegistrationPipeline:
         self.fp32_retries = 0  # fp32_retry_per_step: steps run again in fp32 after a split16 overflow
         self.dropped_pairs = 0  # isolate_failures: pairs that got a failed record because their batch was registered without them
         self.registered_batch = None   # isolate_failures: the batch the last step actually ran on (the caller's, or it without the dropped pairs)
+        self.last_icp = None    # icp_refine: the ICP results of the last ``register`` (one RegistrationResult per pair: status, iterations, fitness)
+        self._icp_dev = None    # ... and the last step's ``eyoc_icp_result`` records on the device
 
     def _mark(self, i):
         if self.timing:
@@ -512,12 +523,13 @@ class RegistrationPipeline:
             res = self.register(batch, seed=seed, return_device=True, maps=maps)
             host, words = self._pinned_set(slot, res)
             host.copy_(res, non_blocking=True)
+            icp = self._icp_readback(slot)
             self.model.range_snapshot(words)
             done = torch.cuda.Event()
             done.record()
             if self.cfg.isolate_failures:
                 batch, maps = self.registered_batch, None      # what a retry runs on: the reduced batch builds cleanly
-            return PendingStep(host, words, done, res, retry=self._retry_args(batch, seed, maps, slot), dropped=self._dropped(batch))
+            return PendingStep(host, words, done, res, retry=self._retry_args(batch, seed, maps, slot), dropped=self._dropped(batch), icp=icp)
         main = torch.cuda.current_stream()
         if getattr(self, "_tail", None) is None:
             self._tail = torch.cuda.Stream(device=batch.coords.device)
@@ -540,10 +552,38 @@ class RegistrationPipeline:
             res = self._match_and_register(batch, F, seed) if self.cfg.use_RANSAC else self._match_and_register_sc2(batch, F, seed)
             host, _ = self._pinned_set(slot, res)
             host.copy_(res, non_blocking=True)
+            icp = self._icp_readback(slot)
             done = torch.cuda.Event()
             done.record(self._tail)
         # F was allocated on the caller's stream and is read on the tail stream: it stays referenced until wait()
-        return PendingStep(host, words, done, res, keep=(F,), retry=self._retry_args(batch, seed, maps, slot), dropped=self._dropped(batch))
+        return PendingStep(host, words, done, res, keep=(F,), retry=self._retry_args(batch, seed, maps, slot), dropped=self._dropped(batch),
+                           icp=icp)
+
+    def _icp_readback(self, slot):
+        """icp_refine: the step's ICP records on their way to the slot's pinned buffer, on the current stream (None when the stage is off)."""
+        if not self.cfg.icp_refine:
+            return None
+        host, _ = self._pinned_set(slot, self._icp_dev)
+        host.copy_(self._icp_dev, non_blocking=True)
+        return host
+
+    def _icp_refine(self, batch, T):
+        """icp_refine: one batched ICP over the pairs' sample sets on the CURRENT stream, started from the back-end's poses ``T f32 [P, 16]``
+        as they are on the device -> the refined poses, f32 ``[P, 16]`` (the fp64 result rounded once).  A pair without a pose (NaN:
+        dropped, degenerate) keeps it and gets BAD_INIT, an empty segment FEW; the records stay in ``_icp_dev``."""
+        from . import icp
+        gate = self.cfg.icp_max_correspondence_distance
+        self._icp_dev = icp.icp_batched(batch.xyz0.reshape(-1, 3), batch.xyz1.reshape(-1, 3), batch.seg, batch.seg,
+                                        2.0 * self.cfg.voxel_size if gate is None else gate, T.to(torch.float64),
+                                        self.cfg.icp_max_iteration)
+        return self._icp_dev.view(torch.float64)[:, :16].to(torch.float32)
+
+    def _decode_icp(self):
+        """icp_refine, ``register``: the ICP records follow the results to the host (the stream is drained by then)."""
+        if self.cfg.icp_refine:
+            from . import icp
+            host = self._icp_dev.cpu()
+            self.last_icp = [icp.decode_icp_result(host[p]) for p in range(host.shape[0])]
 
     def _dropped(self, batch):
         return batch.dropped.copy() if self.cfg.isolate_failures else None
@@ -600,6 +640,8 @@ class RegistrationPipeline:
         finally:
             if iso:
                 self._degenerate(F.device, prev)
+        if self.cfg.icp_refine:
+            res.view(torch.float32)[:, :16] = self._icp_refine(batch, res.view(torch.float32)[:, :16])
         self._mark(3)
         return res
 
@@ -622,12 +664,14 @@ class RegistrationPipeline:
                 return res                # the caller reads back later - and calls model.check_range() then
             words = self._range_snapshot()
             host = res.cpu()
+            self._decode_icp()
             return self._checked(batch, seed, maps, words) or self._flagged(batch, [reg.decode_ransac_result(host[p], n) for p in range(batch.P)])
         T = self._match_and_register_sc2(batch, F, seed)
         if return_device:
             return T
         words = self._range_snapshot()
         Th = T.cpu().numpy().astype(np.float64)
+        self._decode_icp()
         return self._checked(batch, seed, maps, words) or self._flagged(batch, [reg.RegistrationResult(Th[p], 0.0, 0.0) for p in range(batch.P)])
 
     def _flagged(self, batch, results):
@@ -740,6 +784,8 @@ class RegistrationPipeline:
         finally:
             if iso:
                 self._degenerate(dev, prev)
+        if self.cfg.icp_refine:
+            T = self._icp_refine(batch, T.reshape(-1, 16)).reshape(-1, 4, 4)
         self._mark(3)
         return T
 

@@ -1,0 +1,136 @@
+"""Point-to-point ICP refinement on the GPU (``eyoc_icp_batched``, csrc/icp.hip), with the reference's call surfaces.
+
+* ``registration_icp`` stands in for ``o3d.pipelines.registration.registration_icp(pcd0, pcd1, r, init,
+  TransformationEstimationPointToPoint(), ICPConvergenceCriteria(max_iteration=200))`` at ``lib/data_loaders.py:485-515`` (through
+  ``eyoc_amd.o3d`` those lines run unchanged);
+* ``icp_refine`` mirrors ``scripts/SC2_PCR/benchmark_utils.py:40-56``;
+* ``icp_batched`` refines a batch of pairs in one call and leaves the records on the device; ``correspondences`` is one
+  evaluation of the contract (nearest target row under a gate, fp64) on the same cell grid.
+
+The algorithm is restated from Open3D's published source - parity unpinned, see DESIGN.md 4 - and documented in
+``include/eyoc_hip.h``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .eval import _cuda_f32
+from .registration import RegistrationResult
+
+CONVERGED, BAD_INIT, FEW, RANGE = 1, 2, 4, 8      # eyoc_icp_result.status
+RECORD_BYTES = C.sizeof(_lib.IcpResult)           # 160
+
+
+def _segs(seg):
+    seg = [int(v) for v in seg]
+    return (C.c_int32 * len(seg))(*seg), seg
+
+
+def _poses(T, P, device):
+    """``[P, 4, 4]`` / ``[4, 4]`` / ``[P, 16]`` poses (numpy or torch, any float type) -> contiguous f64 ``[P, 16]`` on ``device``."""
+    if not isinstance(T, torch.Tensor):
+        T = torch.from_numpy(np.ascontiguousarray(np.asarray(T, np.float64)))
+    T = T.to(device=device, dtype=torch.float64).reshape(-1, 16)
+    if T.shape[0] == 1 and P > 1:
+        T = T.expand(P, 16)
+    if T.shape[0] != P:
+        raise ValueError(f"{T.shape[0]} poses for {P} pairs")
+    return T.contiguous()
+
+
+def icp_batched(src, tgt, seg_src, seg_tgt, max_correspondence_distance, init=None, max_iteration=30, relative_fitness=1e-6,
+                relative_rmse=1e-6, return_correspondences=False):
+    """All pairs of a batch in one call, nothing read back: ``src f32 [N, 3]`` / ``tgt f32 [M, 3]`` hold the pairs back to back (pair
+    ``b`` = source rows ``seg_src[b]:seg_src[b+1]``, target rows ``seg_tgt[b]:seg_tgt[b+1]``), ``init`` f64 ``[P, 4, 4]`` (host or
+    device; ``None`` = identity).  Returns the ``[P, 160]`` byte tensor of ``eyoc_icp_result`` records on the device (``decode_icp_result``)
+    - and, with ``return_correspondences``, ``int32 [N]``: the target row local to the pair under the returned pose, or -1."""
+    s = _cuda_f32(src).reshape(-1, 3)
+    t = _cuda_f32(tgt, s.device).reshape(-1, 3)
+    ss, seg_s = _segs(seg_src)
+    st, seg_t = _segs(seg_tgt)
+    P = len(seg_s) - 1
+    if len(seg_t) != P + 1 or seg_s[-1] != s.shape[0] or seg_t[-1] != t.shape[0]:
+        raise ValueError("icp_batched: the segments do not describe the clouds")
+    T0 = None if init is None else _poses(init, P, s.device)
+    p = _lib.IcpParams(float(max_correspondence_distance), float(relative_fitness), float(relative_rmse), int(max_iteration), 0)
+    res = torch.empty((P, RECORD_BYTES), dtype=torch.uint8, device=s.device)
+    corr = torch.empty(s.shape[0], dtype=torch.int32, device=s.device) if return_correspondences else None
+    lib = _lib.load()
+    with _lib.on_device(s.device):
+        ws = _lib.workspace(lib.eyoc_icp_workspace_bytes(P, s.shape[0], t.shape[0]), s.device)
+        _lib.check(lib.eyoc_icp_batched(_lib.ctx(s.device.index), _lib.ptr(s), _lib.ptr(t), ss, st, P, _lib.ptr(T0), C.byref(p),
+                                        _lib.ptr(res), _lib.ptr(corr), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "eyoc_icp_batched")
+    return (res, corr) if return_correspondences else res
+
+
+def correspondences(src, tgt, T, max_distance, seg_src=None, seg_tgt=None, return_records=False):
+    """One evaluation under ``T``: -> ``(corr int32 [N], d2 f64 [N])`` on the device - the nearest target row (local to the pair, the
+    lowest row on a tie) with ``d2 < max_distance ** 2``, else -1 / +inf.  One pair unless segments are given."""
+    s = _cuda_f32(src).reshape(-1, 3)
+    t = _cuda_f32(tgt, s.device).reshape(-1, 3)
+    ss, seg_s = _segs([0, s.shape[0]] if seg_src is None else seg_src)
+    st, seg_t = _segs([0, t.shape[0]] if seg_tgt is None else seg_tgt)
+    P = len(seg_s) - 1
+    if len(seg_t) != P + 1 or seg_s[-1] != s.shape[0] or seg_t[-1] != t.shape[0]:
+        raise ValueError("correspondences: the segments do not describe the clouds")
+    Td = _poses(T, P, s.device)
+    res = torch.empty((P, RECORD_BYTES), dtype=torch.uint8, device=s.device)
+    corr = torch.empty(s.shape[0], dtype=torch.int32, device=s.device)
+    d2 = torch.empty(s.shape[0], dtype=torch.float64, device=s.device)
+    lib = _lib.load()
+    with _lib.on_device(s.device):
+        ws = _lib.workspace(lib.eyoc_icp_workspace_bytes(P, s.shape[0], t.shape[0]), s.device)
+        _lib.check(lib.eyoc_icp_correspondences(_lib.ctx(s.device.index), _lib.ptr(s), _lib.ptr(t), ss, st, P, _lib.ptr(Td),
+                                                float(max_distance), _lib.ptr(corr), _lib.ptr(d2), _lib.ptr(res), _lib.ptr(ws), ws.numel(),
+                                                _lib.stream_ptr()), "eyoc_icp_correspondences")
+    return (corr, d2, res) if return_records else (corr, d2)
+
+
+def decode_icp_result(res, corr=None) -> RegistrationResult:
+    """One 160-byte record (device or host tensor, or bytes) -> ``RegistrationResult``; ``corr``: the pair's rows of ``icp_batched``'s
+    correspondence array -> ``correspondence_set int [m, 2]`` (source row, target row)."""
+    raw = bytes(res) if isinstance(res, (bytes, bytearray)) else res.cpu().numpy().tobytes()
+    r = _lib.IcpResult.from_buffer_copy(raw)
+    out = RegistrationResult(np.array(list(r.T), np.float64).reshape(4, 4), float(r.fitness), float(r.inlier_rmse),
+                             inliers=int(r.correspondences), status=int(r.status), iterations=int(r.iterations))
+    if corr is not None:
+        c = corr.cpu().numpy() if isinstance(corr, torch.Tensor) else np.asarray(corr)
+        rows = np.flatnonzero(c >= 0)
+        out.correspondence_set = np.stack([rows, c[rows].astype(np.int64)], 1)
+    return out
+
+
+def _points(a):
+    a = getattr(a, "points", a)
+    if isinstance(a, torch.Tensor):
+        return a
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32)))
+
+
+def registration_icp(source, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None):
+    """Drop-in for Open3D's ``registration_icp`` (point-to-point): ``source / target`` are ``[n, 3]`` points (numpy, torch, or anything
+    with a ``points`` attribute), ``criteria`` any object with ``relative_fitness / relative_rmse / max_iteration`` (default 1e-6,
+    1e-6, 30).  -> ``RegistrationResult`` with ``correspondence_set``, ``iterations`` and ``status``."""
+    if estimation_method is not None and (getattr(estimation_method, "with_scaling", False) or
+                                          type(estimation_method).__name__ != "TransformationEstimationPointToPoint"):
+        raise NotImplementedError("only TransformationEstimationPointToPoint(with_scaling=False) is implemented")
+    if not torch.cuda.is_available():
+        raise _lib.EyocError("no GPU visible: ICP runs on MI355X only (no CPU fallback)")
+    rf, rr, it = (1e-6, 1e-6, 30) if criteria is None else (criteria.relative_fitness, criteria.relative_rmse, criteria.max_iteration)
+    s, t = _points(source), _points(target)
+    T0 = np.eye(4) if init is None else np.asarray(init, np.float64)
+    res, corr = icp_batched(s, t, [0, s.shape[0]], [0, t.shape[0]], max_correspondence_distance, T0[None], it, rf, rr,
+                            return_correspondences=True)
+    return decode_icp_result(res[0], corr)
+
+
+def icp_refine(src_keypts, tgt_keypts, pred_trans, max_correspondence_distance=0.10):
+    """scripts/SC2_PCR/benchmark_utils.py:40-56: ``src_keypts / tgt_keypts [1, n, 3]``, ``pred_trans [1, 4, 4]`` -> the refined
+    ``[1, 4, 4]`` float32 pose on ``pred_trans``'s device (gate 0.10 m, 30 iterations, like the reference)."""
+    r = registration_icp(src_keypts[0].detach(), tgt_keypts[0].detach(), max_correspondence_distance,
+                         pred_trans[0].detach().cpu().numpy().astype(np.float64))
+    return torch.from_numpy(r.transformation[None]).to(device=pred_trans.device, dtype=torch.float32)

@@ -1,4 +1,4 @@
-"""An ``open3d``-shaped namespace for the one Open3D call on the registration path.
+"""An ``open3d``-shaped namespace for the Open3D calls on the registration path: feature-matching RANSAC and point-to-point ICP.
 
 ``scripts/test_kitti.py:159-177`` builds point clouds and features with ``util/pointcloud.py:9-21``
 (``o3d.geometry.PointCloud()``, ``o3d.utility.Vector3dVector``, ``o3d.pipelines.registration.Feature()`` with
@@ -12,6 +12,11 @@ CorrespondenceCheckerBasedOnDistance(d)], RANSACConvergenceCriteria(4000000, 100
 those lines run unchanged; the work happens in ``libeyoc_hip.so`` (``eyoc_amd.registration``).  Only what that call site
 touches exists here - this is not an Open3D re-implementation: other estimation methods, ``ransac_n != 4`` and
 ``mutual_filter=True`` raise ``NotImplementedError``, unknown checkers raise ``TypeError``.
+
+``o3d.pipelines.registration.registration_icp(pcd0, pcd1, 0.2, np.eye(4), TransformationEstimationPointToPoint(),
+ICPConvergenceCriteria(max_iteration=200))`` and ``pcd0.transform(reg.transformation)`` (``lib/data_loaders.py:497-507``) and the legacy
+``o3d.registration.registration_icp`` of ``scripts/SC2_PCR/benchmark_utils.py:52-54`` run unchanged as well (``eyoc_amd.icp``);
+``TransformationEstimationPointToPoint(with_scaling=True)`` and point-to-plane raise ``NotImplementedError``.
 """
 from __future__ import annotations
 
@@ -40,6 +45,12 @@ class PointCloud:
     def __len__(self):
         return len(self.points)
 
+    def transform(self, T):
+        """In place, like Open3D: ``points <- R points + t``."""
+        T = np.asarray(T, np.float64)
+        self.points = self.points @ T[:3, :3].T + T[:3, 3]
+        return self
+
 
 class Feature:
     """``o3d.pipelines.registration.Feature``: ``data`` is ``[dim, n]`` float64 (util/pointcloud.py:17-21)."""
@@ -60,6 +71,20 @@ class Feature:
 class TransformationEstimationPointToPoint:
     def __init__(self, with_scaling=False):
         self.with_scaling = bool(with_scaling)
+
+
+class TransformationEstimationPointToPlane:
+    """Exists so that a call site that builds one gets the shim's ``NotImplementedError`` from ``registration_icp``, not an AttributeError."""
+
+    def __init__(self, kernel=None):
+        self.kernel = kernel
+
+
+class ICPConvergenceCriteria:
+    def __init__(self, relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30):
+        self.relative_fitness = float(relative_fitness)
+        self.relative_rmse = float(relative_rmse)
+        self.max_iteration = int(max_iteration)
 
 
 class CorrespondenceCheckerBasedOnEdgeLength:
@@ -121,6 +146,25 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
         seed=seed, edge_similarity=edge)
 
 
+def registration_icp(source, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None):
+    """Point-to-point ICP with Open3D's positional layout (``init`` defaults to the identity, ``criteria`` to
+    ``ICPConvergenceCriteria()``); the points are handed to the GPU as float32, like every cloud of this package."""
+    from . import icp as _icp
+    if not isinstance(source, PointCloud) or not isinstance(target, PointCloud):
+        raise TypeError("source / target must be eyoc_amd.o3d.geometry.PointCloud")
+    if estimation_method is None:
+        estimation_method = TransformationEstimationPointToPoint(False)
+    if not isinstance(estimation_method, TransformationEstimationPointToPoint):
+        raise NotImplementedError("only point-to-point ICP is implemented (lib/data_loaders.py:501-502)")
+    if estimation_method.with_scaling:
+        raise NotImplementedError("TransformationEstimationPointToPoint(with_scaling=True) is not implemented")
+    criteria = ICPConvergenceCriteria() if criteria is None else criteria
+    if not isinstance(criteria, ICPConvergenceCriteria):
+        raise TypeError("criteria must be an ICPConvergenceCriteria")
+    return _icp.registration_icp(np.asarray(source.points, np.float32), np.asarray(target.points, np.float32),
+                                 float(max_correspondence_distance), np.eye(4) if init is None else init, estimation_method, criteria)
+
+
 geometry = types.SimpleNamespace(PointCloud=PointCloud)
 utility = types.SimpleNamespace(Vector3dVector=_vector3d)
 pipelines = types.SimpleNamespace(registration=types.SimpleNamespace(
@@ -128,4 +172,7 @@ pipelines = types.SimpleNamespace(registration=types.SimpleNamespace(
     CorrespondenceCheckerBasedOnEdgeLength=CorrespondenceCheckerBasedOnEdgeLength,
     CorrespondenceCheckerBasedOnDistance=CorrespondenceCheckerBasedOnDistance,
     RANSACConvergenceCriteria=RANSACConvergenceCriteria, RegistrationResult=RegistrationResult,
-    registration_ransac_based_on_feature_matching=registration_ransac_based_on_feature_matching))
+    registration_ransac_based_on_feature_matching=registration_ransac_based_on_feature_matching,
+    TransformationEstimationPointToPlane=TransformationEstimationPointToPlane, ICPConvergenceCriteria=ICPConvergenceCriteria,
+    registration_icp=registration_icp))
+registration = pipelines.registration      # the pre-0.10 module path scripts/SC2_PCR/benchmark_utils.py:52-54 uses

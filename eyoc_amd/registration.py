@@ -31,7 +31,10 @@ class RegistrationResult:
     best_hypothesis: int = -1
     survivors: int = 0
     status: int = 0                 # harness.RETRIED_FP32 when the step was registered again in fp32 (fp32_retry_per_step);
-                                    # harness.DROPPED_* when the pair was dropped from its batch (isolate_failures)
+                                    # harness.DROPPED_* when the pair was dropped from its batch (isolate_failures);
+                                    # icp.CONVERGED / BAD_INIT / FEW / RANGE on a record of eyoc_amd.icp
+    correspondence_set: np.ndarray | None = None   # ICP only: int [m, 2] (source row, target row) under ``transformation``
+    iterations: int = 0             # ICP only: pose updates done
 
 
 def ransac_from_correspondences(src, tgt, corr_tgt, max_correspondence_distance, max_iteration=4000000, seed=0,

@@ -666,6 +666,52 @@ int eyoc_sc2pcr_set_dense_threshold(eyoc_ctx* ctx, int x);
  * solve and inlier count inside its wave's kernel (default: lane-per-seed kernels behind it).  0 = default; returns the previous bits. */
 int eyoc_sc2pcr_select_kernels(eyoc_ctx* ctx, int legacy_bits);
 
+/* ICP refinement.  Added after 111 without a bump, additive only.
+ * replaces: o3d.pipelines.registration.registration_icp(pcd0, pcd1, r, init, TransformationEstimationPointToPoint(),
+ * ICPConvergenceCriteria(max_iteration)) at lib/data_loaders.py:485-515 and scripts/SC2_PCR/benchmark_utils.py:40-56, for a batch of
+ * independent pairs.  Point-to-point ICP restated from Open3D's published source (parity unpinned):
+ *   T = init; res = eval(T); repeat at most max_iteration times { U = Kabsch over the correspondences; T = U T; prev = res;
+ *   res = eval(T); stop (CONVERGED) if |prev.fitness - res.fitness| < relative_fitness and |prev.inlier_rmse - res.inlier_rmse| <
+ *   relative_rmse }.
+ * eval(T): every source point x (fp32, exact in fp64) is posed p = R x + t in fp64; its correspondence is the target row of the pair
+ * with the smallest d2 = (p - q)^2 summed in fp64 (x, y, z in that order, no fused multiply-add), the lowest row on an exact tie, kept
+ * iff d2 < max_distance^2; fitness = #corr / #source, inlier_rmse = sqrt(sum d2 / #corr) (0 without correspondences).  The posed
+ * points are always T x of the ORIGINAL source, and an evaluation with fewer than 3 correspondences stops the pair with its current T
+ * and the FEW bit.  The search runs on a cell grid of edge max_distance built once per call (27 cells cover the gate; a posed point
+ * within ~1e-16 relative of a cell face AND of the gate at once may miss a neighbour that sits exactly at the gate).
+ * Pairs back to back as in eyoc_ransac_batched_ws: pair b owns source rows [seg_src[b], seg_src[b+1]) and target rows [seg_tgt[b],
+ * seg_tgt[b+1]) (HOST arrays of n_pairs + 1 ints, n_pairs <= 1024, empty segments accepted: T = init, fitness 0, FEW).  Caller-owned
+ * 256-byte aligned workspace of eyoc_icp_workspace_bytes; nothing is allocated and the host never waits inside the call: all
+ * max_iteration + 1 evaluations are enqueued, a finished pair's workgroups return at once.  64 pairs share one set of launches (2 per
+ * evaluation + the grid build: 3 kernels, 1 fill, 2 radix sorts).  No floating-point atomics and no partition that depends on a pair's neighbours: results[b] is
+ * byte-identical from run to run and to a call on pair b alone. */
+enum {
+  EYOC_ICP_CONVERGED = 1,
+  EYOC_ICP_BAD_INIT = 2,   /* non-finite init: T is returned as given, nothing else of the pair is read */
+  EYOC_ICP_FEW = 4,        /* an evaluation left fewer than 3 correspondences (or a segment is empty) */
+  EYOC_ICP_RANGE = 8       /* a non-finite source / target point or a target cell outside +-2^17 cells: T = init */
+};
+typedef struct {
+  double max_distance, relative_fitness, relative_rmse;
+  int32_t max_iteration;
+  int32_t flags;             /* 0 */
+} eyoc_icp_params;           /* 32 bytes */
+typedef struct {
+  double T[16];              /* row-major 4x4 */
+  double fitness, inlier_rmse;
+  int32_t correspondences, iterations, status, reserved;
+} eyoc_icp_result;           /* 160 bytes */
+size_t eyoc_icp_workspace_bytes(int n_pairs, int total_src, int total_tgt);
+/* init_dev: f64 [n_pairs][16] row-major, NULL = identity.  corr_dev: int32 [total_src], the target row LOCAL to the pair under the
+ * returned T or -1; NULL = not wanted. */
+int eyoc_icp_batched(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int32_t* seg_src_host,
+                     const int32_t* seg_tgt_host, int n_pairs, const double* init_dev, const eyoc_icp_params* params,
+                     eyoc_icp_result* results_dev, int32_t* corr_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* One eval(T) and nothing else (iterations 0): corr_dev as above, d2_dev f64 [total_src] (+inf where corr is -1), either may be NULL. */
+int eyoc_icp_correspondences(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int32_t* seg_src_host,
+                             const int32_t* seg_tgt_host, int n_pairs, const double* T_dev, double max_distance, int32_t* corr_dev,
+                             double* d2_dev, eyoc_icp_result* results_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
