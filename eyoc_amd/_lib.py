@@ -51,6 +51,13 @@ class Sc2pcrParams(C.Structure):
                 ("k1", C.c_int32), ("k2", C.c_int32)]
 
 
+class Sc2pcrLayout(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("n", "words", "n_seed", "k1", "k2", "n_part", "col_chunk", "reserved")] +
+                [("csr_cap", C.c_int64), ("total", C.c_uint64)] +
+                [("off_" + k, C.c_uint64) for k in ("ctl", "v", "y", "score", "seeds", "hard", "tight", "knn", "Ts", "dom", "rank",
+                                                    "ptr_h", "col_h", "val_h", "cnt", "blk_dense", "seed_h")])
+
+
 class IcpParams(C.Structure):
     _fields_ = [("max_distance", C.c_double), ("relative_fitness", C.c_double), ("relative_rmse", C.c_double),
                 ("max_iteration", C.c_int32), ("flags", C.c_int32)]
@@ -180,6 +187,7 @@ PROTOTYPES = {
     "eyoc_sc2pcr_set_shortlist_cap": (_i, [_vp, _i]),
     "eyoc_sc2pcr_set_dense_threshold": (_i, [_vp, _i]),
     "eyoc_sc2pcr_select_kernels": (_i, [_vp, _i]),
+    "eyoc_sc2pcr_workspace_layout": (_i, [_i, C.POINTER(Sc2pcrParams), C.POINTER(Sc2pcrLayout)]),
     "eyoc_sc2pcr_batched": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(Sc2pcrParams), _vp, _vp, _i, _vp, _sz,
                                  _vp]),
     "eyoc_icp_workspace_bytes": (_sz, [_i, _i, _i]),

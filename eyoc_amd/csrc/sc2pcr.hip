@@ -1293,6 +1293,23 @@ size_t eyoc_sc2pcr_workspace_bytes(int n, const eyoc_sc2pcr_params* params) {
   return make_plan(n, params).total;
 }
 
+// where every stage leaves its result in the workspace (tests copy it back and check the stages one by one); host only
+int eyoc_sc2pcr_workspace_layout(int n, const eyoc_sc2pcr_params* params, eyoc_sc2pcr_layout* out) {
+  EYOC_REQUIRE(params && out, EYOC_ERR_INVALID, "eyoc_sc2pcr_workspace_layout: NULL argument");
+  EYOC_REQUIRE(n >= 8 && n <= MAX_N, EYOC_ERR_INVALID, "eyoc_sc2pcr_workspace_layout: n %d not in [8, %d]", n, MAX_N);
+  const Plan pl = make_plan(n, params);
+  eyoc_sc2pcr_layout L = {};
+  L.n = pl.n; L.words = pl.words; L.n_seed = pl.n_seed; L.k1 = pl.k1; L.k2 = pl.k2; L.n_part = pl.n_part; L.col_chunk = pl.col_chunk;
+  L.csr_cap = pl.csr_cap; L.total = pl.total;
+  L.off_ctl = pl.off_ctl; L.off_v = pl.off_v; L.off_y = pl.off_y; L.off_score = pl.off_score; L.off_seeds = pl.off_seeds;
+  L.off_hard = pl.off_hard; L.off_tight = pl.off_tight; L.off_knn = pl.off_knn; L.off_Ts = pl.off_Ts;
+  L.off_dom = pl.off_int; L.off_rank = pl.off_int + (size_t)n * 4;     // sc2pcr_chunk: q.rank = q.dom + n
+  L.off_ptr_h = pl.off_ptr_h; L.off_col_h = pl.off_col_h; L.off_val_h = pl.off_val_h; L.off_cnt = pl.off_cnt;
+  L.off_blk_dense = pl.off_blk; L.off_seed_h = pl.off_seed_h;
+  *out = L;
+  return EYOC_OK;
+}
+
 // one chunk of <= SC2_CHUNK pairs: ~70 launches whatever the number of pairs
 static int sc2pcr_chunk(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int32_t* seg_host, int n_pairs,
                         const eyoc_sc2pcr_params* params, float* T_dev, float* fitness_dev, int fitness_stride, char* ws,

@@ -665,6 +665,37 @@ int eyoc_sc2pcr_set_dense_threshold(eyoc_ctx* ctx, int x);
  * seed-fitness sweeps (default: x < T(r), the exact threshold of the correctly rounded sqrtf), bit 3 = every seed's 3 x 3 Kabsch
  * solve and inlier count inside its wave's kernel (default: lane-per-seed kernels behind it).  0 = default; returns the previous bits. */
 int eyoc_sc2pcr_select_kernels(eyoc_ctx* ctx, int legacy_bits);
+/* Read-only view of the caller-owned workspace.  Added after 111 without a bump, additive only; host-only: allocates nothing,
+ * launches nothing, changes no result.  Every stage of eyoc_sc2pcr leaves its result in the workspace; this reports where (byte
+ * offsets from the workspace base, for the same (n, params) the call was made with), so a test can copy the workspace back once and
+ * check each stage on its own.  n outside [8, 16384] or a NULL argument: EYOC_ERR_INVALID, *out untouched.
+ *   off_ctl     8 x int32: converged (the power iteration reached allclose), iters (sweeps applied), best_seed (first maximum of the
+ *               seed-wise fitness), best_fitness (f32), norm (f32: |M v| + 1e-6 of the last sweep), dense (the hard graph has more than
+ *               csr_cap edges: ptr_h holds clamped offsets, col_h / val_h are not written, the sweeps recompute the matrix), 2 x pad
+ *   off_v       f32 [n]            leading eigenvector after `iters` sweeps (off_y: f32 [n], scratch of the last sweep)
+ *   off_score   f32 [n]            dom ? 0 : v
+ *   off_seeds   i32 [n_seed]       the first n_seed entries of the stable descending order of score
+ *   off_hard, off_tight  u64 [n][words]   bit b of word w of row i: cross(i, 64 w + b) < d_thre resp. < d_thre / 2; columns >= n clear
+ *   off_knn     i32 [n_seed][k1]   stable top-k1 of popcount(tight[seed] & tight[j]) * hard[seed][j]
+ *   off_Ts      f32 [n_seed][16]   seed hypotheses, row-major 4 x 4: the fp32 storage of an fp64 Kabsch solve of seed_h
+ *   off_dom     i32 [n]            non-maximum suppression: some j within nms_radius has a larger v
+ *   off_rank    i32 [n]            stable descending rank of score; = off_dom + 4 n, the only offset that is not 256-byte aligned
+ *   off_ptr_h   i32 [n + 1]        CSR of the hard graph: exclusive scan of the row popcounts
+ *   off_col_h   u16 [nnz]          columns, ascending within a row;  off_val_h  f32 [nnz]: max(0, 1 - c^2 / d_thre^2)
+ *   off_cnt     u16 [n_seed][64 words]   second-order counts of the seeds of blocks flagged in blk_dense
+ *   off_blk_dense  u8 [ceil(n_seed / 64)]
+ *   off_seed_h  f64 [n_seed][16]   centroid a (3), centroid b (3), cross-covariance H (9, row-major), one unused
+ * n_seed = int(ratio n); k1 = k2 = 4 when params->k1 > n; total == eyoc_sc2pcr_workspace_bytes(n, params).  n_part column ranges of
+ * col_chunk columns split the NMS and rank sweeps.  Batched: pair b of a call (or 16-pair chunk of a call) lives at
+ * workspace + (b % 16) * S with S = the largest `total` of the call's pairs rounded up to 256; its layout is that of its own (n, params[b]). */
+typedef struct {
+  int32_t n, words, n_seed, k1, k2, n_part, col_chunk, reserved;
+  int64_t csr_cap;
+  uint64_t total;
+  uint64_t off_ctl, off_v, off_y, off_score, off_seeds, off_hard, off_tight, off_knn, off_Ts, off_dom, off_rank, off_ptr_h,
+      off_col_h, off_val_h, off_cnt, off_blk_dense, off_seed_h;
+} eyoc_sc2pcr_layout;
+int eyoc_sc2pcr_workspace_layout(int n, const eyoc_sc2pcr_params* params, eyoc_sc2pcr_layout* out);
 
 /* ICP refinement.  Added after 111 without a bump, additive only.
  * replaces: o3d.pipelines.registration.registration_icp(pcd0, pcd1, r, init, TransformationEstimationPointToPoint(),

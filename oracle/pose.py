@@ -99,6 +99,15 @@ def transform(pts, T):
     return (T[:3, :3] @ pts.T + T[:3, 3:4]).T
 
 
+def kabsch_terms(A, B, w):
+    """The weighted centroids ``[bs,1,3]`` and the cross-covariance ``[bs,3,3]`` of ``rigid_transform_3d`` (common.py:22-33)."""
+    den = w.sum(1, keepdim=True)[:, :, None] + 1e-6
+    cA = (A * w[:, :, None]).sum(1, keepdim=True) / den
+    cB = (B * w[:, :, None]).sum(1, keepdim=True) / den
+    Am, Bm = A - cA, B - cB
+    return cA, cB, Am.permute(0, 2, 1) @ (w[:, :, None] * Bm)
+
+
 def rigid_transform_3d(A, B, weights=None, weight_threshold=0):
     """scripts/SC2_PCR/common.py:7-45.  Weighted centroids with 1e-6 in the denominators,
     ``H = Am^T diag(w) Bm``, ``R = V diag(1,1,det(V U^T)) U^T``, ``t = cB - R cA``.
@@ -106,11 +115,7 @@ def rigid_transform_3d(A, B, weights=None, weight_threshold=0):
     A, B = A.float(), B.float()
     w = torch.ones_like(A[:, :, 0]) if weights is None else weights.float().clone()
     w[w < weight_threshold] = 0
-    den = w.sum(1, keepdim=True)[:, :, None] + 1e-6
-    cA = (A * w[:, :, None]).sum(1, keepdim=True) / den
-    cB = (B * w[:, :, None]).sum(1, keepdim=True) / den
-    Am, Bm = A - cA, B - cB
-    H = Am.permute(0, 2, 1) @ (w[:, :, None] * Bm)
+    cA, cB, H = kabsch_terms(A, B, w)
     U, S, V = torch.svd(H)
     d = torch.det(V @ U.permute(0, 2, 1))
     D = torch.eye(3).repeat(A.shape[0], 1, 1)

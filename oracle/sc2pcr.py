@@ -24,13 +24,18 @@ scripts/SC2_PCR/config_json/config_KITTI.json:1-15.  Stage by stage:
 ``argsort`` ties (integer-valued SC2 counts, zero-padded scores) are implementation-defined in
 the reference (unstable sort); this restatement breaks them towards the lower index.  Only the
 final pose is compared with the golden vectors.
+
+``Matcher.taps``: set it to a dict and ``SC2_PCR`` records what every stage produced (bs == 1): ``hard tight soft`` [n,n],
+``v iters converged`` (global power iteration), ``dom score seeds``, ``sc2`` [S,n], ``knn`` [S,k1], ``seed_h`` [S,15] (centroid a,
+centroid b, cross-covariance of every seed's weighted Kabsch problem), ``Ts fitness best T``.  tests/sc2pcr_stages.py packs them
+into the device's workspace format.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from .pose import rigid_transform_3d, transform
+from .pose import kabsch_terms, rigid_transform_3d, transform
 
 KITTI_CFG = dict(inlier_threshold=0.6, num_node=8000, use_mutual=False, d_thre=0.1,
                  num_iterations=20, ratio=0.2, nms_radius=0.6, max_points=8000, k1=30, k2=20)
@@ -58,15 +63,23 @@ class Matcher:
         self.nms_radius = nms_radius
         self.k1 = k1
         self.k2 = k2
+        self.taps = None
+
+    def _tap(self, **kw):
+        if self.taps is not None:
+            self.taps.update({k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in kw.items()})
 
     # ------------------------------------------------------------------ :170-196
     def cal_leading_eigenvector(self, M, method="power"):
         v = torch.ones_like(M[:, :, 0:1])
         last = v
+        self._sweeps, self._converged = 0, 0
         for _ in range(self.num_iterations):
             v = torch.bmm(M, v)
             v = v / (torch.norm(v, dim=1, keepdim=True) + 1e-6)
+            self._sweeps += 1
             if torch.allclose(v, last):
+                self._converged = 1
                 break
             last = v
         return v.squeeze(-1)
@@ -78,6 +91,7 @@ class Matcher:
         # i survives iff no j within R has a strictly larger score
         dominated = (s[None, :] > s[:, None]) & (dists[0] < R)
         keep = (~dominated.any(dim=1)).float()
+        self._tap(dom=dominated.any(dim=1), score=(scores * keep[None, :])[0])
         return _desc_order(scores * keep[None, :], 1)[:, :max_num]
 
     # ------------------------------------------------------------------ :61-168
@@ -87,6 +101,21 @@ class Matcher:
         if k1 > n_corr:
             k1 = k2 = 4
         nn1 = _desc_order(SC2_measure, 2)[:, :, :k1]                       # [bs, S, k1]
+        s2, t2, w = self.local_consensus(nn1, src, tgt, k2)
+        if self.taps is not None:
+            cA, cB, H = kabsch_terms(s2.reshape(-1, k2, 3), t2.reshape(-1, k2, 3), w)
+            self._tap(knn=nn1[0], seed_h=torch.cat([cA[:, 0], cB[:, 0], H.reshape(-1, 9)], 1))
+        T = rigid_transform_3d(s2.reshape(-1, k2, 3), t2.reshape(-1, k2, 3), w).reshape(bs, -1, 4, 4)
+        pred = torch.einsum("bsnm,bmk->bsnk", T[:, :, :3, :3], src.permute(0, 2, 1)) + T[:, :, :3, 3:4]
+        dist = torch.norm(pred.permute(0, 1, 3, 2) - tgt[:, None, :, :], dim=-1)
+        fitness = (dist < self.inlier_threshold).float().sum(-1)              # [bs, S]
+        best = fitness.argmax(dim=1)
+        self._tap(Ts=T[0], fitness=fitness[0], best=int(best[0]))
+        return T[torch.arange(bs), best], fitness
+
+    def local_consensus(self, nn1, src, tgt, k2):
+        """:80-140 - the seeds' neighbours ``nn1 [1, S, k1]`` -> the k2 survivors ``s2, t2 [1, S, k2, 3]`` and their weights ``[S, k2]``."""
+        bs = nn1.shape[0]
         take = lambda pts, idx: pts[0][idx[0]][None]                          # bs == 1 gather
         s1, t1 = take(src, nn1), take(tgt, nn1)                               # [1, S, k1, 3]
         loc = lambda p: ((p[:, :, :, None, :] - p[:, :, None, :, :]) ** 2).sum(-1) ** 0.5
@@ -101,13 +130,7 @@ class Matcher:
         ar = torch.arange(k2)
         soft[:, ar, ar] = 0
         w = self.cal_leading_eigenvector(soft).reshape(bs, -1, k2)
-        w = (w / (w.sum(-1, keepdim=True) + 1e-6)).reshape(-1, k2)
-        T = rigid_transform_3d(s2.reshape(-1, k2, 3), t2.reshape(-1, k2, 3), w).reshape(bs, -1, 4, 4)
-        pred = torch.einsum("bsnm,bmk->bsnk", T[:, :, :3, :3], src.permute(0, 2, 1)) + T[:, :, :3, 3:4]
-        dist = torch.norm(pred.permute(0, 1, 3, 2) - tgt[:, None, :, :], dim=-1)
-        fitness = (dist < self.inlier_threshold).float().sum(-1)              # [bs, S]
-        best = fitness.argmax(dim=1)
-        return T[torch.arange(bs), best], fitness
+        return s2, t2, (w / (w.sum(-1, keepdim=True) + 1e-6)).reshape(-1, k2)
 
     # ------------------------------------------------------------------ :238-278
     def post_refinement(self, T, src, tgt, it_num, weights=None):
@@ -149,11 +172,14 @@ class Matcher:
         soft = torch.clamp(1.0 - cross ** 2 / self.d_thre ** 2, min=0)
         hard = (cross < self.d_thre).float()
         conf = self.cal_leading_eigenvector(soft)
+        self._tap(v=conf[0], iters=self._sweeps, converged=self._converged)
         seeds = self.pick_seeds(src_len, conf, R=self.nms_radius, max_num=int(n * self.ratio))
         tight = (cross < self.d_thre / 2).float()
         sc2 = torch.matmul(tight[0][seeds[0]][None], tight) * hard[0][seeds[0]][None]
+        self._tap(hard=hard[0] > 0, tight=tight[0] > 0, soft=soft[0], seeds=seeds[0], sc2=sc2[0])
         T, fitness = self.cal_seed_trans(seeds, sc2, src, tgt)
         T = self.post_refinement(T, src, tgt, 20)
+        self._tap(T=T[0])
         return T, fitness
 
     # ------------------------------------------------------------------ :386-413

@@ -38,6 +38,7 @@ def test_struct_sizes_match_header():
     assert C.sizeof(_lib.RansacResult) == 16 * 4 + 4 * 4
     assert C.sizeof(_lib.RansacParams) == 16
     assert C.sizeof(_lib.Sc2pcrParams) == 32
+    assert C.sizeof(_lib.Sc2pcrLayout) == 8 * 4 + 8 + 8 + 17 * 8
     assert C.sizeof(_lib.ModelDesc) == 4 * 4 + 5 * 4 + 5 * 4 + 4 + 4
     assert C.sizeof(_lib.MapsInfo) == 8 + 4 * 4 + (3 * 4 + 1) * 8
 
