@@ -10,16 +10,24 @@ Differences from the reference that are deliberate and documented in DESIGN.md:
 """
 from __future__ import annotations
 
+import contextlib
+import copy
+import json
+import logging
 from dataclasses import dataclass, field
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
+from . import _lib, icp
 from . import registration as reg
 from .eval import gather_rows, knn1_segmented
+from .isolate import batch_drop, remap_rows
 from .metrics import registration_errors
-from .sparse_tensor import SparseTensor
+from .sparse_tensor import CoordinateManager, SparseTensor
 from .synthetic import batch_coords, plant_correspondences, subsample_indices
+from .voxelize import sparse_quantize_batch
 
 
 @dataclass
@@ -100,7 +108,6 @@ def build_with_isolation(batch, build, fault_batches):
     taken out (``batch.without_pairs``: a new batch, the caller's is not modified) and the build runs again - at most MAX_REBUILDS
     times, then the ORIGINAL error is raised.  An error that names no batch index (a row whose own index is outside [0, 1024)) is raised
     as it is."""
-    from . import _lib
     first = None
     for attempt in range(MAX_REBUILDS + 1):
         try:
@@ -132,8 +139,6 @@ def load_config(config, sc2pcr_config=None, use_RANSAC=True, rte_thresh=2.0, rre
     everything else (trainer / loader settings) is ignored.  With ``use_RANSAC=False`` the SC2-PCR constants are merged
     in from ``sc2pcr_config`` (path or dict; the reference reads scripts/SC2_PCR/config_json/config_KITTI.json) exactly
     like test_kitti.py does; ``rte_thresh`` / ``rre_thresh`` are its command-line flags."""
-    import json
-
     def as_dict(c):
         return json.load(open(c)) if isinstance(c, (str, bytes)) or hasattr(c, "__fspath__") else dict(c)
     c = as_dict(config)
@@ -153,6 +158,40 @@ def sample_indices(seed, i, n, n_points):
     return np.random.default_rng(seed * 2 + i + 10**6).choice(n, n_points)
 
 
+
+def distinct_draws(draws, live, n):
+    """The bookkeeping that lets the SC2-PCR path search the DISTINCT rows of its re-sampled draws.  ``draws int64 [P, 2, nn_pts]``: per
+    pair the rows (``< n``) drawn with replacement of its source (``[:, 0]``) and target (``[:, 1]``) sample set; ``live``: the pairs that
+    take part, in order (live pair ``p`` is block ``q`` of every packed array).  -> ``(us, ut, inv, first, seg_a, seg_b, base)``:
+    ``us`` the distinct source rows (ascending, ``+ q n``) with segments ``seg_a``; ``ut`` the distinct target rows in the order of their
+    FIRST draw (``+ q n``) with segments ``seg_b``; ``inv [L nn_pts]`` draw of a source row -> its row of ``us``; ``first`` the first
+    draw (``+ q nn_pts``: a row of the packed target draws) of every row of ``ut``; ``base`` row of ``us`` -> where its pair starts in ``ut``.
+
+    With ``nn_u`` the first arg-min of every ``us`` row over the ``ut`` rows of its pair, ``first[nn_u + base][inv]`` is the first arg-min of
+    every source draw over the target draws of its pair: an arg-min returns the first of equal distances, a duplicated target ties with
+    itself exactly, so the winner among duplicates is the first draw, and the lowest first draw among tied distinct rows is the lowest
+    index overall (tests/test_host_logic.py)."""
+    nn_pts = draws.shape[2]
+    us, ut, inv, first, seg_a, seg_b = [], [], [], [], [0], [0]
+    pos = np.arange(nn_pts, dtype=np.int64)
+    for q, p in enumerate(live):
+        d0, d1 = draws[p, 0], draws[p, 1]
+        present = np.zeros(n, bool)
+        present[d0] = True
+        u0 = np.flatnonzero(present)                                   # distinct source rows
+        i0 = (np.cumsum(present) - 1)[d0]                               # draw -> its distinct row
+        fst = np.full(n, nn_pts, np.int64)
+        np.minimum.at(fst, d1, pos)                                     # first draw of every target row
+        f1 = np.flatnonzero(fst[d1] == pos)                             # the first draws, ascending: distinct targets in that order
+        u1 = d1[f1]
+        us.append(u0 + q * n); inv.append(i0 + seg_a[-1])
+        ut.append(u1 + q * n); first.append(f1 + q * nn_pts)
+        seg_a.append(seg_a[-1] + len(u0)); seg_b.append(seg_b[-1] + len(u1))
+    base = np.repeat(np.asarray(seg_b[:-1], np.int64), np.diff(seg_a))
+    us, ut, inv, first = (np.concatenate(a) if a else np.zeros(0, np.int64) for a in (us, ut, inv, first))
+    return us, ut, inv, first, seg_a, seg_b, base
+
+
 class DeviceBatch:
     """``P`` pairs resident in HBM: batched coordinates/features for the 2P clouds, the voxel centres'
     points, and the (seeded) sample indices of ``random_sample`` (scripts/test_kitti.py:159-160).
@@ -166,52 +205,26 @@ class DeviceBatch:
     def __init__(self, pairs, seeds, device, n_points=5000, descriptor=None, isolate=False):
         """``isolate=True``: a pair with a cloud of 0 voxels is dropped at construction (DROPPED_EMPTY in ``dropped``) instead of
         failing the sample draw; see ``without_pairs`` for what a dropped pair leaves behind."""
-        self.P = len(pairs)
-        self.descriptor = dict(descriptor) if descriptor else None
-        self.beta = float(self.descriptor.get("beta", 8.0)) if self.descriptor else 0.0
-        clouds, feats, self.sizes = [], [], []
-        for p in pairs:
-            for i in (0, 1):
-                clouds.append(p[f"coords{i}"])
-                feats.append(p[f"feats{i}"])
-                self.sizes.append(len(p[f"coords{i}"]))
-        self.offsets = np.concatenate([[0], np.cumsum(self.sizes)])
-        self.coords = torch.from_numpy(batch_coords(clouds)).to(device)
-        self.feats = torch.from_numpy(np.concatenate(feats, 0)).to(device)
-        self.T_gt = [np.asarray(p["T_gt"], np.float32) for p in pairs]
-        sel0, sel1, xyz0, xyz1, self.counts = [], [], [], [], []
-        G0, G1, self.planted = [], [], []
-        self.dropped = np.zeros(self.P, np.int64)     # DROPPED_* bits per pair (0: the pair is live)
-        for j, (p, seed) in enumerate(zip(pairs, seeds)):
-            planted = None
-            if isolate and min(self.sizes[2 * j:2 * j + 2]) == 0:
-                self.dropped[j] = DROPPED_EMPTY
-                if self.descriptor:
-                    self.planted.append(None)
-                self.counts.append(n_points)
-                continue
-            if self.descriptor:
-                planted = plant_correspondences(p, seed, n_points, self.descriptor.get("inlier_ratio", 0.3),
-                                                self.descriptor.get("plant_radius", 0.3), self.descriptor.get("feat_dim", 32))
-                G0.append(planted["G0"]); G1.append(planted["G1"]); self.planted.append(planted["planted"])
-            for i, (sel, xyz) in enumerate(((sel0, xyz0), (sel1, xyz1))):
-                n = self.sizes[2 * j + i]
-                idx = planted[f"sel{i}"] if planted is not None else sample_indices(seed, i, n, n_points)
-                sel.append(idx + self.offsets[2 * j + i])
-                xyz.append(p[f"xyz{i}"][idx])
-            self.counts.append(n_points)
-        self.G0 = torch.from_numpy(np.concatenate(G0)).to(device) if G0 else None
-        self.G1 = torch.from_numpy(np.concatenate(G1)).to(device) if G1 else None
-        self.sel0 = torch.from_numpy(np.concatenate(sel0) if sel0 else np.zeros(0, np.int64)).to(device)
-        self.sel1 = torch.from_numpy(np.concatenate(sel1) if sel1 else np.zeros(0, np.int64)).to(device)
-        # [P, n_points, 3] (the live pairs only, like sel / G, once pairs were dropped)
-        self.xyz0 = torch.from_numpy(np.stack(xyz0) if xyz0 else np.zeros((0, n_points, 3), np.float32)).to(device)
-        self.xyz1 = torch.from_numpy(np.stack(xyz1) if xyz1 else np.zeros((0, n_points, 3), np.float32)).to(device)
-        self.seg = np.arange(self.P + 1) * n_points
-        self.n_points = n_points
-        if self.dropped.any():
-            self.seg = live_segments(self.dropped, n_points)
-            self._remove_clouds(np.flatnonzero(self.dropped))      # the partner clouds of the empty ones
+        clouds = [p[f"coords{i}"] for p in pairs for i in (0, 1)]
+        feats = np.concatenate([p[f"feats{i}"] for p in pairs for i in (0, 1)], 0)
+        self._collate(torch.from_numpy(batch_coords(clouds)).to(device), torch.from_numpy(feats).to(device),
+                      np.concatenate([[0], np.cumsum([len(c) for c in clouds])]), [p["T_gt"] for p in pairs], descriptor)
+        if isolate:
+            self.dropped[np.minimum(self.sizes[0::2], self.sizes[1::2]) == 0] = DROPPED_EMPTY
+        planted = {}
+        if self.descriptor:
+            d = self.descriptor
+            planted = {j: plant_correspondences(pairs[j], seeds[j], n_points, d.get("inlier_ratio", 0.3), d.get("plant_radius", 0.3),
+                                                d.get("feat_dim", 32)) for j in np.flatnonzero(self.dropped == 0)}
+            self.planted = [planted[j]["planted"] if j in planted else None for j in range(self.P)]
+            if planted:
+                self.G0 = torch.from_numpy(np.concatenate([pl["G0"] for pl in planted.values()])).to(device)
+                self.G1 = torch.from_numpy(np.concatenate([pl["G1"] for pl in planted.values()])).to(device)
+
+        def points(i, live, rows, sel):
+            xyz = [pairs[j][f"xyz{i}"][r] for j, r in zip(live, rows)]
+            return torch.from_numpy(np.stack(xyz) if xyz else np.zeros((0, n_points, 3), np.float32)).to(device)
+        self._draw_samples(seeds, n_points, device, points, planted)
 
     @classmethod
     def from_scans(cls, scans, T_gt, seeds, device, voxel_size=0.3, n_points=5000, descriptor=None, isolate=False):
@@ -226,52 +239,59 @@ class DeviceBatch:
         outside the key range or a NaN / inf point, or that has no voxels at all, is dropped at construction (DROPPED_RANGE /
         DROPPED_NONFINITE / DROPPED_EMPTY in ``dropped``, see ``without_pairs``) instead of failing the call.  The live pairs' draws
         are seeded per pair and do not change."""
-        from .voxelize import sparse_quantize_batch
         if descriptor:
             raise ValueError("DeviceBatch.from_scans: the descriptor mode (plant_correspondences) needs host-voxelised pairs")
         if not len(scans) == len(T_gt) == len(seeds):
             raise ValueError(f"DeviceBatch.from_scans: {len(scans)} scan pairs, {len(T_gt)} poses, {len(seeds)} seeds")
-        device = torch.device(device)
-        self = cls.__new__(cls)
-        self.P = len(scans)
-        self.descriptor, self.beta = None, 0.0
         clouds = [c for pair in scans for c in pair]
-        self.dropped = np.zeros(self.P, np.int64)
+        coords, _, kept_xyz, offsets, *faults = sparse_quantize_batch(clouds, voxel_size, 0, device=torch.device(device), isolate=bool(isolate))
+        self = cls.__new__(cls)
+        self._collate(coords, torch.ones((len(coords), 1), dtype=torch.float32, device=coords.device), offsets, T_gt, None)
         if isolate:
-            self.coords, _, kept_xyz, self.offsets, faults = sparse_quantize_batch(clouds, voxel_size, 0, device=device, isolate=True)
-            per_cloud = (np.where(faults[:, 0] > 0, DROPPED_RANGE, 0) | np.where(faults[:, 1] > 0, DROPPED_NONFINITE, 0)).astype(np.int64)
-            per_cloud[(per_cloud == 0) & (np.diff(self.offsets) == 0)] = DROPPED_EMPTY
+            per_cloud = (np.where(faults[0][:, 0] > 0, DROPPED_RANGE, 0) | np.where(faults[0][:, 1] > 0, DROPPED_NONFINITE, 0)).astype(np.int64)
+            per_cloud[(per_cloud == 0) & (np.diff(offsets) == 0)] = DROPPED_EMPTY
             self.dropped = per_cloud[0::2] | per_cloud[1::2]
-        else:
-            self.coords, _, kept_xyz, self.offsets = sparse_quantize_batch(clouds, voxel_size, 0, device=device)
-        self.sizes = [int(v) for v in np.diff(self.offsets)]
-        self.feats = torch.ones((len(self.coords), 1), dtype=torch.float32, device=self.coords.device)
+        self._draw_samples(seeds, n_points, coords.device, lambda i, live, rows, sel: kept_xyz[sel].reshape(-1, n_points, 3))
+        return self
+
+    def _collate(self, coords, feats, offsets, T_gt, descriptor):
+        """What both constructors know once the clouds are collated: the batched rows, the clouds' row ranges, the poses; no pair dropped
+        yet, no descriptors."""
+        self.P = len(T_gt)
+        self.descriptor = dict(descriptor) if descriptor else None
+        self.beta = float(self.descriptor.get("beta", 8.0)) if self.descriptor else 0.0
+        self.coords, self.feats, self.offsets = coords, feats, offsets
+        self.sizes = [int(v) for v in np.diff(offsets)]
         self.T_gt = [np.asarray(T, np.float32) for T in T_gt]
-        sel = ([np.zeros(0, np.int64)], [np.zeros(0, np.int64)])
-        for j, seed in enumerate(seeds):
-            if self.dropped[j]:
-                continue
-            for i in (0, 1):
-                sel[i].append(sample_indices(seed, i, self.sizes[2 * j + i], n_points) + self.offsets[2 * j + i])
-        self.counts = [n_points] * self.P
+        self.dropped = np.zeros(self.P, np.int64)     # DROPPED_* bits per pair (0: the pair is live)
         self.G0 = self.G1 = None
         self.planted = []
-        self.sel0 = torch.from_numpy(np.concatenate(sel[0])).to(self.coords.device)
-        self.sel1 = torch.from_numpy(np.concatenate(sel[1])).to(self.coords.device)
-        self.xyz0 = kept_xyz[self.sel0].reshape(-1, n_points, 3)
-        self.xyz1 = kept_xyz[self.sel1].reshape(-1, n_points, 3)
+
+    def _draw_samples(self, seeds, n_points, device, points, planted=None):
+        """The tail both constructors share: the live pairs' draws (``planted[j]``'s in the descriptor mode, else ``sample_indices``)
+        -> ``sel0 / sel1`` (rows of ``coords``), ``xyz0 / xyz1`` (``points(i, live, rows, sel)``: the points of cloud ``i``'s draws -
+        given as the live pairs and their rows within the cloud, and as ``sel`` - ``[L, n_points, 3]`` on the device), ``seg / counts /
+        n_points``; then the partner clouds of the dropped pairs go (a faulty or empty cloud has no rows already)."""
+        live = np.flatnonzero(self.dropped == 0)
+        sel, xyz = [], []
+        for i in (0, 1):
+            rows = [planted[j][f"sel{i}"] if planted else sample_indices(seeds[j], i, self.sizes[2 * j + i], n_points) for j in live]
+            idx = np.concatenate([np.zeros(0, np.int64)] + [r + self.offsets[2 * j + i] for j, r in zip(live, rows)])
+            sel.append(torch.from_numpy(idx).to(device))
+            xyz.append(points(i, live, rows, sel[i]))
+        self.sel0, self.sel1 = sel
+        self.xyz0, self.xyz1 = xyz     # [P, n_points, 3] (the live pairs only, like sel / G, once pairs were dropped)
+        self.counts = [n_points] * self.P
         self.seg = np.arange(self.P + 1) * n_points
         self.n_points = n_points
         if self.dropped.any():
             self.seg = live_segments(self.dropped, n_points)
-            self._remove_clouds(np.flatnonzero(self.dropped))      # a faulty cloud is empty already: its partner's rows go too
-        return self
+            self._remove_clouds(np.flatnonzero(self.dropped))
 
     def _remove_clouds(self, pairs):
         """Takes the rows of both clouds of ``pairs`` out of ``coords / feats`` (``eyoc_batch_drop``: the other rows keep their order and
         their batch indices), sends ``sel0 / sel1`` - which hold the live pairs only by now - through the row map on the device and
         updates ``sizes / offsets``.  In place: for a batch under construction."""
-        from .isolate import batch_drop, remap_rows
         clouds = [2 * int(p) + i for p in pairs for i in (0, 1)]
         self.coords, self.feats, row_map, kept = batch_drop(self.coords, self.feats, clouds)
         self.sel0, self.sel1 = remap_rows(self.sel0, row_map), remap_rows(self.sel1, row_map)
@@ -285,7 +305,6 @@ class DeviceBatch:
         back to back, ``seg`` gives a dropped pair an EMPTY segment - pair ``b`` still samples with ``seed + b`` in the batched
         back-ends, which answer an empty segment with a failed record (``eyoc_registration_accept_degenerate``) -, ``sizes / offsets``
         are those of the remaining rows and ``dropped`` carries the bits."""
-        import copy
         if isinstance(bits_by_pair, dict):
             bits = np.zeros(self.P, np.int64)
             for p, b in bits_by_pair.items():
@@ -326,6 +345,27 @@ class DeviceBatch:
         return int(self.offsets[-1])
 
 
+class MapsHandle(NamedTuple):
+    """What ``prepare_maps`` returns and ``register`` / ``enqueue`` take as ``maps=``."""
+    cm: CoordinateManager      # the coordinate manager with the maps built
+    ready: torch.cuda.Event    # recorded on the side stream behind the build
+    batch: DeviceBatch         # the batch the maps describe: the caller's own, or (isolate_failures) it without the pairs that failed the build
+
+
+class _Step:
+    """What ONE enqueued step produced (``RegistrationPipeline._step``).  Nothing of it is on the pipeline: ``_publish`` makes a step
+    "the last step", a retry hands its step to whoever asked for it."""
+    __slots__ = ("slot", "timers", "batch", "F", "featured", "matched", "nn_idx", "result", "icp", "words", "host", "icp_host", "done")
+
+    def __init__(self, slot, timers):
+        self.slot, self.timers = slot, timers      # the buffer set the step uses; its four stage-timer events (None: not timed)
+        self.batch = self.F = None                 # the batch the step actually ran on (isolate_failures: reduced) and its features
+        self.featured = self.matched = None        # events: the forward is enqueued / forward and matching are enqueued
+        self.nn_idx = None                         # RANSAC path: the feature correspondences on the device
+        self.result = self.icp = None              # the back-end's records on the device; icp_refine: the ``eyoc_icp_result`` records
+        self.words = self.host = self.icp_host = self.done = None    # the read-back, when it was enqueued with the step
+
+
 class PendingStep:
     """A step whose read-back was enqueued with it (``RegistrationPipeline.enqueue``)."""
 
@@ -347,12 +387,16 @@ class PendingStep:
         self.status = np.zeros(self.host.shape[0], np.int64) if self.dropped is None else np.array(self.dropped, np.int64)
         if overflow and self.retry is not None:
             pipe, batch, seed, maps, slot = self.retry
-            self.host.copy_(pipe._retry_fp32(batch, seed, maps, True, slot).cpu())
+            again = pipe._retry_fp32(batch, seed, maps, slot, pipelined=True)
+            self.host.copy_(again.result.cpu())
             if self.icp is not None:
-                self.icp.copy_(pipe._icp_dev.cpu())
+                self.icp.copy_(again.icp.cpu())
             self.status |= RETRIED_FP32
         self.retry = None
         return self.host, overflow
+
+
+_CALLERS_STREAM = contextlib.nullcontext()      # the tail of a step that stays on the stream of its forward
 
 
 class RegistrationPipeline:
@@ -368,15 +412,22 @@ class RegistrationPipeline:
         self._ev = None
         self.fp32_retries = 0  # fp32_retry_per_step: steps run again in fp32 after a split16 overflow
         self.dropped_pairs = 0  # isolate_failures: pairs that got a failed record because their batch was registered without them
+        # the last step (``_publish``): its events - the forward is enqueued / forward and matching are enqueued, what ``prepare_maps(after=)``
+        # of the NEXT batch may wait for -, the RANSAC path's correspondences (``correspondence_inlier_ratio``), ...
+        self.featured = self.matched = self.last_nn_idx = None
         self.registered_batch = None   # isolate_failures: the batch the last step actually ran on (the caller's, or it without the dropped pairs)
         self.last_icp = None    # icp_refine: the ICP results of the last ``register`` (one RegistrationResult per pair: status, iterations, fitness)
         self._icp_dev = None    # ... and the last step's ``eyoc_icp_result`` records on the device
+        # streams and pinned buffers, made on first use (a stream needs a device)
+        self.side_priority = 0            # of ``prepare_maps``' side stream; read when that stream is made
+        self._side = self._tail = None
+        self._pinned, self._pinned_w, self._stage = {}, {}, {}     # by (slot, shape, dtype) / slot / slot
+        self._range_words = None          # ``register``'s own copy of the guard's words
+        self._ransac_budget = None
 
-    def _mark(self, i):
-        if self.timing:
-            if self._ev is None:
-                self._ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(2)]
-            self._ev[self.slot][i].record()
+    def _mark(self, step, i):
+        if step.timers is not None:
+            step.timers[i].record()
 
     def stage_ms(self, slot=None):
         """``dict(feat=, match=, reg=)`` of the last timed ``register`` of event set ``slot`` (default: the current
@@ -395,323 +446,295 @@ class RegistrationPipeline:
 
     def _features(self, batch, maps):
         """``features`` -> (the features, the batch they belong to): under ``isolate_failures`` that is ``batch`` without the pairs a
-        failed map build named - dropped here, or by ``prepare_maps``, whose handle then carries the reduced batch as a third element."""
+        failed map build named - dropped here, or by ``prepare_maps``, whose handle then carries the reduced batch."""
         check, self.model.range_check = self.model.range_check, False
         try:
-            if maps is not None:
-                cm, ready = maps[:2]
+            if maps is None and not self.cfg.isolate_failures:
+                return self.model(SparseTensor(batch.feats, coordinates=batch.coords)), batch
+            if maps is None:
+                cm, batch = self._build_maps(batch)
+            else:
+                cm, ready, reduced = maps
                 torch.cuda.current_stream().wait_event(ready)
-                if self.cfg.isolate_failures and len(maps) > 2 and maps[2] is not batch:
-                    batch = maps[2]
+                if self.cfg.isolate_failures and reduced is not batch:
+                    batch = reduced
                     batch.record_stream(torch.cuda.current_stream())     # made on the side stream, read on this one
-                return self.model(SparseTensor(batch.feats, coordinate_manager=cm)), batch
-            if self.cfg.isolate_failures:
-                cm, batch = self._build_isolated(batch)
-                return self.model(SparseTensor(batch.feats, coordinate_manager=cm)), batch
-            return self.model(SparseTensor(batch.feats, coordinates=batch.coords)), batch
+            return self.model(SparseTensor(batch.feats, coordinate_manager=cm)), batch
         finally:
             self.model.range_check = check
 
-    def _build_isolated(self, batch):
-        """The maps of ``batch`` on the current stream, faulty pairs dropped -> ``(coordinate manager, the batch it describes)``."""
-        from . import _lib
-        from .sparse_tensor import CoordinateManager
-
+    def _build_maps(self, batch):
+        """The maps of ``batch`` on the current stream -> ``(coordinate manager, the batch it describes)``: under ``isolate_failures``
+        ``batch`` without the pairs whose clouds failed the build."""
         def build(b):
             cm = CoordinateManager(b.coords)
             cm.maps(-1)
             return cm
+        if not self.cfg.isolate_failures:
+            return build(batch), batch
         return build_with_isolation(batch, build, lambda: _lib.fault_batches(batch.coords.device))
 
-    def _degenerate(self, device, on):
-        """isolate_failures: the back-ends' switch for pairs below their minimum (``eyoc_registration_accept_degenerate``) -> previous value."""
-        from . import _lib
-        return _lib.knob("eyoc_registration_accept_degenerate", int(on), device=device)
-
-    def _checked(self, batch, seed, maps, words=None):
-        """After the results were read back: raise on a split16 overflow - or, in automatic mode, switch the model to
-        fp32 MFMAs for good and run the step again.  ``words``: the guard's words as ``_range_snapshot`` fetched them with the results
-        (all clear: nothing overflowed since the last check, no need to ask the device again)."""
-        from . import _lib
-        if words is not None and int(words[0]) == 0 and int(words[3]) == 0:
-            return None
+    @contextlib.contextmanager
+    def _accept_degenerate(self, device):
+        """isolate_failures: the back-ends' switch for pairs below their minimum (``eyoc_registration_accept_degenerate``), on inside the
+        block - a dropped pair is an empty segment and gets a failed record instead of failing the call."""
+        if not self.cfg.isolate_failures:
+            yield
+            return
+        prev = _lib.knob("eyoc_registration_accept_degenerate", 1, device=device)
         try:
-            self.model.check_range()
-            return None
-        except _lib.EyocError as e:
-            if e.code != _lib.ERR_RANGE or self.model.spconv_math != "auto":
-                raise
-            if self.cfg.fp32_retry_per_step:
-                res = self._retry_fp32(batch, seed, maps, False, self.slot)
-                for r in res:
-                    r.status |= RETRIED_FP32
-                return res
-            import logging
-            logging.warning("eyoc_amd: split16 overflow in the registration pipeline; switching the model to fp32 MFMAs")
-            self.model.spconv_math = "fp32"
-            return self.register(batch, seed, False, maps)
+            yield
+        finally:
+            _lib.knob("eyoc_registration_accept_degenerate", prev, device=device)
+
+    def _step(self, batch, seed, maps, slot, timed, tail=None, read_back=False):
+        """Enqueues ONE step - forward, row gather + feature NN + back-end, ICP if configured - and returns what it produced; publishes
+        nothing on the pipeline.  ``slot``: the buffer set (event set, SC2-PCR index staging, pinned read-back buffers).  ``tail``: the
+        stream everything behind the forward goes on (it waits for the forward); None keeps it on the caller's stream.  The
+        arithmetic is the model's ``spconv_math`` of the moment.
+
+        ``read_back``: the read-back of the records (and the ICP records) into the slot's pinned buffers and of the split16 guard's
+        verdict on THIS forward is enqueued with the step, ``done`` recorded behind it.  A read-back issued after the next step was
+        enqueued queues behind that whole step on the stream: the host then never runs ahead of the GPU, and the GPU idles while the
+        host decodes results and launches the next step (measured: 2 ms of a 24 ms step)."""
+        if timed and self._ev is None:
+            self._ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(2)]
+        step = _Step(slot, self._ev[slot] if timed else None)
+        main = torch.cuda.current_stream()
+        self._mark(step, 0)
+        F, step.batch = self._features(batch, maps)
+        step.F = F.F
+        self._mark(step, 1)
+        if read_back:
+            step.words = self._pinned_words(slot)
+            if tail is not None:
+                # the guard's words are this forward's own only until the next forward starts: snapshot them on the forward's stream
+                self.model.range_snapshot(step.words)
+        step.featured = torch.cuda.Event()
+        step.featured.record(main)
+        if tail is not None:
+            tail.wait_event(step.featured)
+        with _CALLERS_STREAM if tail is None else torch.cuda.stream(tail):
+            if tail is not None and self.cfg.isolate_failures and step.batch.dropped.any():
+                step.batch.record_stream(tail)
+            step.result = (self._match_and_register if self.cfg.use_RANSAC else self._match_and_register_sc2)(step, seed)
+            self._mark(step, 3)
+            if read_back:
+                step.host = self._pinned_set(slot, step.result)
+                step.host.copy_(step.result, non_blocking=True)
+                if self.cfg.icp_refine:
+                    step.icp_host = self._pinned_set(slot, step.icp)
+                    step.icp_host.copy_(step.icp, non_blocking=True)
+                if tail is None:
+                    self.model.range_snapshot(step.words)     # one stream: the next forward is behind all of this anyway
+                step.done = torch.cuda.Event()
+                step.done.record(main if tail is None else tail)
+        return step
+
+    def _publish(self, step, count_dropped=True):
+        """``step`` becomes what the pipeline keeps about the LAST step; -> ``step``."""
+        self.featured, self.matched, self.last_nn_idx, self._icp_dev = step.featured, step.matched, step.nn_idx, step.icp
+        if self.cfg.isolate_failures:
+            self.registered_batch = step.batch
+            if count_dropped:
+                self.dropped_pairs += int((step.batch.dropped != 0).sum())
+        return step
 
     @torch.no_grad()
-    def _retry_fp32(self, batch, seed, maps, return_device, slot):
-        """fp32_retry_per_step: this step again with fp32 MFMAs, and back to the model's own arithmetic for the next one.  The re-run
-        uses the overflowed step's own buffer set ``slot`` (the SC2-PCR index staging of the other slot may still feed a step in flight)
-        and, for a pipelined step, leaves what the pipeline keeps about the LAST enqueued step - ``slot``, ``featured`` / ``matched`` (``prepare_maps(after=)``),
-        ``last_nn_idx``, the stage timers - as it was."""
-        from . import _lib
+    def _retry_fp32(self, batch, seed, maps, slot, pipelined):
+        """fp32_retry_per_step: this step again with fp32 MFMAs on the current stream, and back to the model's own arithmetic for the
+        next one -> the step.  The re-run uses the overflowed step's own buffer set ``slot`` (the SC2-PCR index staging of the other
+        slot may still feed a step in flight).  It is not published here: a pipelined step's re-run (``PendingStep.wait``) leaves
+        what the pipeline keeps about the LAST enqueued step, stage timers included, as it was; ``register``'s own IS the last step
+        and ``register`` publishes it."""
         self.fp32_retries += 1
-        if return_device:     # a pipelined step knew of its overflow from its own words: clear the sticky flag the guard still holds
+        if pipelined:     # a pipelined step knew of its overflow from its own words: clear the sticky flag the guard still holds
             try:
                 self.model.check_range()
             except _lib.EyocError as e:
                 if e.code != _lib.ERR_RANGE:
                     raise
-        # (``register``'s own retry IS the last step: what it leaves behind stays)
-        kept = {k: self.__dict__[k] for k in ("slot", "featured", "matched", "last_nn_idx", "timing") if k in self.__dict__} if return_device else {}
-        kept["dropped_pairs"] = self.dropped_pairs      # the step's dropped pairs were counted when it ran first
         math, self.model.spconv_math = self.model.spconv_math, "fp32"
-        if return_device:
-            self.slot, self.timing = slot, False
         try:
-            return self.register(batch, seed, return_device, maps)
+            return self._step(batch, seed, maps, slot, self.timing and not pipelined)
         finally:
             self.model.spconv_math = math
-            self.__dict__.update(kept)
 
     @torch.no_grad()
-    def prepare_maps(self, batch: DeviceBatch, after=None):
+    def prepare_maps(self, batch: DeviceBatch, after=None) -> MapsHandle:
         """Build the coordinate maps of ``batch`` NOW, on a side stream: they only depend on the coordinates, so a
         serving loop builds the next batch's maps (hash / sort / rulebook kernels, latency- and atomics-bound) while the
         previous batch is still in its RANSAC (VALU-bound) on the main stream.  Returns the handle ``register(...,
-        maps=)`` takes; it may be dropped right after the step was enqueued (the maps' workspace is recorded on every stream that
-        reads it, ``CoordinateManager._reading``).  Under ``isolate_failures`` the handle is ``(cm, ready, batch')``: ``batch'`` is ``batch``
-        without the pairs whose clouds failed the build (``batch`` itself if none did), and ``register`` / ``enqueue`` run on it.  ``after``: an event the side stream waits for
+        maps=)`` takes, a ``MapsHandle(cm, ready, batch')``; it may be dropped right after the step was enqueued (the maps' workspace is
+        recorded on every stream that reads it, ``CoordinateManager._reading``).  ``batch'`` is ``batch`` itself or, under
+        ``isolate_failures``, ``batch`` without the pairs whose clouds failed the build, and ``register`` / ``enqueue`` run on it.
+        ``after``: an event the side stream waits for
         first - ``self.matched`` (recorded by ``register`` when its forward and matching are enqueued) puts the build
         beside that step's RANSAC instead of beside whatever the main stream happens to run at enqueue time (the forward:
         both want LDS and the atomics path, and the forward's kernels slow down by ~10 %)."""
-        from .sparse_tensor import CoordinateManager
-        if getattr(self, "_side", None) is None:
-            self._side = torch.cuda.Stream(device=batch.coords.device, priority=getattr(self, "side_priority", 0))
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=batch.coords.device, priority=self.side_priority)
         if after is not None:
             self._side.wait_event(after)
         with torch.cuda.stream(self._side):
-            if self.cfg.isolate_failures:
-                # a failed build has synchronised the side stream and raised: stream and ctx are free for the drop and the rebuild
-                cm, reduced = self._build_isolated(batch)
-                ready = torch.cuda.Event()
-                ready.record(self._side)
-                return cm, ready, reduced
-            cm = CoordinateManager(batch.coords)
-            cm.maps(-1)
+            # (isolate_failures: a failed build has synchronised the side stream and raised: stream and ctx are free for the drop and the rebuild)
+            cm, batch = self._build_maps(batch)
             ready = torch.cuda.Event()
             ready.record(self._side)
-        return cm, ready
+        return MapsHandle(cm, ready, batch)
 
     def enqueue(self, batch: DeviceBatch, seed: int = 0, maps=None, slot: int = 0, tail_stream: bool = False) -> "PendingStep":
         """``register`` for a caller that pipelines steps: everything - the read-back of the ``[P, 84]`` result records (RANSAC path;
-        ``T f32 [P, 4, 4]`` on the SC2-PCR path) into pinned host memory and of the split16 guard's verdict on THIS forward included - is enqueued now; the host
-        waits on ``PendingStep.wait()`` later.  A read-back issued after the next step was enqueued (``register(...,
-        return_device=True)`` + ``.cpu()``) queues behind that whole step on the stream: the host then never runs ahead of the GPU,
-        and the GPU idles while the host decodes results and launches the next step (measured: 2 ms of a 24 ms step).
+        ``T f32 [P, 4, 4]`` on the SC2-PCR path) into pinned host memory and of the split16 guard's verdict on THIS forward included -
+        is enqueued now (``_step(read_back=True)`` says why); the host waits on ``PendingStep.wait()`` later.
         ``slot``: which of the two pinned buffer sets to use (a set is free again once its ``wait()`` returned).
 
-        ``tail_stream=True`` (round 5, two steps in flight): only the forward (+ the guard's snapshot) goes on the caller's
+        ``tail_stream=True`` (two steps in flight): only the forward (+ the guard's snapshot) goes on the caller's
         stream; row gather, feature NN, RANSAC and the read-back of the records go on a second stream of the pipeline that waits
         for the forward.  A caller that enqueues the next step right away gets that step's forward (matrix pipe, LDS) beside this
         step's matching / RANSAC (fp64 VALU, no LDS) - same kernels, same inputs, bit-identical records."""
         self.slot = slot
-        if not tail_stream:
-            res = self.register(batch, seed=seed, return_device=True, maps=maps)
-            host, words = self._pinned_set(slot, res)
-            host.copy_(res, non_blocking=True)
-            icp = self._icp_readback(slot)
-            self.model.range_snapshot(words)
-            done = torch.cuda.Event()
-            done.record()
-            if self.cfg.isolate_failures:
-                batch, maps = self.registered_batch, None      # what a retry runs on: the reduced batch builds cleanly
-            return PendingStep(host, words, done, res, retry=self._retry_args(batch, seed, maps, slot), dropped=self._dropped(batch), icp=icp)
-        main = torch.cuda.current_stream()
-        if getattr(self, "_tail", None) is None:
+        if tail_stream and self._tail is None:
             self._tail = torch.cuda.Stream(device=batch.coords.device)
-        self._mark(0)
-        F, batch = self._features(batch, maps)
-        F = F.F
-        if self.cfg.isolate_failures:
-            self.registered_batch, maps = batch, None
-            self.dropped_pairs += int((batch.dropped != 0).sum())
-        self._mark(1)
-        # the guard's words are this forward's own only until the next forward starts: snapshot them on the forward's stream
-        words = self._pinned_words(slot)
-        self.model.range_snapshot(words)
-        self.featured = torch.cuda.Event()
-        self.featured.record(main)
-        self._tail.wait_event(self.featured)
-        with torch.cuda.stream(self._tail):
-            if self.cfg.isolate_failures and batch.dropped.any():
-                batch.record_stream(self._tail)
-            res = self._match_and_register(batch, F, seed) if self.cfg.use_RANSAC else self._match_and_register_sc2(batch, F, seed)
-            host, _ = self._pinned_set(slot, res)
-            host.copy_(res, non_blocking=True)
-            icp = self._icp_readback(slot)
-            done = torch.cuda.Event()
-            done.record(self._tail)
-        # F was allocated on the caller's stream and is read on the tail stream: it stays referenced until wait()
-        return PendingStep(host, words, done, res, keep=(F,), retry=self._retry_args(batch, seed, maps, slot), dropped=self._dropped(batch),
-                           icp=icp)
+        step = self._publish(self._step(batch, seed, maps, slot, self.timing, self._tail if tail_stream else None, read_back=True))
+        retry = None
+        if self.cfg.fp32_retry_per_step and self.model.spconv_math == "auto":
+            # what a retry runs on - under isolate_failures the reduced batch, which builds cleanly without the handle
+            retry = (self, step.batch, seed, None if self.cfg.isolate_failures else maps, slot)
+        # under ``tail_stream`` F was allocated on the caller's stream and is read on the tail stream: it stays referenced until wait()
+        return PendingStep(step.host, step.words, step.done, step.result, keep=(step.F,) if tail_stream else None, retry=retry,
+                           dropped=step.batch.dropped.copy() if self.cfg.isolate_failures else None, icp=step.icp_host)
 
-    def _icp_readback(self, slot):
-        """icp_refine: the step's ICP records on their way to the slot's pinned buffer, on the current stream (None when the stage is off)."""
-        if not self.cfg.icp_refine:
-            return None
-        host, _ = self._pinned_set(slot, self._icp_dev)
-        host.copy_(self._icp_dev, non_blocking=True)
-        return host
-
-    def _icp_refine(self, batch, T):
+    def _icp_refine(self, step, T):
         """icp_refine: one batched ICP over the pairs' sample sets on the CURRENT stream, started from the back-end's poses ``T f32 [P, 16]``
         as they are on the device -> the refined poses, f32 ``[P, 16]`` (the fp64 result rounded once).  A pair without a pose (NaN:
-        dropped, degenerate) keeps it and gets BAD_INIT, an empty segment FEW; the records stay in ``_icp_dev``."""
-        from . import icp
-        gate = self.cfg.icp_max_correspondence_distance
-        self._icp_dev = icp.icp_batched(batch.xyz0.reshape(-1, 3), batch.xyz1.reshape(-1, 3), batch.seg, batch.seg,
-                                        2.0 * self.cfg.voxel_size if gate is None else gate, T.to(torch.float64),
-                                        self.cfg.icp_max_iteration)
-        return self._icp_dev.view(torch.float64)[:, :16].to(torch.float32)
+        dropped, degenerate) keeps it and gets BAD_INIT, an empty segment FEW; the records stay in ``step.icp``."""
+        batch, gate = step.batch, self.cfg.icp_max_correspondence_distance
+        step.icp = icp.icp_batched(batch.xyz0.reshape(-1, 3), batch.xyz1.reshape(-1, 3), batch.seg, batch.seg,
+                                   2.0 * self.cfg.voxel_size if gate is None else gate, T.to(torch.float64), self.cfg.icp_max_iteration)
+        return step.icp.view(torch.float64)[:, :16].to(torch.float32)
 
-    def _decode_icp(self):
-        """icp_refine, ``register``: the ICP records follow the results to the host (the stream is drained by then)."""
-        if self.cfg.icp_refine:
-            from . import icp
-            host = self._icp_dev.cpu()
-            self.last_icp = [icp.decode_icp_result(host[p]) for p in range(host.shape[0])]
-
-    def _dropped(self, batch):
-        return batch.dropped.copy() if self.cfg.isolate_failures else None
-
-    def _retry_args(self, batch, seed, maps, slot):
-        return (self, batch, seed, maps, slot) if self.cfg.fp32_retry_per_step and self.model.spconv_math == "auto" else None
-
-    def _pinned_stage(self, count):
-        """Pinned int64 staging for the index upload of the SC2-PCR path; one buffer per event slot (``self.slot``: a slot's previous
-        upload was consumed by the time its step's results were read)."""
-        st = self.__dict__.setdefault("_stage", {})
-        buf = st.get(self.slot)
+    def _pinned_stage(self, slot, count):
+        """Pinned int64 staging for the index upload of the SC2-PCR path; one buffer per slot (a slot's previous upload was consumed by
+        the time its step's results were read)."""
+        buf = self._stage.get(slot)
         if buf is None or buf.numel() < count:
-            buf = st[self.slot] = torch.empty(max(count, 1), dtype=torch.int64, pin_memory=True)
+            buf = self._stage[slot] = torch.empty(max(count, 1), dtype=torch.int64, pin_memory=True)
         return buf
 
     def _pinned_words(self, slot):
-        w = self.__dict__.setdefault("_pinned_w", {})
-        if slot not in w:
-            w[slot] = torch.zeros(4, dtype=torch.int32, pin_memory=True)
-        return w[slot]
+        if slot not in self._pinned_w:
+            self._pinned_w[slot] = torch.zeros(4, dtype=torch.int32, pin_memory=True)
+        return self._pinned_w[slot]
 
     def _pinned_set(self, slot, res):
-        bufs = self.__dict__.setdefault("_pinned", {})
         key = (slot, tuple(res.shape), res.dtype)
-        if key not in bufs:
-            bufs[key] = torch.empty(res.shape, dtype=res.dtype, pin_memory=True)
-        return bufs[key], self._pinned_words(slot)
+        if key not in self._pinned:
+            self._pinned[key] = torch.empty(res.shape, dtype=res.dtype, pin_memory=True)
+        return self._pinned[key]
 
-    def _match_and_register(self, batch, F, seed):
+    def _matched(self, step):
+        """Forward and matching are enqueued on the current stream: the step's ``matched`` event (``prepare_maps(after=)``), timer 2."""
+        self._mark(step, 2)
+        step.matched = torch.cuda.Event()
+        step.matched.record()
+
+    def _match_and_register(self, step, seed):
         """Row gather (+ descriptor blend), segmented feature NN and the batched RANSAC of all pairs on the CURRENT stream ->
         ``[P, 84]`` result records on the device."""
+        batch, F = step.batch, step.F
         F0 = gather_rows(F, batch.sel0, batch.G0, batch.beta)     # the sampled rows (+ descriptor blend, if any)
         F1 = gather_rows(F, batch.sel1, batch.G1, batch.beta)
         # isolate_failures: a dropped pair is an empty segment - for the neighbour search, which gives the live rows what the live
         # segments alone give (tests/test_gpu_isolate_batch.py), and for the back-end, where it keeps the pair's slot and every seed
-        iso = self.cfg.isolate_failures
-        nn_idx = knn1_segmented(F0, F1, batch.seg, batch.seg, "SquareL2", return_distance=False)
-        self.last_nn_idx = nn_idx
-        self._mark(2)
-        self.matched = torch.cuda.Event()
-        self.matched.record()
+        step.nn_idx = knn1_segmented(F0, F1, batch.seg, batch.seg, "SquareL2", return_distance=False)
+        self._matched(step)
         # all pairs in one batched call (pair p samples with seed + p, exactly like a per-pair loop would)
         # (the scratch budget - a quarter of the free memory, a driver round trip - is asked for once per pipeline: any launch-chunk
         # size gives the same records)
-        if getattr(self, "_ransac_budget", None) is None:
+        if self._ransac_budget is None:
             self._ransac_budget = reg._ransac_budget(F.device)
-        prev = self._degenerate(F.device, 1) if iso else None
-        try:
+        with self._accept_degenerate(F.device):
             res = reg.ransac_batched_from_correspondences(
-                batch.xyz0.reshape(-1, 3), batch.xyz1.reshape(-1, 3), nn_idx, batch.seg, batch.seg,
+                batch.xyz0.reshape(-1, 3), batch.xyz1.reshape(-1, 3), step.nn_idx, batch.seg, batch.seg,
                 self.cfg.voxel_size * 1.0, self.cfg.ransac_max_iteration, seed=seed,
                 workspace_budget=self._ransac_budget)                                  # [P, 84] bytes on the device
-        finally:
-            if iso:
-                self._degenerate(F.device, prev)
         if self.cfg.icp_refine:
-            res.view(torch.float32)[:, :16] = self._icp_refine(batch, res.view(torch.float32)[:, :16])
-        self._mark(3)
+            res.view(torch.float32)[:, :16] = self._icp_refine(step, res.view(torch.float32)[:, :16])
         return res
 
     @torch.no_grad()
     def register(self, batch: DeviceBatch, seed: int = 0, return_device=False, maps=None):
         """One pass of the hot path over ``P`` pairs -> ``T f32 [P,4,4]`` (host) and per-pair stats."""
-        self._mark(0)
-        F, batch = self._features(batch, maps)   # isolate_failures: the batch without the pairs that failed the map build
-        F = F.F
-        if self.cfg.isolate_failures:
-            self.registered_batch, maps = batch, None
-            self.dropped_pairs += int((batch.dropped != 0).sum())
-        self._mark(1)
-        self.featured = torch.cuda.Event()       # the forward is enqueued: what `prepare_maps(after=)` of the NEXT batch may wait for
-        self.featured.record()
-        n = batch.n_points
-        if self.cfg.use_RANSAC:
-            res = self._match_and_register(batch, F, seed)
-            if return_device:
-                return res                # the caller reads back later - and calls model.check_range() then
-            words = self._range_snapshot()
-            host = res.cpu()
-            self._decode_icp()
-            return self._checked(batch, seed, maps, words) or self._flagged(batch, [reg.decode_ransac_result(host[p], n) for p in range(batch.P)])
-        T = self._match_and_register_sc2(batch, F, seed)
+        step = self._publish(self._step(batch, seed, maps, self.slot, self.timing))
         if return_device:
-            return T
-        words = self._range_snapshot()
-        Th = T.cpu().numpy().astype(np.float64)
-        self._decode_icp()
-        return self._checked(batch, seed, maps, words) or self._flagged(batch, [reg.RegistrationResult(Th[p], 0.0, 0.0) for p in range(batch.P)])
+            return step.result            # the caller reads back later - and calls model.check_range() then
+        return self._read_back(step, seed, maps)
 
-    def _flagged(self, batch, results):
-        """isolate_failures: a dropped pair's result - the failed record (T all NaN, fitness 0, no inliers, best_hypothesis -1) with the
-        pair's DROPPED_* bits in ``status``."""
+    def _read_back(self, step, seed, maps, status=0):
+        """``register``: the records of ``step`` on the host, decoded (``status`` or-ed in) - or, after a split16 overflow in automatic
+        mode, those of the step run again: that step alone in fp32 (``fp32_retry_per_step``), or with the model switched to fp32 MFMAs for good."""
+        words = self._range_snapshot()
+        host = step.result.cpu()
+        if self.cfg.icp_refine:     # the ICP records follow the results to the host (the stream is drained by then)
+            icp_host = step.icp.cpu()
+            self.last_icp = [icp.decode_icp_result(icp_host[p]) for p in range(icp_host.shape[0])]
+        batch = step.batch
+        if self.cfg.isolate_failures:
+            maps = None               # what a re-run runs on: the reduced batch builds cleanly without the handle
+        # words all clear: nothing overflowed since the last check, no need to ask the device again
+        if int(words[0]) != 0 or int(words[3]) != 0:
+            try:
+                self.model.check_range()
+            except _lib.EyocError as e:
+                if e.code != _lib.ERR_RANGE or self.model.spconv_math != "auto" or status:      # (status: this IS the fp32 re-run)
+                    raise
+                if self.cfg.fp32_retry_per_step:
+                    again = self._publish(self._retry_fp32(batch, seed, maps, self.slot, pipelined=False), count_dropped=False)
+                    return self._read_back(again, seed, maps, RETRIED_FP32)
+                logging.warning("eyoc_amd: split16 overflow in the registration pipeline; switching the model to fp32 MFMAs")
+                self.model.spconv_math = "fp32"
+                return self.register(batch, seed, False, maps)
+        if self.cfg.use_RANSAC:
+            results = [reg.decode_ransac_result(host[p], batch.n_points) for p in range(batch.P)]
+        else:
+            Th = host.numpy().astype(np.float64)
+            results = [reg.RegistrationResult(Th[p], 0.0, 0.0) for p in range(batch.P)]
+        # isolate_failures: a dropped pair's result - the failed record (T all NaN, fitness 0, no inliers, best_hypothesis -1) with the
+        # pair's DROPPED_* bits in ``status``
         if self.cfg.isolate_failures:
             for p in np.flatnonzero(batch.dropped):
                 results[p] = reg.RegistrationResult(np.full((4, 4), np.nan), 0.0, 0.0, status=int(batch.dropped[p]))
+        if status:
+            for r in results:
+                r.status |= status
         return results
 
     def _range_snapshot(self):
         """The range guard's words on their way to pinned memory, enqueued IN FRONT of the result read-back: the read-back's own
         synchronisation then covers them, and a clean step needs no second host wait (``check_range`` is a copy + a stream
         synchronisation of its own: 35 us of a single pair's 1.5 ms)."""
-        w = self.__dict__.get("_range_words")
-        if w is None:
-            w = self._range_words = torch.zeros(4, dtype=torch.int32).pin_memory()
-        self.model.range_snapshot(w)
-        return w
+        if self._range_words is None:
+            self._range_words = torch.zeros(4, dtype=torch.int32).pin_memory()
+        self.model.range_snapshot(self._range_words)
+        return self._range_words
 
-    def _match_and_register_sc2(self, batch, F, seed):
+    def _match_and_register_sc2(self, step, seed):
         """SC2-PCR path (scripts/test_kitti.py:179-181) on the CURRENT stream -> ``T f32 [P,4,4]`` on the device.
         Matcher.estimator re-samples both clouds to num_node with replacement, matches them and registers the matched pairs.
         Same draws (pair by pair from one seeded RandomState, source before target) and the same arithmetic as a per-pair loop
         over ``matcher.estimator``, but no per-pair device work: ONE index upload, row gathers, one segmented nearest-neighbour
         launch and one batched SC2-PCR call for all pairs.  The host draws overlap the forward, which is still running.
 
-        Round 5: the 8000 draws of a pair hold only ~4000 distinct rows of either cloud, and a duplicated target ties with itself
-        exactly - such rows (60 %) fell through the MFMA pre-filter into the exact pass (2.3 of the step's 18 ms on 16 pairs).  The
-        neighbour search now runs on the DISTINCT rows: distinct targets in the order of their first draw - the reference's
-        arg-min returns the first of equal distances, so the winner among duplicates is the first draw, and the lowest first draw
-        among tied distinct rows is the lowest index overall -, every draw of a source row takes the result of its row.
+        The 8000 draws of a pair hold only ~4000 distinct rows of either cloud, and a duplicated target ties with itself
+        exactly - such rows (60 %) fall through the MFMA pre-filter into the exact pass (2.3 of the step's 18 ms on 16 pairs).  So the
+        neighbour search runs on the DISTINCT rows (``distinct_draws``), and every draw of a source row takes the result of its row.
         Identical indices (``tests/test_gpu_sc2pcr.py`` compares with the per-pair estimator), a quarter of the products."""
-        n = batch.n_points
+        batch, F, m = step.batch, step.F, self.matcher
+        n, P, dev = batch.n_points, batch.P, F.device
         F0 = gather_rows(F, batch.sel0, batch.G0, batch.beta)
         F1 = gather_rows(F, batch.sel1, batch.G1, batch.beta)
         rng = np.random.RandomState(seed)
-        m = self.matcher
-        P = batch.P
-        dev = F.device
         # isolate_failures: the per-pair arrays hold the live pairs only, back to back (``L`` of them; live pair ``p`` is block ``q``);
         # the draws are still made for all P, so that a live pair's do not depend on who was dropped, and the back-end gets an empty
         # segment for a dropped pair.  Without dropped pairs ``q == p`` and ``L == P``.
@@ -722,71 +745,41 @@ class RegistrationPipeline:
             src_k, tgt_k = batch.xyz0.reshape(-1, 3), batch.xyz1.reshape(-1, 3)
             seg = np.arange(L + 1) * nn_pts
             nn = knn1_segmented(F0, F1, seg, seg, "GemmL2", return_distance=False)      # match_pair's own formula
-            self._mark(2)
-            self.matched = torch.cuda.Event()
-            self.matched.record()
+            self._matched(step)
+            nn = nn + torch.arange(L, device=dev).repeat_interleave(nn_pts) * nn_pts     # local -> packed target row
         else:
             nn_pts = int(m.num_node)
             # RandomState.choice(n, k) IS randint(0, n, k) on the same stream, and one call for all pairs draws what the per-pair
             # calls of Matcher.match_pair draw one after the other (source before target; tests/test_gpu_sc2pcr.py compares)
             draws = rng.randint(0, n, (P, 2, nn_pts)).astype(np.int64, copy=False)
-            us, ut, inv, first, seg_a, seg_b = [], [], [], [], [0], [0]
-            pos = np.arange(nn_pts, dtype=np.int64)
-            for q, p in enumerate(live):
-                d0, d1 = draws[p, 0], draws[p, 1]
-                present = np.zeros(n, bool)
-                present[d0] = True
-                u0 = np.flatnonzero(present)                                   # distinct source rows
-                i0 = (np.cumsum(present) - 1)[d0]                               # draw -> its distinct row
-                fst = np.full(n, nn_pts, np.int64)
-                np.minimum.at(fst, d1, pos)                                     # first draw of every target row
-                f1 = np.flatnonzero(fst[d1] == pos)                             # the first draws, ascending: distinct targets in that order
-                u1 = d1[f1]
-                us.append(u0 + q * n); inv.append(i0 + seg_a[-1])
-                ut.append(u1 + q * n); first.append(f1 + q * nn_pts)
-                seg_a.append(seg_a[-1] + len(u0)); seg_b.append(seg_b[-1] + len(u1))
+            us, ut, inv, first, seg_a, seg_b, base_u = distinct_draws(draws, live, n)
             if L < P:
                 draws = draws[live]                       # the dropped pairs' draws stay out of the upload
             draws += (np.arange(L, dtype=np.int64) * n)[:, None, None]
-            gsi, gti = draws[:, 0].reshape(-1), draws[:, 1].reshape(-1)
-            base_u = np.repeat(np.asarray(seg_b[:-1], np.int64), np.diff(seg_a))     # distinct source row -> first distinct target of its pair
-            if L == 0:
-                inv = us = ut = first = [np.zeros(0, np.int64)]
-            parts = [gsi, gti, np.concatenate(inv), np.concatenate(us), np.concatenate(ut), np.concatenate(first), base_u]
+            parts = [draws[:, 0].reshape(-1), draws[:, 1].reshape(-1), inv, us, ut, first, base_u]
             cuts = np.cumsum([0] + [len(a) for a in parts])
             # ONE upload, from pinned memory: a copy from pageable memory blocks the host until everything enqueued on this stream
             # before it is done - with two steps in flight that is the previous step's whole SC2-PCR (the steps then run one after
             # the other however they were enqueued)
-            stage = self._pinned_stage(int(cuts[-1]))
+            stage = self._pinned_stage(step.slot, int(cuts[-1]))
             np.concatenate(parts, out=stage.numpy()[:cuts[-1]])
             packed = stage[:cuts[-1]].to(dev, non_blocking=True)
             gsi_d, gti_d, inv_d, us_d, ut_d, first_d, base_d = (packed[cuts[k]:cuts[k + 1]] for k in range(7))
             src_k = batch.xyz0.reshape(-1, 3).index_select(0, gsi_d)
             tgt_k = batch.xyz1.reshape(-1, 3).index_select(0, gti_d)
             nn_u = knn1_segmented(gather_rows(F0, us_d), gather_rows(F1, ut_d), seg_a, seg_b, "GemmL2", return_distance=False)
-            self._mark(2)
-            self.matched = torch.cuda.Event()
-            self.matched.record()
+            self._matched(step)
             # distinct source row -> first draw (packed row of tgt_k) of its nearest distinct target; then every draw of that row
             nn = first_d.index_select(0, nn_u + base_d).index_select(0, inv_d)
         keep = min(nn_pts, int(m.max_points))                                            # SC2_PCR.py:318-319 truncation
-        if m.num_node == 'all':
-            base = torch.arange(L, device=dev).repeat_interleave(nn_pts) * nn_pts       # local -> packed target row
-            nn = nn + base
         tgt_m = tgt_k.index_select(0, nn)
         if keep < nn_pts:
             src_k = src_k.reshape(L, nn_pts, 3)[:, :keep].reshape(-1, 3)
             tgt_m = tgt_m.reshape(L, nn_pts, 3)[:, :keep].reshape(-1, 3)
-        iso = self.cfg.isolate_failures
-        prev = self._degenerate(dev, 1) if iso else None
-        try:
+        with self._accept_degenerate(dev):
             T, _, _ = m.SC2_PCR_packed(src_k.contiguous(), tgt_m.contiguous(), live_segments(batch.dropped, keep))
-        finally:
-            if iso:
-                self._degenerate(dev, prev)
         if self.cfg.icp_refine:
-            T = self._icp_refine(batch, T.reshape(-1, 16)).reshape(-1, 4, 4)
-        self._mark(3)
+            T = self._icp_refine(step, T.reshape(-1, 16)).reshape(-1, 4, 4)
         return T
 
     def correspondence_inlier_ratio(self, batch: DeviceBatch, nn_idx=None, thresh=None):

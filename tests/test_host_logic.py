@@ -1,5 +1,5 @@
 """CPU tests of host-side logic of the product package that needs no GPU: the reference-config loader, the planted
-correspondences of the benchmark's descriptor mode, the split of pairs over ranks."""
+correspondences of the benchmark's descriptor mode, the distinct-row bookkeeping of the SC2-PCR draws, the split of pairs over ranks."""
 import json
 import os
 
@@ -44,6 +44,43 @@ def test_planted_correspondences_have_the_stated_inlier_ratio():
     # deterministic in (pair, seed)
     a, b = syn.plant_correspondences(p, 5, 500, 0.3), syn.plant_correspondences(p, 5, 500, 0.3)
     np.testing.assert_array_equal(a["sel0"], b["sel0"]); np.testing.assert_array_equal(a["G1"], b["G1"])
+
+
+def test_distinct_draws_give_the_first_arg_min_over_all_draws():
+    """``harness.distinct_draws`` (the SC2-PCR path searches the DISTINCT rows of its re-sampled draws): with ``nn_u`` a brute-force
+    first arg-min over the distinct rows, ``first[nn_u + base][inv]`` is the brute-force first arg-min over the drawn rows, pair by
+    pair.  Integer-valued features, so that exact ties occur between distinct rows as well as between duplicates; one pair is
+    dropped on odd seeds."""
+    from eyoc_amd.harness import distinct_draws
+    P, n, nn_pts = 4, 50, 120
+
+    def first_argmin(A, B):
+        return ((A[:, None, :] - B[None, :, :]) ** 2).sum(-1).argmin(1)      # numpy's arg-min returns the first of equal values
+    ties_between_distinct_rows = 0
+    for seed in range(20):
+        rng = np.random.RandomState(seed)
+        live = np.array([p for p in range(P) if not (seed % 2 and p == seed % P)])
+        L = len(live)
+        F0, F1 = rng.randint(0, 3, (L * n, 4)).astype(np.float64), rng.randint(0, 3, (L * n, 4)).astype(np.float64)
+        draws = rng.randint(0, n, (P, 2, nn_pts)).astype(np.int64)
+        kept = draws.copy()
+        us, ut, inv, first, seg_a, seg_b, base = distinct_draws(draws, live, n)
+        assert np.array_equal(draws, kept)                                   # the caller packs the draws afterwards
+        assert len(seg_a) == len(seg_b) == L + 1 and seg_a[-1] == len(us) == len(base) and seg_b[-1] == len(ut) == len(first)
+        assert inv.shape == (L * nn_pts,) and all(a.dtype == np.int64 for a in (us, ut, inv, first, base))
+        nn_u = np.concatenate([first_argmin(F0[us[seg_a[q]:seg_a[q + 1]]], F1[ut[seg_b[q]:seg_b[q + 1]]]) for q in range(L)])
+        got = first[nn_u + base][inv]
+        for q, p in enumerate(live):
+            A, B = F0[q * n + draws[p, 0]], F1[q * n + draws[p, 1]]
+            np.testing.assert_array_equal(got[q * nn_pts:(q + 1) * nn_pts], first_argmin(A, B) + q * nn_pts, err_msg=f"seed {seed} pair {p}")
+            assert np.array_equal(np.sort(us[seg_a[q]:seg_a[q + 1]]), np.unique(draws[p, 0]) + q * n)
+            assert np.array_equal(np.sort(ut[seg_b[q]:seg_b[q + 1]]), np.unique(draws[p, 1]) + q * n)
+            d = ((F0[us[seg_a[q]:seg_a[q + 1]]][:, None] - F1[ut[seg_b[q]:seg_b[q + 1]]][None]) ** 2).sum(-1)
+            ties_between_distinct_rows += int(((d == d.min(1, keepdims=True)).sum(1) > 1).sum())
+    assert ties_between_distinct_rows > 100                                  # the case the order of ``ut`` exists for
+    # no live pair at all: empty arrays of the same types
+    us, ut, inv, first, seg_a, seg_b, base = distinct_draws(draws, np.zeros(0, np.int64), n)
+    assert seg_a == [0] and seg_b == [0] and all(a.shape == (0,) and a.dtype == np.int64 for a in (us, ut, inv, first, base))
 
 
 def test_round_robin_shard_covers_every_pair_once():
