@@ -143,6 +143,8 @@ PROTOTYPES = {
     "eyoc_model_pack_host": (_i, [C.POINTER(ModelDesc), C.POINTER(LayerParams), _i, _vp, _sz]),
     "eyoc_model_create": (_i, [_vp, C.POINTER(ModelDesc), C.POINTER(LayerParams), _i, _vp, _sz, C.POINTER(_vp)]),
     "eyoc_model_destroy": (_i, [_vp]),
+    "eyoc_model_repack_workspace_bytes": (_sz, [_vp]),
+    "eyoc_model_repack_device": (_i, [_vp, _vp, C.POINTER(LayerParams), _i, _vp, _sz, _vp]),
     "eyoc_model_fuse_tail": (_i, [_vp, _i]),
     "eyoc_model_workspace_bytes": (_sz, [_vp, _vp]),
     "eyoc_model_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -206,9 +206,295 @@ int check_desc(const eyoc_model_desc* d) {
   return EYOC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Device-side re-pack (eyoc_model_repack_device): the arithmetic of eyoc_model_pack_host, eyoc_spconv_pack_weights and
+// eyoc_spconv_pack_weights_split16 restated as four launches over ALL layers of the plan - fold, fp32 pack + layer maximum, layer
+// scales, split16 pack.  The blob must come out bit for bit as the host writes it, so every float operation below is the host's, in the
+// host's order, unfused (the host is plain x86-64: no FMA), and a NaN an operation produces or passes on is the one SSE gives.
+// Per-layer descriptors travel as kernel arguments (2.7 KB at most): nothing is uploaded, nothing allocated.
+constexpr int RP_MAXL = 48;        // layers of the largest plan (expanded: 46)
+constexpr int RP_CH = 256;         // channels of the widest layer (check_desc)
+
+struct RpFoldLayer {
+  const float *g, *b, *m, *v, *bias;   // the norm folded into the layer (all NULL: none), the convolution's bias (NULL: none)
+  uint32_t b_off, w_off;               // float offsets into the blob: shifts; M_AFFINE's scales
+  uint32_t cout, affine;
+};
+struct RpFoldArgs { RpFoldLayer L[RP_MAXL]; };
+
+struct RpPackLayer {
+  const float* kernel;                 // NULL: M_AFFINE (no weights)
+  uint32_t w_off, w16_off, s_off;
+  uint32_t K, cin, cout, conv1;
+};
+struct RpPackArgs {
+  RpPackLayer L[RP_MAXL];
+  uint32_t blk[RP_MAXL + 1];           // prefix of 256-thread blocks per layer: a block works inside one layer
+  int n;
+};
+
+struct RpWs {                          // the workspace
+  float scale[RP_MAXL][RP_CH];         // folded scale per layer and channel (1 for a layer without a norm)
+  uint32_t maxbits[RP_MAXL];           // bits of max |w * scale| per layer (integer order = float order for non-negative floats)
+  float up[RP_MAXL];                   // 2^sh of the split16 layers
+};
+
+// what SSE's mulss / subss / addss / divss return where the IEEE result r of (a op b) is a NaN: the first NaN operand, quieted, else
+// the default NaN, which is NEGATIVE on x86 (the device's is positive).  (Two NaN operands: the host compiler chooses the order of a
+// commutative operation's operands - such a product is not pinned.)
+__device__ inline float rp_nan(float r, float a, float b) {
+  if (r == r) return r;
+  if (a != a) return __uint_as_float(__float_as_uint(a) | 0x00400000u);
+  if (b != b) return __uint_as_float(__float_as_uint(b) | 0x00400000u);
+  return __uint_as_float(0xffc00000u);
+}
+
+__device__ inline float rp_mul(float a, float b) {
+#pragma clang fp contract(off)
+  return rp_nan(a * b, a, b);
+}
+
+// float -> fp16 as the host's _Float16 conversion: round to nearest even, subnormals kept; a NaN keeps its sign and the top of its payload
+__device__ inline uint16_t rp_half_bits(float v) {
+  if (v != v) {
+    const uint32_t u = __float_as_uint(v);
+    return (uint16_t)(((u >> 16) & 0x8000u) | 0x7e00u | ((u >> 13) & 0x1ffu));
+  }
+  const _Float16 h = (_Float16)v;
+  uint16_t b;
+  __builtin_memcpy(&b, &h, 2);
+  return b;
+}
+
+__device__ inline float rp_half_float(uint16_t b) {
+  _Float16 h;
+  __builtin_memcpy(&h, &b, 2);
+  return (float)h;
+}
+
+// wmax = f 2^e with f in [0.5, 1) (frexp) from the bits of a positive finite float
+__device__ inline int rp_frexp_e(uint32_t bits) {
+  const int E = (int)(bits >> 23);
+  return E ? E - 126 : (31 - __clz((int)bits)) - 148;
+}
+
+__device__ inline float rp_pow2(int sh) { return __uint_as_float((uint32_t)(127 + sh) << 23); }   // sh in [-24, 24]
+
+__device__ inline int rp_find_layer(const uint32_t* blk, int n, uint32_t b) {   // the layer li with blk[li] <= b < blk[li + 1]
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (blk[mid] <= b) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// one block per layer, one thread per channel: scale = gamma / sqrt(var + eps), shift = beta - mean * scale (+ bias)
+__global__ void __launch_bounds__(RP_CH) k_repack_fold(RpFoldArgs a, float eps, float* __restrict__ blob, RpWs* __restrict__ ws) {
+#pragma clang fp contract(off)
+  const int li = blockIdx.x, c = threadIdx.x;
+  const RpFoldLayer& L = a.L[li];
+  if (c == 0) ws->maxbits[li] = 0u;
+  const int pc = (int)((L.cout + 63u) / 64u * 64u);
+  if (c >= pc) return;
+  float s = 1.0f, sh = 0.0f;
+  if (c < (int)L.cout) {
+    if (L.g) {
+      const float var = L.v[c], g = L.g[c], mu = L.m[c], be = L.b[c];
+      const float ve = rp_nan(var + eps, var, eps);
+      float rt = sqrtf(ve);
+      if (rt != rt) rt = ve != ve ? __uint_as_float(__float_as_uint(ve) | 0x00400000u) : __uint_as_float(0xffc00000u);
+      s = rp_nan(g / rt, g, rt);
+      const float ms = rp_mul(mu, s);
+      sh = rp_nan(be - ms, be, ms);
+    }
+    if (L.bias) { const float bi = L.bias[c]; sh = rp_nan(sh + bi, sh, bi); }
+  } else {
+    s = 0.0f;                                                             // the blob's padding
+  }
+  blob[L.b_off + c] = sh;
+  if (L.affine) blob[L.w_off + c] = s;
+  else if (c < (int)L.cout) ws->scale[li][c] = s;
+}
+
+// the fp32 half: one thread per 16-byte fragment of eyoc_spconv_pack_weights' order (the first convolution: plain [K][cin][cout]),
+// and the layer's max |w * scale| by integer atomicMax (a maximum does not depend on the order)
+__global__ void __launch_bounds__(256) k_repack_f32(RpPackArgs a, float* __restrict__ blob, RpWs* __restrict__ ws) {
+  __shared__ uint32_t wave_max[4];
+  const int li = rp_find_layer(a.blk, a.n, blockIdx.x);
+  const RpPackLayer& L = a.L[li];
+  const uint32_t f = (blockIdx.x - a.blk[li]) * 256u + threadIdx.x;      // fragment of the layer
+  const uint32_t elems = L.K * L.cin * L.cout;
+  const float* __restrict__ sc = ws->scale[li];
+  float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+  bool live = false;
+  if (L.conv1) {
+    live = f < (elems + 63u) / 64u * 16u;                                  // with the padding behind the last float
+    const uint32_t i = f * 4u;
+    if (i + 0 < elems) o.x = rp_mul(L.kernel[i + 0], sc[(i + 0) % L.cout]);
+    if (i + 1 < elems) o.y = rp_mul(L.kernel[i + 1], sc[(i + 1) % L.cout]);
+    if (i + 2 < elems) o.z = rp_mul(L.kernel[i + 2], sc[(i + 2) % L.cout]);
+    if (i + 3 < elems) o.w = rp_mul(L.kernel[i + 3], sc[(i + 3) % L.cout]);
+  } else if (f < elems / 4u) {
+    live = true;
+    const uint32_t CT = L.cout >= 128u ? 128u : L.cout, CC = L.cin % 64u == 0u ? 64u : 32u;   // spconv_ct, spconv_cc
+    const uint32_t NS = L.cout / CT, NCC = L.cin / CC, NT = CT / 16u, JQ = CC / 16u;
+    const uint32_t lane = f & 63u;
+    uint32_t r = f >> 6;
+    const uint32_t jq = r % JQ; r /= JQ;
+    const uint32_t nt = r % NT; r /= NT;
+    const uint32_t cc = r % NCC; r /= NCC;
+    const uint32_t s = r % NS, k = r / NS;
+    const uint32_t ci = cc * CC + (jq * 4u + (lane >> 4)) * 4u, co = s * CT + nt * 16u + (lane & 15u);
+    const float* __restrict__ w = L.kernel + ((size_t)k * L.cin + ci) * L.cout + co;
+    const float scv = sc[co];
+    o.x = rp_mul(w[0], scv);
+    o.y = rp_mul(w[L.cout], scv);
+    o.z = rp_mul(w[2 * (size_t)L.cout], scv);
+    o.w = rp_mul(w[3 * (size_t)L.cout], scv);
+  }
+  if (live) *reinterpret_cast<float4*>(blob + L.w_off + (size_t)f * 4u) = o;
+  // the first convolution counts finite values only, the split16 layers everything but NaN (inf included)
+  const uint32_t lim = L.conv1 ? 0x7f7fffffu : 0x7f800000u;
+  uint32_t mx = 0u;
+  {
+    const uint32_t b0 = __float_as_uint(o.x) & 0x7fffffffu, b1 = __float_as_uint(o.y) & 0x7fffffffu;
+    const uint32_t b2 = __float_as_uint(o.z) & 0x7fffffffu, b3 = __float_as_uint(o.w) & 0x7fffffffu;
+    if (b0 <= lim) mx = b0;
+    if (b1 <= lim && b1 > mx) mx = b1;
+    if (b2 <= lim && b2 > mx) mx = b2;
+    if (b3 <= lim && b3 > mx) mx = b3;
+  }
+  for (int d = 32; d; d >>= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)mx, d); mx = t > mx ? t : mx; }
+  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    mx = max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3]));
+    if (mx) atomicMax(&ws->maxbits[li], mx);
+  }
+}
+
+// one wave per layer: sh from the layer's maximum (the two host rules), the blob's 64 scale words, 2^sh for the split16 pack
+__global__ void __launch_bounds__(64) k_repack_scales(RpPackArgs a, float* __restrict__ blob, RpWs* __restrict__ ws) {
+  const int li = blockIdx.x, lane = threadIdx.x;
+  const RpPackLayer& L = a.L[li];
+  if (!L.kernel) return;
+  const uint32_t mb = ws->maxbits[li];
+  float v = 0.0f;
+  if (L.conv1) {                                                           // e = 1 for an all-zero kernel: sh = 8
+    const int e = mb ? rp_frexp_e(mb) : 1;
+    const int sh = min(24, max(-6, 9 - e));
+    v = lane == 0 ? rp_pow2(sh) : lane == 1 ? rp_pow2(-sh) : 0.0f;
+  } else {                                                                 // a zero or non-finite maximum: sh = 0
+    int sh = 0;
+    if (mb && mb < 0x7f800000u) sh = min(24, max(-6, 9 - rp_frexp_e(mb)));
+    if (lane == 0) { v = rp_pow2(-sh); ws->up[li] = rp_pow2(sh); }
+  }
+  blob[L.s_off + lane] = v;
+}
+
+// the split16 half: one thread per PAIR of 16-byte fragments - the hi halves (fragment jq = 2 q) and the lo halves (jq = 2 q + 1, 64
+// fragments further) of the same eight weights, which are read once
+__global__ void __launch_bounds__(256) k_repack_split16(RpPackArgs a, float* __restrict__ blob, const RpWs* __restrict__ ws) {
+#pragma clang fp contract(off)
+  const int li = rp_find_layer(a.blk, a.n, blockIdx.x);
+  const RpPackLayer& L = a.L[li];
+  const uint32_t g = (blockIdx.x - a.blk[li]) * 256u + threadIdx.x;
+  if (g >= L.K * L.cin * L.cout / 8u) return;                              // a thread packs eight weights
+  const uint32_t CT = L.cout >= 128u ? 128u : L.cout, CC = L.cin % 64u == 0u ? 64u : 32u;
+  const uint32_t NS = L.cout / CT, NCC = L.cin / CC, NT = CT / 16u, JQ = CC / 16u;
+  const uint32_t lane = g & 63u;
+  uint32_t r = g >> 6;
+  const uint32_t q = r % (JQ / 2u); r /= JQ / 2u;
+  const size_t f_hi = ((size_t)r * JQ + 2u * q) * 64u + lane;              // r = ((k * NS + s) * NCC + cc) * NT + nt
+  const uint32_t nt = r % NT; r /= NT;
+  const uint32_t cc = r % NCC; r /= NCC;
+  const uint32_t s = r % NS, k = r / NS;
+  const uint32_t ci = cc * CC + q * 32u + (lane >> 4) * 8u, co = s * CT + nt * 16u + (lane & 15u);
+  const float* __restrict__ w = L.kernel + ((size_t)k * L.cin + ci) * L.cout + co;
+  const float scv = ws->scale[li][co], up = ws->up[li];
+  uint32_t hi[4], lo[4];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float v = rp_mul(rp_mul(w[(size_t)e * L.cout], scv), up);
+    const uint16_t hb = rp_half_bits(v);
+    const float hf = rp_half_float(hb);
+    const uint16_t lb = rp_half_bits(rp_nan(v - hf, v, hf));
+    if (e & 1) { hi[e >> 1] |= (uint32_t)hb << 16; lo[e >> 1] |= (uint32_t)lb << 16; }
+    else { hi[e >> 1] = hb; lo[e >> 1] = lb; }
+  }
+  uint4* out = reinterpret_cast<uint4*>(blob + L.w16_off);
+  out[f_hi] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+  out[f_hi + 64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t eyoc_model_repack_workspace_bytes(const eyoc_model* m) { return m ? align_up(sizeof(RpWs)) : 0; }
+
+int eyoc_model_repack_device(eyoc_ctx* ctx, eyoc_model* m, const eyoc_layer_params* layers, int n_layers, void* ws_dev,
+                             size_t ws_bytes, void* stream) {
+  EYOC_REQUIRE(ctx && m && layers && ws_dev, EYOC_ERR_INVALID, "eyoc_model_repack_device: NULL argument");
+  EYOC_REQUIRE(ws_bytes >= eyoc_model_repack_workspace_bytes(m), EYOC_ERR_WORKSPACE,
+               "eyoc_model_repack_device: workspace %zu < required %zu bytes", ws_bytes, eyoc_model_repack_workspace_bytes(m));
+  EYOC_REQUIRE(((uintptr_t)ws_dev & 255) == 0, EYOC_ERR_INVALID, "eyoc_model_repack_device: workspace must be 256-byte aligned");
+  const int n = (int)m->layers.size();
+  EYOC_REQUIRE(n <= RP_MAXL, EYOC_ERR_INVALID, "eyoc_model_repack_device: plan of %d layers (at most %d)", n, RP_MAXL);
+  // everything that can be wrong with `layers` is found here, from the plan, before the first launch (the checks and messages of
+  // eyoc_model_pack_host)
+  RpFoldArgs fa;
+  RpPackArgs p32, p16;
+  memset(&fa, 0, sizeof(fa));
+  memset(&p32, 0, sizeof(p32));
+  uint32_t b32 = 0, b16 = 0;
+  uint32_t blk16[RP_MAXL + 1];
+  for (int li = 0; li < n; ++li) {
+    const LayerPlan& p = m->layers[li];
+    RpFoldLayer& F = fa.L[li];
+    RpPackLayer& P = p32.L[li];
+    p32.blk[li] = b32;
+    blk16[li] = b16;
+    F.b_off = (uint32_t)p.b_off; F.w_off = (uint32_t)p.w_off; F.cout = (uint32_t)p.cout; F.affine = p.map == M_AFFINE;
+    EYOC_REQUIRE(p.cout <= RP_CH, EYOC_ERR_INVALID, "eyoc_model_repack_device: layer '%s' has %d channels", p.name.c_str(), p.cout);
+    const eyoc_layer_params* cv = nullptr;
+    if (p.map != M_AFFINE) {
+      cv = find_layer(layers, n_layers, p.name);
+      EYOC_REQUIRE(cv && cv->kernel && cv->K == p.K && cv->cin == p.cin && cv->cout == p.cout, EYOC_ERR_INVALID,
+                   "eyoc_model_create: layer '%s' missing or shape mismatch (expected K=%d cin=%d cout=%d, got %d %d %d)",
+                   p.name.c_str(), p.K, p.cin, p.cout, cv ? cv->K : -1, cv ? cv->cin : -1, cv ? cv->cout : -1);
+      EYOC_REQUIRE(p.map == M_CONV1 || (p.cin > 0 && p.cin % 32 == 0 && (p.cout == 32 || p.cout == 64 || p.cout == 128 || p.cout == 256)),
+                   EYOC_ERR_INVALID, "pack_weights: unsupported shape C_in %d C_out %d", p.cin, p.cout);
+    }
+    if (!p.norm.empty()) {
+      const eyoc_layer_params* bn = find_layer(layers, n_layers, p.norm);
+      EYOC_REQUIRE(bn && bn->bn_weight && bn->bn_bias && bn->bn_mean && bn->bn_var && bn->cout == p.cout, EYOC_ERR_INVALID,
+                   "eyoc_model_create: norm '%s' missing or wrong width", p.norm.c_str());
+      F.g = bn->bn_weight; F.b = bn->bn_bias; F.m = bn->bn_mean; F.v = bn->bn_var;
+    }
+    if (!cv) continue;
+    if (p.has_bias && cv->bias) F.bias = cv->bias;
+    const size_t elems = (size_t)p.K * p.cin * p.cout;
+    P.kernel = cv->kernel; P.w_off = (uint32_t)p.w_off; P.w16_off = (uint32_t)p.w16_off; P.s_off = (uint32_t)p.s_off;
+    P.K = (uint32_t)p.K; P.cin = (uint32_t)p.cin; P.cout = (uint32_t)p.cout; P.conv1 = p.map == M_CONV1;
+    b32 += (uint32_t)cdiv((long long)(pad64(elems) / 4), 256);
+    if (p.map != M_CONV1) b16 += (uint32_t)cdiv((long long)(elems / 8), 256);
+  }
+  p32.blk[n] = b32; blk16[n] = b16;
+  p32.n = n;
+  p16 = p32;
+  memcpy(p16.blk, blk16, sizeof(uint32_t) * (n + 1));
+  EYOC_REQUIRE(m->blob_floats <= 0xffffffffu, EYOC_ERR_INVALID, "eyoc_model_repack_device: blob of %zu floats", m->blob_floats);
+  hipStream_t st = (hipStream_t)stream;
+  RpWs* ws = (RpWs*)ws_dev;
+  hipLaunchKernelGGL(k_repack_fold, dim3(n), dim3(RP_CH), 0, st, fa, m->desc.bn_eps, m->blob, ws);
+  hipLaunchKernelGGL(k_repack_f32, dim3(b32), dim3(256), 0, st, p32, m->blob, ws);
+  hipLaunchKernelGGL(k_repack_scales, dim3(n), dim3(64), 0, st, p32, m->blob, ws);
+  if (b16) hipLaunchKernelGGL(k_repack_split16, dim3(b16), dim3(256), 0, st, p16, m->blob, (const RpWs*)ws);
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
 
 size_t eyoc_model_blob_floats(const eyoc_model_desc* desc) {
   if (check_desc(desc) != EYOC_OK) return 0;

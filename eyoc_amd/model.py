@@ -104,6 +104,9 @@ class ResUNet2(nn.Module):
         # split16 range guard: True = every split16 forward is followed by eyoc_model_range_check (one stream
         # synchronisation); pipelined callers set it False and call check_range() where they synchronise anyway
         self.range_check = True
+        # True: a re-pack of a live handle (``repack()``, the forward's own after an in-place parameter edit) and the first ``pack()`` of
+        # parameters that already live on the GPU run ``eyoc_model_repack_device`` - no host copy, the handle stays (``repack_device``)
+        self.device_repack = False
         self._probe = False
         self.last_max_activation = None
 
@@ -132,13 +135,7 @@ class ResUNet2(nn.Module):
         # buffers are read from the modules' own dicts every time, so rebinding one (``.to()``, ``register_buffer``) is seen.
         # Round 6: the walk itself runs in C where it can (``map`` over the tensors with the unbound ``data_ptr`` / ``_version`` getters,
         # the modules' child tuples compared as one list): 128 -> 67 us per forward, a single pair's call is 1.5 ms.
-        cache = self.__dict__.get("_eyoc_module_list")
-        if cache is None or [tuple(d.values()) for d in cache[0]] != cache[1]:      # (modules compare by identity)
-            mods = list(self.modules())
-            kid_dicts = [m._modules for m in mods]
-            cache = (kid_dicts, [tuple(d.values()) for d in kid_dicts], [d for m in mods for d in (m._parameters, m._buffers)])
-            self.__dict__["_eyoc_module_list"] = cache
-        ts = [t for t in itertools.chain.from_iterable(map(dict.values, cache[2])) if t is not None]
+        ts = self._tensor_list()
         try:
             vers = tuple(map(_TENSOR_VERSION, ts))
         except RuntimeError:                                                          # inference-mode tensors have no version counter
@@ -151,10 +148,21 @@ class ResUNet2(nn.Module):
             vers = tuple(vers)
         return hash((tuple(map(_TENSOR_PTR, ts)), vers))
 
+    def _tensor_list(self):
+        """Every parameter and buffer of the tree, in module order (the walk ``_weights_version`` describes)."""
+        cache = self.__dict__.get("_eyoc_module_list")
+        if cache is None or [tuple(d.values()) for d in cache[0]] != cache[1]:      # (modules compare by identity)
+            mods = list(self.modules())
+            kid_dicts = [m._modules for m in mods]
+            cache = (kid_dicts, [tuple(d.values()) for d in kid_dicts], [d for m in mods for d in (m._parameters, m._buffers)])
+            self.__dict__["_eyoc_module_list"] = cache
+        return [t for t in itertools.chain.from_iterable(map(dict.values, cache[2])) if t is not None]
+
     def _invalidate(self):
         if self._handle is not None:
             _lib.load().eyoc_model_destroy(self._handle)
         self._handle, self._blob, self._packed_device = None, None, None
+        self.__dict__.pop("_eyoc_device_layers", None)
 
     def load_state_dict(self, state_dict, strict=True):
         out = super().load_state_dict(state_dict, strict=strict)
@@ -170,15 +178,30 @@ class ResUNet2(nn.Module):
         d = self._desc()
         return int(_lib.load().eyoc_model_blob_floats(C.byref(d)))
 
-    def _layer_params(self):
-        """Host-side (numpy) view of every parameter under its ME name; keeps arrays alive."""
+    def _layer_params(self, device=False):
+        """Host-side (numpy) view of every parameter under its ME name; keeps arrays alive.  ``device=True``: the same array over the
+        parameters' own device storage (``eyoc_model_repack_device``) - a tensor is copied only where it is not contiguous fp32, and
+        ``keep`` holds those copies."""
         keep, items = [], []
-        fptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        if device:
+            dev = self._packed_device
+            fptr = lambda t: C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_float))
 
-        def arr(t):
-            a = np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32))
-            keep.append(a)
-            return a
+            def arr(t):
+                t = t.detach()
+                if t.device.type != "cuda" or t.device.index != (dev.index if dev.index is not None else torch.cuda.current_device()):
+                    raise _lib.EyocError(f"repack_device: a parameter lives on {t.device}, the packed blob on {dev}")
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    t = t.contiguous().float()
+                    keep.append(t)
+                return t
+        else:
+            fptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+
+            def arr(t):
+                a = np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32))
+                keep.append(a)
+                return a
 
         for name, mod in self.named_modules():
             if isinstance(mod, _Conv):
@@ -201,7 +224,43 @@ class ResUNet2(nn.Module):
     def repack(self):
         """Fold and upload the current parameters again.  ``forward`` does this on its own when ``_weights_version``
         changed; it is MANDATORY after edits that fingerprint cannot see (``p.data`` edits, writes through views)."""
-        return self.pack(self._packed_device)
+        return self._repack(self._packed_device)
+
+    def _repack(self, device):
+        if self.device_repack and self._handle is not None and self._packed_device == device and self._params_on(device):
+            return self.repack_device()
+        return self.pack(device)
+
+    def _params_on(self, device) -> bool:
+        """Every parameter and buffer lives on ``device`` (a CUDA device; no index = the current one)."""
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        return all(t.device.type == "cuda" and t.device.index == idx for t in self._tensor_list())
+
+    def repack_device(self) -> torch.Tensor:
+        """Fold and pack the current parameters ON THE DEVICE into the live handle's blob (``eyoc_model_repack_device``), on the
+        current stream: no host copy, no synchronisation, and the handle - its blob address, range guard, timing and progress
+        events, math / probe settings - stays.  The blob is byte for byte what ``pack_host()`` gives.  Needs a packed model
+        (``pack()``, also ``pack(from_blob=True)``) and the parameters on the blob's device.  A forward of this model on ANOTHER
+        stream must be ordered against the call by the caller."""
+        if self._handle is None:
+            raise _lib.EyocError("repack_device: no packed model on the device - call pack() first")
+        lib = _lib.load()
+        dev = self._packed_device
+        # the descriptor array is rebuilt only when a tensor was rebound (it holds raw addresses) or needed a copy
+        ptrs = tuple(map(_TENSOR_PTR, self._tensor_list()))
+        cached = self.__dict__.get("_eyoc_device_layers")
+        if cached is not None and cached[0] == ptrs:
+            layers, nl, keep = cached[1:]
+        else:
+            layers, nl, keep = self._layer_params(device=True)
+            self.__dict__["_eyoc_device_layers"] = None if keep else (ptrs, layers, nl, keep)
+        with _lib.on_device(dev):
+            ws = _lib.scratch(lib.eyoc_model_repack_workspace_bytes(self._handle), dev)
+            rc = lib.eyoc_model_repack_device(_lib.ctx(dev.index), self._handle, layers, nl, _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+        _lib.check(rc, "eyoc_model_repack_device")
+        del keep                          # (copies were made on this stream: the allocator reuses them behind the kernels)
+        self._packed_version = self._weights_version()
+        return self._blob
 
     def pack_host(self) -> torch.Tensor:
         """The packed blob as a CPU tensor (``eyoc_model_pack_host``: batch norms folded, fp32 fragment order + split16
@@ -229,8 +288,9 @@ class ResUNet2(nn.Module):
             blob = blob[off:off + n]
         d = self._desc()
         h = C.c_void_p()
+        on_device = not from_blob and self.device_repack and self._params_on(device)   # a handle over the zeroed blob, filled below
         with torch.cuda.device(device):
-            if from_blob:
+            if from_blob or on_device:
                 rc = lib.eyoc_model_create(_lib.ctx(device.index), C.byref(d), None, 0, _lib.ptr(blob), blob.numel(),
                                            C.byref(h))
             else:
@@ -247,6 +307,8 @@ class ResUNet2(nn.Module):
         if self._probe:
             _lib.check(lib.eyoc_model_set_probe(h, 1), "eyoc_model_set_probe")
         self._apply_progress()
+        if on_device:
+            self.repack_device()
         return blob
 
     @property
@@ -269,7 +331,7 @@ class ResUNet2(nn.Module):
         if self._handle is None or self._packed_device != dev:
             self.pack(dev)
         elif self._packed_version is not None and self._packed_version != self._weights_version():
-            self.pack(dev)       # parameters changed in place since the blob was packed (adopted blobs are exempt)
+            self._repack(dev)    # parameters changed in place since the blob was packed (adopted blobs are exempt)
         lib = _lib.load()
         cm = x.coordinate_manager
         maps = cm.maps(-1)        # automatic internal order (Z-order from 8192 rows); in and out stay in the caller's rows

@@ -299,3 +299,36 @@ def forward_layers(model, x: SparseTensor, taps: dict | None = None) -> SparseTe
     if internal:
         out = out.index_select(0, back)
     return SparseTensor(out, coordinate_map_key=x.coordinate_map_key, coordinate_manager=cm)
+
+
+@torch.no_grad()
+def ema_sync(labeler, model, decay: float, debias: float, full_sync: bool = False):
+    """The labeler sync between two training iterations (``lib/trainer.py:1505-1513``) without a host trip: ``full_sync`` copies the
+    model's ``state_dict`` into the labeler's ("Sync"), otherwise every entry - the int64 ``num_batches_tracked`` included - becomes
+    ``(decay * labeler + (1 - decay) * model) / debias`` ("EMA", ``debias = 1 - decay ** num_updates``), bit for bit what the
+    reference's loop over the two ``state_dict``s computes; then the labeler's packed eval plan is re-packed on the device
+    (``labeler.repack_device()``).  Everything is enqueued on the current stream, nothing synchronises.
+
+    A handful of launches instead of 3 x 150: the entries of one dtype are gathered into one flat tensor, the reference's own expression
+    runs once on it (elementwise kernels do not care where an element sits, so every element gets the reference's arithmetic, whatever
+    torch makes of a division by a Python scalar), and ``torch._foreach_copy_`` writes the pieces back in place.  Returns the blob."""
+    if type(labeler) is not type(model):
+        raise ValueError(f"ema_sync: labeler is a {type(labeler).__name__}, the model a {type(model).__name__}")
+    lsd, msd = labeler.state_dict(), model.state_dict()
+    if list(lsd) != list(msd):
+        raise ValueError("ema_sync: the two state_dicts name different entries")
+    ls, ms = list(lsd.values()), list(msd.values())
+    if any(l.device != m.device or l.device.type != "cuda" for l, m in zip(ls, ms)) or len({l.device for l in ls}) != 1:
+        raise ValueError("ema_sync: labeler and model must live on the same GPU")
+    if full_sync:
+        torch._foreach_copy_(ls, ms)
+    else:
+        for dt in {l.dtype for l in ls}:
+            lg = [l for l in ls if l.dtype == dt]
+            mg = [m for l, m in zip(ls, ms) if l.dtype == dt]
+            new = (decay * torch.cat([l.reshape(-1) for l in lg]) + (1 - decay) * torch.cat([m.reshape(-1) for m in mg])) / debias
+            parts = new.to(dt).split([l.numel() for l in lg])              # (float -> int64 truncates, as ``copy_`` does)
+            torch._foreach_copy_(lg, [p.view(l.shape) for p, l in zip(parts, lg)])
+    if labeler._handle is None:
+        return labeler.pack()
+    return labeler.repack_device()

@@ -394,6 +394,19 @@ int eyoc_model_pack_host(const eyoc_model_desc* desc, const eyoc_layer_params* l
 int eyoc_model_create(eyoc_ctx* ctx, const eyoc_model_desc* desc, const eyoc_layer_params* layers,
                       int n_layers, float* blob_dev, size_t blob_floats, eyoc_model** out);
 int eyoc_model_destroy(eyoc_model* model);
+/* Re-pack on the device (additive to EYOC_VERSION 111): folds and packs `layers` - the same struct and the same name matching as
+ * eyoc_model_create, but EVERY pointer is a device pointer to contiguous fp32 on the model's device - into the model's existing
+ * blob, in place, on `stream`.  The blob afterwards is byte for byte what eyoc_model_pack_host writes for the same parameters
+ * (padding floats zero, the scale words included).  The handle keeps its address, blob, range-guard words, timing and progress
+ * events and its math / probe / timing settings.  Shape and name errors are found on the host before anything is enqueued (the
+ * messages of eyoc_model_create; the blob is then untouched).  The call only enqueues four kernels whose per-layer descriptors travel
+ * as kernel arguments: no host synchronisation, no copy, no allocation, no read-back.  workspace_dev: 256-byte aligned,
+ * eyoc_model_repack_workspace_bytes() bytes, free again once the kernels have run.  ORDERING IS THE CALLER'S JOB: a forward of this
+ * model on another stream must neither be in flight while the blob is rewritten nor start before the re-pack has finished; on
+ * `stream` itself the usual stream order holds. */
+size_t eyoc_model_repack_workspace_bytes(const eyoc_model* model);
+int eyoc_model_repack_device(eyoc_ctx* ctx, eyoc_model* model, const eyoc_layer_params* layers, int n_layers,
+                             void* workspace_dev, size_t workspace_bytes, void* stream);
 /* split16 forwards run the network's 1x1 tail (conv1_tr -> ReLU -> final + bias -> row normalisation, model/resunet.py:183-191)
  * as ONE kernel whose 64-channel intermediate never leaves the registers (spconv_tail.hip; BN2C's 96 -> 64 -> 32 widths): mode 1;
  * 2 (default since round 6) = in the epilogue of the last staged stride-1 layer (block2_tr.conv2 of a batch: its 64 output channels
