@@ -19,5 +19,6 @@ from .registration import (Matcher, registration_ransac_based_on_feature_matchin
 from .metrics import registration_errors, apply_transform, evaluate_nn_dist  # noqa: F401
 from .voxelize import sparse_quantize, sparse_quantize_batch, voxelize, extract_features  # noqa: F401
 from .labels import (knn2_segmented, lowe_topk, spherical_filter, similarity_filter, load_dist_sim_map,  # noqa: F401
-                     match_and_filter_corr, correspondences_under_pose)
+                     match_and_filter_corr, correspondences_under_pose, lowe_topk_segmented, pair_filter_batched, posed_nn_grid,
+                     match_and_filter_corr_batched, correspondences_under_pose_batched, corr_through_registration, label_step)
 from .autograd import sparse_conv, contrastive_hardest_negative_loss  # noqa: F401,E402

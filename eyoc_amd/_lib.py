@@ -68,6 +68,10 @@ class IcpResult(C.Structure):
                 ("iterations", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SimSlice(C.Structure):
+    _fields_ = [("table_offset", C.c_int64), ("xlim", C.c_int32), ("ylim", C.c_int32), ("grid1", C.c_float), ("reserved", C.c_int32)]
+
+
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 # name -> (restype, argtypes); every symbol include/eyoc_hip.h declares
 PROTOTYPES = {
@@ -113,6 +117,9 @@ PROTOTYPES = {
     "eyoc_pair_filter": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, C.c_float, _vp, _vp, _vp]),
     "eyoc_pair_filter_similarity": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, C.c_float, C.c_float, C.c_double, _vp, _vp,
                                          _vp]),
+    "eyoc_lowe_topk_segmented": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _vp]),
+    "eyoc_pair_filter_batched": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _vp,
+                                      C.c_float, _vp, C.POINTER(SimSlice), C.c_float, C.c_double, _vp, _vp, _vp]),
     "eyoc_spconv_packed_floats": (_sz, [_i, _i, _i]),
     "eyoc_spconv_pack_weights": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "eyoc_spconv_select_kernel": (_i, [_vp, _i]),
@@ -197,6 +204,9 @@ PROTOTYPES = {
                               _vp, _sz, _vp]),
     "eyoc_icp_correspondences": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _vp, C.c_double, _vp, _vp,
                                       _vp, _vp, _sz, _vp]),
+    "eyoc_posed_nn_grid_workspace_bytes": (_sz, [_i, _i, _i]),
+    "eyoc_posed_nn_grid": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _vp, C.c_float, _vp, C.POINTER(C.c_int32), _vp,
+                                _vp, _vp, _vp, _sz, _vp]),
 }
 
 

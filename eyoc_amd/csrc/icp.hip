@@ -405,6 +405,219 @@ int run(const char* what, eyoc_ctx* ctx, const float* src, const float* tgt, con
   return EYOC_OK;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Posed nearest neighbour with a gate (eyoc_posed_nn_grid): what eyoc_knn2(c = 4) + the 2 m gate of lib/trainer.py:1198-1211 return,
+// without the [n0, n1] sweep.  The grid is the one above (k_icp_build, 16-byte slots, sorted (x, y, z, row) records); the arithmetic is
+// fp32, the brute-force kernel's:  p_r = ((T0 x + T1 y) + T2 z) + T3,  d2 = (dx dx + dy dy) + dz dz,  no contraction.
+//   k_pnn_init    one thread per pair: BAD_INIT for a non-finite pose
+//   k_pnn_keys    targets: cell key; queries: bounds of the selected row, the posed point (stored once, 16 bytes, so the search and the
+//                 key see the same point), its cell key, outputs preset to -1 / +inf
+//   2 x stable radix sort (pair in the top key bits), fill, k_icp_build
+//   k_pnn_search  256 cell-sorted queries of one pair per workgroup, lane = query: 27 probes, minimum over (d2, row), gate
+//
+// Cell edge.  The gate is sqrtf(d2) < r in fp32 (u = 2^-24, sqrtf correctly rounded).  A target that passes it has, per axis, with
+// dxf = fl(p - q) = (p - q)(1 + e), |e| <= u:  fl(dxf dxf) >= dxf^2 (1 - u) and the two additions of non-negative terms lose at most a
+// factor (1 - u) each, so d2 >= dxf^2 (1 - u)^3 (a square that underflows belongs to a |p - q| < 2^-63: inside any cell edge); the gate
+// gives sqrt(d2) < r / (1 - u), hence |p - q| <= |dxf| / (1 - u) < r (1 - u)^-3.5 < r (1 + 4 u).  The cells are floor(v / edge) of the
+// exact fp32 values in fp64: the two rounded quotients are each within 2^-53 * 2^17 = 2^-36 of the true ones (|cell| < 2^17), so they
+// differ by at most |p - q| / edge + 2^-35, and two floors differ by at most 1 when that is <= 1.  edge = r (1 + 2^-20) = r (1 + 16 u)
+// leaves |p - q| / edge < (1 + 4 u) / (1 + 16 u) < 1 - 11 u, and 11 u > 2^-35 (+ one rounding of edge itself, 2^-53): every target that
+// passes the fp32 gate lies in the 27 cells around the query's.  The global minimum over (d2, row), when it passes the gate, is therefore
+// among the candidates, together with every row that ties with it; when it does not pass, nothing does.
+constexpr double PNN_EDGE_MARGIN = 1.0 + 1.0 / 1048576.0;
+
+struct PnnSrc { int base[ICP_CHUNK + 1]; };   // first source row of every pair of the chunk (IcpSegs::src holds the QUERY segments)
+
+__global__ void k_pnn_init(int n_pairs, const float* __restrict__ T, int* __restrict__ status) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n_pairs) return;
+  bool finite = true;
+  for (int k = 0; k < 16; ++k) finite = finite && isfinite(T[(size_t)b * 16 + k]);
+  status[b] = finite ? 0 : EYOC_ICP_BAD_INIT;
+}
+
+__global__ __launch_bounds__(ICP_BLOCK) void k_pnn_keys(IcpSegs s, PnnSrc sb, const float* __restrict__ src, const float* __restrict__ tgt,
+                                                        const float* __restrict__ Ts, const long long* __restrict__ sel, double edge,
+                                                        int* __restrict__ status, unsigned long long* __restrict__ tkey, int* __restrict__ trow,
+                                                        unsigned long long* __restrict__ qkey, int* __restrict__ qrow, float4* __restrict__ qpts,
+                                                        long long* __restrict__ idx_out, float* __restrict__ d2_out) {
+#pragma clang fp contract(off)
+  const int n_tgt = s.tgt[s.n_pairs], n_q = s.src[s.n_pairs];
+  int i = blockIdx.x * ICP_BLOCK + threadIdx.x;
+  if (i < n_tgt) {
+    const int b = pair_of(s.tgt, s.n_pairs, i);
+    trow[i] = i;
+    unsigned long long key = pack_key(b, -COORD_BIAS, -COORD_BIAS, -COORD_BIAS);
+    if (!(status[b] & EYOC_ICP_BAD_INIT)) {
+      int c[3];
+      bool ok = true;
+      for (int k = 0; k < 3; ++k) {
+        const float v = tgt[(size_t)i * 3 + k];
+        ok = ok && isfinite(v) && cell_of((double)v, edge, &c[k]);
+      }
+      if (ok) key = pack_key(b, c[0], c[1], c[2]);
+      else atomicOr(&status[b], EYOC_ICP_RANGE);
+    }
+    tkey[i] = key;
+    return;
+  }
+  i -= n_tgt;
+  if (i >= n_q) return;
+  const int b = pair_of(s.src, s.n_pairs, i);
+  qrow[i] = i;
+  idx_out[i] = -1;
+  if (d2_out) d2_out[i] = INFINITY;
+  unsigned long long key = pack_key(b, -COORD_BIAS, -COORD_BIAS, -COORD_BIAS);
+  float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (!(status[b] & EYOC_ICP_BAD_INIT)) {
+    const long long local = sel ? sel[i] : (long long)(i - s.src[b]);
+    bool ok = local >= 0 && local < (long long)(sb.base[b + 1] - sb.base[b]);      // a selection outside the segment is never read
+    if (ok) {
+      const float* a = src + 3 * ((size_t)sb.base[b] + (size_t)local);
+      const float x = a[0], y = a[1], z = a[2];
+      const float* T = Ts + 16 * (size_t)b;
+      p.x = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+      p.y = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+      p.z = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+      int c[3];
+      ok = isfinite(x) && isfinite(y) && isfinite(z);
+      ok = ok && cell_of((double)p.x, edge, &c[0]) && cell_of((double)p.y, edge, &c[1]) && cell_of((double)p.z, edge, &c[2]);
+      if (ok) key = pack_key(b, c[0], c[1], c[2]);
+    }
+    if (!ok) atomicOr(&status[b], EYOC_ICP_RANGE);
+  }
+  qpts[i] = p;
+  qkey[i] = key;
+}
+
+__global__ __launch_bounds__(ICP_BLOCK) void k_pnn_search(IcpSegs s, const int* __restrict__ qrow_sorted, const float4* __restrict__ qpts, IcpGrid g,
+                                                          double edge, float max_dist, const int* __restrict__ status,
+                                                          long long* __restrict__ idx_out, float* __restrict__ d2_out) {
+#pragma clang fp contract(off)
+  const int b = pair_of(s.wg, s.n_pairs, blockIdx.x);     // uniform: kernel arguments and the workgroup index
+  if (status[b]) return;                                  // every output of the pair stays -1
+  const int local = (blockIdx.x - s.wg[b]) * ICP_BLOCK + threadIdx.x;
+  if (local >= s.src[b + 1] - s.src[b]) return;           // no barrier below
+  const int qi = qrow_sorted[s.src[b] + local];
+  const float4 p = qpts[qi];
+  int c[3];
+  if (!(cell_of((double)p.x, edge, &c[0]) && cell_of((double)p.y, edge, &c[1]) && cell_of((double)p.z, edge, &c[2]))) return;   // (status 0: never)
+  float best = INFINITY;
+  int best_row = -1;
+  for (int ox = -1; ox <= 1; ++ox) {
+    // the first probes of a plane's 9 cells are independent loads: issued together, then resolved one by one
+    unsigned long long key[9];
+    unsigned int slot[9];
+    IcpCell cell[9];
+    const int cx = c[0] + ox;
+#pragma unroll
+    for (int o = 0; o < 9; ++o) {
+      const int cy = c[1] + o / 3 - 1, cz = c[2] + o % 3 - 1;
+      const bool inside = cx >= -COORD_BIAS && cx < COORD_BIAS && cy >= -COORD_BIAS && cy < COORD_BIAS && cz >= -COORD_BIAS && cz < COORD_BIAS;
+      key[o] = inside ? pack_key(b, cx, cy, cz) : KEY_EMPTY;
+      slot[o] = hash_key(key[o]) & g.mask;
+      cell[o] = load_cell(g.cells, slot[o]);
+    }
+#pragma unroll
+    for (int o = 0; o < 9; ++o) {
+      if (key[o] == KEY_EMPTY) continue;
+      IcpCell e = cell[o];
+      unsigned int sl = slot[o];
+      for (unsigned int probes = 0; e.key != key[o] && e.key != KEY_EMPTY && probes < g.mask; ++probes) {   // bounded: never full
+        sl = (sl + 1) & g.mask;
+        e = load_cell(g.cells, sl);
+      }
+      if (e.key != key[o]) continue;
+      const int n = e.more + 1;
+      for (int j = 0; j < n; j += 4) {
+        float4 q4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) q4[u] = g.pts[e.first + (j + u < n ? j + u : n - 1)];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (j + u >= n) break;
+          const float4 q = q4[u];
+          const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+          const float d = (dx * dx + dy * dy) + dz * dz;
+          const int qrow = __float_as_int(q.w);
+          if (d < best || (d == best && qrow < best_row)) { best = d; best_row = qrow; }
+        }
+      }
+    }
+  }
+  const bool hit = best_row >= 0 && sqrtf(best) < max_dist;
+  idx_out[qi] = hit ? best_row : -1;
+  if (d2_out) d2_out[qi] = hit ? best : INFINITY;
+}
+
+struct PnnWorkspace {
+  unsigned long long *tkey, *tkey_sorted, *qkey, *qkey_sorted;
+  IcpCell* cells;
+  int *trow, *trow_sorted, *qrow, *qrow_sorted;
+  float4 *pts, *qpts;
+  void* sort_tmp;
+  size_t sort_bytes;
+  unsigned int cap;
+};
+
+size_t pnn_carve(void* base, size_t bytes, int total_q, int total_tgt, PnnWorkspace* w) {
+  Carver c(base, bytes);
+  w->cap = table_capacity(total_tgt);
+  w->tkey = c.take<unsigned long long>(total_tgt);
+  w->tkey_sorted = c.take<unsigned long long>(total_tgt);
+  w->qkey = c.take<unsigned long long>(total_q);
+  w->qkey_sorted = c.take<unsigned long long>(total_q);
+  w->cells = c.take<IcpCell>(w->cap);
+  w->trow = c.take<int>(total_tgt);
+  w->trow_sorted = c.take<int>(total_tgt);
+  w->qrow = c.take<int>(total_q);
+  w->qrow_sorted = c.take<int>(total_q);
+  w->pts = c.take<float4>(total_tgt);
+  w->qpts = c.take<float4>(total_q);
+  const size_t a = sort_rows64_tmp_bytes(total_tgt > 0 ? total_tgt : 1), b = sort_rows64_tmp_bytes(total_q > 0 ? total_q : 1);
+  w->sort_bytes = a > b ? a : b;
+  w->sort_tmp = c.take<char>(w->sort_bytes);
+  return align_up(c.off);
+}
+
+// one chunk of <= ICP_CHUNK pairs; every pointer is already that of the chunk's first row / query / pair
+int pnn_chunk(const float* src, const float* tgt, const int32_t* seg_src, const int32_t* seg_tgt, const int32_t* seg_q, int n_pairs,
+              const float* T, float max_dist, const int64_t* sel, int64_t* idx_out, float* d2_out, int32_t* status, const PnnWorkspace& w,
+              hipStream_t st) {
+  IcpSegs s;
+  PnnSrc sb;
+  s.n_pairs = n_pairs;
+  for (int b = 0; b <= n_pairs; ++b) {
+    s.src[b] = seg_q[b] - seg_q[0];
+    s.tgt[b] = seg_tgt[b] - seg_tgt[0];
+    sb.base[b] = seg_src[b] - seg_src[0];
+  }
+  s.wg[0] = 0;
+  for (int b = 0; b < n_pairs; ++b) s.wg[b + 1] = s.wg[b] + cdiv(s.src[b + 1] - s.src[b], ICP_BLOCK);
+  const int n_q = s.src[n_pairs], n_tgt = s.tgt[n_pairs], n_wg = s.wg[n_pairs];
+  const double edge = (double)max_dist * PNN_EDGE_MARGIN;
+  hipLaunchKernelGGL(k_pnn_init, dim3(cdiv(n_pairs, 64)), dim3(64), 0, st, n_pairs, T, status);
+  if (n_q + n_tgt > 0)
+    hipLaunchKernelGGL(k_pnn_keys, dim3(cdiv((long long)n_q + n_tgt, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, s, sb, src, tgt, T, (const long long*)sel,
+                       edge, status, w.tkey, w.trow, w.qkey, w.qrow, w.qpts, (long long*)idx_out, d2_out);
+  if (n_q == 0 || n_tgt == 0) {        // nothing to search: every output is already -1
+    EYOC_CHECK_HIP(hipGetLastError());
+    return EYOC_OK;
+  }
+  int rc = sort_rows_by_key64(w.sort_tmp, w.sort_bytes, w.tkey, w.tkey_sorted, w.trow, w.trow_sorted, n_tgt, 60, st);
+  if (rc != EYOC_OK) return rc;
+  rc = sort_rows_by_key64(w.sort_tmp, w.sort_bytes, w.qkey, w.qkey_sorted, w.qrow, w.qrow_sorted, n_q, 60, st);
+  if (rc != EYOC_OK) return rc;
+  EYOC_CHECK_HIP(hipMemsetAsync(w.cells, 0xFF, (size_t)w.cap * sizeof(IcpCell), st));
+  hipLaunchKernelGGL(k_icp_build, dim3(cdiv(n_tgt, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, s, tgt, w.tkey_sorted, w.trow_sorted, status, w.pts, w.cells,
+                     w.cap - 1);
+  const IcpGrid g{w.cells, w.cap - 1, w.pts};
+  hipLaunchKernelGGL(k_pnn_search, dim3(n_wg), dim3(ICP_BLOCK), 0, st, s, w.qrow_sorted, w.qpts, g, edge, max_dist, status, (long long*)idx_out, d2_out);
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
 }  // namespace
 }  // namespace eyoc
 
@@ -435,4 +648,47 @@ extern "C" int eyoc_icp_correspondences(eyoc_ctx* ctx, const float* src_dev, con
   p.flags = 0;
   return eyoc::run("eyoc_icp_correspondences", ctx, src_dev, tgt_dev, seg_src_host, seg_tgt_host, n_pairs, T_dev, p, results_dev, corr_dev,
                    d2_dev, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" size_t eyoc_posed_nn_grid_workspace_bytes(int n_pairs, int total_queries, int total_tgt) {
+  if (n_pairs < 1 || total_queries < 0 || total_tgt < 0) return 0;
+  eyoc::PnnWorkspace w;
+  return eyoc::pnn_carve(nullptr, 0, total_queries, total_tgt, &w);
+}
+
+extern "C" int eyoc_posed_nn_grid(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int32_t* seg_src_host,
+                                  const int32_t* seg_tgt_host, int n_pairs, const float* T_dev, float max_dist, const int64_t* sel_dev,
+                                  const int32_t* seg_sel_host, int64_t* idx_out_dev, float* d2_out_dev, int32_t* status_dev,
+                                  void* workspace_dev, size_t workspace_bytes, void* stream) {
+  using namespace eyoc;
+  const char* what = "eyoc_posed_nn_grid";
+  EYOC_REQUIRE(ctx && seg_src_host && seg_tgt_host && T_dev && status_dev && workspace_dev, EYOC_ERR_INVALID, "%s: NULL argument", what);
+  EYOC_REQUIRE(n_pairs >= 1 && n_pairs <= 1024, EYOC_ERR_INVALID, "%s: n_pairs = %d is outside [1, 1024]", what, n_pairs);
+  EYOC_REQUIRE(((uintptr_t)workspace_dev & 255) == 0, EYOC_ERR_INVALID, "%s: workspace must be 256-byte aligned", what);
+  EYOC_REQUIRE(std::isfinite(max_dist) && max_dist > 0.0f, EYOC_ERR_INVALID, "%s: max_dist must be positive and finite", what);
+  EYOC_REQUIRE((sel_dev == nullptr) == (seg_sel_host == nullptr), EYOC_ERR_INVALID, "%s: a selection needs its segments (and the other way round)", what);
+  const int32_t* seg_q = seg_sel_host ? seg_sel_host : seg_src_host;
+  EYOC_REQUIRE(seg_src_host[0] == 0 && seg_tgt_host[0] == 0 && seg_q[0] == 0, EYOC_ERR_INVALID, "%s: segments must start at 0", what);
+  for (int b = 0; b < n_pairs; ++b)
+    EYOC_REQUIRE(seg_src_host[b + 1] >= seg_src_host[b] && seg_tgt_host[b + 1] >= seg_tgt_host[b] && seg_q[b + 1] >= seg_q[b], EYOC_ERR_INVALID,
+                 "%s: segment offsets must not decrease (pair %d)", what, b);
+  const int total_q = seg_q[n_pairs];
+  EYOC_REQUIRE((seg_src_host[n_pairs] == 0 || src_dev) && (seg_tgt_host[n_pairs] == 0 || tgt_dev) && (total_q == 0 || idx_out_dev), EYOC_ERR_INVALID,
+               "%s: NULL cloud or output", what);
+  EYOC_REQUIRE(total_q == 0 || seg_src_host[n_pairs] > 0, EYOC_ERR_INVALID, "%s: queries without source rows", what);
+  PnnWorkspace w;
+  const size_t need = pnn_carve(workspace_dev, workspace_bytes, total_q, seg_tgt_host[n_pairs], &w);
+  EYOC_REQUIRE(workspace_bytes >= need, EYOC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (eyoc_posed_nn_grid_workspace_bytes)", what, workspace_bytes,
+               need);
+  EYOC_CHECK_HIP(hipSetDevice(ctx->device));
+  for (int b0 = 0; b0 < n_pairs; b0 += ICP_CHUNK) {
+    const int np = n_pairs - b0 < ICP_CHUNK ? n_pairs - b0 : ICP_CHUNK;
+    const size_t so = (size_t)seg_src_host[b0], to = (size_t)seg_tgt_host[b0], qo = (size_t)seg_q[b0];
+    const int rc = pnn_chunk(src_dev ? src_dev + 3 * so : nullptr, tgt_dev ? tgt_dev + 3 * to : nullptr, seg_src_host + b0, seg_tgt_host + b0,
+                             seg_q + b0, np, T_dev + 16 * (size_t)b0, max_dist, sel_dev ? sel_dev + qo : nullptr,
+                             idx_out_dev ? idx_out_dev + qo : nullptr, d2_out_dev ? d2_out_dev + qo : nullptr, status_dev + b0, w,
+                             (hipStream_t)stream);
+    if (rc != EYOC_OK) return rc;
+  }
+  return EYOC_OK;
 }

@@ -530,6 +530,32 @@ int eyoc_pair_filter_similarity(eyoc_ctx* ctx, const float* P0_dev, const float*
                                 const int64_t* idx1_dev, int m, const double* table_dev, int xlim, int ylim, float grid0,
                                 float grid1, double thresh, int64_t* pairs_out_dev, int32_t* n_out_dev, void* stream);
 
+/* The label stages for every pair of a batch at once.  Added after 111 without a bump, additive only.
+ * eyoc_lowe_topk_segmented: d1 / d2 hold the queries of all segments back to back, segment s = rows [seg[s], seg[s+1]) (HOST array of
+ * nseg + 1 ints, seg[0] = 0, nseg <= 2^20), one k <= every segment's length.  mode 0: the Lowe weights of eyoc_lowe_topk; mode 1: weight =
+ * d1 (feature_filter "None" of lib/trainer.py:1072-1073: the order of a stable descending fp64 argsort, NaN last; d2 may be NULL).
+ * idx_out int64 [nseg * k] LOCAL to the segment, w_out f32 [nseg * k] or NULL.  One stable sort whose key holds the segment above the
+ * descending weight: segment s is byte for byte eyoc_lowe_topk on it alone (ties in query order), whatever its neighbours hold.
+ * eyoc_pair_filter_batched: modes 0 / 1 / 2 (= eyoc_pair_filter_similarity) of eyoc_pair_filter for nseg <= 1024 pairs, one workgroup per
+ * pair, 64 pairs per launch.  Pair b owns rows [seg_p0[b], seg_p0[b+1]) of P0, [seg_p1[b], seg_p1[b+1]) of P1 and entries [seg_m[b],
+ * seg_m[b+1]) of idx0 / idx1 (all HOST arrays of nseg + 1 ints starting at 0; the indices are LOCAL to the pair's clouds).  Mode 1 reads
+ * pair b's pose from T_dev f32 [nseg][16] on the device; a non-finite pose keeps nothing.  Mode 2: tables_dev holds fp64 table slices,
+ * slices_host[b] says which one pair b reads (offset in doubles, xlim x ylim row-major, its grid1; grid0 and thresh are the call's).
+ * An entry whose index lies outside its cloud (eyoc_posed_nn_grid's -1) is dropped.  Order-preserving: the survivors of pair b are
+ * rows [seg_m[b], seg_m[b] + count[b]) of pairs_out int64 [seg_m[nseg], 2], count_dev int32 [nseg].  Nothing is read back. */
+typedef struct {
+  int64_t table_offset;
+  int32_t xlim, ylim;
+  float grid1;
+  int32_t reserved;
+} eyoc_sim_slice;            /* 24 bytes */
+int eyoc_lowe_topk_segmented(eyoc_ctx* ctx, const float* d1_dev, const float* d2_dev, const int32_t* seg_host, int nseg, int k, int mode,
+                             int64_t* idx_out_dev, float* w_out_dev, void* stream);
+int eyoc_pair_filter_batched(eyoc_ctx* ctx, int mode, const float* P0_dev, const float* P1_dev, const int64_t* idx0_dev,
+                             const int64_t* idx1_dev, const int32_t* seg_p0_host, const int32_t* seg_p1_host, const int32_t* seg_m_host,
+                             int nseg, const float* T_dev, float radius, const double* tables_dev, const eyoc_sim_slice* slices_host,
+                             float grid0, double thresh, int64_t* pairs_out_dev, int32_t* count_dev, void* stream);
+
 /* replaces: lib.metrics.pdist (lib/metrics.py:22-29): dense out f32 [n,m]; same arithmetic as eyoc_knn1 */
 int eyoc_pdist(eyoc_ctx* ctx, const float* A_dev, int n, const float* B_dev, int m, int c, int dist_type,
                float* out_dev, void* stream);
@@ -755,6 +781,27 @@ int eyoc_icp_batched(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, 
 int eyoc_icp_correspondences(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int32_t* seg_src_host,
                              const int32_t* seg_tgt_host, int n_pairs, const double* T_dev, double max_distance, int32_t* corr_dev,
                              double* d2_dev, eyoc_icp_result* results_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* Posed nearest neighbour with a gate, for a batch of pairs (lib/trainer.py:1198-1211 without the [n0, n1] sweep).  Added after 111
+ * without a bump, additive only.  For every query row of every pair: the target row (LOCAL to the pair) that eyoc_knn2(c = 4) returns for
+ * the posed point against the pair's targets, if that neighbour passes sqrtf(d2) < max_dist, and -1 otherwise.
+ *   posed point  p_r = ((T[4r] x + T[4r+1] y) + T[4r+2] z) + T[4r+3], r = 0..2, every fp32 operation rounded on its own
+ *   d2 = (dx dx + dy dy) + dz dz with dx = p_0 - q_x ..., fp32, no fused multiply-add; the minimum is taken over (d2, target row)
+ *   lexicographically, so an exact tie goes to the lower row whichever cells the two rows sit in.
+ * Pairs back to back like eyoc_icp_batched (seg_src / seg_tgt: HOST arrays of n_pairs + 1 ints from 0, n_pairs <= 1024); T_dev f32
+ * [n_pairs][16] row-major, read on the device.  sel_dev NULL: every source row is a query, outputs are indexed like src.  Otherwise
+ * sel_dev int64 holds the query rows (LOCAL to the pair's source segment) of all pairs back to back, pair b's are entries [seg_sel[b],
+ * seg_sel[b+1]) (HOST), and outputs are indexed like sel_dev.  idx_out int64, d2_out f32 or NULL (+inf where idx is -1).
+ * status_dev int32 [n_pairs]: 0, or EYOC_ICP_BAD_INIT (a non-finite pose) / EYOC_ICP_RANGE (a non-finite point among the targets or the
+ * queries, a selection outside the source segment, a target or posed query outside +-2^17 cells of max_dist); a pair with a status has
+ * every output -1.  The targets are sorted into a cell grid of edge max_dist (1 + 2^-20), built once per call; 27 cells hold every target
+ * that passes the fp32 gate (icp.hip derives the margin).  Caller-owned 256-byte aligned workspace, no allocation, no read-back, no
+ * floating-point atomics: the result does not depend on slot placement, launch chunking (64 pairs) or the other pairs. */
+size_t eyoc_posed_nn_grid_workspace_bytes(int n_pairs, int total_queries, int total_tgt);
+int eyoc_posed_nn_grid(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int32_t* seg_src_host, const int32_t* seg_tgt_host,
+                       int n_pairs, const float* T_dev, float max_dist, const int64_t* sel_dev, const int32_t* seg_sel_host,
+                       int64_t* idx_out_dev, float* d2_out_dev, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes,
+                       void* stream);
 
 #ifdef __cplusplus
 }
