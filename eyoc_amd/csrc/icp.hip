@@ -1,18 +1,28 @@
-// Batched point-to-point ICP on a device-side cell grid (include/eyoc_hip.h, "ICP refinement").
+// The cell grid over 3-D points, and its two users (include/eyoc_hip.h, "ICP refinement" and eyoc_posed_nn_grid).
 //
-// One call = one grid build + (max_iteration + 1) evaluations, nothing read back in between:
-//   k_icp_init   one thread per pair: T = init, BAD_INIT / empty-segment (FEW) pairs are finished here
-//   k_icp_keys   one thread per target / source row: cell key (pair << 54 | biased cell), RANGE for non-finite points and target
-//                cells outside the key range; the source key is the cell of the point under the initial pose
-//   2 x rocPRIM radix sort (stable, pair index in the top key bits: a pair's order never depends on its neighbours)
+// 1. THE GRID: a batch of target clouds as cells of one edge, searched by queries that look at the 27 cells around their own.
+//   target_key   cell key of one target row (pair << 54 | biased cell); tells the caller when the row is non-finite or outside the key range
+//   2 x rocPRIM radix sort (stable, pair index in the top key bits: a pair's order never depends on its neighbours): targets and queries
 //   k_icp_build  target points into sorted order (x, y, z, row local to the pair) + open-addressing table key -> (first row, count), 16 bytes per slot;
 //                integer atomics only - which slot a key lands in may differ from run to run, what a lookup returns does not
-//   k_icp_eval   256 sorted source rows of one pair per workgroup, lane = row: pose in fp64, probe the 27 cells, reduce the 17 sums
+//   probe_cells  the search itself: plane by plane, the 9 first probes of a plane issued together, a bounded linear probe, a run's points
+//                four at a time; the caller's functor sees every candidate once, in an order that only depends on the grid
+//   GridWorkspace / carve_grid / make_segs / build_grid: the arrays, the chunk's segments and the launches between a user's key kernel and its search
+// 2. ICP (eyoc_icp_batched, eyoc_icp_correspondences).  One call = one grid build + (max_iteration + 1) evaluations, nothing read back in between:
+//   k_icp_init   one thread per pair: T = init, BAD_INIT / empty-segment (FEW) pairs are finished here
+//   k_icp_keys   one thread per target / source row: target_key, RANGE for non-finite points and target cells outside the key range; the
+//                source key is the cell of the point under the initial pose
+//   build_grid
+//   k_icp_eval   256 sorted source rows of one pair per workgroup, lane = row: pose in fp64, probe_cells, reduce the 17 sums
 //                lane -> wave -> workgroup in a fixed order, ONE partial record per workgroup (no floating-point atomics)
 //   k_icp_solve  one wave per pair: partials in a fixed order (lane l takes workgroups l, l + 64, ..., then the shuffle tree), fitness / rmse, convergence, Kabsch, T = U T, done flag
 // The evaluation's arithmetic is the contract's expression evaluated in fp64 without contraction (no FMA), so d2 does not depend on
 // how the compiler schedules it.
+// 3. POSED NEAREST NEIGHBOUR (eyoc_posed_nn_grid): k_pnn_init, k_pnn_keys, build_grid, k_pnn_search - fp32 arithmetic, see its section.
+// The users differ in what they do with a candidate (the functor handed to probe_cells), in the query half of their key kernel and in
+// their own arrays; everything else about the grid exists once, here.
 #include <cmath>
+#include <initializer_list>
 
 #include "common.h"
 #include "pose_math.h"
@@ -20,15 +30,17 @@
 namespace eyoc {
 namespace {
 
+// ---------------------------------------------------------------------------------------------------------------------
+// 1. The grid
+// ---------------------------------------------------------------------------------------------------------------------
 constexpr int ICP_BLOCK = 256;
 constexpr int ICP_CHUNK = 64;      // pairs per set of launches: their segments travel as kernel arguments
-constexpr int ICP_SUMS = 17;       // count, sum d2, sum p (3), sum q (3), sum p q^T (9)
 constexpr double CELL_LIMIT = 131072.0;   // |cell| < 2^17 (COORD_BIAS)
 
 struct IcpSegs {
   int n_pairs;
-  int src[ICP_CHUNK + 1], tgt[ICP_CHUNK + 1];
-  int wg[ICP_CHUNK + 1];     // first evaluation workgroup of every pair
+  int src[ICP_CHUNK + 1], tgt[ICP_CHUNK + 1];     // query (ICP: source) and target segments, counted from the chunk's first row
+  int wg[ICP_CHUNK + 1];     // first search workgroup of every pair (ICP_BLOCK queries each)
 };
 
 __device__ inline int pair_of(const int* seg, int n_pairs, int row) {   // seg ascending, row < seg[n_pairs]
@@ -44,6 +56,206 @@ __device__ inline bool cell_of(double v, double edge, int* c) {
   *c = (int)f;
   return true;
 }
+
+// key of target row i of pair b.  *ok = false: the row is not finite or its cell is outside the key range (the caller flags the pair; the
+// key is then the pair's lowest, like every row's of a pair whose pose is bad: nothing of such a pair is read)
+__device__ inline unsigned long long target_key(const float* __restrict__ tgt, int i, int b, double edge, bool bad_init, bool* ok) {
+  *ok = true;
+  if (!bad_init) {
+    int c[3];
+    for (int k = 0; k < 3; ++k) {
+      const float v = tgt[(size_t)i * 3 + k];
+      *ok = *ok && isfinite(v) && cell_of((double)v, edge, &c[k]);
+    }
+    if (*ok) return pack_key(b, c[0], c[1], c[2]);
+  }
+  return pack_key(b, -COORD_BIAS, -COORD_BIAS, -COORD_BIAS);
+}
+
+// one slot of the open-addressing table: 16 bytes, so that a probe is ONE load.  The table is filled with 0xFF bytes: key = KEY_EMPTY
+// and more = -1, i.e. the slot's run holds more + 1 rows starting at sorted row first.
+struct __align__(16) IcpCell {
+  unsigned long long key;
+  int first, more;
+};
+
+struct IcpGrid {
+  const IcpCell* cells;
+  unsigned int mask;
+  const float4* pts;     // sorted target points: x, y, z, row local to the pair (int bits)
+};
+
+__device__ inline IcpCell load_cell(const IcpCell* cells, unsigned int slot) {
+  const uint4 v = *reinterpret_cast<const uint4*>(cells + slot);
+  IcpCell c;
+  c.key = (unsigned long long)v.x | ((unsigned long long)v.y << 32);
+  c.first = (int)v.z; c.more = (int)v.w;
+  return c;
+}
+
+// `skip[b]` != 0: pair b is never searched (and a RANGE pair's keys mean nothing)
+__global__ __launch_bounds__(ICP_BLOCK) void k_icp_build(IcpSegs s, const float* __restrict__ tgt, const unsigned long long* __restrict__ key_sorted,
+                                                         const int* __restrict__ row_sorted, const int* __restrict__ skip, float4* __restrict__ pts,
+                                                         IcpCell* __restrict__ cells, unsigned int mask) {
+  const int i = blockIdx.x * ICP_BLOCK + threadIdx.x;
+  if (i >= s.tgt[s.n_pairs]) return;
+  const unsigned long long key = key_sorted[i];
+  const int b = (int)(key >> 54), row = row_sorted[i];
+  pts[i] = make_float4(tgt[(size_t)row * 3], tgt[(size_t)row * 3 + 1], tgt[(size_t)row * 3 + 2], __int_as_float(row - s.tgt[b]));
+  if (skip[b]) return;
+  unsigned int slot = hash_key(key) & mask;
+  for (unsigned int probes = 0; probes <= mask; ++probes) {     // bounded: capacity >= 2 x rows
+    const unsigned long long seen = atomicCAS(&cells[slot].key, KEY_EMPTY, key);
+    if (seen == KEY_EMPTY || seen == key) {
+      atomicAdd(&cells[slot].more, 1);
+      if (i == 0 || key_sorted[i - 1] != key) cells[slot].first = i;
+      return;
+    }
+    slot = (slot + 1) & mask;
+  }
+}
+
+// The search: every target point in the 27 cells around cell c of pair b goes to each(q) once (q = x, y, z, local row bits), plane by
+// plane (ox), cell by cell (o), in run order.  What a candidate means - the distance expression, the minimum - is the caller's; so is
+// the floating-point mode, which the functor takes from the kernel it is written in.  Grid and functor arrive by value: through a
+// reference to the kernel argument the callers compile to longer code (EXPERIMENTS.md "One cell grid in icp.hip").
+template <typename Each>
+__device__ __forceinline__ void probe_cells(const IcpGrid g, const int b, const int* c, Each each) {
+  for (int ox = -1; ox <= 1; ++ox) {
+    // the first probes of a plane's 9 cells are independent loads: issued together, then resolved one by one
+    unsigned long long key[9];
+    unsigned int slot[9];
+    IcpCell cell[9];
+    const int cx = c[0] + ox;
+#pragma unroll
+    for (int o = 0; o < 9; ++o) {
+      const int cy = c[1] + o / 3 - 1, cz = c[2] + o % 3 - 1;
+      const bool inside = cx >= -COORD_BIAS && cx < COORD_BIAS && cy >= -COORD_BIAS && cy < COORD_BIAS && cz >= -COORD_BIAS && cz < COORD_BIAS;
+      key[o] = inside ? pack_key(b, cx, cy, cz) : KEY_EMPTY;      // KEY_EMPTY is no cell's key (the pair bits are never all ones)
+      slot[o] = hash_key(key[o]) & g.mask;
+      cell[o] = load_cell(g.cells, slot[o]);
+    }
+#pragma unroll
+    for (int o = 0; o < 9; ++o) {
+      if (key[o] == KEY_EMPTY) continue;
+      IcpCell e = cell[o];
+      unsigned int sl = slot[o];
+      for (unsigned int probes = 0; e.key != key[o] && e.key != KEY_EMPTY && probes < g.mask; ++probes) {   // bounded: never full
+        sl = (sl + 1) & g.mask;
+        e = load_cell(g.cells, sl);
+      }
+      if (e.key != key[o]) continue;
+      // the run's points four at a time: the loads of a group are issued together (the index is clamped inside the run, a
+      // repeated point is not evaluated twice)
+      const int n = e.more + 1;
+      for (int j = 0; j < n; j += 4) {
+        float4 q4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) q4[u] = g.pts[e.first + (j + u < n ? j + u : n - 1)];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (j + u >= n) break;
+          each(q4[u]);
+        }
+      }
+    }
+  }
+}
+
+unsigned int table_capacity(int total_tgt) {
+  unsigned int cap = 64;
+  while (cap < 2u * (unsigned)total_tgt) cap <<= 1;
+  return cap;
+}
+
+// what the grid and its two sorts need; a user carves its own arrays behind it
+struct GridWorkspace {
+  unsigned long long *tkey, *tkey_sorted, *qkey, *qkey_sorted;
+  IcpCell* cells;
+  int *trow, *trow_sorted, *qrow, *qrow_sorted;
+  float4* pts;
+  void* sort_tmp;
+  size_t sort_bytes;
+  unsigned int cap;
+};
+
+// the layout for the LARGEST chunk a call with these totals can hold (every chunk reuses it)
+void carve_grid(Carver& c, int total_q, int total_tgt, GridWorkspace* w) {
+  w->cap = table_capacity(total_tgt);
+  w->tkey = c.take<unsigned long long>(total_tgt);
+  w->tkey_sorted = c.take<unsigned long long>(total_tgt);
+  w->qkey = c.take<unsigned long long>(total_q);
+  w->qkey_sorted = c.take<unsigned long long>(total_q);
+  w->cells = c.take<IcpCell>(w->cap);
+  w->trow = c.take<int>(total_tgt);
+  w->trow_sorted = c.take<int>(total_tgt);
+  w->qrow = c.take<int>(total_q);
+  w->qrow_sorted = c.take<int>(total_q);
+  w->pts = c.take<float4>(total_tgt);
+  const size_t a = sort_rows64_tmp_bytes(total_tgt > 0 ? total_tgt : 1), b = sort_rows64_tmp_bytes(total_q > 0 ? total_q : 1);
+  w->sort_bytes = a > b ? a : b;
+  w->sort_tmp = c.take<char>(w->sort_bytes);
+}
+
+// the segments of one chunk of <= ICP_CHUNK pairs, counted from the chunk's first query / target row
+IcpSegs make_segs(const int32_t* seg_q, const int32_t* seg_tgt, int n_pairs) {
+  IcpSegs s;
+  s.n_pairs = n_pairs;
+  for (int b = 0; b <= n_pairs; ++b) {
+    s.src[b] = seg_q[b] - seg_q[0];
+    s.tgt[b] = seg_tgt[b] - seg_tgt[0];
+  }
+  s.wg[0] = 0;
+  for (int b = 0; b < n_pairs; ++b) s.wg[b + 1] = s.wg[b] + cdiv(s.src[b + 1] - s.src[b], ICP_BLOCK);
+  return s;
+}
+
+// from the keys a user's key kernel wrote (both sides non-empty) to the grid its search reads: sorted queries in w.qrow_sorted
+int build_grid(const IcpSegs& s, const float* tgt, const int* skip, const GridWorkspace& w, hipStream_t st, IcpGrid* g) {
+  const int n_q = s.src[s.n_pairs], n_tgt = s.tgt[s.n_pairs];
+  int rc = sort_rows_by_key64(w.sort_tmp, w.sort_bytes, w.tkey, w.tkey_sorted, w.trow, w.trow_sorted, n_tgt, 60, st);
+  if (rc != EYOC_OK) return rc;
+  rc = sort_rows_by_key64(w.sort_tmp, w.sort_bytes, w.qkey, w.qkey_sorted, w.qrow, w.qrow_sorted, n_q, 60, st);
+  if (rc != EYOC_OK) return rc;
+  EYOC_CHECK_HIP(hipMemsetAsync(w.cells, 0xFF, (size_t)w.cap * sizeof(IcpCell), st));
+  hipLaunchKernelGGL(k_icp_build, dim3(cdiv(n_tgt, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, s, tgt, w.tkey_sorted, w.trow_sorted, skip, w.pts, w.cells,
+                     w.cap - 1);
+  *g = IcpGrid{w.cells, w.cap - 1, w.pts};
+  return EYOC_OK;
+}
+
+// The argument checks every entry point shares, before anything touches the device, in the two parts an entry point puts its own
+// checks between.  First what must hold before a segment is read; `pointers`: the caller's mandatory ones, the segments among them.
+int check_grid_head(const char* what, bool pointers, int n_pairs, const void* ws) {
+  EYOC_REQUIRE(pointers, EYOC_ERR_INVALID, "%s: NULL argument", what);
+  EYOC_REQUIRE(n_pairs >= 1 && n_pairs <= 1024, EYOC_ERR_INVALID, "%s: n_pairs = %d is outside [1, 1024]", what, n_pairs);
+  EYOC_REQUIRE(((uintptr_t)ws & 255) == 0, EYOC_ERR_INVALID, "%s: workspace must be 256-byte aligned", what);
+  return EYOC_OK;
+}
+
+// then every segment list of the call (n_pairs + 1 offsets each)
+int check_segments(const char* what, int n_pairs, std::initializer_list<const int32_t*> segs) {
+  for (const int32_t* seg : segs) EYOC_REQUIRE(seg[0] == 0, EYOC_ERR_INVALID, "%s: segments must start at 0", what);
+  for (int b = 0; b < n_pairs; ++b)
+    for (const int32_t* seg : segs)
+      EYOC_REQUIRE(seg[b + 1] >= seg[b], EYOC_ERR_INVALID, "%s: segment offsets must not decrease (pair %d)", what, b);
+  return EYOC_OK;
+}
+
+// every chunk of <= ICP_CHUNK pairs in turn: chunk(first pair, pairs)
+template <typename Chunk>
+int for_each_chunk(int n_pairs, Chunk&& chunk) {
+  for (int b0 = 0; b0 < n_pairs; b0 += ICP_CHUNK) {
+    const int rc = chunk(b0, n_pairs - b0 < ICP_CHUNK ? n_pairs - b0 : ICP_CHUNK);
+    if (rc != EYOC_OK) return rc;
+  }
+  return EYOC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// 2. ICP: the queries are the source rows under the pair's current pose, fp64
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int ICP_SUMS = 17;       // count, sum d2, sum p (3), sum q (3), sum p q^T (9)
 
 __global__ void k_icp_init(IcpSegs s, const double* __restrict__ init, eyoc_icp_result* __restrict__ res, int* __restrict__ done) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -72,19 +284,10 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_keys(IcpSegs s, const float* 
   int i = blockIdx.x * ICP_BLOCK + threadIdx.x;
   if (i < n_tgt) {
     const int b = pair_of(s.tgt, s.n_pairs, i);
+    bool ok;
     trow[i] = i;
-    unsigned long long key = pack_key(b, -COORD_BIAS, -COORD_BIAS, -COORD_BIAS);
-    if (!(res[b].status & EYOC_ICP_BAD_INIT)) {       // a pair with a bad init has nothing else read
-      int c[3];
-      bool ok = true;
-      for (int k = 0; k < 3; ++k) {
-        const float v = tgt[(size_t)i * 3 + k];
-        ok = ok && isfinite(v) && cell_of((double)v, edge, &c[k]);
-      }
-      if (ok) key = pack_key(b, c[0], c[1], c[2]);
-      else { atomicOr(&res[b].status, EYOC_ICP_RANGE); done[b] = 1; }
-    }
-    tkey[i] = key;
+    tkey[i] = target_key(tgt, i, b, edge, res[b].status & EYOC_ICP_BAD_INIT, &ok);
+    if (!ok) { atomicOr(&res[b].status, EYOC_ICP_RANGE); done[b] = 1; }
     return;
   }
   i -= n_tgt;
@@ -94,7 +297,7 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_keys(IcpSegs s, const float* 
   if (corr) corr[i] = -1;
   if (d2) d2[i] = INFINITY;
   unsigned long long key = pack_key(b, -COORD_BIAS, -COORD_BIAS, -COORD_BIAS);
-  if (!(res[b].status & EYOC_ICP_BAD_INIT)) {
+  if (!(res[b].status & EYOC_ICP_BAD_INIT)) {       // a pair with a bad init has nothing else read
     const double x = src[(size_t)i * 3], y = src[(size_t)i * 3 + 1], z = src[(size_t)i * 3 + 2];
     if (!(isfinite(x) && isfinite(y) && isfinite(z))) {
       atomicOr(&res[b].status, EYOC_ICP_RANGE);
@@ -109,48 +312,6 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_keys(IcpSegs s, const float* 
     }
   }
   skey[i] = key;
-}
-
-// one slot of the open-addressing table: 16 bytes, so that a probe is ONE load.  The table is filled with 0xFF bytes: key = KEY_EMPTY
-// and more = -1, i.e. the slot's run holds more + 1 rows starting at sorted row first.
-struct __align__(16) IcpCell {
-  unsigned long long key;
-  int first, more;
-};
-
-struct IcpGrid {
-  const IcpCell* cells;
-  unsigned int mask;
-  const float4* pts;     // sorted target points: x, y, z, row local to the pair (int bits)
-};
-
-__device__ inline IcpCell load_cell(const IcpCell* cells, unsigned int slot) {
-  const uint4 v = *reinterpret_cast<const uint4*>(cells + slot);
-  IcpCell c;
-  c.key = (unsigned long long)v.x | ((unsigned long long)v.y << 32);
-  c.first = (int)v.z; c.more = (int)v.w;
-  return c;
-}
-
-__global__ __launch_bounds__(ICP_BLOCK) void k_icp_build(IcpSegs s, const float* __restrict__ tgt, const unsigned long long* __restrict__ key_sorted,
-                                                         const int* __restrict__ row_sorted, const int* __restrict__ done, float4* __restrict__ pts,
-                                                         IcpCell* __restrict__ cells, unsigned int mask) {
-  const int i = blockIdx.x * ICP_BLOCK + threadIdx.x;
-  if (i >= s.tgt[s.n_pairs]) return;
-  const unsigned long long key = key_sorted[i];
-  const int b = (int)(key >> 54), row = row_sorted[i];
-  pts[i] = make_float4(tgt[(size_t)row * 3], tgt[(size_t)row * 3 + 1], tgt[(size_t)row * 3 + 2], __int_as_float(row - s.tgt[b]));
-  if (done[b]) return;      // never searched (and a RANGE pair's keys mean nothing)
-  unsigned int slot = hash_key(key) & mask;
-  for (unsigned int probes = 0; probes <= mask; ++probes) {     // bounded: capacity >= 2 x rows
-    const unsigned long long seen = atomicCAS(&cells[slot].key, KEY_EMPTY, key);
-    if (seen == KEY_EMPTY || seen == key) {
-      atomicAdd(&cells[slot].more, 1);
-      if (i == 0 || key_sorted[i - 1] != key) cells[slot].first = i;
-      return;
-    }
-    slot = (slot + 1) & mask;
-  }
 }
 
 #pragma clang fp contract(off)
@@ -183,51 +344,13 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_eval(IcpSegs s, const float* 
     double best = INFINITY;
     int best_row = -1;
     float4 best_q = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ok) {
-      for (int ox = -1; ox <= 1; ++ox) {
-        // the first probes of a plane's 9 cells are independent loads: issued together, then resolved one by one
-        unsigned long long key[9];
-        unsigned int slot[9];
-        IcpCell cell[9];
-        const int cx = c[0] + ox;
-#pragma unroll
-        for (int o = 0; o < 9; ++o) {
-          const int cy = c[1] + o / 3 - 1, cz = c[2] + o % 3 - 1;
-          const bool inside = cx >= -COORD_BIAS && cx < COORD_BIAS && cy >= -COORD_BIAS && cy < COORD_BIAS && cz >= -COORD_BIAS && cz < COORD_BIAS;
-          key[o] = inside ? pack_key(b, cx, cy, cz) : KEY_EMPTY;      // KEY_EMPTY is no cell's key (the pair bits are never all ones)
-          slot[o] = hash_key(key[o]) & g.mask;
-          cell[o] = load_cell(g.cells, slot[o]);
-        }
-#pragma unroll
-        for (int o = 0; o < 9; ++o) {
-          if (key[o] == KEY_EMPTY) continue;
-          IcpCell e = cell[o];
-          unsigned int sl = slot[o];
-          for (unsigned int probes = 0; e.key != key[o] && e.key != KEY_EMPTY && probes < g.mask; ++probes) {   // bounded: never full
-            sl = (sl + 1) & g.mask;
-            e = load_cell(g.cells, sl);
-          }
-          if (e.key != key[o]) continue;
-          // the run's points four at a time: the loads of a group are issued together (the index is clamped inside the run, a
-          // repeated point is not evaluated twice)
-          const int n = e.more + 1;
-          for (int j = 0; j < n; j += 4) {
-            float4 q4[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) q4[u] = g.pts[e.first + (j + u < n ? j + u : n - 1)];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              if (j + u >= n) break;
-              const float4 q = q4[u];
-              const double dx = p[0] - (double)q.x, dy = p[1] - (double)q.y, dz = p[2] - (double)q.z;
-              const double d = dx * dx + dy * dy + dz * dz;
-              const int qrow = __float_as_int(q.w);
-              if (d < best || (d == best && qrow < best_row)) { best = d; best_row = qrow; best_q = q; }
-            }
-          }
-        }
-      }
-    }
+    if (ok)
+      probe_cells(g, b, c, [&](const float4 q) {
+        const double dx = p[0] - (double)q.x, dy = p[1] - (double)q.y, dz = p[2] - (double)q.z;
+        const double d = dx * dx + dy * dy + dz * dz;
+        const int qrow = __float_as_int(q.w);
+        if (d < best || (d == best && qrow < best_row)) { best = d; best_row = qrow; best_q = q; }
+      });
     const bool hit = best_row >= 0 && best < r2;
     if (corr) corr[row] = hit ? best_row : -1;
     if (d2_out) d2_out[row] = hit ? best : INFINITY;
@@ -299,77 +422,40 @@ __global__ __launch_bounds__(64) void k_icp_solve(IcpSegs s, const double* __res
   for (int k = 0; k < 12; ++k) r.T[k] = Tn[k];
 }
 
-unsigned int table_capacity(int total_tgt) {
-  unsigned int cap = 64;
-  while (cap < 2u * (unsigned)total_tgt) cap <<= 1;
-  return cap;
-}
-
 struct IcpWorkspace {
-  unsigned long long *tkey, *tkey_sorted, *skey, *skey_sorted;
-  IcpCell* cells;
-  int *trow, *trow_sorted, *srow, *srow_sorted, *done;
-  float4* pts;
+  GridWorkspace grid;
+  int* done;
   double* partial;
-  void* sort_tmp;
-  size_t sort_bytes;
-  unsigned int cap;
 };
 
-// the layout for the LARGEST chunk a call with these totals can hold (every chunk reuses it)
 size_t carve(void* base, size_t bytes, int n_pairs, int total_src, int total_tgt, IcpWorkspace* w) {
   Carver c(base, bytes);
   const int chunk = n_pairs < ICP_CHUNK ? n_pairs : ICP_CHUNK;
-  w->cap = table_capacity(total_tgt);
-  w->tkey = c.take<unsigned long long>(total_tgt);
-  w->tkey_sorted = c.take<unsigned long long>(total_tgt);
-  w->skey = c.take<unsigned long long>(total_src);
-  w->skey_sorted = c.take<unsigned long long>(total_src);
-  w->cells = c.take<IcpCell>(w->cap);
-  w->trow = c.take<int>(total_tgt);
-  w->trow_sorted = c.take<int>(total_tgt);
-  w->srow = c.take<int>(total_src);
-  w->srow_sorted = c.take<int>(total_src);
+  carve_grid(c, total_src, total_tgt, &w->grid);
   w->done = c.take<int>(chunk > 0 ? chunk : 1);
-  w->pts = c.take<float4>(total_tgt);
   w->partial = c.take<double>(((size_t)cdiv(total_src, ICP_BLOCK) + chunk + 1) * ICP_SUMS);
-  const size_t a = sort_rows64_tmp_bytes(total_tgt > 0 ? total_tgt : 1), b = sort_rows64_tmp_bytes(total_src > 0 ? total_src : 1);
-  w->sort_bytes = a > b ? a : b;
-  w->sort_tmp = c.take<char>(w->sort_bytes);
   return align_up(c.off);
 }
 
 // one chunk of <= ICP_CHUNK pairs; every pointer is already that of the chunk's first row
 int run_chunk(const float* src, const float* tgt, const int32_t* seg_src, const int32_t* seg_tgt, int n_pairs, const double* init,
               const eyoc_icp_params& p, eyoc_icp_result* res, int32_t* corr, double* d2, const IcpWorkspace& w, hipStream_t st) {
-  IcpSegs s;
-  s.n_pairs = n_pairs;
-  for (int b = 0; b <= n_pairs; ++b) {
-    s.src[b] = seg_src[b] - seg_src[0];
-    s.tgt[b] = seg_tgt[b] - seg_tgt[0];
-  }
-  s.wg[0] = 0;
-  for (int b = 0; b < n_pairs; ++b) s.wg[b + 1] = s.wg[b] + cdiv(s.src[b + 1] - s.src[b], ICP_BLOCK);
+  const IcpSegs s = make_segs(seg_src, seg_tgt, n_pairs);
   const int n_src = s.src[n_pairs], n_tgt = s.tgt[n_pairs], n_wg = s.wg[n_pairs];
   const double edge = p.max_distance, r2 = p.max_distance * p.max_distance;
   hipLaunchKernelGGL(k_icp_init, dim3(cdiv(n_pairs, 64)), dim3(64), 0, st, s, init, res, w.done);
   if (n_src + n_tgt > 0)
-    hipLaunchKernelGGL(k_icp_keys, dim3(cdiv((long long)n_src + n_tgt, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, s, src, tgt, edge, res, w.done, w.tkey,
-                       w.trow, w.skey, w.srow, corr, d2);
+    hipLaunchKernelGGL(k_icp_keys, dim3(cdiv((long long)n_src + n_tgt, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, s, src, tgt, edge, res, w.done,
+                       w.grid.tkey, w.grid.trow, w.grid.qkey, w.grid.qrow, corr, d2);
   if (n_src == 0 || n_tgt == 0) {       // every pair has an empty segment: k_icp_init finished them all
     EYOC_CHECK_HIP(hipGetLastError());
     return EYOC_OK;
   }
-  int rc = sort_rows_by_key64(w.sort_tmp, w.sort_bytes, w.tkey, w.tkey_sorted, w.trow, w.trow_sorted, n_tgt, 60, st);
+  IcpGrid g;
+  const int rc = build_grid(s, tgt, w.done, w.grid, st, &g);
   if (rc != EYOC_OK) return rc;
-  rc = sort_rows_by_key64(w.sort_tmp, w.sort_bytes, w.skey, w.skey_sorted, w.srow, w.srow_sorted, n_src, 60, st);
-  if (rc != EYOC_OK) return rc;
-  EYOC_CHECK_HIP(hipMemsetAsync(w.cells, 0xFF, (size_t)w.cap * sizeof(IcpCell), st));
-  hipLaunchKernelGGL(k_icp_build, dim3(cdiv(n_tgt, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, s, tgt, w.tkey_sorted, w.trow_sorted, w.done, w.pts,
-                     w.cells, w.cap - 1);
-  const IcpGrid g{w.cells, w.cap - 1, w.pts};
   for (int e = 0; e <= p.max_iteration; ++e) {
-    hipLaunchKernelGGL(k_icp_eval, dim3(n_wg), dim3(ICP_BLOCK), 0, st, s, src, w.srow_sorted, g, edge, r2, res, w.done, w.partial, corr, d2);
+    hipLaunchKernelGGL(k_icp_eval, dim3(n_wg), dim3(ICP_BLOCK), 0, st, s, src, w.grid.qrow_sorted, g, edge, r2, res, w.done, w.partial, corr, d2);
     hipLaunchKernelGGL(k_icp_solve, dim3(n_pairs), dim3(64), 0, st, s, w.partial, res, w.done, e, p.max_iteration, p.relative_fitness,
                        p.relative_rmse);
   }
@@ -379,42 +465,35 @@ int run_chunk(const float* src, const float* tgt, const int32_t* seg_src, const 
 
 int run(const char* what, eyoc_ctx* ctx, const float* src, const float* tgt, const int32_t* seg_src, const int32_t* seg_tgt, int n_pairs,
         const double* init, const eyoc_icp_params& p, eyoc_icp_result* res, int32_t* corr, double* d2, void* ws, size_t ws_bytes, void* stream) {
-  EYOC_REQUIRE(ctx && seg_src && seg_tgt && res && ws, EYOC_ERR_INVALID, "%s: NULL argument", what);
-  EYOC_REQUIRE(n_pairs >= 1 && n_pairs <= 1024, EYOC_ERR_INVALID, "%s: n_pairs = %d is outside [1, 1024]", what, n_pairs);
-  EYOC_REQUIRE(((uintptr_t)ws & 255) == 0, EYOC_ERR_INVALID, "%s: workspace must be 256-byte aligned", what);
+  int bad = check_grid_head(what, ctx && seg_src && seg_tgt && res && ws, n_pairs, ws);
+  if (bad != EYOC_OK) return bad;
   EYOC_REQUIRE(std::isfinite(p.max_distance) && p.max_distance > 0.0, EYOC_ERR_INVALID, "%s: max_distance must be positive and finite", what);
   EYOC_REQUIRE(p.max_iteration >= 0 && p.max_iteration <= 100000, EYOC_ERR_INVALID, "%s: max_iteration = %d is outside [0, 100000]", what,
                p.max_iteration);
-  EYOC_REQUIRE(seg_src[0] == 0 && seg_tgt[0] == 0, EYOC_ERR_INVALID, "%s: segments must start at 0", what);
-  for (int b = 0; b < n_pairs; ++b)
-    EYOC_REQUIRE(seg_src[b + 1] >= seg_src[b] && seg_tgt[b + 1] >= seg_tgt[b], EYOC_ERR_INVALID, "%s: segment offsets must not decrease (pair %d)",
-                 what, b);
+  bad = check_segments(what, n_pairs, {seg_src, seg_tgt});
+  if (bad != EYOC_OK) return bad;
   EYOC_REQUIRE((seg_src[n_pairs] == 0 || src) && (seg_tgt[n_pairs] == 0 || tgt), EYOC_ERR_INVALID, "%s: NULL cloud", what);
   IcpWorkspace w;
   const size_t need = carve(ws, ws_bytes, n_pairs, seg_src[n_pairs], seg_tgt[n_pairs], &w);
   EYOC_REQUIRE(ws_bytes >= need, EYOC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (eyoc_icp_workspace_bytes)", what, ws_bytes, need);
   EYOC_CHECK_HIP(hipSetDevice(ctx->device));
-  for (int b0 = 0; b0 < n_pairs; b0 += ICP_CHUNK) {
-    const int np = n_pairs - b0 < ICP_CHUNK ? n_pairs - b0 : ICP_CHUNK;
+  return for_each_chunk(n_pairs, [&](int b0, int np) {
     const size_t so = (size_t)seg_src[b0], to = (size_t)seg_tgt[b0];
-    const int rc = run_chunk(src ? src + 3 * so : nullptr, tgt ? tgt + 3 * to : nullptr, seg_src + b0, seg_tgt + b0, np,
-                             init ? init + 16 * (size_t)b0 : nullptr, p, res + b0, corr ? corr + so : nullptr, d2 ? d2 + so : nullptr, w,
-                             (hipStream_t)stream);
-    if (rc != EYOC_OK) return rc;
-  }
-  return EYOC_OK;
+    return run_chunk(src ? src + 3 * so : nullptr, tgt ? tgt + 3 * to : nullptr, seg_src + b0, seg_tgt + b0, np,
+                     init ? init + 16 * (size_t)b0 : nullptr, p, res + b0, corr ? corr + so : nullptr, d2 ? d2 + so : nullptr, w,
+                     (hipStream_t)stream);
+  });
 }
 
-
 // ---------------------------------------------------------------------------------------------------------------------
-// Posed nearest neighbour with a gate (eyoc_posed_nn_grid): what eyoc_knn2(c = 4) + the 2 m gate of lib/trainer.py:1198-1211 return,
-// without the [n0, n1] sweep.  The grid is the one above (k_icp_build, 16-byte slots, sorted (x, y, z, row) records); the arithmetic is
-// fp32, the brute-force kernel's:  p_r = ((T0 x + T1 y) + T2 z) + T3,  d2 = (dx dx + dy dy) + dz dz,  no contraction.
+// 3. Posed nearest neighbour with a gate (eyoc_posed_nn_grid): what eyoc_knn2(c = 4) + the 2 m gate of lib/trainer.py:1198-1211 return,
+// without the [n0, n1] sweep.  The second user of the grid of section 1: the queries are selected source rows under the pair's pose, and
+// the arithmetic is fp32, the brute-force kernel's:  p_r = ((T0 x + T1 y) + T2 z) + T3,  d2 = (dx dx + dy dy) + dz dz,  no contraction.
 //   k_pnn_init    one thread per pair: BAD_INIT for a non-finite pose
-//   k_pnn_keys    targets: cell key; queries: bounds of the selected row, the posed point (stored once, 16 bytes, so the search and the
+//   k_pnn_keys    targets: target_key; queries: bounds of the selected row, the posed point (stored once, 16 bytes, so the search and the
 //                 key see the same point), its cell key, outputs preset to -1 / +inf
-//   2 x stable radix sort (pair in the top key bits), fill, k_icp_build
-//   k_pnn_search  256 cell-sorted queries of one pair per workgroup, lane = query: 27 probes, minimum over (d2, row), gate
+//   build_grid
+//   k_pnn_search  256 cell-sorted queries of one pair per workgroup, lane = query: probe_cells, minimum over (d2, row), gate
 //
 // Cell edge.  The gate is sqrtf(d2) < r in fp32 (u = 2^-24, sqrtf correctly rounded).  A target that passes it has, per axis, with
 // dxf = fl(p - q) = (p - q)(1 + e), |e| <= u:  fl(dxf dxf) >= dxf^2 (1 - u) and the two additions of non-negative terms lose at most a
@@ -447,19 +526,10 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_pnn_keys(IcpSegs s, PnnSrc sb, co
   int i = blockIdx.x * ICP_BLOCK + threadIdx.x;
   if (i < n_tgt) {
     const int b = pair_of(s.tgt, s.n_pairs, i);
+    bool ok;
     trow[i] = i;
-    unsigned long long key = pack_key(b, -COORD_BIAS, -COORD_BIAS, -COORD_BIAS);
-    if (!(status[b] & EYOC_ICP_BAD_INIT)) {
-      int c[3];
-      bool ok = true;
-      for (int k = 0; k < 3; ++k) {
-        const float v = tgt[(size_t)i * 3 + k];
-        ok = ok && isfinite(v) && cell_of((double)v, edge, &c[k]);
-      }
-      if (ok) key = pack_key(b, c[0], c[1], c[2]);
-      else atomicOr(&status[b], EYOC_ICP_RANGE);
-    }
-    tkey[i] = key;
+    tkey[i] = target_key(tgt, i, b, edge, status[b] & EYOC_ICP_BAD_INIT, &ok);
+    if (!ok) atomicOr(&status[b], EYOC_ICP_RANGE);
     return;
   }
   i -= n_tgt;
@@ -505,79 +575,34 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_pnn_search(IcpSegs s, const int* 
   if (!(cell_of((double)p.x, edge, &c[0]) && cell_of((double)p.y, edge, &c[1]) && cell_of((double)p.z, edge, &c[2]))) return;   // (status 0: never)
   float best = INFINITY;
   int best_row = -1;
-  for (int ox = -1; ox <= 1; ++ox) {
-    // the first probes of a plane's 9 cells are independent loads: issued together, then resolved one by one
-    unsigned long long key[9];
-    unsigned int slot[9];
-    IcpCell cell[9];
-    const int cx = c[0] + ox;
-#pragma unroll
-    for (int o = 0; o < 9; ++o) {
-      const int cy = c[1] + o / 3 - 1, cz = c[2] + o % 3 - 1;
-      const bool inside = cx >= -COORD_BIAS && cx < COORD_BIAS && cy >= -COORD_BIAS && cy < COORD_BIAS && cz >= -COORD_BIAS && cz < COORD_BIAS;
-      key[o] = inside ? pack_key(b, cx, cy, cz) : KEY_EMPTY;
-      slot[o] = hash_key(key[o]) & g.mask;
-      cell[o] = load_cell(g.cells, slot[o]);
-    }
-#pragma unroll
-    for (int o = 0; o < 9; ++o) {
-      if (key[o] == KEY_EMPTY) continue;
-      IcpCell e = cell[o];
-      unsigned int sl = slot[o];
-      for (unsigned int probes = 0; e.key != key[o] && e.key != KEY_EMPTY && probes < g.mask; ++probes) {   // bounded: never full
-        sl = (sl + 1) & g.mask;
-        e = load_cell(g.cells, sl);
-      }
-      if (e.key != key[o]) continue;
-      const int n = e.more + 1;
-      for (int j = 0; j < n; j += 4) {
-        float4 q4[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) q4[u] = g.pts[e.first + (j + u < n ? j + u : n - 1)];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (j + u >= n) break;
-          const float4 q = q4[u];
-          const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-          const float d = (dx * dx + dy * dy) + dz * dz;
-          const int qrow = __float_as_int(q.w);
-          if (d < best || (d == best && qrow < best_row)) { best = d; best_row = qrow; }
-        }
-      }
-    }
-  }
+  // d2 = (dx dx + dy dy) + dz dz with x and y as an explicit pair: they are the low half of a 16-byte load, an aligned register pair
+  // for the packed subtract and multiply.  Left to itself the compiler pairs y with z, which costs a move per run of points wherever
+  // the register allocator does not happen to place the load on an odd register (EXPERIMENTS.md "One cell grid in icp.hip").
+  typedef float pair_t __attribute__((ext_vector_type(2)));
+  const pair_t pxy = {p.x, p.y};
+  probe_cells(g, b, c, [&](const float4 q) {
+    const pair_t qxy = {q.x, q.y};
+    pair_t dxy = pxy - qxy;
+    dxy *= dxy;
+    const float dz = p.z - q.z;
+    const float d = (dxy.x + dxy.y) + dz * dz;
+    const int qrow = __float_as_int(q.w);
+    if (d < best || (d == best && qrow < best_row)) { best = d; best_row = qrow; }
+  });
   const bool hit = best_row >= 0 && sqrtf(best) < max_dist;
   idx_out[qi] = hit ? best_row : -1;
   if (d2_out) d2_out[qi] = hit ? best : INFINITY;
 }
 
 struct PnnWorkspace {
-  unsigned long long *tkey, *tkey_sorted, *qkey, *qkey_sorted;
-  IcpCell* cells;
-  int *trow, *trow_sorted, *qrow, *qrow_sorted;
-  float4 *pts, *qpts;
-  void* sort_tmp;
-  size_t sort_bytes;
-  unsigned int cap;
+  GridWorkspace grid;
+  float4* qpts;
 };
 
 size_t pnn_carve(void* base, size_t bytes, int total_q, int total_tgt, PnnWorkspace* w) {
   Carver c(base, bytes);
-  w->cap = table_capacity(total_tgt);
-  w->tkey = c.take<unsigned long long>(total_tgt);
-  w->tkey_sorted = c.take<unsigned long long>(total_tgt);
-  w->qkey = c.take<unsigned long long>(total_q);
-  w->qkey_sorted = c.take<unsigned long long>(total_q);
-  w->cells = c.take<IcpCell>(w->cap);
-  w->trow = c.take<int>(total_tgt);
-  w->trow_sorted = c.take<int>(total_tgt);
-  w->qrow = c.take<int>(total_q);
-  w->qrow_sorted = c.take<int>(total_q);
-  w->pts = c.take<float4>(total_tgt);
+  carve_grid(c, total_q, total_tgt, &w->grid);
   w->qpts = c.take<float4>(total_q);
-  const size_t a = sort_rows64_tmp_bytes(total_tgt > 0 ? total_tgt : 1), b = sort_rows64_tmp_bytes(total_q > 0 ? total_q : 1);
-  w->sort_bytes = a > b ? a : b;
-  w->sort_tmp = c.take<char>(w->sort_bytes);
   return align_up(c.off);
 }
 
@@ -585,35 +610,24 @@ size_t pnn_carve(void* base, size_t bytes, int total_q, int total_tgt, PnnWorksp
 int pnn_chunk(const float* src, const float* tgt, const int32_t* seg_src, const int32_t* seg_tgt, const int32_t* seg_q, int n_pairs,
               const float* T, float max_dist, const int64_t* sel, int64_t* idx_out, float* d2_out, int32_t* status, const PnnWorkspace& w,
               hipStream_t st) {
-  IcpSegs s;
+  const IcpSegs s = make_segs(seg_q, seg_tgt, n_pairs);
   PnnSrc sb;
-  s.n_pairs = n_pairs;
-  for (int b = 0; b <= n_pairs; ++b) {
-    s.src[b] = seg_q[b] - seg_q[0];
-    s.tgt[b] = seg_tgt[b] - seg_tgt[0];
-    sb.base[b] = seg_src[b] - seg_src[0];
-  }
-  s.wg[0] = 0;
-  for (int b = 0; b < n_pairs; ++b) s.wg[b + 1] = s.wg[b] + cdiv(s.src[b + 1] - s.src[b], ICP_BLOCK);
+  for (int b = 0; b <= n_pairs; ++b) sb.base[b] = seg_src[b] - seg_src[0];
   const int n_q = s.src[n_pairs], n_tgt = s.tgt[n_pairs], n_wg = s.wg[n_pairs];
   const double edge = (double)max_dist * PNN_EDGE_MARGIN;
   hipLaunchKernelGGL(k_pnn_init, dim3(cdiv(n_pairs, 64)), dim3(64), 0, st, n_pairs, T, status);
   if (n_q + n_tgt > 0)
     hipLaunchKernelGGL(k_pnn_keys, dim3(cdiv((long long)n_q + n_tgt, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, s, sb, src, tgt, T, (const long long*)sel,
-                       edge, status, w.tkey, w.trow, w.qkey, w.qrow, w.qpts, (long long*)idx_out, d2_out);
+                       edge, status, w.grid.tkey, w.grid.trow, w.grid.qkey, w.grid.qrow, w.qpts, (long long*)idx_out, d2_out);
   if (n_q == 0 || n_tgt == 0) {        // nothing to search: every output is already -1
     EYOC_CHECK_HIP(hipGetLastError());
     return EYOC_OK;
   }
-  int rc = sort_rows_by_key64(w.sort_tmp, w.sort_bytes, w.tkey, w.tkey_sorted, w.trow, w.trow_sorted, n_tgt, 60, st);
+  IcpGrid g;
+  const int rc = build_grid(s, tgt, status, w.grid, st, &g);
   if (rc != EYOC_OK) return rc;
-  rc = sort_rows_by_key64(w.sort_tmp, w.sort_bytes, w.qkey, w.qkey_sorted, w.qrow, w.qrow_sorted, n_q, 60, st);
-  if (rc != EYOC_OK) return rc;
-  EYOC_CHECK_HIP(hipMemsetAsync(w.cells, 0xFF, (size_t)w.cap * sizeof(IcpCell), st));
-  hipLaunchKernelGGL(k_icp_build, dim3(cdiv(n_tgt, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, s, tgt, w.tkey_sorted, w.trow_sorted, status, w.pts, w.cells,
-                     w.cap - 1);
-  const IcpGrid g{w.cells, w.cap - 1, w.pts};
-  hipLaunchKernelGGL(k_pnn_search, dim3(n_wg), dim3(ICP_BLOCK), 0, st, s, w.qrow_sorted, w.qpts, g, edge, max_dist, status, (long long*)idx_out, d2_out);
+  hipLaunchKernelGGL(k_pnn_search, dim3(n_wg), dim3(ICP_BLOCK), 0, st, s, w.grid.qrow_sorted, w.qpts, g, edge, max_dist, status,
+                     (long long*)idx_out, d2_out);
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
 }
@@ -662,16 +676,13 @@ extern "C" int eyoc_posed_nn_grid(eyoc_ctx* ctx, const float* src_dev, const flo
                                   void* workspace_dev, size_t workspace_bytes, void* stream) {
   using namespace eyoc;
   const char* what = "eyoc_posed_nn_grid";
-  EYOC_REQUIRE(ctx && seg_src_host && seg_tgt_host && T_dev && status_dev && workspace_dev, EYOC_ERR_INVALID, "%s: NULL argument", what);
-  EYOC_REQUIRE(n_pairs >= 1 && n_pairs <= 1024, EYOC_ERR_INVALID, "%s: n_pairs = %d is outside [1, 1024]", what, n_pairs);
-  EYOC_REQUIRE(((uintptr_t)workspace_dev & 255) == 0, EYOC_ERR_INVALID, "%s: workspace must be 256-byte aligned", what);
+  int bad = check_grid_head(what, ctx && seg_src_host && seg_tgt_host && T_dev && status_dev && workspace_dev, n_pairs, workspace_dev);
+  if (bad != EYOC_OK) return bad;
   EYOC_REQUIRE(std::isfinite(max_dist) && max_dist > 0.0f, EYOC_ERR_INVALID, "%s: max_dist must be positive and finite", what);
   EYOC_REQUIRE((sel_dev == nullptr) == (seg_sel_host == nullptr), EYOC_ERR_INVALID, "%s: a selection needs its segments (and the other way round)", what);
   const int32_t* seg_q = seg_sel_host ? seg_sel_host : seg_src_host;
-  EYOC_REQUIRE(seg_src_host[0] == 0 && seg_tgt_host[0] == 0 && seg_q[0] == 0, EYOC_ERR_INVALID, "%s: segments must start at 0", what);
-  for (int b = 0; b < n_pairs; ++b)
-    EYOC_REQUIRE(seg_src_host[b + 1] >= seg_src_host[b] && seg_tgt_host[b + 1] >= seg_tgt_host[b] && seg_q[b + 1] >= seg_q[b], EYOC_ERR_INVALID,
-                 "%s: segment offsets must not decrease (pair %d)", what, b);
+  bad = check_segments(what, n_pairs, {seg_src_host, seg_tgt_host, seg_q});
+  if (bad != EYOC_OK) return bad;
   const int total_q = seg_q[n_pairs];
   EYOC_REQUIRE((seg_src_host[n_pairs] == 0 || src_dev) && (seg_tgt_host[n_pairs] == 0 || tgt_dev) && (total_q == 0 || idx_out_dev), EYOC_ERR_INVALID,
                "%s: NULL cloud or output", what);
@@ -681,14 +692,10 @@ extern "C" int eyoc_posed_nn_grid(eyoc_ctx* ctx, const float* src_dev, const flo
   EYOC_REQUIRE(workspace_bytes >= need, EYOC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (eyoc_posed_nn_grid_workspace_bytes)", what, workspace_bytes,
                need);
   EYOC_CHECK_HIP(hipSetDevice(ctx->device));
-  for (int b0 = 0; b0 < n_pairs; b0 += ICP_CHUNK) {
-    const int np = n_pairs - b0 < ICP_CHUNK ? n_pairs - b0 : ICP_CHUNK;
+  return for_each_chunk(n_pairs, [&](int b0, int np) {
     const size_t so = (size_t)seg_src_host[b0], to = (size_t)seg_tgt_host[b0], qo = (size_t)seg_q[b0];
-    const int rc = pnn_chunk(src_dev ? src_dev + 3 * so : nullptr, tgt_dev ? tgt_dev + 3 * to : nullptr, seg_src_host + b0, seg_tgt_host + b0,
-                             seg_q + b0, np, T_dev + 16 * (size_t)b0, max_dist, sel_dev ? sel_dev + qo : nullptr,
-                             idx_out_dev ? idx_out_dev + qo : nullptr, d2_out_dev ? d2_out_dev + qo : nullptr, status_dev + b0, w,
-                             (hipStream_t)stream);
-    if (rc != EYOC_OK) return rc;
-  }
-  return EYOC_OK;
+    return pnn_chunk(src_dev ? src_dev + 3 * so : nullptr, tgt_dev ? tgt_dev + 3 * to : nullptr, seg_src_host + b0, seg_tgt_host + b0, seg_q + b0, np,
+                     T_dev + 16 * (size_t)b0, max_dist, sel_dev ? sel_dev + qo : nullptr, idx_out_dev ? idx_out_dev + qo : nullptr,
+                     d2_out_dev ? d2_out_dev + qo : nullptr, status_dev + b0, w, (hipStream_t)stream);
+  });
 }

@@ -30,6 +30,19 @@ def _segs(seg):
     return (C.c_int32 * len(seg))(*seg), seg
 
 
+def _clouds(who, src, tgt, seg_src, seg_tgt, one_pair=False):
+    """What both entry points start from: the clouds as f32 ``[n, 3]`` on one device, their segments as C arrays (``one_pair``: a
+    segment list that is ``None`` means one pair), the number of pairs and the uninitialised ``[P, 160]`` record tensor."""
+    s = _cuda_f32(src).reshape(-1, 3)
+    t = _cuda_f32(tgt, s.device).reshape(-1, 3)
+    ss, seg_s = _segs([0, s.shape[0]] if one_pair and seg_src is None else seg_src)
+    st, seg_t = _segs([0, t.shape[0]] if one_pair and seg_tgt is None else seg_tgt)
+    P = len(seg_s) - 1
+    if len(seg_t) != P + 1 or seg_s[-1] != s.shape[0] or seg_t[-1] != t.shape[0]:
+        raise ValueError(f"{who}: the segments do not describe the clouds")
+    return s, t, ss, st, P, torch.empty((P, RECORD_BYTES), dtype=torch.uint8, device=s.device)
+
+
 def _poses(T, P, device):
     """``[P, 4, 4]`` / ``[4, 4]`` / ``[P, 16]`` poses (numpy or torch, any float type) -> contiguous f64 ``[P, 16]`` on ``device``."""
     if not isinstance(T, torch.Tensor):
@@ -48,16 +61,9 @@ def icp_batched(src, tgt, seg_src, seg_tgt, max_correspondence_distance, init=No
     ``b`` = source rows ``seg_src[b]:seg_src[b+1]``, target rows ``seg_tgt[b]:seg_tgt[b+1]``), ``init`` f64 ``[P, 4, 4]`` (host or
     device; ``None`` = identity).  Returns the ``[P, 160]`` byte tensor of ``eyoc_icp_result`` records on the device (``decode_icp_result``)
     - and, with ``return_correspondences``, ``int32 [N]``: the target row local to the pair under the returned pose, or -1."""
-    s = _cuda_f32(src).reshape(-1, 3)
-    t = _cuda_f32(tgt, s.device).reshape(-1, 3)
-    ss, seg_s = _segs(seg_src)
-    st, seg_t = _segs(seg_tgt)
-    P = len(seg_s) - 1
-    if len(seg_t) != P + 1 or seg_s[-1] != s.shape[0] or seg_t[-1] != t.shape[0]:
-        raise ValueError("icp_batched: the segments do not describe the clouds")
+    s, t, ss, st, P, res = _clouds("icp_batched", src, tgt, seg_src, seg_tgt)
     T0 = None if init is None else _poses(init, P, s.device)
     p = _lib.IcpParams(float(max_correspondence_distance), float(relative_fitness), float(relative_rmse), int(max_iteration), 0)
-    res = torch.empty((P, RECORD_BYTES), dtype=torch.uint8, device=s.device)
     corr = torch.empty(s.shape[0], dtype=torch.int32, device=s.device) if return_correspondences else None
     lib = _lib.load()
     with _lib.on_device(s.device):
@@ -70,15 +76,8 @@ def icp_batched(src, tgt, seg_src, seg_tgt, max_correspondence_distance, init=No
 def correspondences(src, tgt, T, max_distance, seg_src=None, seg_tgt=None, return_records=False):
     """One evaluation under ``T``: -> ``(corr int32 [N], d2 f64 [N])`` on the device - the nearest target row (local to the pair, the
     lowest row on a tie) with ``d2 < max_distance ** 2``, else -1 / +inf.  One pair unless segments are given."""
-    s = _cuda_f32(src).reshape(-1, 3)
-    t = _cuda_f32(tgt, s.device).reshape(-1, 3)
-    ss, seg_s = _segs([0, s.shape[0]] if seg_src is None else seg_src)
-    st, seg_t = _segs([0, t.shape[0]] if seg_tgt is None else seg_tgt)
-    P = len(seg_s) - 1
-    if len(seg_t) != P + 1 or seg_s[-1] != s.shape[0] or seg_t[-1] != t.shape[0]:
-        raise ValueError("correspondences: the segments do not describe the clouds")
+    s, t, ss, st, P, res = _clouds("correspondences", src, tgt, seg_src, seg_tgt, one_pair=True)
     Td = _poses(T, P, s.device)
-    res = torch.empty((P, RECORD_BYTES), dtype=torch.uint8, device=s.device)
     corr = torch.empty(s.shape[0], dtype=torch.int32, device=s.device)
     d2 = torch.empty(s.shape[0], dtype=torch.float64, device=s.device)
     lib = _lib.load()
