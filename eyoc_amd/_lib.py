@@ -155,6 +155,9 @@ PROTOTYPES = {
     "eyoc_model_fuse_tail": (_i, [_vp, _i]),
     "eyoc_model_workspace_bytes": (_sz, [_vp, _vp]),
     "eyoc_model_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "eyoc_model_workspace_bytes_rows": (_sz, [_vp, _vp, _i]),
+    "eyoc_model_forward_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "eyoc_model_sampled_tail": (_i, [_vp, _i]),
     "eyoc_model_num_layers": (_i, [_vp]),
     "eyoc_model_layer_work": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_char_p), C.POINTER(C.c_int64),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -15,7 +15,7 @@ __global__ __launch_bounds__(256) void k_gather_rows(const float* __restrict__ F
   const int t = blockIdx.x * 256 + threadIdx.x;
   const int r = t / L, q = t % L;
   if (r >= n) return;   // L divides 64, so a row never straddles two waves and the shuffles below see whole rows
-  float4 v = *reinterpret_cast<const float4*>(F + (size_t)sel[r] * ld + q * 4);
+  float4 v = *reinterpret_cast<const float4*>(F + (size_t)(sel ? sel[r] : (long long)r) * ld + q * 4);   // sel == NULL: the rows as they are (blend only)
   if (G) {
     const float4 g = *reinterpret_cast<const float4*>(G + (size_t)r * (L * 4) + q * 4);
     v.x += beta * g.x; v.y += beta * g.y; v.z += beta * g.z; v.w += beta * g.w;
@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void k_gather_rows(const float* __restrict__ F
 
 extern "C" int eyoc_gather_rows(eyoc_ctx* ctx, const float* F_dev, int ld, int c, const int64_t* sel_dev, int n,
                                 const float* G_dev, float beta, float* out_dev, void* stream) {
-  EYOC_REQUIRE(ctx && F_dev && sel_dev && out_dev, EYOC_ERR_INVALID, "eyoc_gather_rows: NULL argument");
+  EYOC_REQUIRE(ctx && F_dev && out_dev, EYOC_ERR_INVALID, "eyoc_gather_rows: NULL argument");
   EYOC_REQUIRE(n >= 0 && ld >= c && ld % 4 == 0, EYOC_ERR_INVALID, "eyoc_gather_rows: n %d ld %d c %d", n, ld, c);
   if (n == 0) return EYOC_OK;
   hipStream_t st = (hipStream_t)stream;

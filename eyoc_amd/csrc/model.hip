@@ -55,6 +55,9 @@ struct eyoc_model {
   int progress_layer = -1;
   unsigned int* range = nullptr;      // device: {overflow flag of the forward in flight, max |activation| bits (probe), probe switch, sticky overflow flag} - split16_guard in spconv.h
   int probe = 0;
+  // eyoc_model_forward_rows: the most recent forward computed its last 3^3 layer (index sampled_layer) and the 1x1 tail for
+  // sampled_rows listed rows only (-1: it was a full forward); range word 6 holds the (row, offset) pairs that layer multiplied
+  int sampled_layer = -1, sampled_rows = 0;
 };
 
 namespace {
@@ -677,6 +680,30 @@ size_t eyoc_model_workspace_bytes(const eyoc_model* m, const eyoc_maps* maps) {
   return b + 256;
 }
 
+// eyoc_model_forward_rows: floats it needs beside the full forward's buffers - the compact rows [n_rows, 96] (sampled tail) or the
+// full output [N, out_channels] (fallback), whichever is larger.  Both live in B_X1 when they fit: the first block's input is dead
+// long before the last layer runs.  0 = they fit.
+static size_t rows_region_floats(const eyoc_model* m, const eyoc_maps* maps, int n_rows) {
+  return std::max((size_t)n_rows * 96, (size_t)maps->rows[0] * m->desc.out_channels);
+}
+static size_t rows_extra_floats(const eyoc_model* m, const eyoc_maps* maps, int n_rows) {
+  const size_t need = rows_region_floats(m, maps, n_rows);
+  return need <= (size_t)maps->rows[0] * m->bufs[B_X1].width ? 0 : need;
+}
+
+size_t eyoc_model_workspace_bytes_rows(const eyoc_model* m, const eyoc_maps* maps, int n_rows) {
+  if (!m || !maps || n_rows < 0) return 0;
+  return eyoc_model_workspace_bytes(m, maps) + align_up(rows_extra_floats(m, maps, n_rows) * sizeof(float)) +
+         align_up(spconv_rows_scratch_bytes(maps->rows[0], n_rows));
+}
+
+int eyoc_model_sampled_tail(eyoc_ctx* ctx, int on) {
+  if (!ctx) return -1;
+  const int prev = ctx->knobs.sampled_tail;
+  if (on == 0 || on == 1) ctx->knobs.sampled_tail = on;
+  return prev;
+}
+
 int eyoc_model_num_layers(const eyoc_model* m) { return m ? (int)m->layers.size() : 0; }
 
 int eyoc_model_set_math(eyoc_model* m, int mode) {
@@ -714,12 +741,13 @@ int eyoc_model_layer_ms(eyoc_model* m, float* ms) {
   return EYOC_OK;
 }
 
-int eyoc_model_forward(eyoc_ctx* ctx, const eyoc_model* mc, const eyoc_maps* maps, const float* feats_dev, float* out_dev,
-                       void* ws, size_t ws_bytes, void* stream) {
-  EYOC_REQUIRE(ctx && mc && maps && feats_dev && out_dev && ws, EYOC_ERR_INVALID, "eyoc_model_forward: NULL argument");
-  EYOC_REQUIRE(ws_bytes >= eyoc_model_workspace_bytes(mc, maps), EYOC_ERR_WORKSPACE,
-               "eyoc_model_forward: workspace %zu < required %zu bytes", ws_bytes, eyoc_model_workspace_bytes(mc, maps));
-  EYOC_REQUIRE(((uintptr_t)ws & 255) == 0, EYOC_ERR_INVALID, "eyoc_model_forward: workspace must be 256-byte aligned");
+}  // extern "C"
+
+// eyoc_model_forward (rows_dev == NULL: out_dev is [N, out_channels]) and eyoc_model_forward_rows (out_dev is [n_rows, out_channels],
+// row i = the network's output row rows_dev[i]): one schedule.  With rows, the last 3^3 layer and the 1x1 tail run on the listed rows
+// only where the full forward would fuse them (spconv_rows.hip); otherwise the full output goes to the workspace and its rows are taken.
+static int forward_impl(eyoc_ctx* ctx, const eyoc_model* mc, const eyoc_maps* maps, const float* feats_dev, float* out_dev, void* ws,
+                        size_t ws_bytes, void* stream, const int64_t* rows_dev, int n_rows) {
   eyoc_model* m = const_cast<eyoc_model*>(mc);
   hipStream_t st = (hipStream_t)stream;
   float* buf[B_COUNT];
@@ -729,6 +757,16 @@ int eyoc_model_forward(eyoc_ctx* ctx, const eyoc_model* mc, const eyoc_maps* map
   for (int i = B_X1; i < B_OUT; ++i) buf[i] = cv.take<float>((size_t)maps->rows[m->bufs[i].level] * m->bufs[i].width);
   const size_t ks_bytes = ks_part_bytes(m, maps);
   float* ks_part = ks_bytes ? cv.take<float>(ks_bytes / 4) : nullptr;
+  float* rows_region = nullptr;        // the compact rows / the full output of a forward with a row list
+  void* rows_scratch = nullptr;
+  if (rows_dev) {
+    const size_t extra = rows_extra_floats(m, maps, n_rows);
+    rows_region = extra ? cv.take<float>(extra) : buf[B_X1];
+    rows_scratch = cv.take<unsigned char>(spconv_rows_scratch_bytes(maps->rows[0], n_rows));
+    buf[B_OUT] = rows_region;          // until the sampled tail takes over: the full output, whose rows are taken at the end
+  }
+  m->sampled_layer = -1;
+  m->sampled_rows = 0;
   // arithmetic of the sparse convolutions: SPLIT16 needs the wave-private kernel for EVERY layer (only it reads and
   // writes the format), which round 1 measured to pay off once the finest level alone fills the chip (>= 4096 wave tiles ~ 4 KITTI
   // pairs); small batches stay on fp32, where the launcher picks the workgroup-tiled kernel per layer
@@ -841,7 +879,29 @@ int eyoc_model_forward(eyoc_ctx* ctx, const eyoc_model* mc, const eyoc_maps* map
         const LayerPlan &q1 = m->layers[li + 1], &q2 = m->layers[li + 2];
         if (q1.map == M_IDENT && q1.K == 1 && q1.res_buf < 0 && q2.map == M_IDENT && q2.K == 1 && q2.in_buf == q1.out_buf && q2.res_buf < 0 &&
             !q2.relu && q2.out_buf == B_OUT && q1.out_col == 0 && tail_fusable(q1.cin, q1.cout, q2.cout) && q1.in_buf == p.out_buf &&
-            q1.in_col == p.out_col && q1.cin == p.cout + 32 && spconv_record_path(a) == 1 && spconv_st_can_fuse_tail(a)) {
+            q1.in_col == p.out_col && q1.cin == p.cout + 32 && spconv_record_path(a) == 1 &&
+            (spconv_st_can_fuse_tail(a) || (rows_dev && ctx->knobs.sampled_tail))) {
+          // (a row list does not ask for the 256-row kernel: small inputs, whose full forward runs the tail as a kernel of its own - the
+          // same bits -, take the sampled path too)
+          if (rows_dev && ctx->knobs.sampled_tail && maps->row_perm && spconv_rows_supported(a)) {
+            // the caller reads n_rows rows: this layer for those rows only (compact [n_rows, 96] split16 rows: its 64 channels + the
+            // 32 skip channels), then the tail as a kernel of its own on them - the bits of the fused epilogue
+            EYOC_CHECK_HIP(hipMemsetAsync(m->range + 6, 0, 4, st));
+            rc = launch_spconv_rows(a, a.local, maps->row_perm, rows_dev, n_rows, buf[q1.in_buf] + q1.in_col + p.cout,
+                                    m->bufs[q1.in_buf].width, rows_region, rows_scratch, m->range + 6, st);
+            if (!rc)
+              rc = launch_tail_fused(rows_region, 96, n_rows, m->blob + q1.w16_off, m->blob + q1.s_off, m->blob + q1.b_off, q1.relu,
+                                     m->blob + q2.w16_off, m->blob + q2.s_off, m->blob + q2.b_off, q2.l2norm, out_dev,
+                                     m->desc.out_channels, nullptr, m->range, st);
+            if (rc) return rc;
+            m->sampled_layer = (int)li;
+            m->sampled_rows = n_rows;
+            if (m->timing)
+              for (int e = 1; e <= 3; ++e) EYOC_CHECK_HIP(hipEventRecord(ev[li + e], st));
+            li += 2;
+            continue;
+          }
+          if (!spconv_st_can_fuse_tail(a)) goto unfused;
           a.tail.skip = buf[q1.in_buf] + q1.in_col + p.cout; a.tail.ld_skip = m->bufs[q1.in_buf].width;
           a.tail.w1 = m->blob + q1.w16_off; a.tail.s1 = m->blob + q1.s_off; a.tail.b1 = m->blob + q1.b_off; a.tail.relu1 = q1.relu;
           a.tail.w2 = m->blob + q2.w16_off; a.tail.s2 = m->blob + q2.s_off; a.tail.b2 = m->blob + q2.b_off; a.tail.l2norm = q2.l2norm;
@@ -854,14 +914,40 @@ int eyoc_model_forward(eyoc_ctx* ctx, const eyoc_model* mc, const eyoc_maps* map
           continue;
         }
       }
+    unfused:
       rc = launch_spconv(a, st);
     }
     if (rc) return rc;
     if (m->timing) EYOC_CHECK_HIP(hipEventRecord(ev[li + 1], st));
   }
   if (!progress_recorded) EYOC_CHECK_HIP(hipEventRecord(m->progress_event, st));
+  if (rows_dev && m->sampled_layer < 0)                                  // the fallback: the rows of the full output
+    if (int rc = launch_take_rows(rows_region, maps->rows[0], m->desc.out_channels, rows_dev, n_rows, out_dev, st)) return rc;
   if (m->timing) m->events_valid[m->slot] = 1;
   return EYOC_OK;
+}
+
+extern "C" {
+
+int eyoc_model_forward(eyoc_ctx* ctx, const eyoc_model* mc, const eyoc_maps* maps, const float* feats_dev, float* out_dev,
+                       void* ws, size_t ws_bytes, void* stream) {
+  EYOC_REQUIRE(ctx && mc && maps && feats_dev && out_dev && ws, EYOC_ERR_INVALID, "eyoc_model_forward: NULL argument");
+  EYOC_REQUIRE(ws_bytes >= eyoc_model_workspace_bytes(mc, maps), EYOC_ERR_WORKSPACE,
+               "eyoc_model_forward: workspace %zu < required %zu bytes", ws_bytes, eyoc_model_workspace_bytes(mc, maps));
+  EYOC_REQUIRE(((uintptr_t)ws & 255) == 0, EYOC_ERR_INVALID, "eyoc_model_forward: workspace must be 256-byte aligned");
+  return forward_impl(ctx, mc, maps, feats_dev, out_dev, ws, ws_bytes, stream, nullptr, 0);
+}
+
+int eyoc_model_forward_rows(eyoc_ctx* ctx, const eyoc_model* mc, const eyoc_maps* maps, const float* feats_dev, const int64_t* rows_dev,
+                            int n_rows, float* out_dev, void* ws, size_t ws_bytes, void* stream) {
+  EYOC_REQUIRE(ctx && mc && maps && feats_dev && ws && n_rows >= 0 && (n_rows == 0 || (rows_dev && out_dev)), EYOC_ERR_INVALID,
+               "eyoc_model_forward_rows: NULL argument");
+  EYOC_REQUIRE(mc->desc.out_channels % 4 == 0, EYOC_ERR_INVALID, "eyoc_model_forward_rows: %d output channels", mc->desc.out_channels);
+  EYOC_REQUIRE(ws_bytes >= eyoc_model_workspace_bytes_rows(mc, maps, n_rows), EYOC_ERR_WORKSPACE,
+               "eyoc_model_forward_rows: workspace %zu < required %zu bytes", ws_bytes, eyoc_model_workspace_bytes_rows(mc, maps, n_rows));
+  EYOC_REQUIRE(((uintptr_t)ws & 255) == 0, EYOC_ERR_INVALID, "eyoc_model_forward_rows: workspace must be 256-byte aligned");
+  if (n_rows == 0) return EYOC_OK;                                       // nothing is read: nothing is launched
+  return forward_impl(ctx, mc, maps, feats_dev, out_dev, ws, ws_bytes, stream, rows_dev, n_rows);
 }
 
 int eyoc_model_set_progress_event(eyoc_model* m, int layer, void* hip_event) {
@@ -880,10 +966,21 @@ int eyoc_model_layer_work(eyoc_ctx* ctx, const eyoc_model* m, const eyoc_maps* m
   eyoc_maps_info_t info;
   int rc = eyoc_maps_info(ctx, maps, m->desc.conv1_kernel_size, stream, &info);
   if (rc) return rc;
+  // the handle's most recent forward computed its last three layers for a row list (eyoc_model_forward_rows): their work is what
+  // that forward multiplied - the pairs its rows kernel counted (range word 6), the listed rows for the two 1x1 layers
+  unsigned int sampled_pairs = 0;
+  if (m->sampled_layer >= 0) {
+    EYOC_CHECK_HIP(hipMemcpyAsync(&sampled_pairs, m->range + 6, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    EYOC_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+  }
   for (size_t li = 0; li < m->layers.size(); ++li) {
     const LayerPlan& p = m->layers[li];
-    const double n_out = maps->rows[p.out_level];
+    const bool sampled = m->sampled_layer >= 0 && (int)li >= m->sampled_layer && (int)li <= m->sampled_layer + 2;
+    const double n_out = sampled ? m->sampled_rows : maps->rows[p.out_level];
     double n_in = n_out, pr = 0;
+    if (sampled) {
+      pr = (int)li == m->sampled_layer ? (double)sampled_pairs : n_out;
+    } else
     switch (p.map) {
       case M_CONV1: pr = (double)info.pairs_conv1; break;
       case M_S1: pr = (double)info.pairs_s1[p.level]; break;

@@ -206,6 +206,15 @@ bool tail_fusable(int cin1, int cmid, int cout);
 int launch_tail_fused(const float* in, int ld_in, int n, const float* w1, const float* s1, const float* b1, int relu1, const float* w2,
                       const float* s2, const float* b2, int l2norm, float* out, int ld_out, const int32_t* out_perm, unsigned int* range,
                       hipStream_t st);
+// a stride-1 3^3 SPLIT16 layer (64 output channels) for a LIST of output rows (spconv_rows.hip): `rows_dev` are the caller's row numbers
+// (int64; row_perm = internal -> caller, NULL = identity), `out` [n_rows, cout + 32] SPLIT16 rows - the layer's channels, then a byte
+// copy of the first 32-channel block of `skip`'s row; bit for bit what the staged kernel writes for those rows (`local_dev`: the level's
+// tile records, which say in which pass a neighbour is summed).  *pairs += the (row, offset) pairs multiplied.
+bool spconv_rows_supported(const SpconvArgs& a);
+size_t spconv_rows_scratch_bytes(int n_level_rows, int n_rows);
+int launch_spconv_rows(const SpconvArgs& a, const unsigned char* local_dev, const int32_t* row_perm, const int64_t* rows_dev, int n_rows,
+                       const float* skip, int ld_skip, float* out, void* scratch, unsigned int* pairs, hipStream_t st);
+int launch_take_rows(const float* in, int n, int c, const int64_t* rows_dev, int n_rows, float* out, hipStream_t st);   // out[i] = in[rows[i]]
 bool spconv_rs_fits(const SpconvArgs& a);
 int launch_spconv_wave(const SpconvArgs& a, hipStream_t st);   // wave-private tiling (spconv_wave.hip)
 

@@ -76,16 +76,18 @@ def gather_rows(F: torch.Tensor, sel: torch.Tensor, G: torch.Tensor | None = Non
     """``F[sel]`` in one launch (``eyoc_gather_rows``); with ``G`` ``[len(sel), C]`` the gathered rows are blended
     and re-normalised, ``(F[sel] + beta * G) / |.|`` - the descriptor mode of the synthetic benchmark."""
     F = _cuda_f32(F)
-    sel = sel.to(F.device, torch.int64).contiguous()
+    if sel is not None:                     # (None: every row of ``F`` in place - the blend alone)
+        sel = sel.to(F.device, torch.int64).contiguous()
+    n = F.shape[0] if sel is None else sel.shape[0]
     c = F.shape[1]
-    out = torch.empty((sel.shape[0], c), dtype=torch.float32, device=F.device)
+    out = torch.empty((n, c), dtype=torch.float32, device=F.device)
     if G is not None:
         G = _cuda_f32(G, F.device)
-        if tuple(G.shape) != (sel.shape[0], c):
+        if tuple(G.shape) != (n, c):
             raise ValueError("G must be [len(sel), C]")
     with torch.cuda.device(F.device):
         _lib.check(_lib.load().eyoc_gather_rows(_lib.ctx(F.device.index), _lib.ptr(F), F.stride(0), c, _lib.ptr(sel),
-                                                sel.shape[0], _lib.ptr(G), C.c_float(beta), _lib.ptr(out),
+                                                n, _lib.ptr(G), C.c_float(beta), _lib.ptr(out),
                                                 _lib.stream_ptr()), "eyoc_gather_rows")
     return out
 

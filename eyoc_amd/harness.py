@@ -444,13 +444,16 @@ class RegistrationPipeline:
         # the split16 range check is deferred to where ``register`` synchronises anyway (no host wait after the forward)
         return self._features(batch, maps)[0]
 
-    def _features(self, batch, maps):
+    def _features(self, batch, maps, sampled=False):
         """``features`` -> (the features, the batch they belong to): under ``isolate_failures`` that is ``batch`` without the pairs a
-        failed map build named - dropped here, or by ``prepare_maps``, whose handle then carries the reduced batch."""
+        failed map build named - dropped here, or by ``prepare_maps``, whose handle then carries the reduced batch.
+
+        ``sampled`` (the step): only the rows matching reads, ``model(x, rows=cat(sel0, sel1))`` of the batch the forward runs on -
+        a dense ``[2 P n, C]`` tensor, ``sel0``'s rows first, bit for bit ``model(x).F[rows]``."""
         check, self.model.range_check = self.model.range_check, False
         try:
             if maps is None and not self.cfg.isolate_failures:
-                return self.model(SparseTensor(batch.feats, coordinates=batch.coords)), batch
+                return self._forward(SparseTensor(batch.feats, coordinates=batch.coords), batch, sampled), batch
             if maps is None:
                 cm, batch = self._build_maps(batch)
             else:
@@ -459,9 +462,18 @@ class RegistrationPipeline:
                 if self.cfg.isolate_failures and reduced is not batch:
                     batch = reduced
                     batch.record_stream(torch.cuda.current_stream())     # made on the side stream, read on this one
-            return self.model(SparseTensor(batch.feats, coordinate_manager=cm)), batch
+            return self._forward(SparseTensor(batch.feats, coordinate_manager=cm), batch, sampled), batch
         finally:
             self.model.range_check = check
+
+    def _forward(self, x, batch, sampled):
+        if not sampled:
+            return self.model(x)
+        # the sample is drawn before the forward (``DeviceBatch``), by index only - like the reference's ``random_sample``
+        cached = batch.__dict__.get("_sel01")
+        if cached is None or cached[0] is not batch.sel0 or cached[1] is not batch.sel1:
+            cached = batch.__dict__["_sel01"] = (batch.sel0, batch.sel1, torch.cat((batch.sel0.reshape(-1), batch.sel1.reshape(-1))))
+        return self.model(x, rows=cached[2])
 
     def _build_maps(self, batch):
         """The maps of ``batch`` on the current stream -> ``(coordinate manager, the batch it describes)``: under ``isolate_failures``
@@ -502,8 +514,7 @@ class RegistrationPipeline:
         step = _Step(slot, self._ev[slot] if timed else None)
         main = torch.cuda.current_stream()
         self._mark(step, 0)
-        F, step.batch = self._features(batch, maps)
-        step.F = F.F
+        step.F, step.batch = self._features(batch, maps, sampled=True)     # the sampled rows only: [sel0's rows | sel1's rows]
         self._mark(step, 1)
         if read_back:
             step.words = self._pinned_words(slot)
@@ -639,12 +650,24 @@ class RegistrationPipeline:
         step.matched = torch.cuda.Event()
         step.matched.record()
 
+    def _sampled_halves(self, step):
+        """``step.F`` holds the forward's rows ``sel0`` then ``sel1`` -> what ``gather_rows(F, sel, G, beta)`` gave on the full features:
+        the halves as they are, or blended with the planted descriptors by the same kernel (``eyoc_gather_rows`` without an index
+        list), so that the blended rows keep their bits."""
+        batch, F = step.batch, step.F
+        n0 = batch.sel0.numel()
+        F0, F1 = F[:n0], F[n0:]
+        if batch.G0 is not None:
+            F0 = gather_rows(F0, None, batch.G0, batch.beta)
+        if batch.G1 is not None:
+            F1 = gather_rows(F1, None, batch.G1, batch.beta)
+        return F0, F1
+
     def _match_and_register(self, step, seed):
         """Row gather (+ descriptor blend), segmented feature NN and the batched RANSAC of all pairs on the CURRENT stream ->
         ``[P, 84]`` result records on the device."""
         batch, F = step.batch, step.F
-        F0 = gather_rows(F, batch.sel0, batch.G0, batch.beta)     # the sampled rows (+ descriptor blend, if any)
-        F1 = gather_rows(F, batch.sel1, batch.G1, batch.beta)
+        F0, F1 = self._sampled_halves(step)                        # the sampled rows (+ descriptor blend, if any)
         # isolate_failures: a dropped pair is an empty segment - for the neighbour search, which gives the live rows what the live
         # segments alone give (tests/test_gpu_isolate_batch.py), and for the back-end, where it keeps the pair's slot and every seed
         step.nn_idx = knn1_segmented(F0, F1, batch.seg, batch.seg, "SquareL2", return_distance=False)
@@ -732,8 +755,7 @@ class RegistrationPipeline:
         Identical indices (``tests/test_gpu_sc2pcr.py`` compares with the per-pair estimator), a quarter of the products."""
         batch, F, m = step.batch, step.F, self.matcher
         n, P, dev = batch.n_points, batch.P, F.device
-        F0 = gather_rows(F, batch.sel0, batch.G0, batch.beta)
-        F1 = gather_rows(F, batch.sel1, batch.G1, batch.beta)
+        F0, F1 = self._sampled_halves(step)
         rng = np.random.RandomState(seed)
         # isolate_failures: the per-pair arrays hold the live pairs only, back to back (``L`` of them; live pair ``p`` is block ``q``);
         # the draws are still made for all P, so that a live pair's do not depend on who was dropped, and the back-end gets an empty

@@ -318,12 +318,18 @@ class ResUNet2(nn.Module):
         return self._blob
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x: SparseTensor) -> SparseTensor:
+    def forward(self, x: SparseTensor, rows: torch.Tensor | None = None):
+        """``model(x)`` -> the features of every row, a ``SparseTensor``.  ``model(x, rows=r)`` (eval mode; ``r``: int64 row numbers of
+        ``x``, any order, duplicates allowed) -> the dense tensor ``model(x).F[r]``, bit for bit, from ``eyoc_model_forward_rows``: a
+        caller that reads a sample of the rows (``scripts/test_kitti.py:159-160`` draws it by index only) does not pay the last
+        3x3x3 layer and the 1x1 tail for the rest."""
         if not isinstance(x, SparseTensor):
             raise TypeError("expected an eyoc_amd.SparseTensor")
         if x.F.shape[1] != self.in_channels:
             raise ValueError(f"features have {x.F.shape[1]} channels, model expects {self.in_channels}")
         if self.training:
+            if rows is not None:
+                raise ValueError("model(x, rows=...) is an eval-mode forward: training mode computes every row")
             # training mode: batch statistics + autograd (lib/trainer.py:1655-1676), layer by layer
             from .train import forward_layers
             return forward_layers(self, x)
@@ -336,11 +342,21 @@ class ResUNet2(nn.Module):
         cm = x.coordinate_manager
         maps = cm.maps(-1)        # automatic internal order (Z-order from 8192 rows); in and out stay in the caller's rows
         cm._reading()             # the forward reads the maps on this stream
-        out = torch.empty((len(x), self.out_channels), dtype=torch.float32, device=dev)
+        if rows is not None:
+            rows = rows.to(dev, torch.int64).contiguous().reshape(-1)
+        out = torch.empty((len(x) if rows is None else rows.numel(), self.out_channels), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            ws = _lib.workspace(lib.eyoc_model_workspace_bytes(self._handle, maps), dev)
+            if rows is None:
+                ws = _lib.workspace(lib.eyoc_model_workspace_bytes(self._handle, maps), dev)
+            else:
+                ws = _lib.workspace(lib.eyoc_model_workspace_bytes_rows(self._handle, maps, rows.numel()), dev)
 
             def run():
+                if rows is not None:
+                    _lib.check(lib.eyoc_model_forward_rows(_lib.ctx(dev.index), self._handle, maps, _lib.ptr(x.F), _lib.ptr(rows),
+                                                           rows.numel(), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                               "eyoc_model_forward_rows")
+                    return
                 _lib.check(lib.eyoc_model_forward(_lib.ctx(dev.index), self._handle, maps, _lib.ptr(x.F), _lib.ptr(out),
                                                   _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "eyoc_model_forward")
             run()
@@ -358,6 +374,8 @@ class ResUNet2(nn.Module):
                         run()
                     finally:
                         lib.eyoc_model_set_math(self._handle, -1)
+        if rows is not None:
+            return out
         return SparseTensor(out, coordinate_map_key=x.coordinate_map_key, coordinate_manager=cm)
 
     def check_range(self):

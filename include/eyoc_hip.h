@@ -418,8 +418,29 @@ size_t eyoc_model_workspace_bytes(const eyoc_model* model, const eyoc_maps* maps
 int eyoc_model_forward(eyoc_ctx* ctx, const eyoc_model* model, const eyoc_maps* maps,
                        const float* feats_dev, float* out_dev, void* workspace_dev,
                        size_t workspace_bytes, void* stream);
+/* The forward for a caller that reads a LIST of output rows (additive to EYOC_VERSION 111).  The reference draws its 5000 matching
+ * rows per cloud by index only, after the forward (scripts/test_kitti.py:141-160: the two forwards, then random_sample) - the sample
+ * never depends on the features, so a caller knows it before the forward starts.  rows_dev: int64 [n_rows] row numbers in the caller's
+ * order, each in [0, N1) (a number outside is clamped into the range; duplicates are allowed and computed twice); out_dev f32
+ * [n_rows, out_channels]: row i is, BIT FOR BIT, row rows_dev[i] of what eyoc_model_forward writes for the same inputs - range guard
+ * included: a split16 overflow upstream or in a listed row raises the guard's words and gives NaN rows (an overflow confined to rows
+ * of the last 3^3 layer that nobody listed is not seen: those values are not computed).
+ * Every layer up to the last 3^3 one runs as in eyoc_model_forward.  Where that forward would run the last stride-1 layer on tile
+ * records and the 1x1 tail behind it (split16 arithmetic, Z-ordered maps, a 64-channel layer in front of conv1_tr -> final), only the
+ * listed rows of that layer and of the tail are computed; in every other case the full forward runs into the workspace and its rows
+ * are copied out.  eyoc_model_sampled_tail(ctx, 0) forces the second form (default 1; other values only query; returns the previous
+ * state; per ctx).  n_rows == 0 launches nothing.  Timing: the three layers' time is booked on the first, as the fused tail's is;
+ * eyoc_model_layer_work reports, after such a forward, for those three layers what it multiplied (below). */
+size_t eyoc_model_workspace_bytes_rows(const eyoc_model* model, const eyoc_maps* maps, int n_rows);
+int eyoc_model_forward_rows(eyoc_ctx* ctx, const eyoc_model* model, const eyoc_maps* maps, const float* feats_dev,
+                            const int64_t* rows_dev, int n_rows, float* out_dev, void* workspace_dev, size_t workspace_bytes,
+                            void* stream);
+int eyoc_model_sampled_tail(eyoc_ctx* ctx, int on);
 /* per-layer algorithmic work of the last forward geometry (SURVEY.md 8d formulas); arrays of
  * eyoc_model_num_layers() entries, any may be NULL */
+/* When the handle's most recent forward was an eyoc_model_forward_rows that computed listed rows only, the entries of the last 3^3
+ * layer and of the two 1x1 layers describe THAT forward: the (row, offset) pairs its kernel multiplied (counted on the device) and
+ * n_rows rows; flop and bytes by the same formulas.  After any other forward: the geometry's full work. */
 int eyoc_model_num_layers(const eyoc_model* model);
 int eyoc_model_layer_work(eyoc_ctx* ctx, const eyoc_model* model, const eyoc_maps* maps, void* stream,
                           const char** names, int64_t* pairs, double* flops, double* gather_bytes,
@@ -486,7 +507,8 @@ int eyoc_knn1(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c, cons
  * scripts/test_kitti.py:30-35,159-160 and of Matcher.match_pair (scripts/SC2_PCR/SC2_PCR.py:291-294).
  * With G_dev != NULL (f32 [n,c]) the gathered row is blended and re-normalised,
  * out[i,:] = (F[sel[i],:] + beta * G[i,:]) / |.|_2 : the synthetic benchmark's descriptor mode (random-init
- * weights carry no geometric signal; G plants it at a stated inlier ratio).  c: power of two in [4,256]. */
+ * weights carry no geometric signal; G plants it at a stated inlier ratio).  c: power of two in [4,256].
+ * sel_dev == NULL: sel[i] = i (rows that are already the sample - eyoc_model_forward_rows' output -, blended in place of a gather). */
 int eyoc_gather_rows(eyoc_ctx* ctx, const float* F_dev, int ld, int c, const int64_t* sel_dev, int n,
                      const float* G_dev, float beta, float* out_dev, void* stream);
 
