@@ -13,7 +13,7 @@ from .model import (load_model, ResUNet2, ResUNetBN2, ResUNetBN2B, ResUNetBN2C, 
                     ResUNetBN2E, ResUNetFatBN, MODELS)
 from .eval import find_nn_gpu, pdist, find_corr, find_correspondences, random_sample, knn1_segmented  # noqa: F401
 from .transform_estimation import (est_quad_linear_robust, estimate_transform, pose_estimation,  # noqa: F401
-                                   rigid_transform_3d, transform, integrate_trans)
+                                   rigid_transform_3d, transform, integrate_trans, est_quad_linear_robust_batched)
 from .registration import (Matcher, registration_ransac_based_on_feature_matching,  # noqa: F401
                            ransac_from_correspondences, ransac_batched_from_correspondences, RegistrationResult)
 from .metrics import registration_errors, apply_transform, evaluate_nn_dist  # noqa: F401
@@ -21,4 +21,5 @@ from .voxelize import sparse_quantize, sparse_quantize_batch, voxelize, extract_
 from .labels import (knn2_segmented, lowe_topk, spherical_filter, similarity_filter, load_dist_sim_map,  # noqa: F401
                      match_and_filter_corr, correspondences_under_pose, lowe_topk_segmented, pair_filter_batched, posed_nn_grid,
                      match_and_filter_corr_batched, correspondences_under_pose_batched, corr_through_registration, label_step)
+from .validate import (valid_metrics_batched, decode_valid_records, ValidMeters, ValidStep, valid_step, valid_epoch)  # noqa: F401,E402
 from .autograd import sparse_conv, contrastive_hardest_negative_loss  # noqa: F401,E402

@@ -72,6 +72,11 @@ class SimSlice(C.Structure):
     _fields_ = [("table_offset", C.c_int64), ("xlim", C.c_int32), ("ylim", C.c_int32), ("grid1", C.c_float), ("reserved", C.c_int32)]
 
 
+class ValidRecord(C.Structure):
+    _fields_ = [("loss", C.c_double), ("hit_ratio", C.c_double), ("rte", C.c_double), ("rre", C.c_double), ("cos_rre", C.c_double),
+                ("hits", C.c_int32), ("n_corr", C.c_int32), ("n_points", C.c_int32), ("status", C.c_uint32), ("reserved", C.c_double)]
+
+
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 # name -> (restype, argtypes); every symbol include/eyoc_hip.h declares
 PROTOTYPES = {
@@ -182,6 +187,9 @@ PROTOTYPES = {
     "eyoc_pdist": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "eyoc_kabsch_batched": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "eyoc_irls_quad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "eyoc_irls_quad_batched": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _vp, _vp]),
+    "eyoc_valid_metrics_batched": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, C.POINTER(C.c_int32), _i, _vp, _vp,
+                                        C.c_double, C.c_double, _vp, _vp]),
     "eyoc_ransac": (_i, [_vp, _vp, _vp, _vp, _i, C.POINTER(RansacParams), _vp, _vp]),
     "eyoc_maps_select_orders": (_i, [_vp, _i, _i]),
     "eyoc_ransac_select_pruning": (_i, [_vp, _i]),

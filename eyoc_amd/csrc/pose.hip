@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void kabsch_wave_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
-// IRLS (util/transform_estimation.py:89-116): one workgroup, all iterations inside the kernel.
+// IRLS (util/transform_estimation.py:89-116): one workgroup per pair, all iterations inside the kernel.
 // Unknown x = (rx, ry, rz, tx, ty, tz); per point the three residual rows are
 //   [0, z, -y, 1, 0, 0], [-z, 0, x, 0, 1, 0], [y, -x, 0, 0, 0, 1]  (each scaled by the weight),
 // so the 6x6 normal matrix and right-hand side are 16 weighted moments of the current points.
@@ -145,9 +145,14 @@ __device__ inline bool solve6(double M[6][7]) {  // Gauss-Jordan with partial pi
   return true;
 }
 
-__global__ __launch_bounds__(IRLS_THREADS) void irls_kernel(const float* __restrict__ p0, const float* __restrict__ p1,
-                                                            const float* __restrict__ w0, int n, int iters,
-                                                            float* __restrict__ Tout) {
+// The solver of ONE pair by the calling workgroup: irls_kernel (one pair per launch) and irls_batched_kernel (one pair per workgroup)
+// are this body, so a pair's pose does not depend on which of them ran it.  GATHER: row i pairs with p1[idx1[i]] (indices checked by
+// the caller), else with p1[i].  The points are re-read every iteration - L2-resident after the first sweep - and never kept in
+// registers: 1024 threads leave 128 VGPRs per lane, and the 16 fp64 sums with the fp64 pose take half of them.
+template <bool GATHER>
+__device__ __forceinline__ void irls_body(const float* __restrict__ p0, const float* __restrict__ p1,
+                                          const long long* __restrict__ idx1, const float* __restrict__ w0, int n, int iters,
+                                          float* __restrict__ Tout) {
   __shared__ double red[(IRLS_THREADS / 64) * 16];
   __shared__ double Tsh[12];  // current accumulated [R | t], row-major 3x4
   if (threadIdx.x < 12) Tsh[threadIdx.x] = (threadIdx.x % 5 == 0) ? 1.0 : 0.0;  // entries 0,5,10 = identity
@@ -169,7 +174,8 @@ __global__ __launch_bounds__(IRLS_THREADS) void irls_kernel(const float* __restr
       const double x = T[0] * ox + T[1] * oy + T[2] * oz + T[3];
       const double y = T[4] * ox + T[5] * oy + T[6] * oz + T[7];
       const double z = T[8] * ox + T[9] * oy + T[10] * oz + T[11];
-      const double rx = p1[3 * i] - x, ry = p1[3 * i + 1] - y, rz = p1[3 * i + 2] - z;
+      const float* q = p1 + 3 * (GATHER ? (size_t)idx1[i] : (size_t)i);
+      const double rx = q[0] - x, ry = q[1] - y, rz = q[2] - z;
       double w;
       if (it == 0) w = w0 ? (double)w0[i] : 1.0;
       else w = par_w / (sqrt(rx * rx + ry * ry + rz * rz) + par_w);
@@ -216,6 +222,46 @@ __global__ __launch_bounds__(IRLS_THREADS) void irls_kernel(const float* __restr
   }
 }
 
+__global__ __launch_bounds__(IRLS_THREADS) void irls_kernel(const float* __restrict__ p0, const float* __restrict__ p1,
+                                                            const float* __restrict__ w0, int n, int iters,
+                                                            float* __restrict__ Tout) {
+  irls_body<false>(p0, p1, nullptr, w0, n, iters, Tout);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same solver for every pair of a batch (eyoc_irls_quad_batched): workgroup b of a launch solves pair b of the chunk, IRLS_CHUNK
+// pairs per launch.  The correspondence (p0[i], p1[idx1[i]]) is gathered inside the sweep, never materialised.
+// ------------------------------------------------------------------------------------------------
+constexpr int IRLS_CHUNK = 64;
+struct IrlsSegs {
+  int n_seg;
+  int r0[IRLS_CHUNK], n0[IRLS_CHUNK], r1[IRLS_CHUNK], n1[IRLS_CHUNK];   // first row and row count of the pair's p0 / p1 segment
+};
+
+template <bool GATHER>
+__global__ __launch_bounds__(IRLS_THREADS) void irls_batched_kernel(IrlsSegs s, const float* __restrict__ p0, const float* __restrict__ p1,
+                                                                    const long long* __restrict__ idx1, const float* __restrict__ w0,
+                                                                    int iters, float* __restrict__ Tout) {
+  const int b = blockIdx.x;
+  const int n = s.n0[b], n1 = s.n1[b];
+  const size_t r0 = (size_t)s.r0[b];
+  float* T = Tout + 16 * (size_t)b;
+  // an empty pair, or one with an index outside its p1 segment: 16 NaNs.  The indices are checked in a sweep of their own BEFORE the
+  // first point is read, so a bad index never becomes an address; the decision is uniform over the workgroup.
+  int bad = n == 0;
+  if (GATHER) {
+    for (int i = threadIdx.x; i < n; i += IRLS_THREADS) {
+      const long long j = idx1[r0 + i];
+      bad |= (j < 0 || j >= (long long)n1);
+    }
+  }
+  if (__syncthreads_or(bad)) {
+    if (threadIdx.x < 16) T[threadIdx.x] = __builtin_nanf("");
+    return;
+  }
+  irls_body<GATHER>(p0 + 3 * r0, p1 + 3 * (size_t)s.r1[b], GATHER ? idx1 + r0 : nullptr, w0 ? w0 + r0 : nullptr, n, iters, T);
+}
+
 }  // namespace
 
 extern "C" {
@@ -240,6 +286,39 @@ int eyoc_irls_quad(eyoc_ctx* ctx, const float* p0_dev, const float* p1_dev, cons
   EYOC_REQUIRE(n >= 1 && iters >= 0, EYOC_ERR_INVALID, "eyoc_irls_quad: n %d iters %d", n, iters);
   hipLaunchKernelGGL(irls_kernel, dim3(1), dim3(IRLS_THREADS), 0, (hipStream_t)stream, p0_dev, p1_dev, w_dev, n, iters,
                      T_dev);
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
+int eyoc_irls_quad_batched(eyoc_ctx* ctx, const float* p0_dev, const float* p1_dev, const int64_t* idx1_dev, const float* w_dev,
+                           const int32_t* seg0_host, const int32_t* seg1_host, int nseg, int iters, float* T_dev, void* stream) {
+  EYOC_REQUIRE(ctx && seg0_host && seg1_host && T_dev, EYOC_ERR_INVALID, "eyoc_irls_quad_batched: NULL argument");
+  EYOC_REQUIRE(nseg >= 1 && nseg <= 1024, EYOC_ERR_INVALID, "eyoc_irls_quad_batched: nseg = %d is outside [1, 1024]", nseg);
+  EYOC_REQUIRE(iters >= 0, EYOC_ERR_INVALID, "eyoc_irls_quad_batched: iters %d", iters);
+  EYOC_REQUIRE(seg0_host[0] == 0 && seg1_host[0] == 0, EYOC_ERR_INVALID, "eyoc_irls_quad_batched: segments must start at 0");
+  for (int b = 0; b < nseg; ++b) {
+    EYOC_REQUIRE(seg0_host[b + 1] >= seg0_host[b] && seg1_host[b + 1] >= seg1_host[b], EYOC_ERR_INVALID,
+                 "eyoc_irls_quad_batched: segment offsets must not decrease (pair %d)", b);
+    EYOC_REQUIRE(idx1_dev || seg1_host[b + 1] == seg0_host[b + 1], EYOC_ERR_INVALID,
+                 "eyoc_irls_quad_batched: without idx1 row i pairs with row i, and the segments of pair %d differ", b);
+  }
+  if (seg0_host[nseg] > 0) EYOC_REQUIRE(p0_dev && p1_dev, EYOC_ERR_INVALID, "eyoc_irls_quad_batched: NULL argument");
+  hipStream_t st = (hipStream_t)stream;
+  IrlsSegs s;
+  for (int b0 = 0; b0 < nseg; b0 += IRLS_CHUNK) {
+    s.n_seg = nseg - b0 < IRLS_CHUNK ? nseg - b0 : IRLS_CHUNK;
+    for (int b = 0; b < IRLS_CHUNK; ++b) {
+      const int k = b < s.n_seg ? b0 + b : -1;
+      s.r0[b] = k < 0 ? 0 : seg0_host[k]; s.n0[b] = k < 0 ? 0 : seg0_host[k + 1] - seg0_host[k];
+      s.r1[b] = k < 0 ? 0 : seg1_host[k]; s.n1[b] = k < 0 ? 0 : seg1_host[k + 1] - seg1_host[k];
+    }
+    if (idx1_dev)
+      hipLaunchKernelGGL(irls_batched_kernel<true>, dim3(s.n_seg), dim3(IRLS_THREADS), 0, st, s, p0_dev, p1_dev,
+                         (const long long*)idx1_dev, w_dev, iters, T_dev + 16 * (size_t)b0);
+    else
+      hipLaunchKernelGGL(irls_batched_kernel<false>, dim3(s.n_seg), dim3(IRLS_THREADS), 0, st, s, p0_dev, p1_dev,
+                         (const long long*)nullptr, w_dev, iters, T_dev + 16 * (size_t)b0);
+  }
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
 }

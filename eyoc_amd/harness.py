@@ -694,6 +694,13 @@ class RegistrationPipeline:
             return step.result            # the caller reads back later - and calls model.check_range() then
         return self._read_back(step, seed, maps)
 
+    def validate(self, batch: DeviceBatch, pcd0=None, hit_ratio_thresh=0.1, maps=None):
+        """The validation step of the reference (lib/trainer.py:340-378) for all pairs of ``batch``: sampled forward, feature NN, the
+        batched IRLS pose and the loop's metrics, one read-back -> ``validate.ValidStep`` (``eyoc_amd.validate.valid_step`` documents the
+        arguments and the two deviations: seeded draws, ``pcd0=None``).  ``_step``'s registration routes are not involved."""
+        from .validate import valid_step
+        return valid_step(self, batch, pcd0, hit_ratio_thresh, maps)
+
     def _read_back(self, step, seed, maps, status=0):
         """``register``: the records of ``step`` on the host, decoded (``status`` or-ed in) - or, after a split16 overflow in automatic
         mode, those of the step run again: that step alone in fp32 (``fp32_retry_per_step``), or with the model switched to fp32 MFMAs for good."""

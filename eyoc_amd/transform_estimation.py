@@ -8,6 +8,8 @@ no host hop).
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
 
 from . import _lib
@@ -32,6 +34,44 @@ def est_quad_linear_robust(pts0, pts1, weight=None, iters=20):
 
 
 estimate_transform = est_quad_linear_robust
+
+
+def _segments(seg, rows, who):
+    """A segment list -> (the C array the library takes, the ints); it must describe ``rows`` rows."""
+    seg = [int(v) for v in seg]
+    if len(seg) < 2 or seg[0] != 0 or seg[-1] != rows:
+        raise ValueError(f"{who}: segments {seg[:1]}..{seg[-1:]} do not describe {rows} rows")
+    return (C.c_int32 * len(seg))(*seg), seg
+
+
+def est_quad_linear_robust_batched(P0, P1, seg0, seg1=None, idx1=None, weight=None, iters=20):
+    """``est_quad_linear_robust`` for every pair of a batch in one call (``eyoc_irls_quad_batched``: one workgroup per pair, one launch
+    per 64 pairs, nothing read back) -> ``T f32 [P, 4, 4]`` on the device.
+
+    Pair ``b`` owns rows ``seg0[b]:seg0[b+1]`` of ``P0 [*, 3]`` (and of ``weight [*]``) and rows ``seg1[b]:seg1[b+1]`` of ``P1 [*, 3]``
+    (``seg1=None``: the same segments).  ``idx1 int64 [len(P0)]`` - local to the pair's ``P1`` segment, what ``knn1_segmented`` returns -
+    makes row ``i`` of a pair the correspondence ``(P0[i], P1[idx1[i]])``; without it row ``i`` pairs with row ``i``.  A pair's pose has
+    the bytes ``est_quad_linear_robust`` gives for its gathered arrays alone; an empty pair, or one with an index outside its segment,
+    gets a NaN pose."""
+    p0 = _cuda_f32(P0).reshape(-1, 3)
+    p1 = _cuda_f32(P1, p0.device).reshape(-1, 3)
+    s0, seg0 = _segments(seg0, p0.shape[0], "est_quad_linear_robust_batched (seg0)")
+    s1, seg1 = _segments(seg0 if seg1 is None else seg1, p1.shape[0], "est_quad_linear_robust_batched (seg1)")
+    if len(seg1) != len(seg0):
+        raise ValueError("seg0 and seg1 must list the same number of pairs")
+    if idx1 is not None:
+        idx1 = idx1.to(p0.device, torch.int64).contiguous().reshape(-1)
+        if idx1.numel() != p0.shape[0]:
+            raise ValueError("idx1 must have one entry per row of P0")
+    w = None if weight is None else _cuda_f32(weight, p0.device).reshape(-1)
+    if w is not None and w.numel() != p0.shape[0]:
+        raise ValueError("weight must have one entry per row of P0")
+    P = len(seg0) - 1
+    T = torch.empty((P, 4, 4), dtype=torch.float32, device=p0.device)
+    with _lib.on_device(p0.device):
+        _lib.check(_lib.load().eyoc_irls_quad_batched(_lib.ctx(p0.device.index), _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(idx1), _lib.ptr(w),
+                                                      s0, s1, P, int(iters), _lib.ptr(T), _lib.stream_ptr()), "eyoc_irls_quad_batched")
+    return T
 
 
 def rigid_transform_3d(A, B, weights=None, weight_threshold=0):

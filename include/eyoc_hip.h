@@ -594,6 +594,49 @@ int eyoc_kabsch_batched(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, c
 int eyoc_irls_quad(eyoc_ctx* ctx, const float* p0_dev, const float* p1_dev, const float* w_dev, int n,
                    int iters, float* T_dev, void* stream);
 
+/* The validation step of the reference (lib/trainer.py:321-403, `_valid_epoch`) behind the neighbour search, for every pair of a batch:
+ * the IRLS pose and the loop's metrics.  Added after 111 without a bump, additive only.  Two launches per 64 pairs in all, no host
+ * synchronisation, nothing read back.
+ *
+ * eyoc_irls_quad_batched: eyoc_irls_quad for nseg <= 1024 pairs, one workgroup per pair, 64 pairs per launch.  Pair b owns rows
+ * [seg0[b], seg0[b+1]) of p0 f32 [*,3] and of w f32 [*] (or NULL) and rows [seg1[b], seg1[b+1]) of p1 f32 [*,3] (HOST arrays of nseg + 1
+ * ints starting at 0, the convention of eyoc_pair_filter_batched).  idx1 int64 [seg0[nseg]] is LOCAL to the pair's p1 segment - what
+ * eyoc_knn1 writes -: row i of the pair is the correspondence (p0[i], p1[idx1[i]]), the xyz1[inds1[nn_inds]] of find_corr
+ * (lib/trainer.py:405-419), gathered inside the sweep and never materialised.  idx1 == NULL: row i pairs with row i, and the two
+ * segment arrays must agree.  T f32 [nseg][16].  Pair b's 64 bytes are exactly what eyoc_irls_quad writes for that pair's gathered
+ * arrays alone (the two kernels are one body), whatever the other segments hold and wherever the pair stands in the batch.  An empty
+ * segment gets 16 NaNs.  The indices of a pair are checked before any of its points is read: one outside its segment never becomes an
+ * address, the pair gets 16 NaNs, the other pairs are untouched.  nseg outside [1, 1024], decreasing offsets, idx1 == NULL with
+ * differing segments: EYOC_ERR_INVALID. */
+int eyoc_irls_quad_batched(eyoc_ctx* ctx, const float* p0_dev, const float* p1_dev, const int64_t* idx1_dev, const float* w_dev,
+                           const int32_t* seg0_host, const int32_t* seg1_host, int nseg, int iters, float* T_dev, void* stream);
+
+/* eyoc_valid_metrics_batched: one record per pair from the correspondence arrays above, the pair's FULL source cloud - rows [segx[b],
+ * segx[b+1]) of x0 f32 [*,3] -, T_est f32 [nseg][16] on the device (read where eyoc_irls_quad_batched wrote it) and T_gt f32 [nseg][16].
+ * fp64 arithmetic on the fp32 inputs without contraction; sums reduced lane -> wave -> workgroup in a fixed order, so a pair's record is
+ * byte-identical alone, in a batch and from run to run.
+ *   loss      corr_dist (lib/metrics.py:13-19, weight None): the mean over the full cloud of min(|T_est x - T_gt x|, max_dist)
+ *   hits      correspondences with sqrt(|R_gt p0 + t_gt - p1[idx1]|^2 + 1e-6) < hit_thresh (lib/trainer.py:421-424); hit_ratio = hits / n_corr
+ *   rte       |t_est - t_gt|
+ *   cos_rre   (trace(R_est^T R_gt) - 1) / 2;  rre = acos(cos_rre), NaN when the cosine leaves [-1, 1]: lib/trainer.py:367-370 does not
+ *             clamp and skips the NaN (scripts/test_kitti.py's clamp is NOT applied here)
+ * status: EMPTY - no correspondences: hit_ratio and loss are NaN.  BAD_INDEX - an index outside the pair's p1 segment (clamped into it
+ * before the load): hit_ratio is NaN, hits 0.  POSE_NONFINITE - T_est holds a non-finite entry: loss, rte and rre are NaN, hits are still
+ * counted.  An empty x0 segment gives loss NaN and nothing else. */
+#define EYOC_VALID_EMPTY 1u
+#define EYOC_VALID_BAD_INDEX 2u
+#define EYOC_VALID_POSE_NONFINITE 4u
+typedef struct {
+  double loss, hit_ratio, rte, rre, cos_rre;
+  int32_t hits, n_corr, n_points;
+  uint32_t status;
+  double reserved;
+} eyoc_valid_record;         /* 64 bytes */
+int eyoc_valid_metrics_batched(eyoc_ctx* ctx, const float* p0_dev, const float* p1_dev, const int64_t* idx1_dev,
+                               const int32_t* seg0_host, const int32_t* seg1_host, const float* x0_dev, const int32_t* segx_host, int nseg,
+                               const float* T_est_dev, const float* T_gt_dev, double hit_thresh, double max_dist,
+                               eyoc_valid_record* records_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * training-mode support (lib/trainer.py:1655-1676 back-propagates through the network in train mode)
  * --------------------------------------------------------------------------------------------- */
