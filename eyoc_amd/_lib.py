@@ -218,6 +218,11 @@ PROTOTYPES = {
     "eyoc_posed_nn_grid_workspace_bytes": (_sz, [_i, _i, _i]),
     "eyoc_posed_nn_grid": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _vp, C.c_float, _vp, C.POINTER(C.c_int32), _vp,
                                 _vp, _vp, _vp, _sz, _vp]),
+    "eyoc_radius_matches_workspace_bytes": (_sz, [_i, _i, _i]),
+    "eyoc_radius_matches_count": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _vp, C.c_double, _i, _vp, _vp,
+                                       _vp, _sz, _vp]),
+    "eyoc_radius_matches_fill": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _vp, C.c_double, _i, _vp, _vp,
+                                      C.c_int64, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

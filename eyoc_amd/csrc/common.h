@@ -232,6 +232,8 @@ int maps_ensure_table(eyoc_maps* maps, int kind, int level, hipStream_t st);
 size_t sort_rows64_tmp_bytes(int n);
 int sort_rows_by_key64(void* tmp, size_t tmp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out, const int* vals_in,
                        int* vals_out, int n, int bits, hipStream_t st);
+size_t scan_offsets64_tmp_bytes(int n);
+int scan_offsets64(void* tmp, size_t tmp_bytes, long long* data, int n, hipStream_t st);
 size_t sort_rows_tmp_bytes(int n, int bits);
 int sort_rows_by_key(void* tmp, size_t tmp_bytes, const unsigned int* keys_in, unsigned int* keys_out, const int* vals_in,
                      int* vals_out, int n, int bits, hipStream_t st);

@@ -1,4 +1,4 @@
-// The cell grid over 3-D points, and its two users (include/eyoc_hip.h, "ICP refinement" and eyoc_posed_nn_grid).
+// The cell grid over 3-D points, and its three users (include/eyoc_hip.h, "ICP refinement", eyoc_posed_nn_grid and eyoc_radius_matches_*).
 //
 // 1. THE GRID: a batch of target clouds as cells of one edge, searched by queries that look at the 27 cells around their own.
 //   target_key   cell key of one target row (pair << 54 | biased cell); tells the caller when the row is non-finite or outside the key range
@@ -8,6 +8,7 @@
 //   probe_cells  the search itself: plane by plane, the 9 first probes of a plane issued together, a bounded linear probe, a run's points
 //                four at a time; the caller's functor sees every candidate once, in an order that only depends on the grid
 //   GridWorkspace / carve_grid / make_segs / build_grid: the arrays, the chunk's segments and the launches between a user's key kernel and its search
+//                (carve_grid's `tables` > 1 + chunk_grid: one table per chunk, for the user whose grids outlive their chunk)
 // 2. ICP (eyoc_icp_batched, eyoc_icp_correspondences).  One call = one grid build + (max_iteration + 1) evaluations, nothing read back in between:
 //   k_icp_init   one thread per pair: T = init, BAD_INIT / empty-segment (FEW) pairs are finished here
 //   k_icp_keys   one thread per target / source row: target_key, RANGE for non-finite points and target cells outside the key range; the
@@ -19,6 +20,8 @@
 // The evaluation's arithmetic is the contract's expression evaluated in fp64 without contraction (no FMA), so d2 does not depend on
 // how the compiler schedules it.
 // 3. POSED NEAREST NEIGHBOUR (eyoc_posed_nn_grid): k_pnn_init, k_pnn_keys, build_grid, k_pnn_search - fp32 arithmetic, see its section.
+// 4. RADIUS MATCHES (eyoc_radius_matches_count / _fill): EVERY target inside the gate, fp64; a count pass, a scan and a fill pass over grids
+//    that stay in the workspace between the two calls, see its section.
 // The users differ in what they do with a candidate (the functor handed to probe_cells), in the query half of their key kernel and in
 // their own arrays; everything else about the grid exists once, here.
 #include <cmath>
@@ -168,6 +171,12 @@ unsigned int table_capacity(int total_tgt) {
   return cap;
 }
 
+// slots for `tables` tables that hold total_tgt rows between them.  One table is sized exactly; of several, each has
+// table_capacity(its own rows) slots, which is 64 or less than 4 x its rows: 64 per table + 4 per row hold them all
+size_t table_slots(int total_tgt, int tables) {
+  return tables <= 1 ? (size_t)table_capacity(total_tgt) : (size_t)64 * tables + (size_t)4 * total_tgt;
+}
+
 // what the grid and its two sorts need; a user carves its own arrays behind it
 struct GridWorkspace {
   unsigned long long *tkey, *tkey_sorted, *qkey, *qkey_sorted;
@@ -179,14 +188,16 @@ struct GridWorkspace {
   unsigned int cap;
 };
 
-// the layout for the LARGEST chunk a call with these totals can hold (every chunk reuses it)
-void carve_grid(Carver& c, int total_q, int total_tgt, GridWorkspace* w) {
+// the layout for the LARGEST chunk a call with these totals can hold.  tables = 1: every chunk reuses it.  tables > 1 (a user whose
+// grids outlive their chunk): the row arrays are the call's, a chunk uses its own rows of them, and `cells` has room for one table per
+// chunk behind one another (chunk_grid)
+void carve_grid(Carver& c, int total_q, int total_tgt, int tables, GridWorkspace* w) {
   w->cap = table_capacity(total_tgt);
   w->tkey = c.take<unsigned long long>(total_tgt);
   w->tkey_sorted = c.take<unsigned long long>(total_tgt);
   w->qkey = c.take<unsigned long long>(total_q);
   w->qkey_sorted = c.take<unsigned long long>(total_q);
-  w->cells = c.take<IcpCell>(w->cap);
+  w->cells = c.take<IcpCell>(table_slots(total_tgt, tables));
   w->trow = c.take<int>(total_tgt);
   w->trow_sorted = c.take<int>(total_tgt);
   w->qrow = c.take<int>(total_q);
@@ -431,7 +442,7 @@ struct IcpWorkspace {
 size_t carve(void* base, size_t bytes, int n_pairs, int total_src, int total_tgt, IcpWorkspace* w) {
   Carver c(base, bytes);
   const int chunk = n_pairs < ICP_CHUNK ? n_pairs : ICP_CHUNK;
-  carve_grid(c, total_src, total_tgt, &w->grid);
+  carve_grid(c, total_src, total_tgt, 1, &w->grid);
   w->done = c.take<int>(chunk > 0 ? chunk : 1);
   w->partial = c.take<double>(((size_t)cdiv(total_src, ICP_BLOCK) + chunk + 1) * ICP_SUMS);
   return align_up(c.off);
@@ -601,7 +612,7 @@ struct PnnWorkspace {
 
 size_t pnn_carve(void* base, size_t bytes, int total_q, int total_tgt, PnnWorkspace* w) {
   Carver c(base, bytes);
-  carve_grid(c, total_q, total_tgt, &w->grid);
+  carve_grid(c, total_q, total_tgt, 1, &w->grid);
   w->qpts = c.take<float4>(total_q);
   return align_up(c.off);
 }
@@ -630,6 +641,258 @@ int pnn_chunk(const float* src, const float* tgt, const int32_t* seg_src, const 
                      (long long*)idx_out, d2_out);
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// 4. Radius matches (eyoc_radius_matches_count / eyoc_radius_matches_fill): util/pointcloud.py:53-66 for a batch of pairs - for every
+// source row under the pair's pose EVERY target row with d2 < radius^2, as (i, j), ascending by (d2, j) inside a source row, cut to the
+// first K.  The third user of the grid of section 1; fp64 like ICP, the posed point evaluated as eyoc_posed_nn_grid writes it.
+//   k_rm_init    one thread per pair: BAD_INIT for a non-finite pose
+//   k_rm_keys    targets: target_key; sources: the posed point in fp64, stored as three doubles (the count, the fill and the key see the
+//                same point), its cell key, the row's count preset to 0.  RANGE is set here
+//   build_grid
+//   k_rm_count   256 cell-sorted source rows of one pair per workgroup, lane = row: probe_cells, count d2 < r2, min(count, K) at the
+//                row's ORIGINAL index
+//   exclusive 64-bit scan over all source rows of the call (rocPRIM, integers): offsets, offsets[total_src] = total
+//   k_rm_fill    the same traversal; the lane owns pairs_out / d2_out [offsets[i], offsets[i + 1]) and inserts every match at its
+//                place by (d2, j) - d2_out is the key's storage, nothing of size `total` lives in the workspace
+// The output length depends on the data, so the host reads the total between the two calls and every chunk's grid has to survive
+// until the fill: the row arrays of the workspace are the call's totals, a chunk uses its own rows, and the tables of the chunks sit
+// behind one another (chunk_grid).
+//
+// Cell edge.  (i, j) is a match iff d2 < r2, r2 = fl(r r) <= r^2 (1 + u), u = 2^-53, everything fp64.  The posed point p is a stored
+// fp64 value and q an fp32 one, exact in fp64; per axis dxf = fl(p - q) = (p - q)(1 + e), |e| <= u, fl(dxf dxf) >= dxf^2 (1 - u), and
+// the two additions of non-negative terms lose at most a factor (1 - u) each: d2 >= dxf^2 (1 - u)^3 (a square that underflows belongs
+// to a |p - q| < 2^-500: inside any cell edge that passes the r2 > 0 a match needs).  A match therefore has |p - q| <= |dxf| / (1 - u)
+// < r (1 + u)^0.5 (1 - u)^-2.5 < r (1 + 4 u) on every axis.  The cells are floor(fl(v / edge)): with |cell| < 2^17 each rounded quotient
+// is within 2^17 * 2^-53 = 2^-36 of the true one, so the two quotients differ by at most |p - q| / edge + 2^-35, and two floors differ by
+// at most 1 when that is <= 1.  edge = fl(r (1 + 2^-20)) >= r (1 + 2^-20)(1 - u) leaves |p - q| / edge < (1 + 4 u) / ((1 + 2^-20)(1 - u))
+// < 1 - 2^-21, and 2^-21 > 2^-35: every match lies in the 27 cells around the source's, with no exception at a cell face (the ICP grid,
+// edge = r, has one).  So the matches found are exactly those of the n0 x n1 sweep.
+constexpr double RM_EDGE_MARGIN = 1.0 + 1.0 / 1048576.0;
+
+__global__ void k_rm_init(int n_pairs, const double* __restrict__ T, int* __restrict__ status) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n_pairs) return;
+  bool finite = true;
+  if (T)
+    for (int k = 0; k < 16; ++k) finite = finite && isfinite(T[(size_t)b * 16 + k]);
+  status[b] = finite ? 0 : EYOC_ICP_BAD_INIT;
+}
+
+__global__ __launch_bounds__(ICP_BLOCK) void k_rm_keys(IcpSegs s, const float* __restrict__ src, const float* __restrict__ tgt,
+                                                       const double* __restrict__ Ts, double edge, int* __restrict__ status,
+                                                       unsigned long long* __restrict__ tkey, int* __restrict__ trow,
+                                                       unsigned long long* __restrict__ qkey, int* __restrict__ qrow, double* __restrict__ qpts,
+                                                       long long* __restrict__ counts) {
+#pragma clang fp contract(off)
+  const int n_tgt = s.tgt[s.n_pairs], n_q = s.src[s.n_pairs];
+  int i = blockIdx.x * ICP_BLOCK + threadIdx.x;
+  if (i < n_tgt) {
+    const int b = pair_of(s.tgt, s.n_pairs, i);
+    bool ok;
+    trow[i] = i;
+    tkey[i] = target_key(tgt, i, b, edge, status[b] & EYOC_ICP_BAD_INIT, &ok);
+    if (!ok) atomicOr(&status[b], EYOC_ICP_RANGE);
+    return;
+  }
+  i -= n_tgt;
+  if (i >= n_q) return;
+  const int b = pair_of(s.src, s.n_pairs, i);
+  qrow[i] = i;
+  counts[i] = 0;
+  unsigned long long key = pack_key(b, -COORD_BIAS, -COORD_BIAS, -COORD_BIAS);
+  double p[3] = {0.0, 0.0, 0.0};
+  if (!(status[b] & EYOC_ICP_BAD_INIT)) {
+    const float xf = src[(size_t)i * 3], yf = src[(size_t)i * 3 + 1], zf = src[(size_t)i * 3 + 2];
+    const double x = xf, y = yf, z = zf;
+    bool ok = isfinite(xf) && isfinite(yf) && isfinite(zf);
+    int c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      double t[4];
+#pragma unroll
+      for (int l = 0; l < 4; ++l) t[l] = Ts ? Ts[(size_t)b * 16 + 4 * k + l] : (k == l ? 1.0 : 0.0);     // NULL: the identity
+      p[k] = ((t[0] * x + t[1] * y) + t[2] * z) + t[3];
+      ok = ok && cell_of(p[k], edge, &c[k]);
+    }
+    if (ok) key = pack_key(b, c[0], c[1], c[2]);
+    else atomicOr(&status[b], EYOC_ICP_RANGE);
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) qpts[(size_t)i * 3 + k] = p[k];
+  qkey[i] = key;
+}
+
+// what count and fill share: the workgroup's pair and the lane's source row (sorted by cell), its stored posed point and its cell.
+// false: nothing to do for this lane (a pair with a status, a lane past the pair's rows).  No barrier anywhere in the two kernels.
+__device__ __forceinline__ bool rm_query(const IcpSegs& s, const int* __restrict__ qrow_sorted, const double* __restrict__ qpts, double edge,
+                                         const int* __restrict__ status, int* b, int* qi, double* p, int* c) {
+  *b = pair_of(s.wg, s.n_pairs, blockIdx.x);     // uniform: kernel arguments and the workgroup index
+  if (status[*b]) return false;
+  const int local = (blockIdx.x - s.wg[*b]) * ICP_BLOCK + threadIdx.x;
+  if (local >= s.src[*b + 1] - s.src[*b]) return false;
+  *qi = qrow_sorted[s.src[*b] + local];
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    p[k] = qpts[(size_t)*qi * 3 + k];
+    ok = ok && cell_of(p[k], edge, &c[k]);
+  }
+  return ok;     // (status 0: always)
+}
+
+__global__ __launch_bounds__(ICP_BLOCK) void k_rm_count(IcpSegs s, const int* __restrict__ qrow_sorted, const double* __restrict__ qpts, IcpGrid g,
+                                                        double edge, double r2, int max_per_source, const int* __restrict__ status,
+                                                        long long* __restrict__ counts) {
+#pragma clang fp contract(off)
+  int b, qi, c[3];
+  double p[3];
+  if (!rm_query(s, qrow_sorted, qpts, edge, status, &b, &qi, p, c)) return;
+  int n = 0;     // at most the pair's target rows
+  probe_cells(g, b, c, [&](const float4 q) {
+    const double dx = p[0] - (double)q.x, dy = p[1] - (double)q.y, dz = p[2] - (double)q.z;
+    const double d = (dx * dx + dy * dy) + dz * dz;
+    n += d < r2;
+  });
+  counts[qi] = max_per_source > 0 && n > max_per_source ? max_per_source : n;
+}
+
+// offsets: the scan, counted like `counts` from the chunk's first source row.  The lane's slice is [offsets[qi], offsets[qi + 1]); a
+// slice that does not lie inside [0, total) is not written (a `total` that is not the scan's, a workspace touched since the count).
+__global__ __launch_bounds__(ICP_BLOCK) void k_rm_fill(IcpSegs s, const int* __restrict__ qrow_sorted, const double* __restrict__ qpts, IcpGrid g,
+                                                       double edge, double r2, const int* __restrict__ status,
+                                                       const long long* __restrict__ offsets, long long total, long long* pairs_out,
+                                                       double* d2_out) {
+#pragma clang fp contract(off)
+  int b, qi, c[3];
+  double p[3];
+  if (!rm_query(s, qrow_sorted, qpts, edge, status, &b, &qi, p, c)) return;
+  const long long lo = offsets[qi], hi = offsets[qi + 1];
+  if (lo < 0 || hi <= lo || hi > total) return;
+  const long long len = hi - lo, i_local = qi - s.src[b];
+  long long* const jj = pairs_out + 2 * lo + 1;     // the slice's j column (stride 2)
+  double* const dd = d2_out + lo;
+  for (long long k = 0; k < len; ++k) pairs_out[2 * (lo + k)] = i_local;
+  long long n = 0;
+  probe_cells(g, b, c, [&](const float4 q) {
+    const double dx = p[0] - (double)q.x, dy = p[1] - (double)q.y, dz = p[2] - (double)q.z;
+    const double d = (dx * dx + dy * dy) + dz * dz;
+    if (!(d < r2)) return;
+    const long long j = __float_as_int(q.w);
+    long long pos;
+    if (n < len) pos = n++;
+    else {                              // full (the slice is the first K of the list): the largest leaves if the new match is smaller
+      pos = len - 1;
+      const double dl = dd[pos];
+      if (!(d < dl || (d == dl && j < jj[2 * pos]))) return;
+    }
+    for (; pos > 0; --pos) {            // entries above (d2, j) move up one place
+      const double dp = dd[pos - 1];
+      const long long jp = jj[2 * (pos - 1)];
+      if (dp < d || (dp == d && jp < j)) break;
+      dd[pos] = dp;
+      jj[2 * pos] = jp;
+    }
+    dd[pos] = d;
+    jj[2 * pos] = j;
+  });
+}
+
+struct RmWorkspace {
+  GridWorkspace grid;     // row arrays: the call's totals; cells: every chunk's table, behind one another
+  double* qpts;           // the posed source points, 3 doubles per row
+  void* scan_tmp;
+  size_t scan_bytes;
+};
+
+size_t rm_carve(void* base, size_t bytes, int n_pairs, int total_src, int total_tgt, RmWorkspace* w) {
+  Carver c(base, bytes);
+  carve_grid(c, total_src, total_tgt, cdiv(n_pairs, ICP_CHUNK), &w->grid);
+  w->qpts = c.take<double>((size_t)total_src * 3);
+  w->scan_bytes = scan_offsets64_tmp_bytes(total_src + 1);
+  w->scan_tmp = c.take<char>(w->scan_bytes);
+  return align_up(c.off);
+}
+
+// the grid arrays of one chunk inside a workspace carved for several tables: its own rows of the row arrays (the chunk's first source
+// / target row: so / to), its table `cell0` slots into `cells`, sized for its own targets
+GridWorkspace chunk_grid(const GridWorkspace& w, size_t so, size_t to, size_t cell0, int n_tgt) {
+  GridWorkspace v = w;
+  v.tkey += to; v.tkey_sorted += to; v.trow += to; v.trow_sorted += to; v.pts += to;
+  v.qkey += so; v.qkey_sorted += so; v.qrow += so; v.qrow_sorted += so;
+  v.cells += cell0;
+  v.cap = table_capacity(n_tgt);
+  return v;
+}
+
+// one chunk of <= ICP_CHUNK pairs; every pointer is already that of the chunk's first row / pair, `gw` the chunk's own grid arrays
+int rm_count_chunk(const float* src, const float* tgt, const IcpSegs& s, const double* T, double radius, int max_per_source,
+                   long long* counts, int32_t* status, const GridWorkspace& gw, double* qpts, hipStream_t st) {
+  const int n_src = s.src[s.n_pairs], n_tgt = s.tgt[s.n_pairs], n_wg = s.wg[s.n_pairs];
+  const double edge = radius * RM_EDGE_MARGIN, r2 = radius * radius;
+  hipLaunchKernelGGL(k_rm_init, dim3(cdiv(s.n_pairs, 64)), dim3(64), 0, st, s.n_pairs, T, status);
+  if (n_src + n_tgt > 0)
+    hipLaunchKernelGGL(k_rm_keys, dim3(cdiv((long long)n_src + n_tgt, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, s, src, tgt, T, edge, status, gw.tkey,
+                       gw.trow, gw.qkey, gw.qrow, qpts, counts);
+  if (n_src == 0 || n_tgt == 0) {        // nothing to search: every count is already 0
+    EYOC_CHECK_HIP(hipGetLastError());
+    return EYOC_OK;
+  }
+  IcpGrid g;
+  const int rc = build_grid(s, tgt, status, gw, st, &g);
+  if (rc != EYOC_OK) return rc;
+  hipLaunchKernelGGL(k_rm_count, dim3(n_wg), dim3(ICP_BLOCK), 0, st, s, gw.qrow_sorted, qpts, g, edge, r2, max_per_source, status, counts);
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
+int rm_fill_chunk(const IcpSegs& s, double radius, const long long* offsets, long long total, const int32_t* status, long long* pairs_out,
+                  double* d2_out, const GridWorkspace& gw, const double* qpts, hipStream_t st) {
+  if (s.src[s.n_pairs] == 0 || s.tgt[s.n_pairs] == 0) return EYOC_OK;     // the count built no grid for this chunk
+  const IcpGrid g{gw.cells, gw.cap - 1, gw.pts};
+  hipLaunchKernelGGL(k_rm_fill, dim3(s.wg[s.n_pairs]), dim3(ICP_BLOCK), 0, st, s, gw.qrow_sorted, qpts, g, radius * RM_EDGE_MARGIN, radius * radius,
+                     status, offsets, total, pairs_out, d2_out);
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
+// both entry points: fill = false is the count (total, pairs_out and d2_out unused)
+int rm_run(const char* what, bool fill, eyoc_ctx* ctx, const float* src, const float* tgt, const int32_t* seg_src, const int32_t* seg_tgt, int n_pairs,
+           const double* T, double radius, int max_per_source, int64_t* offsets, int32_t* status, int64_t total, int64_t* pairs_out,
+           double* d2_out, void* ws, size_t ws_bytes, void* stream) {
+  int bad = check_grid_head(what, ctx && seg_src && seg_tgt && offsets && status && ws, n_pairs, ws);
+  if (bad != EYOC_OK) return bad;
+  EYOC_REQUIRE(std::isfinite(radius) && radius > 0.0, EYOC_ERR_INVALID, "%s: radius must be positive and finite", what);
+  EYOC_REQUIRE(max_per_source >= 0, EYOC_ERR_INVALID, "%s: max_per_source = %d is negative (0 = all)", what, max_per_source);
+  bad = check_segments(what, n_pairs, {seg_src, seg_tgt});
+  if (bad != EYOC_OK) return bad;
+  const int total_src = seg_src[n_pairs], total_tgt = seg_tgt[n_pairs];
+  EYOC_REQUIRE((total_src == 0 || src) && (total_tgt == 0 || tgt), EYOC_ERR_INVALID, "%s: NULL cloud", what);
+  if (fill) {
+    EYOC_REQUIRE(total >= 0, EYOC_ERR_INVALID, "%s: total = %lld is negative", what, (long long)total);
+    EYOC_REQUIRE(total == 0 || (pairs_out && d2_out), EYOC_ERR_INVALID, "%s: NULL output for %lld matches", what, (long long)total);
+  }
+  RmWorkspace w;
+  const size_t need = rm_carve(ws, ws_bytes, n_pairs, total_src, total_tgt, &w);
+  EYOC_REQUIRE(ws_bytes >= need, EYOC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (eyoc_radius_matches_workspace_bytes)", what, ws_bytes, need);
+  EYOC_CHECK_HIP(hipSetDevice(ctx->device));
+  if (fill && total == 0) return EYOC_OK;
+  hipStream_t st = (hipStream_t)stream;
+  size_t cell0 = 0;
+  const int rc = for_each_chunk(n_pairs, [&](int b0, int np) {
+    const size_t so = (size_t)seg_src[b0], to = (size_t)seg_tgt[b0];
+    const IcpSegs s = make_segs(seg_src + b0, seg_tgt + b0, np);
+    const GridWorkspace gw = chunk_grid(w.grid, so, to, cell0, s.tgt[np]);
+    cell0 += gw.cap;
+    if (fill)
+      return rm_fill_chunk(s, radius, (const long long*)offsets + so, total, status + b0, (long long*)pairs_out, d2_out, gw, w.qpts + 3 * so, st);
+    return rm_count_chunk(src ? src + 3 * so : nullptr, tgt ? tgt + 3 * to : nullptr, s, T ? T + 16 * (size_t)b0 : nullptr, radius, max_per_source,
+                          (long long*)offsets + so, status + b0, gw, w.qpts + 3 * so, st);
+  });
+  if (rc != EYOC_OK || fill) return rc;
+  EYOC_CHECK_HIP(hipMemsetAsync(offsets + total_src, 0, sizeof(int64_t), st));
+  return scan_offsets64(w.scan_tmp, w.scan_bytes, (long long*)offsets, total_src + 1, st);
 }
 
 }  // namespace
@@ -698,4 +961,26 @@ extern "C" int eyoc_posed_nn_grid(eyoc_ctx* ctx, const float* src_dev, const flo
                      T_dev + 16 * (size_t)b0, max_dist, sel_dev ? sel_dev + qo : nullptr, idx_out_dev ? idx_out_dev + qo : nullptr,
                      d2_out_dev ? d2_out_dev + qo : nullptr, status_dev + b0, w, (hipStream_t)stream);
   });
+}
+
+extern "C" size_t eyoc_radius_matches_workspace_bytes(int n_pairs, int total_src, int total_tgt) {
+  if (n_pairs < 1 || total_src < 0 || total_tgt < 0) return 0;
+  eyoc::RmWorkspace w;
+  return eyoc::rm_carve(nullptr, 0, n_pairs, total_src, total_tgt, &w);
+}
+
+extern "C" int eyoc_radius_matches_count(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int32_t* seg_src_host,
+                                         const int32_t* seg_tgt_host, int n_pairs, const double* T_dev, double radius, int max_per_source,
+                                         int64_t* offsets_dev, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return eyoc::rm_run("eyoc_radius_matches_count", false, ctx, src_dev, tgt_dev, seg_src_host, seg_tgt_host, n_pairs, T_dev, radius, max_per_source,
+                      offsets_dev, status_dev, 0, nullptr, nullptr, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int eyoc_radius_matches_fill(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int32_t* seg_src_host,
+                                        const int32_t* seg_tgt_host, int n_pairs, const double* T_dev, double radius, int max_per_source,
+                                        const int64_t* offsets_dev, const int32_t* status_dev, int64_t total, int64_t* pairs_out_dev,
+                                        double* d2_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return eyoc::rm_run("eyoc_radius_matches_fill", true, ctx, src_dev, tgt_dev, seg_src_host, seg_tgt_host, n_pairs, T_dev, radius, max_per_source,
+                      const_cast<int64_t*>(offsets_dev), const_cast<int32_t*>(status_dev), total, pairs_out_dev, d2_out_dev, workspace_dev,
+                      workspace_bytes, stream);
 }

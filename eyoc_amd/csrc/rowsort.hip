@@ -1,9 +1,10 @@
 // Stable key sort of row indices (rocPRIM radix sort), used by the coordinate maps to order the row tiles of a
-// transposed convolution by neighbour pattern.  Kept in its own translation unit: rocPRIM's templates are the
-// slowest thing in the build.
+// transposed convolution by neighbour pattern, and the 64-bit exclusive scan that turns per-row counts into offsets
+// (radius matches, icp.hip).  Kept in its own translation unit: rocPRIM's templates are the slowest thing in the build.
 #include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include "common.h"
 
@@ -36,6 +37,20 @@ int sort_rows_by_key64(void* tmp, size_t tmp_bytes, const unsigned long long* ke
                        int* vals_out, int n, int bits, hipStream_t st) {
   size_t need = tmp_bytes;                                             // sized for 64 bits: enough for any narrower sort
   EYOC_CHECK_HIP(rocprim::radix_sort_pairs(tmp, need, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, (unsigned)bits, st));
+  return EYOC_OK;
+}
+
+size_t scan_offsets64_tmp_bytes(int n) {
+  size_t bytes = 0;
+  (void)rocprim::exclusive_scan(nullptr, bytes, (const long long*)nullptr, (long long*)nullptr, 0ll, (size_t)(n > 0 ? n : 1),
+                                rocprim::plus<long long>(), (hipStream_t)0);
+  return bytes;
+}
+
+// counts -> offsets in place: data[i] = data[0] + ... + data[i - 1] (64-bit integers: the result does not depend on the partition)
+int scan_offsets64(void* tmp, size_t tmp_bytes, long long* data, int n, hipStream_t st) {
+  size_t need = tmp_bytes;
+  EYOC_CHECK_HIP(rocprim::exclusive_scan(tmp, need, (const long long*)data, data, 0ll, (size_t)n, rocprim::plus<long long>(), st));
   return EYOC_OK;
 }
 

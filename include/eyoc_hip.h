@@ -868,6 +868,44 @@ int eyoc_posed_nn_grid(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev
                        int64_t* idx_out_dev, float* d2_out_dev, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes,
                        void* stream);
 
+/* Ground-truth matching indices by radius search, for a batch of pairs (util/pointcloud.py:53-66, get_matching_indices: Open3D's
+ * search_radius_vector_3d around every posed source point; lib/data_loaders.py:948-954 calls it for every training / validation pair,
+ * util/pointcloud.py:42-50 with K = 1).  Added after 111 without a bump, additive only.
+ * Pairs back to back like eyoc_icp_batched: pair b owns source rows [seg_src[b], seg_src[b+1]) and target rows [seg_tgt[b],
+ * seg_tgt[b+1]) (HOST arrays of n_pairs + 1 ints from 0, n_pairs <= 1024, empty segments accepted: no matches).  T_dev f64
+ * [n_pairs][16] row-major, read on the device; NULL = the identity for every pair.
+ *   posed point  p_k = ((T[4k] x + T[4k+1] y) + T[4k+2] z) + T[4k+3], k = 0..2; fp32 coordinates are exact in fp64
+ *   d2 = (dx dx + dy dy) + dz dz with dx = p_0 - q_x ...; all of it fp64, every operation rounded on its own (no fused multiply-add)
+ *   match        (i, j) iff d2 < radius * radius, the product formed once in fp64, the comparison strict (what Open3D returns for a
+ *                target at exactly the radius is unpinned)
+ *   order        inside a source row the matches ascend by (d2, j) - Open3D's sorted radius search, an exact tie in d2 going to the
+ *                lower target row; that is the row's list.  max_per_source = K > 0 keeps the first K entries of the list (the
+ *                reference's idx[:K]), 0 keeps all.  The result is ordered by pair, then by source row, then by the list; i and j are
+ *                LOCAL to the pair.
+ * status_dev int32 [n_pairs]: 0, or EYOC_ICP_BAD_INIT (a non-finite pose; nothing else of the pair is read) / EYOC_ICP_RANGE (a
+ * non-finite source or target point, a target or posed source whose cell floor(v / edge) lies outside [-2^17, 2^17), edge = radius *
+ * (1 + 2^-20) in fp64).  A pair with a status has no matches.
+ * The result is EXACTLY the brute-force decision over all n0 x n1 candidates: the cell edge has a margin over the radius, so the 27
+ * cells around a source's cell hold every match, also at a cell face (icp.hip derives it).  No floating-point atomics; pair b's slice
+ * of the output is byte-identical from run to run, to a call on pair b alone, and for any position of the pair in the batch.
+ * The output length is known on the device only, hence two calls:
+ *   count  builds the grids, counts every source row's matches (at most K) and writes the exclusive 64-bit scan over ALL source rows
+ *          of the call to offsets_dev [total_src + 1]: row r (counted over the whole call) owns entries [offsets[r], offsets[r+1]),
+ *          offsets[total_src] is the total.  The grids stay in the workspace.
+ *   fill   takes the same arguments, the offsets, the total the host read, and the workspace UNTOUCHED since the count; it searches again
+ *          and writes pairs_out_dev int64 [total][2] = (i, j) and d2_out_dev f64 [total].  EYOC_ERR_INVALID for total < 0 or a NULL
+ *          output with total > 0; a source row whose slice does not lie inside [0, total) is not written.
+ * Caller-owned 256-byte aligned workspace of eyoc_radius_matches_workspace_bytes (every 64-pair chunk keeps its own grid in it);
+ * nothing is allocated and the host never waits inside either call. */
+size_t eyoc_radius_matches_workspace_bytes(int n_pairs, int total_src, int total_tgt);
+int eyoc_radius_matches_count(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int32_t* seg_src_host,
+                              const int32_t* seg_tgt_host, int n_pairs, const double* T_dev, double radius, int max_per_source,
+                              int64_t* offsets_dev, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int eyoc_radius_matches_fill(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int32_t* seg_src_host,
+                             const int32_t* seg_tgt_host, int n_pairs, const double* T_dev, double radius, int max_per_source,
+                             const int64_t* offsets_dev, const int32_t* status_dev, int64_t total, int64_t* pairs_out_dev,
+                             double* d2_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
