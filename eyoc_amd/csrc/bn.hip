@@ -15,7 +15,10 @@ namespace {
 constexpr int BN_BLOCKS = 1024;      // partial-sum workgroups (4 per CU)
 
 // partial[b][0..c) = sum of a, partial[b][c..2c) = sum of b over the block's rows; a / b chosen by MODE:
-//   MODE 0: a = x, b = x^2                       (forward statistics)
+//   MODE 0: a = x - s, b = (x - s)^2             (forward statistics; s = the channel's value in row 0.  Sums of x and x^2 lose the
+//                                                 variance to cancellation once |mean| / sigma is large: measured up to 1e-4 of the
+//                                                 variance at |mean| / sigma = 1e5.  About a sample of the column (x[0] - mean)^2 <= n var,
+//                                                 so b / n - (a / n)^2 cancels at most log2(n) of the 53 bits; a constant column gives 0.)
 //   MODE 1: a = dy', b = dy' * xhat              (backward sums; dy' = dy where y > 0 when a ReLU followed, xhat from mean / invstd)
 template <int MODE>
 __global__ __launch_bounds__(256) void k_bn_partial(const float* __restrict__ x, int ld_x, const float* __restrict__ y, int ld_y,
@@ -28,11 +31,13 @@ __global__ __launch_bounds__(256) void k_bn_partial(const float* __restrict__ x,
   double a = 0.0, b = 0.0;
   float mean = 0.f, invstd = 0.f;
   if (MODE == 1) { mean = mean_var[ch]; invstd = 1.0f / sqrtf(mean_var[c + ch] + eps); }
+  const double shift = MODE == 0 ? (double)x[ch] : 0.0;
   for (int r = r0 + sub; r < r1; r += nsub) {
     const float xv = x[(size_t)r * ld_x + ch];
     if (MODE == 0) {
-      a += (double)xv;
-      b += (double)xv * (double)xv;
+      const double d = (double)xv - shift;
+      a += d;
+      b += d * d;
     } else {
       float g = dy[(size_t)r * ld_dy + ch];
       if (y && !(y[(size_t)r * ld_y + ch] > 0.0f)) g = 0.0f;
@@ -50,7 +55,7 @@ __global__ __launch_bounds__(256) void k_bn_partial(const float* __restrict__ x,
   }
 }
 
-// MODE 0: out[ch] = mean, out[c + ch] = biased variance.  MODE 1: out[ch] = sum a (dbeta), out[c + ch] = sum b (dgamma).
+// MODE 0: out[ch] = mean, out[c + ch] = biased variance (from the sums about x0[ch], row 0 of the input).  MODE 1: out[ch] = sum a (dbeta), out[c + ch] = sum b (dgamma).
 // One workgroup per TWO channels: thread t adds the partial sums of column (t & 3) = (channel, a / b) over the blocks t >> 2,
 // t >> 2 + 64, ... in ascending order, then the 64 per-thread sums meet in a fixed tree - bit-reproducible whatever the timing.
 // (Round 5: one thread per channel walked all <= 1024 partial blocks alone, 49 us of dependent loads per call and 42 calls per
@@ -58,7 +63,8 @@ __global__ __launch_bounds__(256) void k_bn_partial(const float* __restrict__ x,
 // MODE 0 with `running` != NULL also moves the running statistics like nn.BatchNorm1d: running = (1 - m) running + m batch, the
 // variance unbiased (n / (n - 1)) - one launch instead of five element-wise ones per norm.
 template <int MODE>
-__global__ __launch_bounds__(256) void k_bn_final(const double* __restrict__ partial, int blocks, int n, int c, float* __restrict__ out0,
+__global__ __launch_bounds__(256) void k_bn_final(const double* __restrict__ partial, const float* __restrict__ x0, int blocks, int n, int c,
+                                                  float* __restrict__ out0,
                                                   float* __restrict__ out1, float* __restrict__ run_mean, float* __restrict__ run_var,
                                                   float momentum) {
   __shared__ double red[256];
@@ -77,8 +83,8 @@ __global__ __launch_bounds__(256) void k_bn_final(const double* __restrict__ par
   if (threadIdx.x < 4 && ab == 0 && ch < c) {            // threads 0 and 2: one per channel
     const double a = red[threadIdx.x], b = red[threadIdx.x + 1];
     if (MODE == 0) {
-      const double m = a / n;
-      double v = b / n - m * m;
+      const double ms = a / n, m = (double)x0[ch] + ms;
+      double v = b / n - ms * ms;
       if (v < 0.0) v = 0.0;
       out0[ch] = (float)m;
       out1[ch] = (float)v;
@@ -165,7 +171,7 @@ static int bn_train_forward(eyoc_ctx* ctx, const float* x_dev, int n, int c, int
   const int nb = bn_blocks(n);
   hipLaunchKernelGGL(k_bn_partial<0>, dim3(nb), dim3(256), 0, st, x_dev, ld_x, (const float*)nullptr, 0, (const float*)nullptr, 0, n, c,
                      (const float*)nullptr, eps, (double*)ws_dev);
-  hipLaunchKernelGGL(k_bn_final<0>, dim3(cdiv(c, 2)), dim3(256), 0, st, (const double*)ws_dev, nb, n, c, mean_var_dev, mean_var_dev + c,
+  hipLaunchKernelGGL(k_bn_final<0>, dim3(cdiv(c, 2)), dim3(256), 0, st, (const double*)ws_dev, x_dev, nb, n, c, mean_var_dev, mean_var_dev + c,
                      run_mean_dev, run_var_dev, momentum);
   hipLaunchKernelGGL(k_bn_apply, dim3(cdiv((long long)n * (c / 4), 256)), dim3(256), 0, st, x_dev, ld_x, n, c, mean_var_dev, gamma_dev, beta_dev, eps,
                      relu, y_dev, ld_y);
@@ -199,7 +205,7 @@ int eyoc_bn_train_backward(eyoc_ctx* ctx, const float* x_dev, int ld_x, const fl
   hipStream_t st = (hipStream_t)stream;
   const int nb = bn_blocks(n);
   hipLaunchKernelGGL(k_bn_partial<1>, dim3(nb), dim3(256), 0, st, x_dev, ld_x, y_dev, ld_y, dy_dev, ld_dy, n, c, mean_var_dev, eps, (double*)ws_dev);
-  hipLaunchKernelGGL(k_bn_final<1>, dim3(cdiv(c, 2)), dim3(256), 0, st, (const double*)ws_dev, nb, n, c, dbeta_dev, dgamma_dev, (float*)nullptr,
+  hipLaunchKernelGGL(k_bn_final<1>, dim3(cdiv(c, 2)), dim3(256), 0, st, (const double*)ws_dev, (const float*)nullptr, nb, n, c, dbeta_dev, dgamma_dev, (float*)nullptr,
                      (float*)nullptr, 0.0f);
   hipLaunchKernelGGL(k_bn_backward_apply, dim3(cdiv((long long)n * c, 256)), dim3(256), 0, st, x_dev, ld_x, y_dev, ld_y, dy_dev, ld_dy, n, c,
                      mean_var_dev, gamma_dev, eps, dbeta_dev, dgamma_dev, dx_dev, ld_dx);

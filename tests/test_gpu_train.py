@@ -221,7 +221,7 @@ def test_advice_r5_gather_window_rows_and_running_statistics_versions(setup):
     lib = _lib.load()
     F = torch.from_numpy(feats).cuda()
     Gc = gather_window(cm, F, 3)                                       # the caller's rows (this small cloud's maps keep them)
-    prev = lib.eyoc_maps_internal_order(_lib.ctx(0), 1)                # Z-order forced for the second set
+    prev = lib.eyoc_maps_internal_order(_lib.ctx(0), 1) - 2            # Z-order forced for the second set (the call returns the old mode + 2)
     try:
         cmz = eyoc_amd.SparseTensor(torch.from_numpy(feats).cuda(), coordinates=torch.from_numpy(coords).cuda()).coordinate_manager
         mz = cmz.maps()
