@@ -223,6 +223,12 @@ PROTOTYPES = {
                                        _vp, _sz, _vp]),
     "eyoc_radius_matches_fill": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _vp, C.c_double, _i, _vp, _vp,
                                       C.c_int64, _vp, _vp, _vp, _sz, _vp]),
+    "eyoc_cloud_centroids_workspace_bytes": (_sz, [_i, _i]),
+    "eyoc_cloud_centroids": (_i, [_vp, _vp, _i, C.POINTER(C.c_int64), _i, _i, _vp, _vp, _sz, _vp]),
+    "eyoc_augment_poses": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "eyoc_voxelize_batched_posed_workspace_bytes": (_sz, [_i, _i]),
+    "eyoc_voxelize_batched_posed": (_i, [_vp, _vp, _i, C.POINTER(C.c_int64), _i, _i, _vp, _vp, C.c_double, _i, _vp, _vp, _vp,
+                                         C.POINTER(C.c_int64), _vp, _sz, _vp, _vp]),
 }
 
 

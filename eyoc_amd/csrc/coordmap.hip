@@ -534,6 +534,70 @@ __global__ void k_quantize(const float* __restrict__ xyz, int n, int stride, flo
   }
 }
 
+// k_quantize under the training loader's augmentation (eyoc_voxelize_batched_posed; lib/data_loaders.py:919-920, :931-932, :940-943,
+// :969-970, :978): the point is posed and scaled in fp64, every operation rounded on its own,
+//   q_k = ((T[4k] x + T[4k+1] y) + T[4k+2] z) + T[4k+3],  p'_k = s q_k,  c_k = floor(p'_k / v)
+// (pose: f64 [n_clouds][16], scale: f64 [n_clouds] or NULL = no product at all), and pxyz[i] = (float)p' is kept for the compaction:
+// the kept point is the rounding of the very p' its key came from.  A fault is a p' that is not finite (a NaN / inf point or pose) or
+// whose cell lies outside the key range; nothing is cast then.  kIsolate counts it like k_quantize (the row holds its cloud and
+// zeros); otherwise the row's x is INT_MAX, which k_insert_runs counts, and bad names the first such cloud.
+template <bool kIsolate>
+__global__ void k_quantize_posed(const float* __restrict__ xyz, int n, int stride, const double* __restrict__ pose,
+                                 const double* __restrict__ scale, double voxel, const int64_t* __restrict__ pt_off, int n_clouds,
+                                 int batch_base, int32_t* __restrict__ coords, float* __restrict__ pxyz, int* __restrict__ bad,
+                                 int* __restrict__ faults) {
+#pragma clang fp contract(off)
+  __shared__ int cloud0;
+  const int i0 = blockIdx.x * blockDim.x;
+  if (n_clouds > 1) {
+    if (threadIdx.x == 0) {
+      int lo = 0, hi = n_clouds - 1;
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (pt_off[mid] <= i0) lo = mid; else hi = mid - 1;
+      }
+      cloud0 = lo;
+    }
+    __syncthreads();
+  }
+  const int i = i0 + threadIdx.x;
+  if (i >= n) return;
+  int b = 0;
+  if (n_clouds > 1) {
+    b = cloud0;
+    while (pt_off[b + 1] <= i) ++b;
+  }
+  const float* p = xyz + (size_t)i * stride;
+  const double x = p[0], y = p[1], z = p[2];
+  const double* T = pose + 16 * (size_t)b;
+  constexpr double LIM = COORD_BIAS - 16;   // k_insert's test
+  int c[3];
+  bool finite = true, out = false;
+  for (int k = 0; k < 3; ++k) {
+    double q = ((T[4 * k] * x + T[4 * k + 1] * y) + T[4 * k + 2] * z) + T[4 * k + 3];
+    if (scale) q = scale[b] * q;
+    pxyz[3 * (size_t)i + k] = (float)q;
+    const double f = floor(q / voxel);
+    if (f >= -LIM && f < LIM) {
+      c[k] = (int)f;
+    } else {                      // (a NaN fails both comparisons)
+      c[k] = 0;
+      if (isfinite(q)) out = true; else finite = false;
+    }
+  }
+  int4 r = make_int4(batch_base + b, c[0], c[1], c[2]);
+  if (!finite || out) {
+    if constexpr (kIsolate) {
+      atomicAdd(&faults[2 * b + (finite ? 0 : 1)], 1);
+      r = make_int4(batch_base + b, 0, 0, 0);
+    } else {
+      r.y = 0x7fffffff;
+      atomicMax(bad, n_clouds - b);
+    }
+  }
+  reinterpret_cast<int4*>(coords)[i] = r;
+}
+
 // the clouds' row offsets in the compacted output: the exclusive scan of the flags at a cloud's first point is the scanned partial sum
 // of its tile plus the flags from the tile's start to that point (deterministic, no atomics).  One wave per boundary pt_off[j],
 // j <= n_clouds; a boundary at n (empty clouds at the end, and pt_off[n_clouds]) is the total.
@@ -1185,6 +1249,11 @@ size_t eyoc_voxelize_batched_isolating_workspace_bytes(int n_points_total, int n
   return eyoc_voxelize_batched_workspace_bytes(n_points_total, n_clouds) + align_up((size_t)n_clouds * 8 + 8);
 }
 
+size_t eyoc_voxelize_batched_posed_workspace_bytes(int n_points_total, int n_clouds) {   // + the posed fp32 points
+  if (n_points_total < 0 || n_clouds < 1) return 0;
+  return eyoc_voxelize_batched_isolating_workspace_bytes(n_points_total, n_clouds) + align_up((size_t)n_points_total * 12) + 256;
+}
+
 }  // extern "C"
 
 namespace {
@@ -1194,9 +1263,17 @@ namespace {
 // (uploaded through the ctx's pinned staging; one cloud needs none), vox_off_host: [n_clouds + 1] out.
 // faults_host ([n_clouds][2] out, or NULL): the isolating variant - per-cloud fault counts instead of an error, faulty clouds skipped;
 // the counts sit behind the row offsets and come back in the same copy.
+// posed (or NULL): eyoc_voxelize_batched_posed - k_quantize_posed takes k_quantize's place, and the compaction copies the kept points
+// from the posed fp32 points that kernel left at the workspace's end, not from the raw ones.
+struct PosedArgs {
+  const double *pose, *scale;
+  double voxel;
+};
+
 int voxelize_run(eyoc_ctx* ctx, const char* who, const float* xyz_dev, int n, int stride, const int64_t* pt_off_host,
                  int n_clouds, float voxel_size, int batch_base, int32_t* sel_dev, int32_t* coords_dev, float* xyz_out_dev,
-                 int64_t* vox_off_host, void* ws, size_t ws_bytes, hipStream_t st, int32_t* faults_host = nullptr) {
+                 int64_t* vox_off_host, void* ws, size_t ws_bytes, hipStream_t st, int32_t* faults_host = nullptr,
+                 const PosedArgs* posed = nullptr) {
   Carver cv(ws, ws_bytes);
   const bool iso = faults_host != nullptr;
   // [0] range errors, [1] first bad cloud (n_clouds - b), [2] total, [64..] row offsets, isolating: [fo ..] fault counts (8-byte aligned)
@@ -1213,6 +1290,7 @@ int voxelize_run(eyoc_ctx* ctx, const char* who, const float* xyz_dev, int n, in
   t.keys = cv.take<unsigned long long>(cap);
   t.vals = cv.take<int>(cap);
   t.mask = cap - 1;
+  float* pxyz = posed ? cv.take<float>((size_t)n * 3) : nullptr;
   EYOC_REQUIRE(cv.ok(), EYOC_ERR_WORKSPACE, "%s: internal workspace accounting error (%zu > %zu)", who, cv.off, cv.cap);
   // pinned staging: the point offsets up at 0, the counters and row offsets back behind them
   const size_t up_bytes = n_clouds > 1 ? align_up((size_t)(n_clouds + 1) * 8) : 0;
@@ -1229,17 +1307,23 @@ int voxelize_run(eyoc_ctx* ctx, const char* who, const float* xyz_dev, int n, in
   if (iso) EYOC_CHECK_HIP(hipMemsetAsync(faults, 0, (size_t)n_clouds * 2 * sizeof(int), st));
   EYOC_CHECK_HIP(hipMemsetAsync(t.keys, 0xFF, (size_t)cap * 8, st));
   EYOC_CHECK_HIP(hipMemsetAsync(t.vals, 0x7F, (size_t)cap * 4, st));
-  if (iso) {
-    hipLaunchKernelGGL(k_quantize<true>, dim3(cdiv(n, 256)), dim3(256), 0, st, xyz_dev, n, stride, voxel_size, (const int64_t*)pt_off,
-                       n_clouds, batch_base, raw, counters + 1, faults);
-    hipLaunchKernelGGL(k_insert_runs<true>, dim3(cdiv(n, 256)), dim3(256), 0, st, (const int32_t*)raw, n, t, slot, counters,
-                       (const int*)faults, batch_base);
-  } else {
-    hipLaunchKernelGGL(k_quantize<false>, dim3(cdiv(n, 256)), dim3(256), 0, st, xyz_dev, n, stride, voxel_size, (const int64_t*)pt_off,
-                       n_clouds, batch_base, raw, counters + 1, (int*)nullptr);
-    hipLaunchKernelGGL(k_insert_runs<false>, dim3(cdiv(n, 256)), dim3(256), 0, st, (const int32_t*)raw, n, t, slot, counters,
-                       (const int*)nullptr, 0);
-  }
+  const dim3 qg(cdiv(n, 256)), qb(256);
+  if (posed && iso)
+    hipLaunchKernelGGL(k_quantize_posed<true>, qg, qb, 0, st, xyz_dev, n, stride, posed->pose, posed->scale, posed->voxel,
+                       (const int64_t*)pt_off, n_clouds, batch_base, raw, pxyz, counters + 1, faults);
+  else if (posed)
+    hipLaunchKernelGGL(k_quantize_posed<false>, qg, qb, 0, st, xyz_dev, n, stride, posed->pose, posed->scale, posed->voxel,
+                       (const int64_t*)pt_off, n_clouds, batch_base, raw, pxyz, counters + 1, (int*)nullptr);
+  else if (iso)
+    hipLaunchKernelGGL(k_quantize<true>, qg, qb, 0, st, xyz_dev, n, stride, voxel_size, (const int64_t*)pt_off, n_clouds, batch_base, raw,
+                       counters + 1, faults);
+  else
+    hipLaunchKernelGGL(k_quantize<false>, qg, qb, 0, st, xyz_dev, n, stride, voxel_size, (const int64_t*)pt_off, n_clouds, batch_base, raw,
+                       counters + 1, (int*)nullptr);
+  if (iso)
+    hipLaunchKernelGGL(k_insert_runs<true>, qg, qb, 0, st, (const int32_t*)raw, n, t, slot, counters, (const int*)faults, batch_base);
+  else
+    hipLaunchKernelGGL(k_insert_runs<false>, qg, qb, 0, st, (const int32_t*)raw, n, t, slot, counters, (const int*)nullptr, 0);
   hipLaunchKernelGGL(k_flag, dim3(cdiv(n, 256)), dim3(256), 0, st, slot, t.vals, n, flag, (int*)nullptr);
   const int nb = cdiv(n, SCAN_TILE);
   hipLaunchKernelGGL(k_scan_partials, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, n, partial);
@@ -1248,7 +1332,8 @@ int voxelize_run(eyoc_ctx* ctx, const char* who, const float* xyz_dev, int n, in
     hipLaunchKernelGGL(k_cloud_offsets, dim3(cdiv(n_clouds + 1, 4)), dim3(256), 0, st, (const int*)flag, (const int*)partial,
                        (const int*)(counters + 2), n, (const int64_t*)pt_off, n_clouds, counters + 64);
   hipLaunchKernelGGL(k_compact<true>, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, partial, slot, raw, n, 1, coords_dev, t.vals,
-                     sel_dev, (const int64_t*)pt_off, n_clouds, batch_base, xyz_dev, stride, xyz_out_dev);
+                     sel_dev, (const int64_t*)pt_off, n_clouds, batch_base, posed ? (const float*)pxyz : xyz_dev, posed ? 3 : stride,
+                     xyz_out_dev);
   EYOC_CHECK_HIP(hipGetLastError());
   EYOC_CHECK_HIP(hipMemcpyAsync(host, counters, (size_t)back * sizeof(int), hipMemcpyDeviceToHost, st));
   EYOC_CHECK_HIP(hipStreamSynchronize(st));
@@ -1294,12 +1379,13 @@ int eyoc_voxelize(eyoc_ctx* ctx, const float* xyz_dev, int n, int stride, float 
 static int voxelize_batched(const char* who, bool isolating, eyoc_ctx* ctx, const float* xyz_dev, int stride,
                             const int64_t* point_offsets, int n_clouds, int n_points, float voxel_size, int batch_base,
                             int32_t* sel_dev, int32_t* coords_dev, float* xyz_out_dev, int64_t* voxel_offsets, void* ws,
-                            size_t ws_bytes, void* stream, int32_t* cloud_faults) {
+                            size_t ws_bytes, void* stream, int32_t* cloud_faults, const PosedArgs* posed = nullptr) {
   EYOC_REQUIRE(ctx && point_offsets && voxel_offsets && (!isolating || cloud_faults), EYOC_ERR_INVALID, "%s: NULL argument", who);
   EYOC_REQUIRE(n_clouds >= 1 && n_clouds <= 1024, EYOC_ERR_INVALID, "%s: %d clouds (1 .. 1024)", who, n_clouds);
   EYOC_REQUIRE(n_points >= 0 && n_points <= (1 << 30), EYOC_ERR_INVALID, "%s: %d points in all (0 .. 2^30)", who,
                n_points);
-  EYOC_REQUIRE(stride >= 3 && voxel_size > 0.0f, EYOC_ERR_INVALID, "%s: stride %d voxel %g", who, stride, voxel_size);
+  EYOC_REQUIRE(stride >= 3 && (posed ? posed->voxel > 0.0 : voxel_size > 0.0f), EYOC_ERR_INVALID, "%s: stride %d voxel %g", who, stride,
+               posed ? posed->voxel : (double)voxel_size);
   EYOC_REQUIRE(batch_base >= 0 && batch_base + n_clouds <= 1024, EYOC_ERR_RANGE,
                "%s: batch indices %d .. %d (< 1024)", who, batch_base, batch_base + n_clouds - 1);
   EYOC_REQUIRE(point_offsets[0] == 0, EYOC_ERR_INVALID, "%s: point_offsets[0] = %lld", who, (long long)point_offsets[0]);
@@ -1315,13 +1401,14 @@ static int voxelize_batched(const char* who, bool isolating, eyoc_ctx* ctx, cons
     for (int b = 0; b <= n_clouds; ++b) voxel_offsets[b] = 0;
     return EYOC_OK;
   }
-  EYOC_REQUIRE(xyz_dev && sel_dev && coords_dev && ws, EYOC_ERR_INVALID, "%s: NULL argument", who);
-  const size_t need = isolating ? eyoc_voxelize_batched_isolating_workspace_bytes(n_points, n_clouds)
-                                 : eyoc_voxelize_batched_workspace_bytes(n_points, n_clouds);
+  EYOC_REQUIRE(xyz_dev && sel_dev && coords_dev && ws && (!posed || posed->pose), EYOC_ERR_INVALID, "%s: NULL argument", who);
+  const size_t need = posed       ? eyoc_voxelize_batched_posed_workspace_bytes(n_points, n_clouds)
+                      : isolating ? eyoc_voxelize_batched_isolating_workspace_bytes(n_points, n_clouds)
+                                  : eyoc_voxelize_batched_workspace_bytes(n_points, n_clouds);
   EYOC_REQUIRE(((uintptr_t)ws & 255) == 0 && ws_bytes >= need, EYOC_ERR_WORKSPACE,
                "%s: workspace %zu < required %zu bytes (256-byte aligned)", who, ws_bytes, need);
   return voxelize_run(ctx, who, xyz_dev, n_points, stride, point_offsets, n_clouds, voxel_size, batch_base,
-                      sel_dev, coords_dev, xyz_out_dev, voxel_offsets, ws, ws_bytes, (hipStream_t)stream, cloud_faults);
+                      sel_dev, coords_dev, xyz_out_dev, voxel_offsets, ws, ws_bytes, (hipStream_t)stream, cloud_faults, posed);
 }
 
 int eyoc_voxelize_batched(eyoc_ctx* ctx, const float* xyz_dev, int stride, const int64_t* point_offsets, int n_clouds,
@@ -1337,6 +1424,15 @@ int eyoc_voxelize_batched_isolating(eyoc_ctx* ctx, const float* xyz_dev, int str
                                     int32_t* cloud_faults) {
   return voxelize_batched("eyoc_voxelize_batched_isolating", true, ctx, xyz_dev, stride, point_offsets, n_clouds, n_points,
                           voxel_size, batch_base, sel_dev, coords_dev, xyz_out_dev, voxel_offsets, ws, ws_bytes, stream, cloud_faults);
+}
+
+int eyoc_voxelize_batched_posed(eyoc_ctx* ctx, const float* xyz_dev, int stride, const int64_t* point_offsets, int n_clouds, int n_points,
+                                const double* pose_dev, const double* scale_dev, double voxel_size, int batch_base, int32_t* sel_dev,
+                                int32_t* coords_dev, float* xyz_out_dev, int64_t* voxel_offsets, void* ws, size_t ws_bytes, void* stream,
+                                int32_t* cloud_faults) {
+  const PosedArgs posed{pose_dev, scale_dev, voxel_size};
+  return voxelize_batched("eyoc_voxelize_batched_posed", cloud_faults != nullptr, ctx, xyz_dev, stride, point_offsets, n_clouds, n_points,
+                          0.0f, batch_base, sel_dev, coords_dev, xyz_out_dev, voxel_offsets, ws, ws_bytes, stream, cloud_faults, &posed);
 }
 
 int eyoc_maps_free(eyoc_maps* maps) {

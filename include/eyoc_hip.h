@@ -46,6 +46,8 @@ typedef enum {
  *     eyoc_registration_accept_degenerate (a binding checks for the symbols).
  *     Later still, per-pair failure isolation adds eyoc_batch_drop(_workspace_bytes), eyoc_remap_rows and
  *     eyoc_voxelize_batched_isolating(_workspace_bytes), again found by symbol; nothing that existed changes.
+ *     Training batches from raw scans add eyoc_cloud_centroids(_workspace_bytes), eyoc_augment_poses and
+ *     eyoc_voxelize_batched_posed(_workspace_bytes) the same way.
  * 110 (round 6): the kernel-selection setters and eyoc_ransac_workspace_bytes take the ctx first (round 5), eyoc_maps_gather_window
  * refuses Z-ordered maps again and eyoc_maps_gather_window_internal exists, eyoc_model_workspace_bytes depends on the maps' size class */
 #define EYOC_VERSION 111
@@ -905,6 +907,60 @@ int eyoc_radius_matches_fill(eyoc_ctx* ctx, const float* src_dev, const float* t
                              const int32_t* seg_tgt_host, int n_pairs, const double* T_dev, double radius, int max_per_source,
                              const int64_t* offsets_dev, const int32_t* status_dev, int64_t total, int64_t* pairs_out_dev,
                              double* d2_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * training batches from raw scans: the augmentation of the reference's loader for a whole batch (PairDataset.__getitem__ with
+ * use_random_rotation, lib/data_loaders.py:912-943, :969-978).  Added after 111 without a bump, additive only.
+ * Every fp64 expression below is evaluated as written, left to right inside its brackets, every operation rounded on its own (no fused
+ * multiply-add).  fp32 inputs are exact in fp64.
+ * --------------------------------------------------------------------------------------------- */
+
+/* replaces: np.mean(pcd, axis=0) of sample_random_trans (lib/data_loaders.py:99), as an fp64 mean.
+ * Packed clouds in the layout of eyoc_voxelize_batched (xyz_dev, stride >= 3, HOST point_offsets [n_clouds + 1], empty clouds allowed,
+ * n_clouds <= 1024).  centroid_dev f64 [n_clouds][4] = (mean x, mean y, mean z, count); an empty cloud gives four zeros.
+ * The sums are reduced lane -> wave -> workgroup -> cloud in an order fixed by the cloud's own size (workgroups of 256 threads take 4096
+ * consecutive points each, thread t adds points t, t + 256, ...; a cloud's workgroup sums are added in order, then divided by the count):
+ * no floating-point atomics, and a cloud's 32 bytes are the same alone, at any position in a batch and from run to run.
+ * Stream-ordered, no synchronisation, no allocation; caller-owned 256-byte aligned workspace. */
+size_t eyoc_cloud_centroids_workspace_bytes(int n_points_total, int n_clouds);
+int eyoc_cloud_centroids(eyoc_ctx* ctx, const float* xyz_dev, int stride, const int64_t* point_offsets, int n_clouds, int n_points,
+                         double* centroid_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* replaces: sample_random_trans's T (lib/data_loaders.py:94-100, the rotation R given) for both clouds of every pair, the pair's pose
+ * trans = T1 @ M2 @ np.linalg.inv(T0) (:917) and the scaling of its translation (:933).  One launch, one thread per pair, n_pairs <= 512.
+ * rot_dev f64 [2 n_pairs][9] row-major (pair b: clouds 2b, 2b + 1), centroid_dev as eyoc_cloud_centroids wrote it, scale_dev f64
+ * [n_pairs] or NULL (no product), M2_dev f64 [n_pairs][16] row-major (its last row is not read).
+ *   pose_dev f64 [2 n_pairs][16]:  T_c = [R | t], t_k = (R[k][0] (-m_0) + R[k][1] (-m_1)) + R[k][2] (-m_2), last row 0 0 0 1
+ *   T_gt_dev f64 [n_pairs][16] = (T_1 M2) inv(T_0), in this order:
+ *     A[i][j] = (T1[i][0] M[0][j] + T1[i][1] M[1][j]) + T1[i][2] M[2][j]                       j < 3
+ *     A[i][3] = ((T1[i][0] M[0][3] + T1[i][1] M[1][3]) + T1[i][2] M[2][3]) + T1[i][3]
+ *     u[k]    = -((R0[0][k] t0[0] + R0[1][k] t0[1]) + R0[2][k] t0[2])                           inv(T_0) = [R0^T | u], the rigid inverse
+ *     G[i][j] = (A[i][0] R0[j][0] + A[i][1] R0[j][1]) + A[i][2] R0[j][2]                       j < 3
+ *     G[i][3] = ((A[i][0] u[0] + A[i][1] u[1]) + A[i][2] u[2]) + A[i][3],  then  G[i][3] = s G[i][3]  when scale_dev is given
+ *   and the last row 0 0 0 1. */
+int eyoc_augment_poses(eyoc_ctx* ctx, const double* rot_dev, const double* centroid_dev, const double* scale_dev, const double* M2_dev,
+                       int n_pairs, double* pose_dev, double* T_gt_dev, void* stream);
+
+/* replaces: apply_transform with the fp64 pose (lib/data_loaders.py:134-137, :919-920), scale * xyz (:931-932), the fp64
+ * sparse_quantize(xyz / voxel_size) and floor(xyz[sel] / voxel_size).int() (:940-943, :969-970), the .float() of the kept points (:978)
+ * and the sparse_collate of collate_pair_fn (:65-66), for a whole batch.
+ * eyoc_voxelize_batched's arguments and outputs, plus pose_dev f64 [n_clouds][16] row-major (last row not read), scale_dev f64
+ * [n_clouds] or NULL (no product), an fp64 voxel_size and cloud_faults (HOST out int32 [n_clouds][2], or NULL).  Per point (x, y, z):
+ *   q_k  = ((T[4k] x + T[4k+1] y) + T[4k+2] z) + T[4k+3]        the posed point of eyoc_radius_matches_*
+ *   p'_k = s q_k
+ *   c_k  = floor(p'_k / voxel_size)                              IEEE division
+ * then key, first-hit de-duplication, row offsets and compaction exactly as eyoc_voxelize_batched: coords int32 [.,4] = (batch_base + b,
+ * c), sel ascending per cloud, xyz_out f32 [.,3] = (float)p' of the same p' the key was formed from, voxel_offsets as there.
+ * A point is faulty when a p'_k is not finite (a NaN / inf point or pose) or, all p' finite, a c_k lies outside the key range.
+ * With cloud_faults: the contract of eyoc_voxelize_batched_isolating - cloud_faults[b][0] counts cloud b's finite posed points out of
+ * range, [b][1] its non-finite ones, a cloud with a count has an empty row range and every other cloud's rows are unchanged; EYOC_OK.
+ * With NULL: EYOC_ERR_RANGE, the message names the first cloud holding a faulty point.
+ * Synchronises `stream` once per call; n_points = 0 launches nothing.  The workspace also holds the posed fp32 points. */
+size_t eyoc_voxelize_batched_posed_workspace_bytes(int n_points_total, int n_clouds);
+int eyoc_voxelize_batched_posed(eyoc_ctx* ctx, const float* xyz_dev, int stride, const int64_t* point_offsets, int n_clouds, int n_points,
+                                const double* pose_dev, const double* scale_dev, double voxel_size, int batch_base, int32_t* sel_dev,
+                                int32_t* coords_dev, float* xyz_out_dev, int64_t* voxel_offsets, void* workspace_dev,
+                                size_t workspace_bytes, void* stream, int32_t* cloud_faults);
 
 #ifdef __cplusplus
 }
