@@ -15,7 +15,9 @@
 //    27 + 27 + 27 hash probes (3/4 of which would be misses that walk a probe chain).
 //  * rulebooks are output-stationary tables nbr[27][n_out] (k-major so that the 64 rows of a wave
 //    read/write one contiguous segment per offset).
+#include <cstddef>
 #include <cstdlib>
+#include <memory>
 
 #include "spconv.h"
 #include "derive.h"
@@ -791,12 +793,477 @@ hipEvent_t* fill_event(eyoc_maps* m, int kind, int level) {
   return nullptr;
 }
 
+// ---- eyoc_maps_build: the device counter block and what comes back of it
+// 128 words at the workspace's start, zeroed once.  The kernels are handed pointers to single fields or to a sub-block, so the order
+// of the fields is theirs: k_levels_fill writes scan_total[1 .. 3], k_count_levels a whole Levels block and both masks.
+struct Counters {
+  struct Faults {
+    int range, dup;                      // rows outside the key range / duplicate rows, as the level kernels count them
+    int scan_total[EYOC_MAX_LEVELS];     // [l >= 1]: rows of level l by the level's own scan
+    int pad[2];
+  } faults;
+  struct Overflow {                      // tiles a record builder could not stage: stride-1, transposed (Morton tiles), strided l -> l + 1, wide stride-1
+    int s1, up, down[EYOC_MAX_LEVELS - 1], s1w;
+    int pad[2];
+  } overflow;
+  struct Levels {                        // k_count_levels
+    int misfit;                          // rows that do not fit the speculated key width
+    int rows[EYOC_MAX_LEVELS - 1];       // rows of level 1 .. 3
+    int range, dup;
+    int max_coord, max_batch;            // largest |coordinate| / batch index: the next build's speculation
+  } levels;
+  int pad[40];
+  unsigned int dup_mask[32], range_mask[32];   // bit b: batch index b holds such a row (eyoc_maps_last_fault_batches)
+};
+static_assert(sizeof(Counters) == 128 * sizeof(int) && offsetof(Counters, overflow) == 8 * sizeof(int) &&
+              offsetof(Counters, levels) == 16 * sizeof(int) && offsetof(Counters, dup_mask) == 64 * sizeof(int) &&
+              offsetof(Counters, range_mask) == 96 * sizeof(int), "the kernels' layout");
+
+// the ctx's pinned staging during a build: every read-back has its own fields
+struct ReadBack {
+  Counters sorted;                           // sort_z: the block from `levels` on (k_count_levels' counts and masks)
+  Counters level1;                           // levels_hashed, level 1: the whole block after the insert, and again after k_children
+  alignas(128) Counters::Faults late;        // read_back_records (aligned: the runtime sizes its copy kernel by the destination's alignment) ...
+  alignas(128) Counters::Overflow overflow;
+  int upc_overflow[EYOC_MAX_LEVELS];         // ... the class-major records' own overflow words (spconv_upc.hip)
+  int level_rows;                            // levels_hashed, levels 2 and 3: the level's scan total
+};
+static_assert(sizeof(ReadBack) <= 32768, "eyoc_create's pinned staging");
+
 // a failed build's fault masks (dup [32], range [32], read back with its error counts) -> the ctx, for eyoc_maps_last_fault_batches:
 // the mask of the kind the build fails with, only (the caller-order path stops at the range check before it looks for duplicates)
-void keep_fault_masks(eyoc_ctx* ctx, const int* h, int code) {
-  if (code == EYOC_ERR_DUPLICATE) memcpy(ctx->fault_dup, h, 32 * sizeof(uint32_t));
-  if (code == EYOC_ERR_RANGE) memcpy(ctx->fault_range, h + 32, 32 * sizeof(uint32_t));
+void keep_fault_masks(eyoc_ctx* ctx, const unsigned int* masks, int code) {
+  if (code == EYOC_ERR_DUPLICATE) memcpy(ctx->fault_dup, masks, 32 * sizeof(uint32_t));
+  if (code == EYOC_ERR_RANGE) memcpy(ctx->fault_range, masks + 32, 32 * sizeof(uint32_t));
 }
+
+// the two faults of the input: EYOC_ERR_RANGE / EYOC_ERR_DUPLICATE with `count` rows; masks: a read-back's dup_mask (range_mask follows it)
+int data_fault(eyoc_ctx* ctx, int code, int count, const unsigned int* masks) {
+  if (code == EYOC_ERR_RANGE)
+    set_error("eyoc_maps_build: %d coordinate rows outside the supported key range (|c| < 2^17 - 16, 0 <= batch < 1024)", count);
+  else
+    set_error("eyoc_maps_build: %d duplicate coordinate rows (a sparse tensor needs unique coordinates)", count);
+  keep_fault_masks(ctx, masks, code);
+  return code;
+}
+
+#define MAPS_TRY(expr) do { if (int _rc = (expr)) return _rc; } while (0)
+
+// One build, stage by stage (eyoc_maps_build_ordered lists them).  Every stage takes what it needs from the carver, checks that it
+// fitted (fits()) and only then enqueues work, so a build that does not fit its workspace stops before it writes outside it.  The
+// stages take in the order the arrays have always had in the workspace, and two places rely on it: prefill_links_and_top_table fills
+// the three child lists and the top table's keys with ONE fill, and levels_fused borrows `flag` for its tile partials.
+struct MapBuild {
+  eyoc_ctx* ctx;
+  const eyoc_ctx::Knobs& kn;
+  const int32_t* coords_dev;
+  const int n;
+  hipStream_t st;
+  Carver cv;
+  std::unique_ptr<eyoc_maps> m{new eyoc_maps()};      // freed on every failure exit; ~eyoc_maps waits for pending fills
+  ReadBack* host;
+  Counters* dev = nullptr;
+  int *slot = nullptr, *flag = nullptr, *partial = nullptr;
+  bool zorder, use_up, use_upc, lazy, use_down;
+  int pre_rows[EYOC_MAX_LEVELS];                      // Z-order: known before the levels are built
+  // tiling orders (plan_orders): segment numbers per table, -1 = no order
+  static constexpr int TAG_SHIFT = UP_KEY_BITS, TAG_BITS = 4;   // pattern keys < 2^11, window number, segment tag above (at most 10 segments)
+  int seg_up[EYOC_MAX_LEVELS], seg_s1[EYOC_MAX_LEVELS], seg_dn[EYOC_MAX_LEVELS], seg_base[3 * EYOC_MAX_LEVELS];
+  size_t total = 0, sort_bytes = 0;
+  int wshift = -1;
+  unsigned int *key_in = nullptr, *key_out = nullptr;
+  int* row_in = nullptr;
+  int32_t* perm_all = nullptr;
+  void* sort_tmp = nullptr;
+
+  MapBuild(eyoc_ctx* ctx_, const int32_t* coords, int n_, void* ws, size_t ws_bytes, hipStream_t st_, int order)
+      : ctx(ctx_), kn(ctx_->knobs), coords_dev(coords), n(n_), st(st_), cv(ws, ws_bytes), host((ReadBack*)ctx_->pinned) {
+    const int order_mode = kn.maps_internal_order >= 0 ? kn.maps_internal_order : order;   // the ctx's switch (tests) beats the call's wish
+    zorder = order_mode > 0 || (order_mode < 0 && n >= ZORDER_MIN_ROWS);
+    // transposed tables on Z-ordered maps: class-major tiles (spconv_upc.hip) for batches, Morton tiles (spconv_up.hip) below
+    // UPC_MIN_ROWS voxels - the partition's five small launches per level cost a single pair (60 k voxels) more than its kernel saves
+    // (eyoc_spconv_upc_min_rows, default 2^17)
+    use_upc = kn.up_kernel == 2 && n >= kn.upc_min_rows;
+    use_up = kn.up_kernel == 1 || (kn.up_kernel == 2 && !use_upc);
+    // lazy tables (common.h eyoc_maps): the level-0 stride-1 table and the transposed tables are read by their record builders only
+    lazy = zorder && use_upc && kn.maps_lazy_tables != 0;
+    // strided tables (outputs = the rows of level l + 1) in 128-row tiles: batches only - a single pair's 97 level-1 tiles do not fill the chip
+    use_down = kn.down_kernel == 1 && n >= kn.upc_min_rows;
+    m->n_levels = EYOC_MAX_LEVELS;
+    m->rows[0] = pre_rows[0] = n;
+    for (int l = 1; l < EYOC_MAX_LEVELS; ++l) pre_rows[l] = 0;
+  }
+
+  int fits() const {
+    EYOC_REQUIRE(cv.ok(), EYOC_ERR_WORKSPACE, "eyoc_maps_build: internal workspace accounting error (%zu > %zu)", cv.off, cv.cap);
+    return EYOC_OK;
+  }
+
+  // ---- level 0: the caller's rows
+  int start() {
+    dev = cv.take<Counters>(1);
+    slot = cv.take<int>(n);
+    flag = cv.take<int>(n);
+    partial = cv.take<int>(n / SCAN_TILE + 2);
+    m->coords[0] = cv.take<int32_t>((size_t)n * 4);
+    MAPS_TRY(fits());
+    EYOC_CHECK_HIP(hipMemsetAsync(dev, 0, sizeof(Counters), st));
+    return EYOC_OK;
+  }
+
+  int copy_rows() {   // ... in the caller's order
+    EYOC_CHECK_HIP(hipMemcpyAsync(m->coords[0], coords_dev, (size_t)n * 16, hipMemcpyDeviceToDevice, st));
+    return EYOC_OK;
+  }
+
+  // ... in Z-order: Morton sort, every level's row count and the validation with one read-back
+  int sort_z() {
+    unsigned long long* zk_in = cv.take<unsigned long long>(n);
+    unsigned long long* zk_out = cv.take<unsigned long long>(n);
+    int* zr_in = cv.take<int>(n);
+    m->row_perm = cv.take<int32_t>(n);
+    const size_t zb = sort_rows64_tmp_bytes(n);
+    void* ztmp = cv.take<char>(zb);
+    MAPS_TRY(fits());
+    // The key width is speculated from the ctx's previous build (KITTI-shaped clouds: 10 + 10 + 10 + 7 bits = five 8-bit radix
+    // passes instead of eight); a batch that does not fit sorts once more with the full width.
+    int kbits = ctx->zorder_kbits, bbits = ctx->zorder_bbits;
+    const Counters::Levels& lv = host->sorted.levels;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      if (attempt) EYOC_CHECK_HIP(hipMemsetAsync(&dev->levels, 0, sizeof(dev->levels), st));
+      hipLaunchKernelGGL(k_morton_key, dim3(cdiv(n, 256)), dim3(256), 0, st, coords_dev, n, kbits, zk_in, zr_in);
+      MAPS_TRY(sort_rows_by_key64(ztmp, zb, zk_in, zk_out, zr_in, m->row_perm, n, 3 * (kbits + 1) + bbits, st));
+      hipLaunchKernelGGL(k_gather_coords, dim3(cdiv(n, 256)), dim3(256), 0, st, coords_dev, m->row_perm, n, m->coords[0]);
+      hipLaunchKernelGGL(k_count_levels, dim3(cdiv(n, 256) < 1024 ? cdiv(n, 256) : 1024), dim3(256), 0, st, m->coords[0], n, kbits, bbits,
+                         &dev->levels.misfit, dev->dup_mask);
+      // (the fault masks ride along: they end the block)
+      EYOC_CHECK_HIP(hipMemcpyAsync(&host->sorted.levels, &dev->levels, sizeof(Counters) - offsetof(Counters, levels), hipMemcpyDeviceToHost, st));
+      EYOC_CHECK_HIP(hipStreamSynchronize(st));
+      if (lv.misfit == 0) break;                                        // every row fitted the speculated width
+      kbits = 17; bbits = 10;
+    }
+    // next build: one bit of head room over what this one needed
+    int kb = 1, bb = 1;
+    while (kb < 17 && (1 << kb) <= lv.max_coord) ++kb;
+    while (bb < 10 && (1 << bb) <= lv.max_batch) ++bb;
+    ctx->zorder_kbits = kb + 1 < 17 ? kb + 1 : 17;
+    ctx->zorder_bbits = bb + 1 < 10 ? bb + 1 : 10;
+    if (lv.range != 0) return data_fault(ctx, EYOC_ERR_RANGE, lv.range, host->sorted.dup_mask);
+    if (lv.dup != 0) return data_fault(ctx, EYOC_ERR_DUPLICATE, lv.dup, host->sorted.dup_mask);
+    for (int l = 1; l < EYOC_MAX_LEVELS; ++l) pre_rows[l] = lv.rows[l - 1];
+    return EYOC_OK;
+  }
+
+  // Level 0 needs no hash table: validation rides on the level-1 build (range check in its k_insert, duplicate
+  // rows = two rows in one child slot in k_children); the first convolution walks the octree (spconv.hip).  The
+  // table's memory stays reserved so that maps_build_table0 can build it for the hash-probing fallback.
+  int reserve_table0() {
+    const unsigned int cap = table_capacity(n);
+    m->table[0].keys = cv.take<unsigned long long>(cap);
+    m->table[0].vals = cv.take<int>(cap);
+    m->table[0].mask = cap - 1;
+    m->table0_built = false;
+    return fits();
+  }
+
+  // Z-ordered rows: every level's row count is known by now, so the links' and the coarsest table's fills go out up front - between the
+  // short dependent kernels of a level each costs a launch gap (a single pair: five fills, ~8 us apiece on the critical path)
+  int prefill_links_and_top_table() {
+    for (int l = 1; l < EYOC_MAX_LEVELS; ++l) m->children[l - 1] = cv.take<int32_t>((size_t)pre_rows[l] * 8);
+    HashTable& tt = m->table[EYOC_MAX_LEVELS - 1];
+    const unsigned int top_cap = table_capacity(pre_rows[EYOC_MAX_LEVELS - 2]);
+    tt.keys = cv.take<unsigned long long>(top_cap);
+    tt.vals = cv.take<int>(top_cap);
+    tt.mask = top_cap - 1;
+    MAPS_TRY(fits());
+    // RELIES ON THE CARVE ORDER: the three link arrays and the table's keys were taken back to back just above and all start as 0xFF
+    // bytes - ONE fill (the alignment gaps between them belong to nobody) instead of four; a fill is a ~5 us launch on the build's critical path
+    EYOC_CHECK_HIP(hipMemsetAsync(m->children[0], 0xFF, (size_t)((char*)(tt.keys + top_cap) - (char*)m->children[0]), st));
+    EYOC_CHECK_HIP(hipMemsetAsync(tt.vals, 0x7F, (size_t)top_cap * 4, st));
+    return EYOC_OK;
+  }
+
+  // ---- the coarser levels, three ways
+  // Z-ordered rows, both ways: the row counts are k_count_levels'; the same arrays in the same order
+  int carve_sorted_levels() {
+    for (int l = 1; l < EYOC_MAX_LEVELS; ++l) {
+      m->rows[l] = pre_rows[l];
+      m->coords[l] = cv.take<int32_t>((size_t)m->rows[l] * 4);
+      m->parent[l - 1] = cv.take<int32_t>((size_t)m->rows[l - 1]);
+    }
+    return fits();
+  }
+  // the coarsest level's table (k_neighbours probes it): its UNIQUE rows are inserted - one uncontended CAS per voxel instead of one
+  // per finer row, four neighbouring lanes fighting over every slot (118 -> ~20 us on the bench batch).  Filled up front (prefill_links_and_top_table).
+  void insert_top_rows() {
+    const int lt = EYOC_MAX_LEVELS - 1;
+    hipLaunchKernelGGL(k_insert, dim3(cdiv(m->rows[lt], 256)), dim3(256), 0, st, m->coords[lt], m->rows[lt], 1 << lt, m->table[lt], (int*)nullptr,
+                       &dev->faults.range);
+  }
+
+  // all three in two launches (k_levels_count / k_levels_fill)
+  int levels_fused() {
+    MAPS_TRY(carve_sorted_levels());
+    LevelOut lo;
+    for (int l = 1; l < EYOC_MAX_LEVELS; ++l) { lo.coords[l - 1] = m->coords[l]; lo.parent[l - 1] = m->parent[l - 1]; lo.children[l - 1] = m->children[l - 1]; }
+    const int tiles = cdiv(n, LV_TILE);
+    // RELIES ON THE CARVE ORDER: [tiles][4] <= n ints (n < 4: the carver's 256-byte granule) - the flag array is free on this path
+    int* part = flag;
+    hipLaunchKernelGGL(k_levels_count, dim3(tiles), dim3(LV_BLOCK), 0, st, m->coords[0], n, part, &dev->faults.range);
+    hipLaunchKernelGGL(k_levels_fill, dim3(tiles), dim3(LV_BLOCK), 0, st, m->coords[0], n, part, lo, &dev->faults.scan_total[1]);
+    insert_top_rows();
+    return EYOC_OK;
+  }
+
+  // level by level without a hash table: adjacent rows (see k_flag_sorted)
+  int levels_sorted() {
+    MAPS_TRY(carve_sorted_levels());
+    for (int l = 1; l < EYOC_MAX_LEVELS; ++l) {
+      const int n_src = m->rows[l - 1], ts2 = 1 << l, nb = cdiv(n_src, SCAN_TILE);
+      const int32_t* src = m->coords[l - 1];
+      hipLaunchKernelGGL(k_flag_sorted, dim3(cdiv(n_src, 256)), dim3(256), 0, st, src, n_src, ts2, flag,
+                         l == 1 ? &dev->faults.range : (int*)nullptr, l == 1 ? &dev->faults.dup : (int*)nullptr);
+      hipLaunchKernelGGL(k_scan_partials, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, n_src, partial);
+      hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(SCAN_BLOCK), 0, st, partial, nb, &dev->faults.scan_total[l]);
+      hipLaunchKernelGGL(k_compact_sorted, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, partial, src, n_src, ts2, l - 1,
+                         m->coords[l], m->parent[l - 1], m->children[l - 1]);
+    }
+    insert_top_rows();
+    return EYOC_OK;
+  }
+
+  // the caller's order: the table of a level is built from the previous level's rows, whose number comes back level by level
+  int levels_hashed() {
+    for (int l = 1; l < EYOC_MAX_LEVELS; ++l) {
+      const int n_src = m->rows[l - 1], ts2 = 1 << l, nb = cdiv(n_src, SCAN_TILE);
+      const int32_t* src = m->coords[l - 1];
+      HashTable& t = m->table[l];
+      const unsigned int cap = table_capacity(n_src);
+      t.keys = cv.take<unsigned long long>(cap);
+      t.vals = cv.take<int>(cap);
+      t.mask = cap - 1;
+      MAPS_TRY(fits());
+      EYOC_CHECK_HIP(hipMemsetAsync(t.keys, 0xFF, (size_t)cap * 8, st));
+      EYOC_CHECK_HIP(hipMemsetAsync(t.vals, 0x7F, (size_t)cap * 4, st));
+      hipLaunchKernelGGL(k_insert, dim3(cdiv(n_src, 256)), dim3(256), 0, st, src, n_src, ts2, t, slot, &dev->faults.range,
+                         l == 1 ? dev->range_mask : (unsigned int*)nullptr);
+      hipLaunchKernelGGL(k_flag, dim3(cdiv(n_src, 256)), dim3(256), 0, st, slot, t.vals, n_src, flag, (int*)nullptr);
+      hipLaunchKernelGGL(k_scan_partials, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, n_src, partial);
+      hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(SCAN_BLOCK), 0, st, partial, nb, &dev->faults.scan_total[l]);
+      if (l == 1) {   // the level's total, the error counts and the fault masks in one copy
+        EYOC_CHECK_HIP(hipMemcpyAsync(&host->level1, dev, sizeof(Counters), hipMemcpyDeviceToHost, st));
+        EYOC_CHECK_HIP(hipStreamSynchronize(st));
+        if (host->level1.faults.range != 0) return data_fault(ctx, EYOC_ERR_RANGE, host->level1.faults.range, host->level1.dup_mask);
+        m->rows[l] = host->level1.faults.scan_total[l];
+      } else {
+        EYOC_CHECK_HIP(hipMemcpyAsync(&host->level_rows, &dev->faults.scan_total[l], sizeof(int), hipMemcpyDeviceToHost, st));
+        EYOC_CHECK_HIP(hipStreamSynchronize(st));
+        m->rows[l] = host->level_rows;
+      }
+      m->coords[l] = cv.take<int32_t>((size_t)m->rows[l] * 4);
+      m->parent[l - 1] = cv.take<int32_t>((size_t)n_src);
+      m->children[l - 1] = cv.take<int32_t>((size_t)m->rows[l] * 8);
+      MAPS_TRY(fits());
+      EYOC_CHECK_HIP(hipMemsetAsync(m->children[l - 1], 0xFF, (size_t)m->rows[l] * 32, st));
+      hipLaunchKernelGGL(k_compact<false>, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, partial, slot, src, n_src, ts2,
+                         m->coords[l], t.vals, (int32_t*)nullptr);
+      // octree links fine (l-1) <-> coarse (l); same stream, so k_compact's re-labelling is visible
+      hipLaunchKernelGGL(k_children, dim3(cdiv(n_src, 256)), dim3(256), 0, st, slot, t.vals, src, n_src, l - 1,
+                         m->parent[l - 1], m->children[l - 1], l == 1 ? &dev->faults.dup : (int*)nullptr,
+                         l == 1 ? dev->dup_mask : (unsigned int*)nullptr);
+      if (l == 1) {   // the duplicate count and the fault masks in one copy
+        EYOC_CHECK_HIP(hipMemcpyAsync(&host->level1, dev, sizeof(Counters), hipMemcpyDeviceToHost, st));
+        EYOC_CHECK_HIP(hipStreamSynchronize(st));
+        if (host->level1.faults.dup != 0) return data_fault(ctx, EYOC_ERR_DUPLICATE, host->level1.faults.dup, host->level1.dup_mask);
+      }
+    }
+    return EYOC_OK;
+  }
+
+  // ---- rulebooks: hash probes at the coarsest level only, everything else derived top-down
+  int neighbour_tables() {
+    for (int l = 0; l < EYOC_MAX_LEVELS; ++l) {
+      m->nbr_s1[l] = cv.take<int32_t>((size_t)27 * m->rows[l]);
+      if (l + 1 < EYOC_MAX_LEVELS) {
+        m->nbr_down[l] = cv.take<int32_t>((size_t)27 * m->rows[l + 1]);
+        m->nbr_up[l] = cv.take<int32_t>((size_t)27 * m->rows[l]);
+        if (lazy) {
+          m->up8[l] = cv.take<int32_t>((size_t)8 * m->rows[l]);
+          m->up_ready[l] = false;
+        }
+      }
+    }
+    if (lazy) m->s1_ready[0] = false;
+    MAPS_TRY(fits());
+    const int top = EYOC_MAX_LEVELS - 1;
+    hipLaunchKernelGGL(k_neighbours, dim3(cdiv(m->rows[top], 256)), dim3(256), 0, st, m->coords[top], m->rows[top],
+                       m->table[top], 1 << top, 1, m->nbr_s1[top]);
+    return EYOC_OK;
+  }
+
+  // ---- tiling orders (perm_up / perm_s1): every ordered table contributes a segment of (key, row) pairs tagged with
+  // its segment number in the high key bits, and ONE stable radix sort orders all segments at once (seven separate
+  // rocPRIM sorts cost 38 small launches, 0.7 ms per 64-cloud batch).  The orders only serve the wave-private
+  // convolution kernel, which takes over above ~4000 row tiles: small levels (single-pair latency path) skip them.
+  // Which tables get one, and the sort's arrays: host arithmetic, nothing is enqueued.
+  int plan_orders() {
+    const bool s1_order = kn.maps_s1_order != 0;
+    int n_seg = 0;
+    for (int l = 0; l < EYOC_MAX_LEVELS; ++l) {
+      seg_up[l] = seg_s1[l] = seg_dn[l] = -1;
+      // Z-ordered maps tile the strided convolutions in natural order: a tile's 64 coarse rows read their (adjacent)
+      // children, which beats the pattern order's fuller chunks (2.38 -> 2.25 ms for the three layers;
+      // eyoc_maps_select_orders(-1, 1) restores the sort)
+      const bool dn_order = kn.maps_down_order == 1;
+      if (l + 1 < EYOC_MAX_LEVELS && m->rows[l + 1] >= kn.maps_order_min_rows && (dn_order || !zorder)) {   // outputs of the strided conv l -> l+1
+        seg_dn[l] = n_seg; seg_base[n_seg++] = (int)total; total += m->rows[l + 1];
+      }
+      if (m->rows[l] < kn.maps_order_min_rows) continue;
+      // the transposed tables' order serves the gathering kernels only: Z-ordered maps with the staged transposed kernel (which sorts
+      // inside its tiles) skip it - and with it the whole radix sort, nothing else being ordered there (0.3 ms per 128-cloud batch)
+      if (l + 1 < EYOC_MAX_LEVELS && !(zorder && (use_up || use_upc))) { seg_up[l] = n_seg; seg_base[n_seg++] = (int)total; total += m->rows[l]; }
+      if (s1_order && !zorder) { seg_s1[l] = n_seg; seg_base[n_seg++] = (int)total; total += m->rows[l]; }
+    }
+    wshift = zorder ? kn.maps_window_shift : -1;
+    key_in = cv.take<unsigned int>(total);
+    key_out = cv.take<unsigned int>(total);
+    row_in = cv.take<int>(total);
+    perm_all = cv.take<int32_t>(total);
+    sort_bytes = sort_rows_tmp_bytes((int)total, TAG_SHIFT + TAG_BITS);
+    sort_tmp = cv.take<char>(sort_bytes);
+    return fits();
+  }
+
+  int derive_tables() {
+    for (int l = EYOC_MAX_LEVELS - 2; l >= 0; --l) {
+      const int nl = m->rows[l], nc = m->rows[l + 1];
+      const int su = seg_up[l];
+      if (lazy) {
+        // levels >= 1: the stride-1 table (the next finer level derives from it) + the compact transposed table; level 0: nothing here -
+        // its tile-record builder derives the windows itself and writes up8[0] on the way (build_local_rulebook_derived, tile_records)
+        if (l > 0)
+          hipLaunchKernelGGL((k_derive_fine<true, 2>), dim3(cdiv(nl, 256)), dim3(256), 0, st, m->coords[l], nl, l, m->parent[l], m->children[l],
+                             m->nbr_s1[l + 1], nc, m->nbr_s1[l], m->up8[l], (unsigned int*)nullptr, (int*)nullptr, 0u, wshift);
+      } else {
+        hipLaunchKernelGGL((k_derive_fine<true, 1>), dim3(cdiv(nl, 256)), dim3(256), 0, st, m->coords[l], nl, l, m->parent[l],
+                           m->children[l], m->nbr_s1[l + 1], nc, m->nbr_s1[l], m->nbr_up[l],
+                           su >= 0 ? key_in + seg_base[su] : (unsigned int*)nullptr, su >= 0 ? row_in + seg_base[su] : (int*)nullptr,
+                           (unsigned int)(su >= 0 ? su : 0) << TAG_SHIFT, wshift);
+      }
+      hipLaunchKernelGGL(k_derive_down, dim3(cdiv(nc, 256)), dim3(256), 0, st, nc, m->children[l], m->nbr_s1[l + 1],
+                         m->nbr_down[l]);
+    }
+    return EYOC_OK;
+  }
+
+  int order_keys() {   // (the transposed tables' keys: k_derive_fine, above)
+    for (int l = 0; l + 1 < EYOC_MAX_LEVELS; ++l) {
+      const int sd = seg_dn[l];
+      if (sd < 0) continue;
+      hipLaunchKernelGGL(k_children_key, dim3(cdiv(m->rows[l + 1], 256)), dim3(256), 0, st, m->children[l], m->rows[l + 1],
+                         key_in + seg_base[sd], row_in + seg_base[sd], (unsigned int)sd << TAG_SHIFT, wshift);
+    }
+    for (int l = 0; l < EYOC_MAX_LEVELS; ++l) {
+      const int ss = seg_s1[l];
+      if (ss < 0) continue;
+      const int bits = l == 0 ? 2 : 4;   // level 0 feeds the 32-channel, bandwidth-bound layers: keep more locality
+      hipLaunchKernelGGL(k_pattern_key, dim3(cdiv(m->rows[l], 256)), dim3(256), 0, st, m->nbr_s1[l], m->rows[l], bits,
+                         key_in + seg_base[ss], row_in + seg_base[ss], (unsigned int)ss << TAG_SHIFT, wshift);
+    }
+    return EYOC_OK;
+  }
+
+  int sort_orders() {
+    if (total == 0) return EYOC_OK;
+    MAPS_TRY(sort_rows_by_key(sort_tmp, sort_bytes, key_in, key_out, row_in, perm_all, (int)total, TAG_SHIFT + TAG_BITS, st));
+    for (int l = 0; l < EYOC_MAX_LEVELS; ++l) {
+      if (seg_up[l] >= 0) m->perm_up[l] = perm_all + seg_base[seg_up[l]];
+      if (seg_s1[l] >= 0) m->perm_s1[l] = perm_all + seg_base[seg_s1[l]];
+      if (seg_dn[l] >= 0) m->perm_down[l] = perm_all + seg_base[seg_dn[l]];
+    }
+    return EYOC_OK;
+  }
+
+  // ---- local rulebooks (tile-local input stage of the sparse convolution): only for Z-ordered rows.  The builders' overflow words
+  // are zero since start()'s fill of the whole block (nothing in between writes them).
+  int tile_records() {
+    unsigned char* upc_scratch[EYOC_MAX_LEVELS] = {};
+    // the coarsest level's stride-1 table in 128-row tiles too: its layers have 256 channels, and a workgroup of 128 rows x 128 channels
+    // stages a tile's rows once per 128 output channels instead of once per 64 (block4: 0.89 -> 0.78 ms per layer on the bench batch; the
+    // 128-channel layers of level 2 measured level - 0.84 -> 0.83 - and keep the 256-row tiles)
+    const int top = EYOC_MAX_LEVELS - 1;
+    const bool s1_wide = use_down && kn.s1_wide;
+    for (int l = 0; l < EYOC_MAX_LEVELS; ++l) {
+      m->local_s1[l] = cv.take<unsigned char>(local_rulebook_bytes(m->rows[l]));
+      if (l < top && use_up) m->local_up[l] = cv.take<unsigned char>(local_rulebook_up_bytes(m->rows[l]));   // the transposed table whose outputs are this level's rows
+      if (l < top && use_upc) {                                                                               // ... in class-major order (spconv_upc.hip)
+        m->local_upc[l] = cv.take<unsigned char>(upc_kept_bytes(m->rows[l]));
+        upc_scratch[l] = cv.take<unsigned char>(upc_scratch_bytes(m->rows[l]));
+      }
+    }
+    if (s1_wide) m->local_s1w[top] = cv.take<unsigned char>(local_rulebook128_bytes(m->rows[top]));
+    for (int l = 0; l < top && use_down; ++l) m->local_down[l] = cv.take<unsigned char>(local_rulebook128_bytes(m->rows[l + 1]));
+    MAPS_TRY(fits());
+    Counters::Overflow& ovf = dev->overflow;
+    for (int l = 0; l < EYOC_MAX_LEVELS; ++l) {
+      if (lazy && l == 0) {
+        DeriveSrc src;
+        src.coords = m->coords[0]; src.parent = m->parent[0]; src.children = m->children[0]; src.s1c = m->nbr_s1[1];
+        src.nc = m->rows[1]; src.sh = 0; src.up8 = m->up8[0];
+        MAPS_TRY(build_local_rulebook_derived(src, m->rows[0], m->local_s1[0], &ovf.s1, st, kn.st_group));
+      } else {
+        MAPS_TRY(build_local_rulebook(m->nbr_s1[l], 27, m->rows[l], m->local_s1[l], &ovf.s1, st, kn.st_group));
+      }
+      if (l < top && use_up) MAPS_TRY(build_local_rulebook_up(m->nbr_up[l], 27, m->rows[l], m->local_up[l], &ovf.up, st));
+      if (l < top && use_upc)
+        MAPS_TRY(build_upc(lazy ? m->up8[l] : m->nbr_up[l], m->coords[l], 1 << l, m->rows[l], m->local_upc[l], upc_scratch[l], st, lazy));
+    }
+    if (s1_wide) MAPS_TRY(build_local_rulebook128(m->nbr_s1[top], 27, m->rows[top], m->local_s1w[top], &ovf.s1w, st, kn.st_group));
+    for (int l = 0; l < top && use_down; ++l)
+      MAPS_TRY(build_local_rulebook128(m->nbr_down[l], 27, m->rows[l + 1], m->local_down[l], &ovf.down[l], st, kn.st_group));
+    return EYOC_OK;
+  }
+
+  // the second synchronisation: the scans' own verdicts and totals, and the records that overflowed
+  int read_back_records() {
+    for (int l = 0; l < EYOC_MAX_LEVELS; ++l) {
+      host->upc_overflow[l] = 0;
+      if (m->local_upc[l])
+        EYOC_CHECK_HIP(hipMemcpyAsync(&host->upc_overflow[l], upc_overflow_ptr(m->local_upc[l]), sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    EYOC_CHECK_HIP(hipMemcpyAsync(&host->overflow, &dev->overflow, sizeof(host->overflow), hipMemcpyDeviceToHost, st));
+    EYOC_CHECK_HIP(hipMemcpyAsync(&host->late, &dev->faults, sizeof(host->late), hipMemcpyDeviceToHost, st));   // errors + the scans' own totals
+    EYOC_CHECK_HIP(hipStreamSynchronize(st));
+    // the masks: k_count_levels', read back by sort_z (the level kernels count these faults again but keep no masks)
+    if (host->late.range != 0) return data_fault(ctx, EYOC_ERR_RANGE, host->late.range, host->sorted.dup_mask);
+    if (host->late.dup != 0) return data_fault(ctx, EYOC_ERR_DUPLICATE, host->late.dup, host->sorted.dup_mask);
+    for (int l = 1; l < EYOC_MAX_LEVELS; ++l)
+      EYOC_REQUIRE(host->late.scan_total[l] == m->rows[l], EYOC_ERR_INVALID,
+                   "eyoc_maps_build: internal error - level %d has %d rows by its scan, %d by the up-front count", l, host->late.scan_total[l], m->rows[l]);
+    const Counters::Overflow& ovf = host->overflow;
+    if (ovf.s1 != 0) {   // a tile with more distinct input rows than two passes stage (does not happen for Z-ordered rows): no staged kernel
+      for (int l = 0; l < EYOC_MAX_LEVELS; ++l) m->local_s1[l] = nullptr;
+      MAPS_TRY(maps_ensure_table(m.get(), EYOC_MAP_S1, 0, st));   // the gathering kernels read the table
+    }
+    if (ovf.up != 0)   // ... more than 639 distinct coarse rows under a 256-row tile
+      for (int l = 0; l < EYOC_MAX_LEVELS; ++l) m->local_up[l] = nullptr;
+    for (int l = 0; l + 1 < EYOC_MAX_LEVELS; ++l)   // a 128-row coarse tile with more than 1278 distinct fine rows: that strided table stays on the gathering kernel
+      if (ovf.down[l] != 0) m->local_down[l] = nullptr;
+    if (ovf.s1w != 0)
+      for (int l = 0; l < EYOC_MAX_LEVELS; ++l) m->local_s1w[l] = nullptr;
+    for (int l = 0; l < EYOC_MAX_LEVELS; ++l)   // a class tile with more than 1278 distinct coarse rows: that table stays on the gathering kernels
+      if (host->upc_overflow[l] != 0) {
+        m->local_upc[l] = nullptr;
+        MAPS_TRY(maps_ensure_table(m.get(), EYOC_MAP_UP, l, st));
+      }
+    return EYOC_OK;
+  }
+
+  int finish() {
+    EYOC_CHECK_HIP(hipGetLastError());
+    return fits();                          // the backstop: every stage has checked its own takes
+  }
+};
 
 }  // namespace
 
@@ -841,393 +1308,23 @@ int eyoc_maps_build_ordered(eyoc_ctx* ctx, const int32_t* coords_dev, int n, voi
   EYOC_REQUIRE(((uintptr_t)ws & 255) == 0, EYOC_ERR_INVALID, "eyoc_maps_build: workspace must be 256-byte aligned");
   EYOC_REQUIRE(ws_bytes >= eyoc_maps_workspace_bytes(n), EYOC_ERR_WORKSPACE,
                "eyoc_maps_build: workspace %zu < required %zu bytes", ws_bytes, eyoc_maps_workspace_bytes(n));
-  hipStream_t st = (hipStream_t)stream;
-  Carver cv(ws, ws_bytes);
-  eyoc_maps* m = new eyoc_maps();
-  m->n_levels = EYOC_MAX_LEVELS;
-  int* counters = cv.take<int>(128);      // [0] range errors, [1] duplicates, [2+l] coarse totals; [64, 128): the fault masks
-  unsigned int* fault_masks = (unsigned int*)(counters + 64);   // dup [32], range [32] (eyoc_maps_last_fault_batches)
-  int* slot = cv.take<int>(n);
-  int* flag = cv.take<int>(n);
-  int* partial = cv.take<int>(n / SCAN_TILE + 2);
-  int* host = (int*)ctx->pinned;
-#define FAIL_HIP(expr)                                                                       \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess) {                                                                  \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);  \
-      delete m;                                                                              \
-      return EYOC_ERR_HIP;                                                                   \
-    }                                                                                        \
-  } while (0)
-
-  FAIL_HIP(hipMemsetAsync(counters, 0, 128 * sizeof(int), st));
-  // ---- level 0: the caller's rows, in the caller's order
-  m->rows[0] = n;
-  m->coords[0] = cv.take<int32_t>((size_t)n * 4);
-  const eyoc_ctx::Knobs& kn = ctx->knobs;
-  const int order_mode = kn.maps_internal_order >= 0 ? kn.maps_internal_order : order;   // the ctx's switch (tests) beats the call's wish
-  const bool zorder = order_mode > 0 || (order_mode < 0 && n >= ZORDER_MIN_ROWS);
-  int pre_rows[EYOC_MAX_LEVELS] = {n, 0, 0, 0};                          // Z-order: known before the levels are built
-  if (zorder) {
-    unsigned long long* zk_in = cv.take<unsigned long long>(n);
-    unsigned long long* zk_out = cv.take<unsigned long long>(n);
-    int* zr_in = cv.take<int>(n);
-    m->row_perm = cv.take<int32_t>(n);
-    const size_t zb = sort_rows64_tmp_bytes(n);
-    void* ztmp = cv.take<char>(zb);
-    // The key width is speculated from the ctx's previous build (KITTI-shaped clouds: 10 + 10 + 10 + 7 bits = five 8-bit radix
-    // passes instead of eight); a batch that does not fit sorts once more with the full width.
-    int kbits = ctx->zorder_kbits, bbits = ctx->zorder_bbits;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-      if (attempt) FAIL_HIP(hipMemsetAsync(counters + 16, 0, (EYOC_MAX_LEVELS + 4) * sizeof(int), st));
-      hipLaunchKernelGGL(k_morton_key, dim3(cdiv(n, 256)), dim3(256), 0, st, coords_dev, n, kbits, zk_in, zr_in);
-      if (int rc = sort_rows_by_key64(ztmp, zb, zk_in, zk_out, zr_in, m->row_perm, n, 3 * (kbits + 1) + bbits, st)) { delete m; return rc; }
-      hipLaunchKernelGGL(k_gather_coords, dim3(cdiv(n, 256)), dim3(256), 0, st, coords_dev, m->row_perm, n, m->coords[0]);
-      // every level's row count - and the validation - now, with one read-back
-      hipLaunchKernelGGL(k_count_levels, dim3(cdiv(n, 256) < 1024 ? cdiv(n, 256) : 1024), dim3(256), 0, st, m->coords[0], n, kbits, bbits,
-                         counters + 16, fault_masks);
-      // (the fault masks ride along: host[64, 128))
-      FAIL_HIP(hipMemcpyAsync(host + 16, counters + 16, (128 - 16) * sizeof(int), hipMemcpyDeviceToHost, st));
-      FAIL_HIP(hipStreamSynchronize(st));
-      if (host[16] == 0) break;                                         // every row fitted the speculated width
-      kbits = 17; bbits = 10;
-    }
-    {
-      // next build: one bit of head room over what this one needed
-      int kb = 1, bb = 1;
-      while (kb < 17 && (1 << kb) <= host[16 + EYOC_MAX_LEVELS + 2]) ++kb;
-      while (bb < 10 && (1 << bb) <= host[16 + EYOC_MAX_LEVELS + 3]) ++bb;
-      ctx->zorder_kbits = kb + 1 < 17 ? kb + 1 : 17;
-      ctx->zorder_bbits = bb + 1 < 10 ? bb + 1 : 10;
-    }
-    if (host[16 + EYOC_MAX_LEVELS] != 0) {
-      set_error("eyoc_maps_build: %d coordinate rows outside the supported key range (|c| < 2^17 - 16, 0 <= batch < 1024)",
-                host[16 + EYOC_MAX_LEVELS]);
-      keep_fault_masks(ctx, host + 64, EYOC_ERR_RANGE);
-      delete m;
-      return EYOC_ERR_RANGE;
-    }
-    if (host[16 + EYOC_MAX_LEVELS + 1] != 0) {
-      set_error("eyoc_maps_build: %d duplicate coordinate rows (a sparse tensor needs unique coordinates)", host[16 + EYOC_MAX_LEVELS + 1]);
-      keep_fault_masks(ctx, host + 64, EYOC_ERR_DUPLICATE);
-      delete m;
-      return EYOC_ERR_DUPLICATE;
-    }
-    for (int l = 1; l < EYOC_MAX_LEVELS; ++l) pre_rows[l] = host[16 + l];
-  } else {
-    FAIL_HIP(hipMemcpyAsync(m->coords[0], coords_dev, (size_t)n * 16, hipMemcpyDeviceToDevice, st));
+  MapBuild b(ctx, coords_dev, n, ws, ws_bytes, (hipStream_t)stream, order);
+  MAPS_TRY(b.start());
+  MAPS_TRY(b.zorder ? b.sort_z() : b.copy_rows());
+  MAPS_TRY(b.reserve_table0());
+  if (b.zorder) MAPS_TRY(b.prefill_links_and_top_table());
+  MAPS_TRY(!b.zorder ? b.levels_hashed() : b.kn.maps_fused_levels ? b.levels_fused() : b.levels_sorted());
+  MAPS_TRY(b.neighbour_tables());
+  MAPS_TRY(b.plan_orders());
+  MAPS_TRY(b.derive_tables());
+  MAPS_TRY(b.order_keys());
+  MAPS_TRY(b.sort_orders());
+  if (b.zorder) {
+    MAPS_TRY(b.tile_records());
+    MAPS_TRY(b.read_back_records());
   }
-  // Level 0 needs no hash table: validation rides on the level-1 build (range check in its k_insert, duplicate
-  // rows = two rows in one child slot in k_children); the first convolution walks the octree (spconv.hip).  The
-  // table's memory stays reserved so that maps_build_table0 can build it for the hash-probing fallback.
-  {
-    const unsigned int cap = table_capacity(n);
-    m->table[0].keys = cv.take<unsigned long long>(cap);
-    m->table[0].vals = cv.take<int>(cap);
-    m->table[0].mask = cap - 1;
-    m->table0_built = false;
-  }
-  // Z-ordered rows: every level's row count is known by now, so the links' and the coarsest table's fills go out up front - between the
-  // short dependent kernels of a level each costs a launch gap (a single pair: five fills, ~8 us apiece on the critical path)
-  unsigned int top_cap = 0;
-  if (zorder) {
-    for (int l = 1; l < EYOC_MAX_LEVELS; ++l) m->children[l - 1] = cv.take<int32_t>((size_t)pre_rows[l] * 8);
-    HashTable& tt = m->table[EYOC_MAX_LEVELS - 1];
-    top_cap = table_capacity(pre_rows[EYOC_MAX_LEVELS - 2]);
-    tt.keys = cv.take<unsigned long long>(top_cap);
-    tt.vals = cv.take<int>(top_cap);
-    tt.mask = top_cap - 1;
-    // the three link arrays and the table's keys are carved back to back and all start as 0xFF bytes: ONE fill (the alignment gaps
-    // between them belong to nobody) instead of four - a fill is a ~5 us launch on the build's critical path
-    FAIL_HIP(hipMemsetAsync(m->children[0], 0xFF, (size_t)((char*)(tt.keys + top_cap) - (char*)m->children[0]), st));
-    FAIL_HIP(hipMemsetAsync(tt.vals, 0x7F, (size_t)top_cap * 4, st));
-  }
-  const bool fused_levels = zorder && kn.maps_fused_levels;
-  if (fused_levels) {
-    // all three coarser levels in two launches (k_levels_count / k_levels_fill); carved in the order the level loop below carves them
-    LevelOut lo;
-    for (int l = 1; l < EYOC_MAX_LEVELS; ++l) {
-      m->rows[l] = pre_rows[l];
-      m->coords[l] = cv.take<int32_t>((size_t)m->rows[l] * 4);
-      m->parent[l - 1] = cv.take<int32_t>((size_t)m->rows[l - 1]);
-      lo.coords[l - 1] = m->coords[l]; lo.parent[l - 1] = m->parent[l - 1]; lo.children[l - 1] = m->children[l - 1];
-    }
-    const int tiles = cdiv(n, LV_TILE);
-    int* part = flag;                                                  // [tiles][4] <= n ints: the flag array is free on this path
-    hipLaunchKernelGGL(k_levels_count, dim3(tiles), dim3(LV_BLOCK), 0, st, m->coords[0], n, part, counters);
-    hipLaunchKernelGGL(k_levels_fill, dim3(tiles), dim3(LV_BLOCK), 0, st, m->coords[0], n, part, lo, counters + 3);
-    const int lt = EYOC_MAX_LEVELS - 1;
-    hipLaunchKernelGGL(k_insert, dim3(cdiv(m->rows[lt], 256)), dim3(256), 0, st, m->coords[lt], m->rows[lt], 1 << lt, m->table[lt], (int*)nullptr, counters);
-  }
-  for (int l = 1; l < EYOC_MAX_LEVELS && !fused_levels; ++l) {
-    // table of THIS level is built from the previous level's rows
-    const int n_src = m->rows[l - 1];
-    const int32_t* src = m->coords[l - 1];
-    const int ts2 = 1 << l;
-    const int nb = cdiv(n_src, SCAN_TILE);
-    const bool sorted_level = zorder;                                  // adjacent rows (see k_flag_sorted); only the coarsest level gets a table, below
-    HashTable& t = m->table[l];
-    if (sorted_level) {
-      hipLaunchKernelGGL(k_flag_sorted, dim3(cdiv(n_src, 256)), dim3(256), 0, st, src, n_src, ts2, flag,
-                         l == 1 ? counters : (int*)nullptr, l == 1 ? counters + 1 : (int*)nullptr);
-    } else {
-      const unsigned int cap = table_capacity(n_src);
-      t.keys = cv.take<unsigned long long>(cap);
-      t.vals = cv.take<int>(cap);
-      t.mask = cap - 1;
-      FAIL_HIP(hipMemsetAsync(t.keys, 0xFF, (size_t)cap * 8, st));
-      FAIL_HIP(hipMemsetAsync(t.vals, 0x7F, (size_t)cap * 4, st));
-      hipLaunchKernelGGL(k_insert, dim3(cdiv(n_src, 256)), dim3(256), 0, st, src, n_src, ts2, t, slot, counters,
-                         l == 1 ? fault_masks + 32 : (unsigned int*)nullptr);
-      hipLaunchKernelGGL(k_flag, dim3(cdiv(n_src, 256)), dim3(256), 0, st, slot, t.vals, n_src, flag, (int*)nullptr);
-    }
-    hipLaunchKernelGGL(k_scan_partials, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, n_src, partial);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(SCAN_BLOCK), 0, st, partial, nb, counters + 2 + l);
-    if (zorder) {
-      m->rows[l] = pre_rows[l];
-    } else {
-    if (l == 1) {   // the level's total, the error counts and the fault masks in one copy (host[128, 256))
-      FAIL_HIP(hipMemcpyAsync(host + 128, counters, 128 * sizeof(int), hipMemcpyDeviceToHost, st));
-      FAIL_HIP(hipStreamSynchronize(st));
-      host[0] = host[128 + 2 + l]; host[1] = host[128]; host[2] = host[128 + 1];
-    } else {
-      FAIL_HIP(hipMemcpyAsync(host, counters + 2 + l, sizeof(int), hipMemcpyDeviceToHost, st));
-      FAIL_HIP(hipStreamSynchronize(st));
-    }
-    if (l == 1 && host[1] != 0) {
-      set_error("eyoc_maps_build: %d coordinate rows outside the supported key range (|c| < 2^17 - 16, 0 <= batch < 1024)", host[1]);
-      keep_fault_masks(ctx, host + 128 + 64, EYOC_ERR_RANGE);
-      delete m;
-      return EYOC_ERR_RANGE;
-    }
-    if (l == 1 && sorted_level && host[2] != 0) {
-      set_error("eyoc_maps_build: %d duplicate coordinate rows (a sparse tensor needs unique coordinates)", host[2]);
-      keep_fault_masks(ctx, host + 128 + 64, EYOC_ERR_DUPLICATE);
-      delete m;
-      return EYOC_ERR_DUPLICATE;
-    }
-    m->rows[l] = host[0];
-    }
-    m->coords[l] = cv.take<int32_t>((size_t)m->rows[l] * 4);
-    m->parent[l - 1] = cv.take<int32_t>((size_t)n_src);
-    if (!zorder) {
-      m->children[l - 1] = cv.take<int32_t>((size_t)m->rows[l] * 8);
-      FAIL_HIP(hipMemsetAsync(m->children[l - 1], 0xFF, (size_t)m->rows[l] * 32, st));
-    }
-    if (sorted_level) {
-      hipLaunchKernelGGL(k_compact_sorted, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, partial, src, n_src, ts2, l - 1,
-                         m->coords[l], m->parent[l - 1], m->children[l - 1]);
-      if (l + 1 == EYOC_MAX_LEVELS) {
-        // the coarsest level's table (k_neighbours probes it): its UNIQUE rows are inserted - one uncontended CAS per voxel
-        // instead of one per finer row, four neighbouring lanes fighting over every slot (118 -> ~20 us on the bench batch)
-        // (table allocated and filled up front, above)
-        hipLaunchKernelGGL(k_insert, dim3(cdiv(m->rows[l], 256)), dim3(256), 0, st, m->coords[l], m->rows[l], ts2, t, (int*)nullptr, counters);
-      }
-      continue;
-    }
-    hipLaunchKernelGGL(k_compact<false>, dim3(nb), dim3(SCAN_BLOCK), 0, st, flag, partial, slot, src, n_src, ts2,
-                       m->coords[l], t.vals, (int32_t*)nullptr);
-    // octree links fine (l-1) <-> coarse (l); same stream, so k_compact's re-labelling is visible
-    hipLaunchKernelGGL(k_children, dim3(cdiv(n_src, 256)), dim3(256), 0, st, slot, t.vals, src, n_src, l - 1,
-                       m->parent[l - 1], m->children[l - 1], l == 1 ? counters + 1 : (int*)nullptr,
-                       l == 1 ? fault_masks : (unsigned int*)nullptr);
-    if (l == 1) {   // the duplicate count and the fault masks in one copy
-      FAIL_HIP(hipMemcpyAsync(host + 128, counters, 128 * sizeof(int), hipMemcpyDeviceToHost, st));
-      FAIL_HIP(hipStreamSynchronize(st));
-      host[0] = host[128 + 1];
-      if (host[0] != 0) {
-        set_error("eyoc_maps_build: %d duplicate coordinate rows (a sparse tensor needs unique coordinates)", host[0]);
-        keep_fault_masks(ctx, host + 128 + 64, EYOC_ERR_DUPLICATE);
-        delete m;
-        return EYOC_ERR_DUPLICATE;
-      }
-    }
-  }
-  // ---- rulebooks: hash probes at the coarsest level only, everything else derived top-down
-  // transposed tables on Z-ordered maps: class-major tiles (spconv_upc.hip) for batches, Morton tiles (spconv_up.hip) below
-  // UPC_MIN_ROWS voxels - the partition's five small launches per level cost a single pair (60 k voxels) more than its kernel saves
-  // (eyoc_spconv_upc_min_rows, default 2^17)
-  const bool use_upc = kn.up_kernel == 2 && n >= kn.upc_min_rows;
-  const bool use_up = kn.up_kernel == 1 || (kn.up_kernel == 2 && !use_upc);
-  // lazy tables (common.h eyoc_maps): the level-0 stride-1 table and the transposed tables are read by their record builders only
-  const bool lazy = zorder && use_upc && kn.maps_lazy_tables != 0;
-  for (int l = 0; l < EYOC_MAX_LEVELS; ++l) {
-    m->nbr_s1[l] = cv.take<int32_t>((size_t)27 * m->rows[l]);
-    if (l + 1 < EYOC_MAX_LEVELS) {
-      m->nbr_down[l] = cv.take<int32_t>((size_t)27 * m->rows[l + 1]);
-      m->nbr_up[l] = cv.take<int32_t>((size_t)27 * m->rows[l]);
-      if (lazy) {
-        m->up8[l] = cv.take<int32_t>((size_t)8 * m->rows[l]);
-        m->up_ready[l] = false;
-      }
-    }
-  }
-  if (lazy) m->s1_ready[0] = false;
-  {
-    const int top = EYOC_MAX_LEVELS - 1;
-    hipLaunchKernelGGL(k_neighbours, dim3(cdiv(m->rows[top], 256)), dim3(256), 0, st, m->coords[top], m->rows[top],
-                       m->table[top], 1 << top, 1, m->nbr_s1[top]);
-  }
-  // ---- tiling orders (perm_up / perm_s1): every ordered table contributes a segment of (key, row) pairs tagged with
-  // its segment number in the high key bits, and ONE stable radix sort orders all segments at once (seven separate
-  // rocPRIM sorts cost 38 small launches, 0.7 ms per 64-cloud batch).  The orders only serve the wave-private
-  // convolution kernel, which takes over above ~4000 row tiles: small levels (single-pair latency path) skip them.
-  const bool s1_order = kn.maps_s1_order != 0;
-  int seg_up[EYOC_MAX_LEVELS], seg_s1[EYOC_MAX_LEVELS], seg_dn[EYOC_MAX_LEVELS], seg_base[3 * EYOC_MAX_LEVELS], n_seg = 0;
-  size_t total = 0;
-  for (int l = 0; l < EYOC_MAX_LEVELS; ++l) {
-    seg_up[l] = seg_s1[l] = seg_dn[l] = -1;
-    // Z-ordered maps tile the strided convolutions in natural order: a tile's 64 coarse rows read their (adjacent)
-    // children, which beats the pattern order's fuller chunks (2.38 -> 2.25 ms for the three layers;
-    // eyoc_maps_select_orders(-1, 1) restores the sort)
-    const bool dn_order = kn.maps_down_order == 1;
-    if (l + 1 < EYOC_MAX_LEVELS && m->rows[l + 1] >= kn.maps_order_min_rows && (dn_order || !zorder)) {   // outputs of the strided conv l -> l+1
-      seg_dn[l] = n_seg; seg_base[n_seg++] = (int)total; total += m->rows[l + 1];
-    }
-    if (m->rows[l] < kn.maps_order_min_rows) continue;
-    // the transposed tables' order serves the gathering kernels only: Z-ordered maps with the staged transposed kernel (which sorts
-    // inside its tiles) skip it - and with it the whole radix sort, nothing else being ordered there (0.3 ms per 128-cloud batch)
-    if (l + 1 < EYOC_MAX_LEVELS && !(zorder && (use_up || use_upc))) { seg_up[l] = n_seg; seg_base[n_seg++] = (int)total; total += m->rows[l]; }
-    if (s1_order && !zorder) { seg_s1[l] = n_seg; seg_base[n_seg++] = (int)total; total += m->rows[l]; }
-  }
-  constexpr int TAG_SHIFT = UP_KEY_BITS, TAG_BITS = 4;   // pattern keys < 2^11, window number, segment tag above (at most 10 segments)
-  const int wshift = zorder ? kn.maps_window_shift : -1;
-  unsigned int* key_in = cv.take<unsigned int>(total);
-  unsigned int* key_out = cv.take<unsigned int>(total);
-  int* row_in = cv.take<int>(total);
-  int32_t* perm_all = cv.take<int32_t>(total);
-  const size_t sort_bytes = sort_rows_tmp_bytes((int)total, TAG_SHIFT + TAG_BITS);
-  void* sort_tmp = cv.take<char>(sort_bytes);
-  for (int l = EYOC_MAX_LEVELS - 2; l >= 0; --l) {
-    const int nl = m->rows[l], nc = m->rows[l + 1];
-    const int su = seg_up[l];
-    if (lazy) {
-      // levels >= 1: the stride-1 table (the next finer level derives from it) + the compact transposed table; level 0: nothing here -
-      // its tile-record builder derives the windows itself and writes up8[0] on the way (build_local_rulebook_derived, below)
-      if (l > 0)
-        hipLaunchKernelGGL((k_derive_fine<true, 2>), dim3(cdiv(nl, 256)), dim3(256), 0, st, m->coords[l], nl, l, m->parent[l], m->children[l],
-                           m->nbr_s1[l + 1], nc, m->nbr_s1[l], m->up8[l], (unsigned int*)nullptr, (int*)nullptr, 0u, wshift);
-    } else {
-      hipLaunchKernelGGL((k_derive_fine<true, 1>), dim3(cdiv(nl, 256)), dim3(256), 0, st, m->coords[l], nl, l, m->parent[l],
-                         m->children[l], m->nbr_s1[l + 1], nc, m->nbr_s1[l], m->nbr_up[l],
-                         su >= 0 ? key_in + seg_base[su] : (unsigned int*)nullptr, su >= 0 ? row_in + seg_base[su] : (int*)nullptr,
-                         (unsigned int)(su >= 0 ? su : 0) << TAG_SHIFT, wshift);
-    }
-    hipLaunchKernelGGL(k_derive_down, dim3(cdiv(nc, 256)), dim3(256), 0, st, nc, m->children[l], m->nbr_s1[l + 1],
-                       m->nbr_down[l]);
-  }
-  for (int l = 0; l + 1 < EYOC_MAX_LEVELS; ++l) {
-    const int sd = seg_dn[l];
-    if (sd < 0) continue;
-    hipLaunchKernelGGL(k_children_key, dim3(cdiv(m->rows[l + 1], 256)), dim3(256), 0, st, m->children[l], m->rows[l + 1],
-                       key_in + seg_base[sd], row_in + seg_base[sd], (unsigned int)sd << TAG_SHIFT, wshift);
-  }
-  for (int l = 0; l < EYOC_MAX_LEVELS; ++l) {
-    const int ss = seg_s1[l];
-    if (ss < 0) continue;
-    const int bits = l == 0 ? 2 : 4;   // level 0 feeds the 32-channel, bandwidth-bound layers: keep more locality
-    hipLaunchKernelGGL(k_pattern_key, dim3(cdiv(m->rows[l], 256)), dim3(256), 0, st, m->nbr_s1[l], m->rows[l], bits,
-                       key_in + seg_base[ss], row_in + seg_base[ss], (unsigned int)ss << TAG_SHIFT, wshift);
-  }
-  if (total > 0) {
-    if (int rc = sort_rows_by_key(sort_tmp, sort_bytes, key_in, key_out, row_in, perm_all, (int)total, TAG_SHIFT + TAG_BITS, st)) {
-      delete m;
-      return rc;
-    }
-    for (int l = 0; l < EYOC_MAX_LEVELS; ++l) {
-      if (seg_up[l] >= 0) m->perm_up[l] = perm_all + seg_base[seg_up[l]];
-      if (seg_s1[l] >= 0) m->perm_s1[l] = perm_all + seg_base[seg_s1[l]];
-      if (seg_dn[l] >= 0) m->perm_down[l] = perm_all + seg_base[seg_dn[l]];
-    }
-  }
-  // ---- local rulebooks of the stride-1 tables (tile-local input stage of the sparse convolution): only for Z-ordered rows
-  if (zorder) {
-    // counters [8] stride-1, [9] transposed, [10 + l] strided table l, [13] wide level-3 tiles: zero since the fill of all 64 words at the top (nothing in between writes them)
-    for (int l = 0; l < EYOC_MAX_LEVELS; ++l) {
-      m->local_s1[l] = cv.take<unsigned char>(local_rulebook_bytes(m->rows[l]));
-      if (lazy && l == 0) {
-        DeriveSrc src;
-        src.coords = m->coords[0]; src.parent = m->parent[0]; src.children = m->children[0]; src.s1c = m->nbr_s1[1];
-        src.nc = m->rows[1]; src.sh = 0; src.up8 = m->up8[0];
-        if (int rc = build_local_rulebook_derived(src, m->rows[0], m->local_s1[0], counters + 8, st, kn.st_group)) { delete m; return rc; }
-      } else if (int rc = build_local_rulebook(m->nbr_s1[l], 27, m->rows[l], m->local_s1[l], counters + 8, st, kn.st_group)) { delete m; return rc; }
-      if (l + 1 < EYOC_MAX_LEVELS && use_up) {   // the transposed table whose outputs are this level's rows
-        m->local_up[l] = cv.take<unsigned char>(local_rulebook_up_bytes(m->rows[l]));
-        if (int rc = build_local_rulebook_up(m->nbr_up[l], 27, m->rows[l], m->local_up[l], counters + 9, st)) { delete m; return rc; }
-      }
-      if (l + 1 < EYOC_MAX_LEVELS && use_upc) {   // ... in class-major order (spconv_upc.hip)
-        m->local_upc[l] = cv.take<unsigned char>(upc_kept_bytes(m->rows[l]));
-        unsigned char* scratch = cv.take<unsigned char>(upc_scratch_bytes(m->rows[l]));
-        if (m->local_upc[l]) {
-          if (int rc = build_upc(lazy ? m->up8[l] : m->nbr_up[l], m->coords[l], 1 << l, m->rows[l], m->local_upc[l], scratch, st, lazy)) { delete m; return rc; }
-        } else if (int rc = maps_ensure_table(m, EYOC_MAP_UP, l, st)) { delete m; return rc; }
-      }
-    }
-    // strided tables (outputs = the rows of level l + 1) in 128-row tiles: batches only - a single pair's 97 level-1 tiles do not fill the chip
-    const bool use_down = kn.down_kernel == 1 && n >= kn.upc_min_rows;
-    // the coarsest level's stride-1 table in 128-row tiles too: its layers have 256 channels, and a workgroup of 128 rows x 128 channels
-    // stages a tile's rows once per 128 output channels instead of once per 64 (block4: 0.89 -> 0.78 ms per layer on the bench batch; the
-    // 128-channel layers of level 2 measured level - 0.84 -> 0.83 - and keep the 256-row tiles)
-    for (int l = EYOC_MAX_LEVELS - 1; l < EYOC_MAX_LEVELS && use_down && kn.s1_wide; ++l) {
-      m->local_s1w[l] = cv.take<unsigned char>(local_rulebook128_bytes(m->rows[l]));
-      if (m->local_s1w[l])
-        if (int rc = build_local_rulebook128(m->nbr_s1[l], 27, m->rows[l], m->local_s1w[l], counters + 13, st, kn.st_group)) { delete m; return rc; }
-    }
-    for (int l = 0; l + 1 < EYOC_MAX_LEVELS && use_down; ++l) {
-      m->local_down[l] = cv.take<unsigned char>(local_rulebook128_bytes(m->rows[l + 1]));
-      if (m->local_down[l])
-        if (int rc = build_local_rulebook128(m->nbr_down[l], 27, m->rows[l + 1], m->local_down[l], counters + 10 + l, st, kn.st_group)) { delete m; return rc; }
-    }
-    for (int l = 0; l < EYOC_MAX_LEVELS; ++l) {
-      host[16 + l] = 0;
-      if (m->local_upc[l]) FAIL_HIP(hipMemcpyAsync(host + 16 + l, upc_overflow_ptr(m->local_upc[l]), sizeof(int), hipMemcpyDeviceToHost, st));
-    }
-    FAIL_HIP(hipMemcpyAsync(host, counters + 8, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
-    FAIL_HIP(hipMemcpyAsync(host + 32, counters, 8 * sizeof(int), hipMemcpyDeviceToHost, st));   // errors + the scans' own totals
-    FAIL_HIP(hipStreamSynchronize(st));
-    if (host[32] != 0) {
-      set_error("eyoc_maps_build: %d coordinate rows outside the supported key range (|c| < 2^17 - 16, 0 <= batch < 1024)", host[32]);
-      keep_fault_masks(ctx, host + 64, EYOC_ERR_RANGE);     // k_count_levels' masks, read back with the level counts
-      delete m;
-      return EYOC_ERR_RANGE;
-    }
-    if (host[33] != 0) {
-      set_error("eyoc_maps_build: %d duplicate coordinate rows (a sparse tensor needs unique coordinates)", host[33]);
-      keep_fault_masks(ctx, host + 64, EYOC_ERR_DUPLICATE);
-      delete m;
-      return EYOC_ERR_DUPLICATE;
-    }
-    for (int l = 1; l < EYOC_MAX_LEVELS; ++l)
-      if (host[32 + 2 + l] != m->rows[l]) {
-        set_error("eyoc_maps_build: internal error - level %d has %d rows by its scan, %d by the up-front count", l, host[32 + 2 + l], m->rows[l]);
-        delete m;
-        return EYOC_ERR_INVALID;
-      }
-    if (host[0] != 0) {   // a tile with more distinct input rows than two passes stage (does not happen for Z-ordered rows): no staged kernel
-      for (int l = 0; l < EYOC_MAX_LEVELS; ++l) m->local_s1[l] = nullptr;
-      if (int rc = maps_ensure_table(m, EYOC_MAP_S1, 0, st)) { delete m; return rc; }   // the gathering kernels read the table
-    }
-    if (host[1] != 0)   // ... more than 639 distinct coarse rows under a 256-row tile
-      for (int l = 0; l < EYOC_MAX_LEVELS; ++l) m->local_up[l] = nullptr;
-    for (int l = 0; l + 1 < EYOC_MAX_LEVELS; ++l)   // a 128-row coarse tile with more than 1278 distinct fine rows: that strided table stays on the gathering kernel
-      if (host[2 + l] != 0) m->local_down[l] = nullptr;
-    if (host[5] != 0)
-      for (int l = 0; l < EYOC_MAX_LEVELS; ++l) m->local_s1w[l] = nullptr;
-    for (int l = 0; l < EYOC_MAX_LEVELS; ++l)   // a class tile with more than 1278 distinct coarse rows: that table stays on the gathering kernels
-      if (host[16 + l] != 0) {
-        m->local_upc[l] = nullptr;
-        if (int rc = maps_ensure_table(m, EYOC_MAP_UP, l, st)) { delete m; return rc; }
-      }
-  }
-  FAIL_HIP(hipGetLastError());
-#undef FAIL_HIP
-  if (!cv.ok()) {
-    set_error("eyoc_maps_build: internal workspace accounting error (%zu > %zu)", cv.off, cv.cap);
-    delete m;
-    return EYOC_ERR_WORKSPACE;
-  }
-  *out = m;
+  MAPS_TRY(b.finish());
+  *out = b.m.release();
   return EYOC_OK;
 }
 

@@ -341,3 +341,49 @@ def test_fused_level_construction_equals_the_per_level_kernels():
     finally:
         _lib.knob("eyoc_maps_fused_levels", 1)
         _lib.knob("eyoc_maps_internal_order", prev_order)
+
+
+def test_a_build_never_writes_past_the_workspace_it_was_given():
+    """A valid cloud whose voxels are alone at every stride keeps all its rows on all four levels, and from 2^17 rows on (class-major and
+    128-row tile records, the default knobs) the arrays of such a build can outgrow `eyoc_maps_workspace_bytes`.
+    The build may then refuse (EYOC_ERR_WORKSPACE), but it must not touch a byte behind the `ws_bytes` it was told: the allocation
+    here is twice that, its upper half a canary.  Two clouds on a lattice of pitch 16, 141 120 rows in all."""
+    import ctypes as C
+    from eyoc_amd import _lib
+    lib = _lib.load()
+    rng = np.random.default_rng(23)
+    lattice = 16 * np.stack(np.meshgrid(np.arange(42), np.arange(42), np.arange(40), indexing="ij"), -1).reshape(-1, 3)
+    coords = np.concatenate([np.concatenate([np.full((len(lattice), 1), b), lattice[rng.permutation(len(lattice))]], 1)
+                             for b in range(2)]).astype(np.int32)
+    n = len(coords)
+    assert n == 141120
+    dev = torch.device("cuda", torch.cuda.current_device())
+    xyz = torch.from_numpy(coords).to(dev)
+    bound = int(lib.eyoc_maps_workspace_bytes(n))
+    ws = _lib.workspace(2 * bound, dev)
+    canary = ws[bound:]
+    canary.fill_(0xA5)
+
+    def build(ws_bytes):
+        h = C.c_void_p()
+        rc = lib.eyoc_maps_build_ordered(_lib.ctx(dev.index), _lib.ptr(xyz), n, _lib.ptr(ws), ws_bytes, _lib.stream_ptr(), -1, C.byref(h))
+        torch.cuda.synchronize()
+        return rc, h
+
+    def all_rows_on_every_level_then_free(h):
+        rows = [int(lib.eyoc_maps_rows(h, l)) for l in range(4)]
+        lib.eyoc_maps_free(h)
+        assert rows == [n] * 4
+
+    rc, h = build(bound)
+    overwritten = int((canary != 0xA5).sum())                            # (a plain int: a failing assert must not format 0.5 GB tensors)
+    print(f"build with ws_bytes = bound = {bound}: rc {rc}, canary bytes overwritten {overwritten}")
+    if rc == 0:
+        all_rows_on_every_level_then_free(h)
+    assert overwritten == 0, "the build wrote behind the workspace it was given"
+    assert rc in (0, _lib.ERR_WORKSPACE), lib.eyoc_last_error()
+    if rc != 0:
+        assert not h.value
+    rc, h = build(2 * bound)
+    assert rc == 0, lib.eyoc_last_error()
+    all_rows_on_every_level_then_free(h)
