@@ -90,7 +90,8 @@ def small_maps(seed=0, n=2500):
     return oc.build_maps(syn.batch_coords([c.astype(np.int32)]))
 
 
-@pytest.mark.parametrize("cin,cout", [(32, 32), (64, 64), (32, 64), (128, 128), (256, 256), (256, 64), (128, 256), (96, 64)])
+@pytest.mark.parametrize("cin,cout", [(32, 32), (64, 64), (32, 64), (128, 128), (256, 256), (256, 64), (128, 256), (96, 64),
+                                      (192, 64), (384, 128)])       # 6 and 12 input blocks: the concat inputs of BN2B / BN2D / FatBN
 def test_stride1_layer_shapes(cin, cout):
     maps = small_maps()
     nbr = maps["s1"][0]
@@ -131,6 +132,12 @@ def test_strided_transposed_and_identity_maps():
     W1 = (rng.normal(size=(1, 96, 64)) / 10).astype(np.float32)
     x96 = rng.normal(size=(n1, 96)).astype(np.float32)
     assert rel_err(run_layer(None, x96, W1, relu=True), oracle_layer(None, x96, W1, relu=True)) < REL
+    # conv1_tr of the other channel tables: FatBN 160 -> 128, BN2E 256 -> 64, BN2 96 -> 32 (`final` with its row normalisation has no
+    # layer-level entry point - eyoc_spconv leaves l2norm off: tests/test_gpu_channel_tables.py checks it through the whole forward)
+    for cin, cout in ((160, 128), (256, 64), (96, 32)):
+        W = (rng.normal(size=(1, cin, cout)) / np.sqrt(cin)).astype(np.float32)
+        x = rng.normal(size=(n1, cin)).astype(np.float32)
+        assert rel_err(run_layer(None, x, W, relu=True), oracle_layer(None, x, W, relu=True)) < REL, (cin, cout)
 
 
 @pytest.mark.parametrize("n", [1, 15, 16, 17, 63, 64, 65, 200, 5000])

@@ -111,7 +111,8 @@ def maps():
     return small_maps(0, 4000)
 
 
-@pytest.mark.parametrize("cin,cout", [(32, 32), (64, 64), (32, 64), (128, 128), (256, 64), (128, 256), (96, 64), (64, 32)])
+@pytest.mark.parametrize("cin,cout", [(32, 32), (64, 64), (32, 64), (128, 128), (256, 64), (128, 256), (96, 64), (64, 32),
+                                      (192, 64), (384, 128)])       # 6 and 12 input blocks: the concat inputs of BN2B / BN2D / FatBN
 def test_split16_layer_is_as_accurate_as_fp32_mfma(maps, cin, cout, split16_kernel):
     """Against an fp64 restatement: the split16 layer's error must be of the order of the fp32-MFMA layer's own
     (both ~1e-7 relative to the largest output), three orders of magnitude inside the 1e-4 bar."""
@@ -158,6 +159,13 @@ def test_split16_identity_strided_transposed_and_ragged(maps):
     W1 = (rng.normal(size=(1, 96, 64)) / 10).astype(np.float32)
     x96 = rng.normal(size=(n1, 96)).astype(np.float32)
     assert rel_err(run_layer_split(None, x96, W1, relu=True), layer_f64(None, x96, W1, relu=True)) < 2e-6
+    # conv1_tr of the other channel tables: FatBN 160 -> 128, BN2E 256 -> 64, BN2 96 -> 32 (`final` with its row normalisation has no
+    # layer-level entry point - eyoc_spconv_ex leaves l2norm off: tests/test_gpu_channel_tables.py checks it through the whole forward)
+    rng1 = np.random.default_rng(31)                       # (its own generator: the ragged cases below keep their draws)
+    for cin, cout in ((160, 128), (256, 64), (96, 32)):
+        W = (rng1.normal(size=(1, cin, cout)) / np.sqrt(cin)).astype(np.float32)
+        x = rng1.normal(size=(n1, cin)).astype(np.float32)
+        assert rel_err(run_layer_split(None, x, W, relu=True), layer_f64(None, x, W, relu=True)) < 2e-6, (cin, cout)
     for n in (1, 17, 65, 200):
         from oracle import coords as oc
         c = np.unique(rng.integers(-6, 6, size=(4 * n + 8, 3)), axis=0)[:n]
@@ -342,7 +350,8 @@ def morton_maps():
     return oc.build_maps(coords[morton_order(coords)])
 
 
-@pytest.mark.parametrize("cin,cout,level", [(64, 64, 0), (32, 32, 0), (128, 128, 1), (256, 256, 2), (64, 64, 1)])
+@pytest.mark.parametrize("cin,cout,level", [(64, 64, 0), (32, 32, 0), (128, 128, 1), (256, 256, 2), (64, 64, 1),
+                                            (128, 128, 0)])       # ResUNetBN2E block1, BN2E / FatBN block2_tr: 128 channels on the finest level
 def test_staged_kernel_vs_fp64(morton_maps, cin, cout, level):
     """Tile-local input stage (spconv_st.hip) on Morton-ordered rows: local rulebooks never overflow, every distinct input
     row is staged once per 32-channel block, results at the split16 accuracy against the fp64 restatement."""
@@ -447,6 +456,49 @@ def test_staged_kernel_refuses_channel_widths_it_cannot_tile(morton_maps):
     W = (rng.normal(size=(27, 64, 96)) / 10).astype(np.float32)
     with pytest.raises(Exception):
         run_layer_staged(nbr, x, W)
+
+
+@pytest.mark.parametrize("cin,ld,col,cout", [(32, 160, 128, 64), (128, 256, 128, 128)])
+def test_staged_kernel_reads_a_column_slice_of_a_concat_buffer(morton_maps, cin, ld, col, cout):
+    """The skip half of a concat buffer as a staged layer's input: 32 of 160 floats at column 128 (ResUNetFatBN's B_CAT1, read by
+    conv2) and 128 of 256 at column 128 (ResUNetBN2E's) - the column offset and leading dimension of the tile-local stage.  The other
+    columns of the input hold a sentinel that wrecks the result if read; the output is a column slice too, and nothing outside it
+    is written.  (Layer level reaches the staged kernel through its stride-1 records only; the 128-row strided records, which read
+    these very buffers in the forward, are switched off and on per table in tests/test_gpu_channel_tables.py.)"""
+    L, lib = _lib()
+    nbr = morton_maps["s1"][0]
+    n = nbr.shape[1]
+    rng = np.random.default_rng(cin + ld)
+    x = np.abs(rng.normal(size=(n, cin))).astype(np.float32)
+    W = (rng.normal(size=(27, cin, cout)) / np.sqrt(9 * cin)).astype(np.float32)
+    b = rng.normal(size=cout).astype(np.float32)
+    want = layer_f64(nbr, x, W, bias=b, relu=True)
+    packed, os_ = np.zeros(W.size, np.float32), np.zeros(1, np.float32)
+    assert lib.eyoc_spconv_pack_weights_split16(W.ctypes.data, None, 27, cin, cout, packed.ctypes.data, os_.ctypes.data) == 0
+    dev = torch.device("cuda")
+    nd = torch.from_numpy(np.ascontiguousarray(nbr, np.int32)).to(dev)
+    local = torch.zeros(int(lib.eyoc_spconv_local_rulebook_bytes(n)), dtype=torch.uint8, device=dev)
+    ovf = torch.zeros(1, dtype=torch.int32, device=dev)
+    L.check(lib.eyoc_spconv_build_local_rulebook(L.ctx(), L.ptr(nd), 27, n, L.ptr(local), L.ptr(ovf), L.stream_ptr()))
+    assert int(ovf.item()) == 0
+    xin = torch.full((n, ld), 777.0, device=dev)
+    xd = torch.from_numpy(x).to(dev)
+    L.check(lib.eyoc_split16_encode(L.ctx(), L.ptr(xd), n, cin, cin, C.c_void_p(xin.data_ptr() + 4 * col), ld, L.stream_ptr()))   # in place
+    ld_out, col_out = cout + 64, 32
+    wd, osd, bd = torch.from_numpy(packed).to(dev), torch.from_numpy(os_).to(dev), torch.from_numpy(b).to(dev)
+    for out_split in (1, 0):
+        out = torch.full((n, ld_out), -555.0, device=dev)
+        L.check(lib.eyoc_spconv_staged(L.ctx(), L.ptr(nd), L.ptr(local), n, n, C.c_void_p(xin.data_ptr() + 4 * col), ld, cin, L.ptr(wd), cout,
+                                       L.ptr(bd), None, 0, 1, C.c_void_p(out.data_ptr() + 4 * col_out), ld_out, out_split, L.ptr(osd),
+                                       L.stream_ptr()), "eyoc_spconv_staged")
+        torch.cuda.synchronize()
+        assert bool((out[:, :col_out] == -555.0).all()) and bool((out[:, col_out + cout:] == -555.0).all()), "wrote outside its columns"
+        assert bool((xin[:, :col] == 777.0).all()) and bool((xin[:, col + cin:] == 777.0).all())
+        got = out[:, col_out:col_out + cout].contiguous()
+        got = (decode(got) if out_split else got).cpu().numpy()
+        e = rel_err(got, want)
+        print(f"staged {cin} of {ld} at column {col} -> {cout}, split store {out_split}: err {e:.2e}")
+        assert e < 2e-6                                    # the bar of test_staged_kernel_vs_fp64
 
 
 def test_first_convolution_as_mfma_gemm_with_a_3x3x3_window():

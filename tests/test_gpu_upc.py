@@ -110,7 +110,10 @@ def test_partition_and_records():
         assert (seen == 1).all()
 
 
-@pytest.mark.parametrize("lvl,cin,cout", [(0, 128, 64), (1, 256, 64), (2, 256, 128), (1, 64, 64), (0, 32, 128)])
+# the second row: the other channel tables' transposed layers - 6 input blocks of 32 (BN2B conv3_tr, BN2D conv2_tr: 192 -> 64; FatBN
+# conv2_tr: 192 -> 128), 12 (FatBN conv3_tr: 384 -> 128), 256 output channels (FatBN conv4_tr), BN2D / BN2E conv3_tr's 256 -> 128 on level 0
+@pytest.mark.parametrize("lvl,cin,cout", [(0, 128, 64), (1, 256, 64), (2, 256, 128), (1, 64, 64), (0, 32, 128),
+                                          (1, 192, 64), (0, 192, 64), (0, 192, 128), (1, 384, 128), (2, 256, 256), (0, 256, 128)])
 def test_layer_against_fp64_and_the_gathering_kernel(lvl, cin, cout):
     from eyoc_amd import _lib as L
     cm, maps, info, lib = _maps(_clouds(3, seed0=7))
