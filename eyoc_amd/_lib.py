@@ -193,6 +193,8 @@ PROTOTYPES = {
     "eyoc_ransac": (_i, [_vp, _vp, _vp, _vp, _i, C.POINTER(RansacParams), _vp, _vp]),
     "eyoc_maps_select_orders": (_i, [_vp, _i, _i]),
     "eyoc_ransac_select_pruning": (_i, [_vp, _i]),
+    "eyoc_ransac_select_generate": (_i, [_vp, _i]),
+    "eyoc_knn_pack_targets": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _vp, _sz, _vp, _vp]),
     "eyoc_registration_accept_degenerate": (_i, [_vp, _i]),
     "eyoc_ransac_transform_store": (_i, [_vp, _i]),
     "eyoc_ransac_workspace_bytes": (_sz, [_vp, _i, _i, _i, _sz]),

@@ -113,7 +113,8 @@ struct eyoc_ctx {
     int st_ksplit = 1;                 // eyoc_spconv_st_ksplit
     int ransac_store = 1 << 20;        // eyoc_ransac_transform_store
     int ransac_prune = 2;              // eyoc_ransac_select_pruning: 0 full sweeps, 1 reference pruning, 2 + survivors stop counting once they cannot reach the largest count (round 6)
-    int accept_degenerate = 0;         // eyoc_registration_accept_degenerate: batched RANSAC / SC2-PCR give pairs below their minimum a failed record
+    int ransac_generate = 1;           // eyoc_ransac_select_generate: 1 k_generate_q (16-bit records, banded edge checks, two workgroups per CU), 0 the exact round-6 k_generate; k_fit decides either way
+    int accept_degenerate = 0;        // eyoc_registration_accept_degenerate: batched RANSAC / SC2-PCR give pairs below their minimum a failed record
   } knobs;
 };
 // the switches of a call: the ctx's, or the defaults where an internal launcher was handed no ctx

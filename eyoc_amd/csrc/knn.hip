@@ -252,47 +252,69 @@ __device__ inline float split_scale(float maxabs) {
 // B operand of v_mfma_f32_16x16x32_f16 per tile of 16 targets, 3 x 64 float4: [0] lane (g, j): the fp16 hi halves of
 // channels 8 g .. 8 g + 7 of target 16 t + j, scaled by the target's split_scale; [1] the lo halves; [2] (|b_j|^2,
 // 1 / scale_j, 0, 0) (padding targets: norm +inf, everything else 0)
+// A wave packs PK_TILES tiles, lane (g, j) of a tile loading only its own eight channels of target j.  The squared norm is the sum the
+// first version of this kernel took over the whole row in every lane, spelled out so that it stays that sum bit for bit: per four
+// channels (x, y, z, w) the term w^2 + (z^2 + (x^2 + fl(y^2))) with one rounding per fused step, and the eight terms of a row added
+// from channel 0 upwards - each lane group computes its two terms, the groups exchange them, every lane adds all eight in that order.
+constexpr int PK_TILES = 4;
+__device__ inline float pack_term(const float4 v) { return fmaf(v.w, v.w, fmaf(v.z, v.z, fmaf(v.x, v.x, v.y * v.y))); }
+
 template <int C>
-__global__ void knn_pack_targets_mfma(const float* __restrict__ B, SegArgs seg, SegMfma sm, float* __restrict__ Bm,
-                                      int* __restrict__ bmax_bits, int zero_norm) {
+__global__ __launch_bounds__(256) void knn_pack_targets_mfma(const float* __restrict__ B, SegArgs seg, SegMfma sm, float* __restrict__ Bm,
+                                                             int* __restrict__ bmax_bits, int zero_norm) {
   static_assert(C == 32, "one 16x16x32 MFMA spans the 32 channels");
+  __shared__ int wmax[4];
   const int s = blockIdx.z;
   const int b0 = seg.b[s], nb = seg.b[s + 1] - b0;
   const int n16 = (nb + 15) / 16;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;        // (tile, lane)
-  if (idx >= n16 * 64) return;
-  const int t = idx >> 6, l = idx & 63, j = 16 * t + (l & 15), g = l >> 4;
-  float4* dst = reinterpret_cast<float4*>(Bm + sm.bm_off[s]) + (size_t)t * 3 * 64 + l;
-  const bool ok = j < nb;
-  const float* row = B + (size_t)(b0 + (ok ? j : 0)) * C;
-  float n2 = 0.f, mx = 0.f;
-  float mine[8];
+  const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, g = l >> 4;
+  const int t0 = (blockIdx.x * 4 + wave) * PK_TILES;
+  int nb2 = 0;                                                         // bits of the largest |b|^2 this lane has seen
 #pragma unroll
-  for (int q = 0; q < C / 4; ++q) {
-    const float4 v = *reinterpret_cast<const float4*>(row + 4 * q);
-    n2 += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-    mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-    if ((q >> 1) == g) { mine[4 * (q & 1)] = v.x; mine[4 * (q & 1) + 1] = v.y; mine[4 * (q & 1) + 2] = v.z; mine[4 * (q & 1) + 3] = v.w; }
-  }
-  if (!(n2 == n2)) mx = __builtin_nanf("");                            // a NaN element: fmaxf would have dropped it
-  const float sc = split_scale(mx);
-  half8_t hi, lo;
+  for (int u = 0; u < PK_TILES; ++u) {
+    const int t = t0 + u, j = 16 * t + (l & 15);
+    if (t >= n16) break;                                               // wave-uniform
+    float4* dst = reinterpret_cast<float4*>(Bm + sm.bm_off[s]) + (size_t)t * 3 * 64 + l;
+    const bool ok = j < nb;
+    const float4* row = reinterpret_cast<const float4*>(B + (size_t)(b0 + (ok ? j : 0)) * C) + 2 * g;
+    const float4 v0 = row[0], v1 = row[1];
+    const float mine[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+    const float term0 = pack_term(v0), term1 = pack_term(v1);
+    float mx = fmaxf(fmaxf(fmaxf(fabsf(v0.x), fabsf(v0.y)), fmaxf(fabsf(v0.z), fabsf(v0.w))),
+                     fmaxf(fmaxf(fabsf(v1.x), fabsf(v1.y)), fmaxf(fabsf(v1.z), fabsf(v1.w))));
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    float n2 = __shfl(term0, l & 15, 64) + __shfl(term1, l & 15, 64);
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float x = ok ? mine[i] * sc : 0.0f;
-    const _Float16 h = (_Float16)x;
-    hi[i] = h;
-    lo[i] = (_Float16)(x - (float)h);
+    for (int h = 1; h < 4; ++h) {
+      n2 = n2 + __shfl(term0, (l & 15) + 16 * h, 64);
+      n2 = n2 + __shfl(term1, (l & 15) + 16 * h, 64);
+    }
+    if (!(n2 == n2)) mx = __builtin_nanf("");                          // a NaN element: fmaxf would have dropped it
+    const float sc = split_scale(mx);
+    half8_t hi, lo;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float x = ok ? mine[i] * sc : 0.0f;
+      const _Float16 h = (_Float16)x;
+      hi[i] = h;
+      lo[i] = (_Float16)(x - (float)h);
+    }
+    dst[0] = __builtin_bit_cast(float4, hi);
+    dst[64] = __builtin_bit_cast(float4, lo);
+    dst[128] = make_float4(ok ? (zero_norm ? 0.0f : n2) : __builtin_inff(), ok ? 1.0f / sc : 0.0f, 0.f, 0.f);   // zero_norm: score -2 <a, b>
+    nb2 = max(nb2, (ok && n2 == n2) ? __float_as_int(n2) : 0);        // non-negative floats order like ints
   }
-  dst[0] = __builtin_bit_cast(float4, hi);
-  dst[64] = __builtin_bit_cast(float4, lo);
-  dst[128] = make_float4(ok ? (zero_norm ? 0.0f : n2) : __builtin_inff(), ok ? 1.0f / sc : 0.0f, 0.f, 0.f);   // zero_norm: score -2 <a, b>
-  // the segment's largest |b|^2: one atomic per wave (= per tile of 16 targets), not per target - 5000 atomics on one word
-  // per segment were most of this kernel's time
-  int nb2 = (ok && n2 == n2) ? __float_as_int(n2) : 0;                // non-negative floats order like ints
+  // the segment's largest |b|^2: one atomic per workgroup (= per 16 tiles of 16 targets).  One per target - 5000 on one word per
+  // segment - was most of this kernel's time at first, and one per tile still put ~310 in a row on every segment's word
 #pragma unroll
   for (int d = 8; d >= 1; d >>= 1) nb2 = max(nb2, __shfl_xor(nb2, d, 64));
-  if (l == 0 && nb2 > 0) atomicMax(bmax_bits + s, nb2);
+  if (l == 0) wmax[wave] = nb2;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int m = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+    if (m > 0) atomicMax(bmax_bits + s, m);
+  }
 }
 
 __global__ void knn_row_norms(const float* __restrict__ A, int n, int C, float* __restrict__ out) {
@@ -543,6 +565,40 @@ extern "C" int eyoc_knn_prefilter(eyoc_ctx* ctx, int mode) {
   return prev;
 }
 
+// bmax (one word per segment) must be zero when this runs
+static void launch_pack_targets(const float* B_dev, const SegArgs& seg, const SegMfma& sm, int nseg, int max_nb, float* Bm, int* bmax,
+                                int zero_norm, hipStream_t st) {
+  hipLaunchKernelGGL(knn_pack_targets_mfma<32>, dim3(eyoc::cdiv(eyoc::cdiv(max_nb, 16), 4 * PK_TILES), 1, nseg), dim3(256), 0, st, B_dev, seg,
+                     sm, Bm, bmax, zero_norm);
+}
+
+// floats of the packed targets of segments of `nb` rows: 3 x 64 float4 per tile of 16 targets
+static long long packed_target_floats(int nb) { return (long long)eyoc::cdiv(nb, 16) * 3 * 64 * 4; }
+
+extern "C" int eyoc_knn_pack_targets(eyoc_ctx* ctx, const float* B_dev, const int32_t* seg_b, int nseg, int zero_norm, float* packed_dev,
+                                     size_t packed_floats, int32_t* bmax_dev, void* stream) {
+  EYOC_REQUIRE(ctx && B_dev && seg_b && packed_dev && bmax_dev, EYOC_ERR_INVALID, "eyoc_knn_pack_targets: NULL argument");
+  EYOC_REQUIRE(nseg >= 1 && nseg <= MAX_SEG, EYOC_ERR_INVALID, "eyoc_knn_pack_targets: nseg %d not in [1,%d]", nseg, MAX_SEG);
+  hipStream_t st = (hipStream_t)stream;
+  SegArgs seg = {};
+  SegMfma sm;
+  long long floats = 0;
+  int max_nb = 0;
+  for (int s = 0; s <= nseg; ++s) seg.b[s] = seg_b[s];
+  for (int s = 0; s < nseg; ++s) {
+    const int nb = seg_b[s + 1] - seg_b[s];
+    EYOC_REQUIRE(nb >= 0, EYOC_ERR_INVALID, "eyoc_knn_pack_targets: negative segment length");
+    max_nb = nb > max_nb ? nb : max_nb;
+    sm.bm_off[s] = floats;
+    floats += packed_target_floats(nb);
+  }
+  EYOC_REQUIRE((size_t)floats <= packed_floats, EYOC_ERR_INVALID, "eyoc_knn_pack_targets: %lld floats needed, %zu given", floats, packed_floats);
+  EYOC_CHECK_HIP(hipMemsetAsync(bmax_dev, 0, (size_t)nseg * sizeof(int32_t), st));
+  if (max_nb > 0) launch_pack_targets(B_dev, seg, sm, nseg, max_nb, packed_dev, bmax_dev, zero_norm ? 1 : 0, st);
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
 static int knn_run(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c, const int32_t* seg_a,
                    const int32_t* seg_b, int nseg, int dist_type, int64_t* idx_dev, float* dist_dev, float* second_dev,
                    void* stream, bool dot = false) {
@@ -581,7 +637,7 @@ static int knn_run(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c,
   for (int s = 0; s < nseg; ++s) {
     waves += eyoc::cdiv(seg_a[s + 1] - seg_a[s], MF_ROWS);
     sm.bm_off[s] = bm_floats;
-    bm_floats += (long long)eyoc::cdiv(seg_b[s + 1] - seg_b[s], 16) * 3 * 64 * 4;   // 3 x 64 float4 per tile of 16 targets
+    bm_floats += packed_target_floats(seg_b[s + 1] - seg_b[s]);
   }
   const bool prefilter = prefilter_env != 0 && !dot && !second_dev && !dist_dev && dist_type != 1 && c == 32 && max_nb > 0 &&
                          (waves >= 512 || prefilter_env == 2);   // (round 5: a single pair - 79 waves, each walking all 5000 targets - takes 0.15 ms here against 0.10 in the exact kernel)
@@ -603,8 +659,7 @@ static int knn_run(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c,
     int* bmax = (int*)((char*)ctx->scratch + off_bx);
     int* fcnt = bmax + MAX_SEG;
     EYOC_CHECK_HIP(hipMemsetAsync(bmax, 0, 2 * MAX_SEG * sizeof(int), st));
-    hipLaunchKernelGGL(knn_pack_targets_mfma<32>, dim3(eyoc::cdiv((long long)eyoc::cdiv(max_nb, 16) * 64, 256), 1, nseg), dim3(256), 0, st,
-                       B_dev, seg, sm, Bm, bmax, dist_type == 2 ? 1 : 0);
+    launch_pack_targets(B_dev, seg, sm, nseg, max_nb, Bm, bmax, dist_type == 2 ? 1 : 0, st);
     hipLaunchKernelGGL(knn_row_norms, dim3(eyoc::cdiv(n_total, 256)), dim3(256), 0, st, A_dev, n_total, c, anorm);
     if (dist_type == 2)
       hipLaunchKernelGGL((knn_mfma_kernel<32, 2>), dim3(eyoc::cdiv(max_na, 4 * MF_ROWS), 1, nseg), dim3(256), 0, st, A_dev, Bm, seg,

@@ -5,7 +5,9 @@
 //   1. generate: one lane per hypothesis h - counter-hash sampler (bit-identical to
 //      oracle/ransac.py), edge-length checker, 4-point Kabsch in fp64, distance checker.  Survivors
 //      (typically well under a few percent) append h to a compact list with one atomic.
-//      The survivor's transform (12 doubles) is stored next to its index.
+//      The survivor's transform (12 doubles) is stored next to its index.  (Two kernels: k_generate_q / k_generate pass on every
+//      hypothesis that MAY pass the edge checker - the default form on 16-bit records with an error band, conservatively - and
+//      k_fit decides the checker exactly, fits and checks distances.)
 //   2. count: a wave takes 16 survivors at a time and sweeps all correspondences, 4 per lane held in registers
 //      as doubles; the 16 transforms are wave-uniform and come through the scalar cache as SGPR operands of
 //      v_fma_f64 (17 VALU instructions per (hypothesis, correspondence), no loads or conversions in the
@@ -34,6 +36,7 @@ __device__ inline void sample_pair(unsigned long long base, unsigned long long c
 }
 
 // Correspondence records of all pairs of a batch: 6 floats (source point, matched target point).
+constexpr int CNT_STRIDE = 64;   // ints between the counters of two pairs: [0] survivors, [1] largest inlier count, [2] candidates, [3] bits of the largest |coordinate|
 constexpr int CHUNK = 64;  // pairs per launch (the per-pair kernels - bucket, rmse, select - are one workgroup per pair: 8 pairs per launch left them at 8 workgroups on 256 CUs, eight times per 64-pair batch)
 struct PairArgs {          // a chunk of pairs; segment bounds travel as kernel arguments (no H2D copy)
   int s0[CHUNK], n[CHUNK], t0[CHUNK];   // first source row, correspondences, first target row of each pair
@@ -61,11 +64,20 @@ __global__ void k_gather_targets(const float* __restrict__ src, const float* __r
   const int s0 = a.s0[c], n = a.n[c];
   float* rec = a.rec;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const long long j = a.t0[c] + corr[s0 + i];
-  float* r = rec + (size_t)(s0 + i) * 6;
-  r[0] = src[3 * (size_t)(s0 + i)]; r[1] = src[3 * (size_t)(s0 + i) + 1]; r[2] = src[3 * (size_t)(s0 + i) + 2];
-  r[3] = tgt[3 * j]; r[4] = tgt[3 * j + 1]; r[5] = tgt[3 * j + 2];
+  // the pair's largest |coordinate|, source and target (the scale of k_generate_q's 16-bit records): non-negative floats order like
+  // their bit patterns and a NaN's bits lie above infinity's, so one word per pair says how large the pair is AND whether all of it is finite
+  unsigned int m = 0;
+  if (i < n) {
+    const long long j = a.t0[c] + corr[s0 + i];
+    float* r = rec + (size_t)(s0 + i) * 6;
+    r[0] = src[3 * (size_t)(s0 + i)]; r[1] = src[3 * (size_t)(s0 + i) + 1]; r[2] = src[3 * (size_t)(s0 + i) + 2];
+    r[3] = tgt[3 * j]; r[4] = tgt[3 * j + 1]; r[5] = tgt[3 * j + 2];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) m = max(m, __float_as_uint(fabsf(r[k])));
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) m = max(m, (unsigned int)__shfl_xor((int)m, d, 64));
+  if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(reinterpret_cast<unsigned int*>(a.n_surv + c * CNT_STRIDE + 3), m);
 }
 
 // the four sampled correspondences of hypothesis h and the edge-length checker on them
@@ -152,10 +164,12 @@ __device__ inline bool hypothesis(const float* __restrict__ rec, unsigned int n,
   return fit_and_check_distance(s, q, max_dist, R, t);
 }
 
-constexpr int CNT_STRIDE = 64;
 constexpr int GEN_THREADS = 1024;
 constexpr int GEN_BLOCKS_MIN = 8, GEN_BLOCKS_TOTAL = 256;   // workgroups per pair: 256 over the pairs of a launch - one per CU (512 = two rounds of workgroups, each copying the records again: a single pair took 104 us instead of 59) - (every workgroup copies its pair's records to LDS first: 64 per pair at 64 pairs per launch was 4096 copies of 120 KB), at least 8
 constexpr int LDS_RECORDS = 6016;                    // 6016 * 24 B = 141 KB of the 160 KB LDS (+ 16 KB of queues)
+// the compact form (k_generate_q): 12 bytes per record.  Up to GEN_Q_PAIRED records two workgroups share a CU (2 x (64 KB + 16 KB of
+// queues) = the 160 KB), and the launch is sized for two per CU; up to LDS_RECORDS_Q one workgroup still has its records in LDS
+constexpr int LDS_RECORDS_Q = 12000, GEN_Q_PAIRED = (80 * 1024 - 2 * (GEN_THREADS / 64) * 128 * 4) / 12, GEN_Q_BLOCKS_TOTAL = 512;
 
 __device__ inline unsigned long long pair_base(unsigned int seed, int b) {
   return (unsigned long long)(seed + (unsigned)b) * 0x9E3779B97F4A7C15ull;
@@ -166,27 +180,106 @@ __device__ inline unsigned long long pair_base(unsigned int seed, int b) {
 // The edge-length checker rejects ~99 % of the hypotheses even at a 30 % inlier ratio, but in lock step a wave pays
 // for the 4-point Kabsch (a Jacobi eigen-solver) whenever ONE of its 64 lanes gets through - about half of all waves
 // at that ratio (k_generate 0.2 -> 1.0 ms per 8 pairs).  So the wave queues the hypotheses that pass the edge check
-// in LDS and only fits them 64 at a time, all lanes busy.
-template <bool IN_LDS>
-__global__ __launch_bounds__(GEN_THREADS) void k_generate(PairArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lrec[];
-  __shared__ int queue[GEN_THREADS / 64][128], queue1[GEN_THREADS / 64][128];
-  const int c = blockIdx.y, b = a.pair0 + c;
-  const int s0 = a.s0[c], n = a.n[c];
-  const float* rec = a.rec + (size_t)s0 * 6;
-  if (IN_LDS) {
-    for (int i = threadIdx.x; i < n * 6 / 2; i += GEN_THREADS)
-      reinterpret_cast<float2*>(lrec)[i] = reinterpret_cast<const float2*>(rec)[i];
-    __syncthreads();
-    rec = lrec;
+// in LDS and only fits them 64 at a time, all lanes busy (generate_loop below; since round 5 the fit itself is k_fit's).
+//
+// The two forms of a pair's records the loop samples from: `first` is the first of the six edge checks (samples 0 and 1),
+// `six` all of them; either may pass a hypothesis the exact expression rejects (k_fit decides), never the other way round.
+struct ExactRecords {          // round 6: the fp32 records (LDS or global memory), the oracle's fp64 expressions
+  const float* rec;
+  double edge_sim;
+  __device__ bool first(unsigned int n, unsigned long long base, unsigned int h) const { return first_edge_ok(rec, n, base, h, edge_sim); }
+  __device__ bool six(unsigned int n, unsigned long long base, unsigned int h) const {
+    double s[4][3], q[4][3];
+    return sample_and_check_edges(rec, n, base, h, edge_sim, s, q);
   }
+};
+
+// ---- compact records (eyoc_ransac_select_generate 1).  A coordinate x becomes the 16-bit integer q = rint(x / step), step a
+// power of two with max |x| / step <= 32767 over the pair's source and target points (k_gather_targets leaves that maximum).  The
+// division is exact (a power of two, the pair's magnitude limited to [1e-18, 1e18]) and rint rounds to nearest, so x / step = q + e
+// with |e| <= 1/2.  In units of the step an edge vector is D = Dq + E, Dq the integer difference (|Dq_i| <= 65534: exact in fp32) and
+// |E_i| <= 1, hence | |D| - |Dq| | <= sqrt(3), and for any k in (0, 1), from 2 sqrt(3) |Dq| <= k |Dq|^2 + 3 / k,
+//
+//     (1 - k) |Dq|^2 - 3 (1/k - 1)  <=  |D|^2  <=  (1 + k) |Dq|^2 + 3 (1 + 1/k).
+//
+// The exact checker rejects an edge when ds2 < e2 dt2 or dt2 < e2 ds2 (e2 = edge_sim^2 <= 1; the step^2 on both sides cancels).
+// With a = |Dq_s|^2 and b = |Dq_t|^2 the first is certain once (1 + k) a + 3 (1 + 1/k) < e2 ((1 - k) b - 3 (1/k - 1)), for which
+//
+//     (1 + k) a + 6 / k  <  e2 (1 - k) b                                                                              (*)
+//
+// suffices (e2 <= 1), and the second likewise with a and b exchanged.  k = 2^-8: 6 / k = 1536, a band of 0.4 % on the length ratio,
+// and edges of fewer than ~44 steps (0.17 m at KITTI's 2^-8 m step; coincident samples among them) are never decided here.
+// Rounding: a and b are three fp32 operations on exact non-negative terms (relative error <= 3 u, u = 2^-24), the left side of (*)
+// one fma and the right side one product more, the constants rounded away from the decision: at most 5 u on either side, and
+// every term is non-negative, so nothing cancels.  The fp64 evaluation the result is compared with carries ~2^-50 of its own.  Both
+// are covered by a factor (1 + 2^-20) = 1 + 16 u on the left and (1 - 2^-20) on the right; QK = 1537 > 1536 (1 + 2^-20).
+// A hypothesis (*) does not reject in either direction is a candidate.  Pairs with a NaN or infinite coordinate, or a magnitude
+// outside [1e-18, 1e18] (all-zero pairs included), get no candidate list at all: k_fit evaluates the exact expression on every one of
+// their hypotheses (a candidate count of -1 tells it so) - the round-6 decision, slower, for inputs that are degenerate anyway.
+constexpr float QK = 1537.0f;
+__device__ inline bool compact_scale(unsigned int max_bits, float& inv_step) {
+  const float M = __uint_as_float(max_bits);
+  if (!(M >= 1e-18f && M <= 1e18f)) return false;                     // false for NaN / inf bits as well
+  int e;
+  (void)frexpf(M, &e);                                                 // M = m 2^e, m in [0.5, 1): M 2^(15 - e) < 2^15
+  float inv = ldexpf(1.0f, 15 - e);
+  if (M * inv > 32767.0f) inv *= 0.5f;                                 // 32768 would not fit
+  inv_step = inv;
+  return true;
+}
+__device__ inline bool pair_is_compact(const PairArgs& a, int c, float& inv_step) {
+  return compact_scale((unsigned int)a.n_surv[c * CNT_STRIDE + 3], inv_step);
+}
+__device__ inline float edge_len2(const float p[3], const float r[3]) {
+  const float dx = p[0] - r[0], dy = p[1] - r[1], dz = p[2] - r[2];    // integers below 2^17: exact
+  return fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+}
+struct CompactRecords {        // two planes in LDS: (x, y | z, qx) as 8 bytes and (qy, qz) as 4 bytes per record, 16-bit fields
+  const uint2* xyzq;
+  const unsigned int* qyz;
+  float c_up, c_dn;            // (1 + k)(1 + 2^-20) rounded up, e2 (1 - k)(1 - 2^-20) rounded down
+  __device__ void load(unsigned int i, float s[3], float q[3]) const {
+    const uint2 v = xyzq[i];
+    const unsigned int w = qyz[i];
+    s[0] = (float)(short)(v.x & 0xFFFFu); s[1] = (float)((int)v.x >> 16); s[2] = (float)(short)(v.y & 0xFFFFu);
+    q[0] = (float)((int)v.y >> 16); q[1] = (float)(short)(w & 0xFFFFu); q[2] = (float)((int)w >> 16);
+  }
+  __device__ bool edge(const float sa[3], const float qa[3], const float sb[3], const float qb[3]) const {
+    const float ds2 = edge_len2(sa, sb), dt2 = edge_len2(qa, qb);
+    return !(fmaf(ds2, c_up, QK) < dt2 * c_dn || fmaf(dt2, c_up, QK) < ds2 * c_dn);
+  }
+  __device__ bool first(unsigned int n, unsigned long long base, unsigned int h) const {
+    unsigned int i0, i1;
+    sample_pair(base, 2ull * h, n, i0, i1);
+    float sa[3], qa[3], sb[3], qb[3];
+    load(i0, sa, qa); load(i1, sb, qb);
+    return edge(sa, qa, sb, qb);
+  }
+  __device__ bool six(unsigned int n, unsigned long long base, unsigned int h) const {
+    unsigned int idx[4];
+    sample_pair(base, 2ull * h, n, idx[0], idx[1]);
+    sample_pair(base, 2ull * h + 1, n, idx[2], idx[3]);
+    float s[4][3], q[4][3];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) load(idx[j], s[j], q[j]);
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = i + 1; j < 4; ++j) ok &= edge(s[i], q[i], s[j], q[j]);   // branch-free: the six edges in lock step
+    return ok;
+  }
+};
+
+template <class Records>
+__device__ __forceinline__ void generate_loop(const PairArgs& a, int c, const Records recs, int (*queue)[128], int (*queue1)[128]) {
+  const int b = a.pair0 + c, n = a.n[c];
   const unsigned long long base = pair_base(a.seed, b);
   int* ncand = a.n_surv + c * CNT_STRIDE + 2;              // the pair's candidate counter ([0] survivors, [1] largest count)
   int* cand = a.cnts + (size_t)c * a.H;                    // candidates wait in the pair's count array (k_count writes it after k_fit)
   const int lane = threadIdx.x & 63;
   int* wq = queue[threadIdx.x >> 6];
   int queued = 0;   // wave-uniform
-  const double edge_sim = (double)a.edge_sim;
   // Round 5: the hypotheses that pass all six edge checks (~1 %) are handed to k_fit - 64 at a time, one atomic per wave and
   // one coalesced store - instead of being fitted here: the 4-point Kabsch (a Jacobi eigen-solver in fp64) needs more registers
   // than the 128 a 1024-thread workgroup leaves a lane (400 bytes of scratch per lane, also paid by the sampling loop around it)
@@ -208,7 +301,7 @@ __global__ __launch_bounds__(GEN_THREADS) void k_generate(PairArgs a) {
   for (int r = 0; r <= rounds; ++r) {                       // the extra round drains the first queue
     if (r < rounds) {
       const int h = r * stride + blockIdx.x * GEN_THREADS + threadIdx.x;
-      const bool pass1 = h < a.H && first_edge_ok(rec, (unsigned)n, base, (unsigned)h, edge_sim);
+      const bool pass1 = h < a.H && recs.first((unsigned)n, base, (unsigned)h);
       const unsigned long long m1 = __ballot(pass1);
       if (pass1) wq1[queued1 + __popcll(m1 & ((1ull << lane) - 1ull))] = h;
       queued1 += __popcll(m1);
@@ -218,11 +311,7 @@ __global__ __launch_bounds__(GEN_THREADS) void k_generate(PairArgs a) {
       int h2;
       if (drain) { h2 = lane < queued1 ? wq1[lane] : -1; queued1 = 0; }
       else { queued1 -= 64; h2 = wq1[queued1 + lane]; }
-      bool pass = false;
-      if (h2 >= 0) {
-        double s[4][3], q[4][3];
-        pass = sample_and_check_edges(rec, (unsigned)n, base, (unsigned)h2, edge_sim, s, q);
-      }
+      const bool pass = h2 >= 0 && recs.six((unsigned)n, base, (unsigned)h2);
       const unsigned long long m = __ballot(pass);
       if (pass) wq[queued + __popcll(m & ((1ull << lane) - 1ull))] = h2;
       queued += __popcll(m);
@@ -235,6 +324,52 @@ __global__ __launch_bounds__(GEN_THREADS) void k_generate(PairArgs a) {
   flush(lane < queued ? wq[lane] : -1);
 }
 
+// the exact form (eyoc_ransac_select_generate 0, and launches with a pair larger than LDS_RECORDS_Q)
+template <bool IN_LDS>
+__global__ __launch_bounds__(GEN_THREADS) void k_generate(PairArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lrec[];
+  __shared__ int queue[GEN_THREADS / 64][128], queue1[GEN_THREADS / 64][128];
+  const int c = blockIdx.y;
+  const int s0 = a.s0[c], n = a.n[c];
+  const float* rec = a.rec + (size_t)s0 * 6;
+  if (IN_LDS) {
+    for (int i = threadIdx.x; i < n * 6 / 2; i += GEN_THREADS)
+      reinterpret_cast<float2*>(lrec)[i] = reinterpret_cast<const float2*>(rec)[i];
+    __syncthreads();
+    rec = lrec;
+  }
+  generate_loop(a, c, ExactRecords{rec, (double)a.edge_sim}, queue, queue1);
+}
+
+// the compact form: 12 bytes per record, 76 KB of LDS at 5000 records with the queues, at most 64 registers - two workgroups per CU
+__global__ __launch_bounds__(GEN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_generate_q(PairArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lrec[];
+  __shared__ int queue[GEN_THREADS / 64][128], queue1[GEN_THREADS / 64][128];
+  const int c = blockIdx.y;
+  const int s0 = a.s0[c], n = a.n[c];
+  float inv_step;
+  if (!pair_is_compact(a, c, inv_step)) {                                // workgroup-uniform: no usable scale - k_fit walks ALL hypotheses of this pair
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.n_surv[c * CNT_STRIDE + 2] = -1;
+    return;
+  }
+  uint2* xyzq = reinterpret_cast<uint2*>(lrec);
+  unsigned int* qyz = reinterpret_cast<unsigned int*>(xyzq + n);
+  const float2* rec = reinterpret_cast<const float2*>(a.rec + (size_t)s0 * 6);
+  for (int i = threadIdx.x; i < n; i += GEN_THREADS) {
+    const float2 p0 = rec[3 * i], p1 = rec[3 * i + 1], p2 = rec[3 * i + 2];
+    const unsigned int x = (unsigned int)(int)rintf(p0.x * inv_step) & 0xFFFFu, y = (unsigned int)(int)rintf(p0.y * inv_step) << 16;
+    const unsigned int z = (unsigned int)(int)rintf(p1.x * inv_step) & 0xFFFFu, qx = (unsigned int)(int)rintf(p1.y * inv_step) << 16;
+    const unsigned int qy = (unsigned int)(int)rintf(p2.x * inv_step) & 0xFFFFu, qz = (unsigned int)(int)rintf(p2.y * inv_step) << 16;
+    xyzq[i] = make_uint2(x | y, z | qx);
+    qyz[i] = qy | qz;
+  }
+  __syncthreads();
+  const double e2 = (double)a.edge_sim * (double)a.edge_sim;
+  const float c_up = __double2float_ru((1.0 + 0x1p-8) * (1.0 + 0x1p-20));
+  const float c_dn = __double2float_rd(e2 * (1.0 - 0x1p-8) * (1.0 - 0x1p-20));
+  generate_loop(a, c, CompactRecords{xyzq, qyz, c_up, c_dn}, queue, queue1);
+}
+
 // 4-point fit + distance checker of the queued candidates: one lane per candidate, 256-thread workgroups (the whole register
 // file: no scratch), records from global memory (a pair's 120 KB stay in L2).  Survivors append their hypothesis number and
 // transform exactly as the fused kernel did; which slot a survivor gets depends on atomics, the results do not.
@@ -244,14 +379,17 @@ __global__ __launch_bounds__(256) void k_fit(PairArgs a) {
   const int n = a.n[c];
   const unsigned long long base = pair_base(a.seed, a.pair0 + c);
   int* cnt = a.n_surv + c * CNT_STRIDE;
-  const int ncand = cnt[2];
+  const bool all = cnt[2] < 0;                              // k_generate_q made no list for this pair (no usable scale): every hypothesis is a candidate
+  const int ncand = all ? a.H : cnt[2];
   const int* __restrict__ cand = a.cnts + (size_t)c * a.H;
   int* surv = a.surv + (size_t)c * a.H;
   const double edge_sim = (double)a.edge_sim, max_dist = (double)a.max_dist;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < ncand; i += gridDim.x * 256) {
-    const int h = cand[i];
+    const int h = all ? i : cand[i];
     double s[4][3], q[4][3], R[3][3], t[3];
-    sample_and_check_edges(rec, (unsigned)n, base, (unsigned)h, edge_sim, s, q);   // re-draws the sample (cheaper than queueing 24 doubles)
+    // re-draws the sample (cheaper than queueing 24 doubles) and DECIDES the edge checks: k_generate's compact form passes on what
+    // its band cannot reject (under the exact form nothing fails here)
+    if (!sample_and_check_edges(rec, (unsigned)n, base, (unsigned)h, edge_sim, s, q)) continue;
     if (!fit_and_check_distance(s, q, max_dist, R, t)) continue;
     const int slot = atomicAdd(cnt, 1);
     surv[slot] = h;
@@ -833,14 +971,17 @@ int ransac_run(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const 
   a.rec_sorted = (float*)(sc + l.off_rs); a.rr_sorted = (float*)(sc + l.off_rr); a.bucket_end = (int*)(sc + l.off_be); a.pmax = (double*)(sc + l.off_pm);
   const int pruned = ctx->knobs.ransac_prune && max_n <= 8192 ? 1 : 0;
   const int want_bound = ctx->knobs.ransac_prune >= 2 ? 1 : 0;
+  // eyoc_ransac_select_generate 1: the compact records, where a launch's pairs fit the LDS in that form and the band's derivation holds
+  // (0 < edge_similarity <= 1)
+  const bool compact = ctx->knobs.ransac_generate == 1 && max_n <= LDS_RECORDS_Q && p->edge_similarity > 0.0f && p->edge_similarity <= 1.0f;
   const bool in_lds = max_n <= LDS_RECORDS;
-  const size_t lds_bytes = in_lds ? (size_t)max_n * 24 : 0;
-  if (in_lds) {
-    if (!ctx->ransac_attr_set) {
-      EYOC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_generate<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         LDS_RECORDS * 24));
-      ctx->ransac_attr_set = true;
-    }
+  const size_t lds_bytes = compact ? (size_t)max_n * 12 : in_lds ? (size_t)max_n * 24 : 0;
+  if (!ctx->ransac_attr_set) {
+    EYOC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_generate<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       LDS_RECORDS * 24));
+    EYOC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_generate_q), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       LDS_RECORDS_Q * 12));
+    ctx->ransac_attr_set = true;
   }
   for (int p0 = 0; p0 < n_pairs; p0 += chunk) {
     const int nc = n_pairs - p0 < chunk ? n_pairs - p0 : chunk;
@@ -859,7 +1000,10 @@ int ransac_run(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const 
     hipLaunchKernelGGL(k_gather_targets, dim3(cdiv(chunk_max, 256), nc), dim3(256), 0, st, src_dev, tgt_dev,
                        (const long long*)corr_tgt_dev, a);
     const int gen_blocks = GEN_BLOCKS_TOTAL / nc > GEN_BLOCKS_MIN ? GEN_BLOCKS_TOTAL / nc : GEN_BLOCKS_MIN;
-    if (in_lds) hipLaunchKernelGGL(k_generate<true>, dim3(gen_blocks, nc), dim3(GEN_THREADS), lds_bytes, st, a);
+    if (compact) {
+      const int total = max_n <= GEN_Q_PAIRED ? GEN_Q_BLOCKS_TOTAL : GEN_BLOCKS_TOTAL;
+      hipLaunchKernelGGL(k_generate_q, dim3(total / nc > GEN_BLOCKS_MIN ? total / nc : GEN_BLOCKS_MIN, nc), dim3(GEN_THREADS), lds_bytes, st, a);
+    } else if (in_lds) hipLaunchKernelGGL(k_generate<true>, dim3(gen_blocks, nc), dim3(GEN_THREADS), lds_bytes, st, a);
     else hipLaunchKernelGGL(k_generate<false>, dim3(gen_blocks, nc), dim3(GEN_THREADS), 0, st, a);
     hipLaunchKernelGGL(k_fit, dim3(2048 / nc > 8 ? 2048 / nc : 8, nc), dim3(256), 0, st, a);
     if (pruned) hipLaunchKernelGGL(k_bucket, dim3(nc), dim3(256), 0, st, a);
@@ -963,6 +1107,13 @@ extern "C" int eyoc_ransac_select_pruning(eyoc_ctx* ctx, int on) {
   if (!ctx) return -1;
   const int prev = ctx->knobs.ransac_prune;
   if (on >= 0 && on <= 2) ctx->knobs.ransac_prune = on;
+  return prev;
+}
+
+extern "C" int eyoc_ransac_select_generate(eyoc_ctx* ctx, int form) {
+  if (!ctx) return -1;
+  const int prev = ctx->knobs.ransac_generate;
+  if (form == 0 || form == 1) ctx->knobs.ransac_generate = form;
   return prev;
 }
 

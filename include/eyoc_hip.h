@@ -488,6 +488,12 @@ int eyoc_model_timing_slot(eyoc_model* model, int slot);
  * mode 0: never, 1 (default): when the query fills the chip (>= 512 waves of 64 rows), 2: always; < 0 only queries.
  * Returns the previous mode.  Per ctx; for tests and profiling. */
 int eyoc_knn_prefilter(eyoc_ctx* ctx, int mode);
+/* The pre-filter's packing of the targets alone, into caller-owned device memory (tests): for the `nseg` segments seg_b[s] ..
+ * seg_b[s + 1] of B [*, 32], segment after segment, per tile of 16 targets 3 x 64 float4 - the fp16 hi halves of the power-of-two
+ * scaled rows in MFMA operand order, the lo halves, and (|b|^2, 1 / scale, 0, 0) per lane (padding targets: +inf, 0; zero_norm != 0:
+ * norm 0) - `packed_floats` >= sum over s of ceil(nb_s / 16) * 768; bmax_dev[s] = bits of the segment's largest |b|^2 (0 if empty). */
+int eyoc_knn_pack_targets(eyoc_ctx* ctx, const float* B_dev, const int32_t* seg_b, int nseg, int zero_norm, float* packed_dev,
+                          size_t packed_floats, int32_t* bmax_dev, void* stream);
 /* ------------------------------------------------------------------------------------------------
  * feature matching
  *   replaces: lib.eval.find_nn_gpu + lib.metrics.pdist (lib/eval.py:18-48, lib/metrics.py:22-29)
@@ -726,6 +732,14 @@ int eyoc_ransac_batched(eyoc_ctx* ctx, const float* src_dev, const float* tgt_de
  * cannot win stay partial; it is applied to launch chunks of >= 32 pairs (every wave polls one word per pair: on fewer words the
  * polling costs more than the skipped work).  Other values only query.  Returns the previous state.  Per ctx; for tests / profiling. */
 int eyoc_ransac_select_pruning(eyoc_ctx* ctx, int on);
+/* Form of the hypothesis generator: 1 (default) samples from 16-bit fixed-point records (one power-of-two step per pair, from the
+ * pair's largest |coordinate|) and rejects a hypothesis only where a rigorous error band proves that the exact edge-length
+ * expression rejects it; 0 evaluates the exact fp64 expression on the fp32 records.  Either way the fit kernel re-evaluates the exact
+ * expression and drops what fails, so the survivors and every result record are the same bytes.  A pair with a non-finite
+ * coordinate, or whose largest |coordinate| lies outside [1e-18, 1e18] (all zeros included), has no usable step: the fit kernel
+ * evaluates the exact expression on every hypothesis of that pair.  Launches with more than 12000 correspondences in a pair, or an
+ * edge_similarity outside (0, 1], take form 0.  Other values only query.  Returns the previous state.  Per ctx; for tests / profiling. */
+int eyoc_ransac_select_generate(eyoc_ctx* ctx, int form);
 /* Per-pair failure isolation of the batched back-ends (default 0).  With 1, eyoc_ransac_batched(_ws) accepts pairs with 0..3
  * correspondences and eyoc_sc2pcr_batched pairs with 0..7 rows (empty segments included) instead of failing the call: such a pair
  * gets a defined failed output - RANSAC: T all NaN, best_hypothesis -1, survivors 0, inliers 0, inlier_rmse 0; SC2-PCR: T all NaN,
