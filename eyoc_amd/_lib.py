@@ -77,6 +77,16 @@ class ValidRecord(C.Structure):
                 ("hits", C.c_int32), ("n_corr", C.c_int32), ("n_points", C.c_int32), ("status", C.c_uint32), ("reserved", C.c_double)]
 
 
+class HclossRecord(C.Structure):
+    _fields_ = [("sum_pos", C.c_double), ("sum01", C.c_double), ("sum10", C.c_double), ("n_used", C.c_int32), ("k01", C.c_int32),
+                ("k10", C.c_int32), ("status", C.c_uint32), ("pos_loss", C.c_float), ("neg_loss", C.c_float)]
+
+
+class HclossLayout(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("anchors", "tile", "n_used", "table_slots")] +
+                [(k, C.c_uint64) for k in ("total", "off_record", "off_tstar", "off_dist", "off_pos_d2", "off_flags")])
+
+
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 # name -> (restype, argtypes); every symbol include/eyoc_hip.h declares
 PROTOTYPES = {
@@ -231,6 +241,11 @@ PROTOTYPES = {
     "eyoc_voxelize_batched_posed_workspace_bytes": (_sz, [_i, _i]),
     "eyoc_voxelize_batched_posed": (_i, [_vp, _vp, _i, C.POINTER(C.c_int64), _i, _i, _vp, _vp, C.c_double, _i, _vp, _vp, _vp,
                                          C.POINTER(C.c_int64), _vp, _sz, _vp, _vp]),
+    "eyoc_hcloss_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "eyoc_hcloss_workspace_layout": (_i, [_i, _i, _i, _i, _i, C.POINTER(HclossLayout)]),
+    "eyoc_hcloss_forward": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, C.c_float, C.c_float, _vp, _vp, _sz, _vp]),
+    "eyoc_hcloss_backward": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, C.c_float, C.c_float, _vp, _vp, _vp, _vp,
+                                  _vp, _sz, _vp]),
 }
 
 

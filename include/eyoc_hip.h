@@ -976,6 +976,70 @@ int eyoc_voxelize_batched_posed(eyoc_ctx* ctx, const float* xyz_dev, int stride,
                                 int32_t* coords_dev, float* xyz_out_dev, int64_t* voxel_offsets, void* workspace_dev,
                                 size_t workspace_bytes, void* stream, int32_t* cloud_faults);
 
+/* ------------------------------------------------------------------------------------------------
+ * hardest-contrastive loss and its gradient on device-resident positives (lib/trainer.py:935-991).  Added after 111 without a bump,
+ * additive only.
+ * replaces: contrastive_hardest_negative_loss and the autograd walk behind it, after the three np.random draws.
+ *   F0, F1      f32 [n0, c], [n1, c], c in {16, 32, 64}
+ *   pairs       int64 [n_pairs, 2] on the device: all known positives (collated rows)
+ *   used        int64 [n_used] indices into pairs (the positive sub-sample), NULL = all of them (n_used == n_pairs)
+ *   sel0, sel1  int64 [s0], [s1] candidate rows of F0 / F1
+ * Per used positive p = (i, j), a0 = F0[i], a1 = F1[j]; no contraction:
+ *   pos_d2 = f32(sum_c (a0_c - a1_c)^2 in fp64), pos_term = max(pos_d2 - pos_thresh, 0) in fp32
+ *   01: t* = the t in [0, s1) with the smallest sqrtf(d2(a0, F1[sel1[t]]) + 1e-7f) in fp32, channels left to right, ties to the lowest
+ *       t (the arithmetic and the answer of eyoc_knn1 with dist_type 1 on the gathered rows); dist = f32(sqrt(d2 + 1e-7f) in fp64) of
+ *       that pair (the search's own fp32 chain is up to 8 ulp off over 64 channels; the value kept is rounded once); masked when i + sel1[t*] * scale, scale = max(n0, n1), is one of the n_pairs keys
+ *       pairs[:,0] + pairs[:,1] * scale (an open-addressing table of integer compare-and-swaps: membership does not depend on the order
+ *       of pairs), else term = max(neg_thresh - dist, 0)^2
+ *   10: the mirror image, a1 against F0[sel0[t]], key sel0[t*] + j * scale.
+ * The three sums (pos_term, kept term01, kept term10) are fp64 sums of the fp32 terms in a fixed order: lane -> wave (one workgroup of
+ * EYOC_HCLOSS_ANCHORS positives), then the workgroups in order in a final pass.  pos_loss = f32(sum / n_used), neg_loss =
+ * f32((s01 / k01 + s10 / k10) / 2); a mean over nothing is NaN.  Every row index of pairs, used, sel0 and sel1 is checked before a
+ * feature is read through it: a bad one is skipped, sets EYOC_HCLOSS_BAD_INDEX and makes both losses (and, in the backward, every
+ * row that receives a contribution) NaN.  The per-positive results stay in the workspace (eyoc_hcloss_workspace_layout) for the backward.
+ *
+ * Backward, per positive: d/da0 = g_pos (2 / n_used) [pos_d2 - pos_thresh > 0] (a0 - a1), d/da1 its negative; 01, kept and dist <
+ * neg_thresh: w = -g_neg max(neg_thresh - dist, 0) / (k01 dist), d/da0 = w (a0 - b), d/db = -w (a0 - b), b = F1[sel1[t*]]; 10 mirrors it.
+ * No floating-point atomics: a row of dF0 sums its own contributions in fp64 and rounds once, in the order (anchor entries by p: positive
+ * term, then 01; then candidate entries of direction 10 by p) - dF1: (anchor entries by p: positive term, then 10; then candidate entries
+ * of 01) -, entry k of the row's list going to slot k mod (256 / c) and the slots added in order.  A row's bytes depend on its own list
+ * only; rows nothing touches are +0.0f.  dF0 [n0, c], dF1 [n1, c] are written completely.
+ *
+ * Launches: forward 5 (one fill, table build and index check, search, terms, final pass), backward 4 (two fills, weights, row sums), whatever
+ * the sizes.  Stream-ordered: no synchronisation, no allocation, no floating-point atomics, nothing read back; caller-owned 256-byte
+ * aligned workspace, which the backward reads as the forward of the SAME arguments left it.
+ * --------------------------------------------------------------------------------------------- */
+#define EYOC_HCLOSS_BAD_INDEX 1u
+#define EYOC_HCLOSS_ANCHORS 64      /* positives per workgroup of the search */
+#define EYOC_HCLOSS_TILE 128        /* candidate rows staged through LDS at a time */
+#define EYOC_HCLOSS_MASKED 1u       /* flags: the direction's hardest negative is a known positive (or there is no candidate) */
+#define EYOC_HCLOSS_VALID 2u        /* flags: the positive's own indices were in range */
+
+typedef struct eyoc_hcloss_record {
+  double sum_pos, sum01, sum10;
+  int32_t n_used, k01, k10;
+  uint32_t status;
+  float pos_loss, neg_loss;
+} eyoc_hcloss_record;               /* 48 bytes */
+
+/* byte offsets into the workspace: record (eyoc_hcloss_record), tstar int32 [2][n_used] (-1: none), dist f32 [2][n_used], pos_d2 f32
+ * [n_used], flags uint32 [2][n_used]; [0] is direction 01, [1] direction 10 */
+typedef struct eyoc_hcloss_layout {
+  int32_t anchors, tile, n_used, table_slots;
+  uint64_t total, off_record, off_tstar, off_dist, off_pos_d2, off_flags;
+} eyoc_hcloss_layout;
+
+size_t eyoc_hcloss_workspace_bytes(int n_pairs, int n_used, int s0, int s1, int c);
+int eyoc_hcloss_workspace_layout(int n_pairs, int n_used, int s0, int s1, int c, eyoc_hcloss_layout* out);
+int eyoc_hcloss_forward(eyoc_ctx* ctx, const float* F0_dev, int n0, const float* F1_dev, int n1, int c, const int64_t* pairs_dev,
+                        int n_pairs, const int64_t* used_dev, int n_used, const int64_t* sel0_dev, int s0, const int64_t* sel1_dev,
+                        int s1, float pos_thresh, float neg_thresh, eyoc_hcloss_record* record_out_dev, void* workspace_dev,
+                        size_t workspace_bytes, void* stream);
+int eyoc_hcloss_backward(eyoc_ctx* ctx, const float* F0_dev, int n0, const float* F1_dev, int n1, int c, const int64_t* pairs_dev,
+                         int n_pairs, const int64_t* used_dev, int n_used, const int64_t* sel0_dev, int s0, const int64_t* sel1_dev,
+                         int s1, float pos_thresh, float neg_thresh, const float* g_pos_dev, const float* g_neg_dev, float* dF0_dev,
+                         float* dF1_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,8 @@ from eyoc_amd import synthetic as syn  # noqa: E402
 from eyoc_amd.autograd import contrastive_hardest_negative_loss  # noqa: E402
 from eyoc_amd.harness import DeviceBatch, RegistrationConfig, RegistrationPipeline  # noqa: E402
 
+if os.environ.get("LOSS_ROUTE", "existing") == "device":      # the device-side loss (eyoc_amd/loss.py) instead of the torch-op route
+    from eyoc_amd.loss import hardest_contrastive_loss as contrastive_hardest_negative_loss  # noqa: E402,F811
 ITERS = int(os.environ.get("ITERS", "400"))
 N_TRAIN = int(os.environ.get("N_TRAIN", "24"))
 BEAMS, AZ = int(os.environ.get("BEAMS", "32")), int(os.environ.get("AZ", "1000"))
