@@ -87,6 +87,18 @@ class HclossLayout(C.Structure):
                 [(k, C.c_uint64) for k in ("total", "off_record", "off_tstar", "off_dist", "off_pos_d2", "off_flags")])
 
 
+class TripletRecord(C.Structure):
+    _fields_ = ([(k, C.c_double) for k in ("sum_rand", "sum01", "sum10", "sum_pos_dist", "sum_rand_neg", "sum_d01", "sum_d10")] +
+                [(k, C.c_int32) for k in ("n_used", "n_rand", "k_rand", "k01", "k10")] + [("status", C.c_uint32)] +
+                [(k, C.c_float) for k in ("loss", "pos_dist_mean", "neg_dist_mean")] + [("reserved", C.c_int32)])
+
+
+class TripletLayout(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("anchors", "tile", "n_used", "n_rand", "table_slots", "n_contrib")] +
+                [(k, C.c_uint64) for k in ("total", "off_record", "off_tstar", "off_dist", "off_pos_dist", "off_term", "off_flags",
+                                           "off_rand_pos", "off_rand_neg", "off_rand_term", "off_rand_flags", "off_contrib_key")])
+
+
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 # name -> (restype, argtypes); every symbol include/eyoc_hip.h declares
 PROTOTYPES = {
@@ -246,6 +258,12 @@ PROTOTYPES = {
     "eyoc_hcloss_forward": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, C.c_float, C.c_float, _vp, _vp, _sz, _vp]),
     "eyoc_hcloss_backward": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, C.c_float, C.c_float, _vp, _vp, _vp, _vp,
                                   _vp, _sz, _vp]),
+    "eyoc_triplet_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "eyoc_triplet_workspace_layout": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(TripletLayout)]),
+    "eyoc_triplet_forward": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, C.c_float, _vp, _vp, _sz,
+                                  _vp]),
+    "eyoc_triplet_backward": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, C.c_float, _vp, _vp, _vp,
+                                   _vp, _sz, _vp]),
 }
 
 

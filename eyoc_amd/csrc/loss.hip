@@ -14,6 +14,7 @@
 // in fp32, channels in order, no contraction, sqrtf(acc + 1e-7f) - so t* is eyoc_knn1's.  The two values of a positive that enter the
 // loss (pos_d2, and dist of the chosen candidate) are then evaluated once more with an fp64 accumulator and rounded to fp32 once:
 // an fp32 chain over 64 channels is up to 8 ulp from the exact value, and the stage tests hold these values to one ulp of fp64.
+// The triplet losses of the reference's other two trainers follow below the hardest-contrastive entry points, on the same table and search.
 #include "pose_math.h"
 
 using namespace eyoc;
@@ -524,6 +525,33 @@ __global__ __launch_bounds__(HC_THREADS) void hc_rows_kernel(const float* __rest
   dF[(size_t)row * C + threadIdx.x] = w.ctl->rec.status ? __builtin_nanf("") : (float)total;
 }
 
+// the first three launches of a forward, shared by the hardest-contrastive and the triplet losses: the fill (control block, key table,
+// search minima), the key table with the index check, the search of both directions
+int launch_prep_search(const float* F0, int n0, const float* F1, int n1, int c, const long long* P, int n_pairs, const long long* U, int n_used,
+                       const long long* S0, int s0, const long long* S1, int s1, const HcWs& w, hipStream_t st) {
+  EYOC_CHECK_HIP(hipMemsetAsync(w.ctl, 0, w.fill_bytes, st));
+  int n_max = n_pairs;
+  n_max = n_used > n_max ? n_used : n_max;
+  n_max = s0 > n_max ? s0 : n_max;
+  n_max = s1 > n_max ? s1 : n_max;
+  int pg = cdiv(n_max, HC_THREADS);
+  pg = pg < 1 ? 1 : (pg > 4096 ? 4096 : pg);
+  hipLaunchKernelGGL(hc_prep_kernel, dim3(pg), dim3(HC_THREADS), 0, st, P, n_pairs, U, n_used, S0, s0, S1, s1, n0, n1, n_max, w);
+  // the candidate tiles split over grid.z until ~512 workgroups are in flight (the answer does not depend on the split)
+  const int s_max = s0 > s1 ? s0 : s1;
+  int tiles = cdiv(s_max, HC_T), zs = cdiv(512, 2 * w.nwg);
+  tiles = tiles < 1 ? 1 : tiles;
+  zs = zs > tiles ? tiles : zs;
+  const dim3 grid(w.nwg, 2, zs);
+#define HC_SEARCH(CC) \
+  hipLaunchKernelGGL((hc_search_kernel<CC>), grid, dim3(HC_THREADS), 0, st, F0, n0, F1, n1, P, n_pairs, U, n_used, S0, s0, S1, s1, w)
+  if (c == 16) HC_SEARCH(16);
+  else if (c == 32) HC_SEARCH(32);
+  else HC_SEARCH(64);
+#undef HC_SEARCH
+  return EYOC_OK;
+}
+
 int check_args(const char* what, const eyoc_ctx* ctx, const void* F0, int n0, const void* F1, int n1, int c, const void* pairs, int n_pairs,
                const void* used, int n_used, const void* sel0, int s0, const void* sel1, int s1, const void* ws, size_t ws_bytes) {
   EYOC_REQUIRE(ctx, EYOC_ERR_INVALID, "%s: NULL ctx", what);
@@ -580,30 +608,15 @@ int eyoc_hcloss_forward(eyoc_ctx* ctx, const float* F0, int n0, const float* F1,
   const long long* U = (const long long*)used;
   const long long* S0 = (const long long*)sel0;
   const long long* S1 = (const long long*)sel1;
-  EYOC_CHECK_HIP(hipMemsetAsync(w.ctl, 0, w.fill_bytes, st));
-  int n_max = n_pairs;
-  n_max = n_used > n_max ? n_used : n_max;
-  n_max = s0 > n_max ? s0 : n_max;
-  n_max = s1 > n_max ? s1 : n_max;
-  int pg = cdiv(n_max, HC_THREADS);
-  pg = pg < 1 ? 1 : (pg > 4096 ? 4096 : pg);
-  hipLaunchKernelGGL(hc_prep_kernel, dim3(pg), dim3(HC_THREADS), 0, st, P, n_pairs, U, n_used, S0, s0, S1, s1, n0, n1, n_max, w);
-  // the candidate tiles split over grid.z until ~512 workgroups are in flight (the answer does not depend on the split)
-  const int s_max = s0 > s1 ? s0 : s1;
-  int tiles = cdiv(s_max, HC_T), zs = cdiv(512, 2 * w.nwg);
-  tiles = tiles < 1 ? 1 : tiles;
-  zs = zs > tiles ? tiles : zs;
-  const dim3 grid(w.nwg, 2, zs), grid_terms(w.nwg, 2);
-#define HC_FWD(CC)                                                                                                                    \
-  do {                                                                                                                                \
-    hipLaunchKernelGGL((hc_search_kernel<CC>), grid, dim3(HC_THREADS), 0, st, F0, n0, F1, n1, P, n_pairs, U, n_used, S0, s0, S1, s1, w); \
-    hipLaunchKernelGGL((hc_terms_kernel<CC>), grid_terms, dim3(64), 0, st, F0, n0, F1, n1, P, n_pairs, U, n_used, S0, s0, S1, s1,      \
-                       pos_thresh, neg_thresh, w);                                                                                    \
-  } while (0)
-  if (c == 16) HC_FWD(16);
-  else if (c == 32) HC_FWD(32);
-  else HC_FWD(64);
-#undef HC_FWD
+  if (int rc = launch_prep_search(F0, n0, F1, n1, c, P, n_pairs, U, n_used, S0, s0, S1, s1, w, st)) return rc;
+  const dim3 grid_terms(w.nwg, 2);
+#define HC_TERMS(CC)                                                                                                               \
+  hipLaunchKernelGGL((hc_terms_kernel<CC>), grid_terms, dim3(64), 0, st, F0, n0, F1, n1, P, n_pairs, U, n_used, S0, s0, S1, s1, pos_thresh, \
+                     neg_thresh, w)
+  if (c == 16) HC_TERMS(16);
+  else if (c == 32) HC_TERMS(32);
+  else HC_TERMS(64);
+#undef HC_TERMS
   hipLaunchKernelGGL(hc_final_kernel, dim3(1), dim3(HC_THREADS), 0, st, n_used, w, record_out);
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
@@ -634,6 +647,474 @@ int eyoc_hcloss_backward(eyoc_ctx* ctx, const float* F0, int n0, const float* F1
   else if (c == 32) HC_ROWS(32);
   else HC_ROWS(64);
 #undef HC_ROWS
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Triplet and hardest-triplet loss (lib/trainer.py:567-621, :701-782; include/eyoc_hip.h has the contract).  The workspace starts with
+// an HcWs of the same (n_pairs, n_used): hc_prep_kernel and hc_search_kernel run on it unchanged (key table, index check, t*).
+// Forward, 5 launches: the fill, hc_prep_kernel, hc_search_kernel, tr_terms_kernel (grid.y = direction 01, direction 10, random triplets;
+// lane = term), tr_final_kernel.  Backward: two fills, tr_weights_kernel (three contribution entries per term, entry number = sequence
+// number), one stable sort of (destination, entry number) by rocPRIM's radix_sort_pairs, tr_rows_kernel (one workgroup per sorted position; the first position
+// of a run of equal destinations adds the run in order, every other one leaves after two loads: linear in the list).
+namespace {
+
+static_assert(sizeof(eyoc_triplet_record) == 96, "eyoc_triplet_record is 96 bytes");
+static_assert(EYOC_TRIPLET_BAD_INDEX == EYOC_HCLOSS_BAD_INDEX, "hc_prep_kernel and hc_search_kernel set the shared status word");
+
+struct TrWs {
+  HcWs hc;                     // ctl (status), table, best; tstar, dist and flags [2][n_used] are used as the hcloss forward uses them
+  eyoc_triplet_record* rec;
+  float* pos_dist;             // [n_used]
+  float* term;                 // [2][n_used]
+  float *rpos, *rneg, *rterm;  // [n_rand]
+  unsigned int* rflags;        // [n_rand]
+  int nblk;                    // workgroups of the terms kernel per part (>= 1)
+  double* part_sum;            // [3][nblk][3]
+  int* part_cnt;               // [3][nblk]
+  int ncon;                    // 3 (n_rand + 2 n_used) contribution entries
+  unsigned int *ckey, *ckey_s; // destination 2 row + matrix + 1, 0 = empty; sorted
+  int *cidx, *cidx_s;          // entry numbers; sorted along
+  float *cwq, *cwn;            // the two factors of an entry
+  int *crq, *crn;              // the rows of the OTHER matrix they scale the difference to
+  void* sort_tmp;
+  size_t sort_bytes;
+  size_t total;
+};
+
+TrWs tr_carve(void* base, size_t bytes, int n_pairs, int n_used, int n_rand) {
+  TrWs w;
+  w.hc = carve(base, bytes, n_pairs, n_used);
+  Carver cv(base ? (char*)base + w.hc.total : nullptr, bytes > w.hc.total ? bytes - w.hc.total : 0);
+  const size_t n = (size_t)n_used, nr = (size_t)n_rand;
+  w.rec = (eyoc_triplet_record*)cv.take<char>(256);
+  w.pos_dist = cv.take<float>(n);
+  w.term = cv.take<float>(2 * n);
+  w.rpos = cv.take<float>(nr);
+  w.rneg = cv.take<float>(nr);
+  w.rterm = cv.take<float>(nr);
+  w.rflags = cv.take<unsigned int>(nr);
+  const int most = n_used > n_rand ? n_used : n_rand;
+  w.nblk = most > 0 ? cdiv(most, HC_A) : 1;
+  w.part_sum = cv.take<double>(9 * (size_t)w.nblk);
+  w.part_cnt = cv.take<int>(3 * (size_t)w.nblk);
+  w.ncon = 3 * (n_rand + 2 * n_used);
+  const size_t nc = (size_t)w.ncon;
+  w.ckey = cv.take<unsigned int>(nc);
+  w.ckey_s = cv.take<unsigned int>(nc);
+  w.cidx = cv.take<int>(nc);
+  w.cidx_s = cv.take<int>(nc);
+  w.cwq = cv.take<float>(nc);
+  w.cwn = cv.take<float>(nc);
+  w.crq = cv.take<int>(nc);
+  w.crn = cv.take<int>(nc);
+  w.sort_bytes = align_up(sort_rows_tmp_bytes(w.ncon, 32));
+  w.sort_tmp = cv.take<char>(w.sort_bytes);
+  w.total = w.hc.total + align_up(cv.off);
+  return w;
+}
+
+// grid (workgroups of 64 terms, part): part 0 / 1 = hardest direction 01 / 10 (lane = used positive), part 2 = random triplets
+template <int C>
+__global__ __launch_bounds__(64) void tr_terms_kernel(const float* __restrict__ F0, int n0, const float* __restrict__ F1, int n1,
+                                                      const long long* __restrict__ pairs, int n_pairs,
+                                                      const long long* __restrict__ used, int n_used,
+                                                      const long long* __restrict__ sel0, int s0, const long long* __restrict__ sel1,
+                                                      int s1, const long long* __restrict__ rand_idx,
+                                                      const long long* __restrict__ negatives, int n_rand, float margin, TrWs w) {
+#pragma clang fp contract(off)
+  const int part = blockIdx.y;
+  const int lane = threadIdx.x;
+  const int e = blockIdx.x * HC_A + lane;
+  const unsigned long long scale = (unsigned long long)(n0 > n1 ? n0 : n1);
+  double v0 = 0.0, v1 = 0.0, v2 = 0.0;   // the kept term; the positive distance (part 0) or the kept negative distance (part 2); d01 / d10
+  int kept = 0, bad = 0;
+  float a[C];
+  if (part < 2) {
+    const int dir = part, p = e;
+    const long long* __restrict__ sel = dir ? sel0 : sel1;
+    const float* __restrict__ FB = dir ? F0 : F1;
+    const int s = dir ? s0 : s1;
+    long long i, j;
+    const bool ok = load_anchor<C>(p, dir, F0, n0, F1, n1, pairs, n_pairs, used, n_used, a, i, j, bad);
+    if (ok) {
+      const float pos = (float)sqrt(row_d2(a, dir ? F0 + (size_t)i * C : F1 + (size_t)j * C) + (double)1e-7f);
+      unsigned int flags = EYOC_TRIPLET_VALID;
+      float dist = 0.0f, term = 0.0f;
+      int tstar = -1;
+      const unsigned long long raw = s > 0 ? w.hc.best[(size_t)dir * n_used + p] : 0ull;   // 0: no candidate was compared
+      const int best_t = (int)(unsigned int)(~raw & 0xFFFFFFFFull);
+      if (raw != 0ull && best_t >= 0 && best_t < s) {
+        tstar = best_t;
+        const unsigned long long r = (unsigned long long)sel[best_t];   // in range: only checked candidates are compared
+        dist = (float)sqrt(row_d2(a, FB + (size_t)r * C) + (double)1e-7f);
+        v2 = (double)dist;
+        const unsigned long long key = dir ? r + (unsigned long long)j * scale : (unsigned long long)i + r * scale;
+        kept = key_member(w.hc, key + 1ull) ? 0 : 1;
+      }
+      if (kept) {
+        const float t = (pos + margin) - dist;
+        if (t > 0.0f) {
+          term = t;
+          flags |= EYOC_TRIPLET_ACTIVE;
+        }
+        v0 = (double)term;
+      } else {
+        flags |= EYOC_TRIPLET_MASKED;
+      }
+      w.hc.tstar[(size_t)dir * n_used + p] = tstar;
+      w.hc.dist[(size_t)dir * n_used + p] = dist;
+      w.hc.flags[(size_t)dir * n_used + p] = flags;
+      w.term[(size_t)dir * n_used + p] = term;
+      if (dir == 0) {
+        w.pos_dist[p] = pos;
+        v1 = (double)pos;
+      }
+    } else if (p < n_used) {   // a positive with a bad index: nothing read, nothing counted
+      w.hc.tstar[(size_t)dir * n_used + p] = -1;
+      w.hc.dist[(size_t)dir * n_used + p] = 0.0f;
+      w.hc.flags[(size_t)dir * n_used + p] = EYOC_TRIPLET_MASKED;
+      w.term[(size_t)dir * n_used + p] = 0.0f;
+      if (dir == 0) w.pos_dist[p] = 0.0f;
+    }
+  } else if (e < n_rand) {
+    const int r = e;
+    const long long u = rand_idx[r], n = negatives[r];
+    long long ia = -1, iq = -1;
+    bool ok = u >= 0 && u < n_pairs && n >= 0 && n < n1;
+    if (u >= 0 && u < n_pairs) {
+      ia = pairs[2 * (size_t)u];
+      iq = pairs[2 * (size_t)u + 1];
+      ok = ok && ia >= 0 && ia < n0 && iq >= 0 && iq < n1;
+    }
+    float pos = 0.0f, neg = 0.0f, term = 0.0f;
+    unsigned int flags = EYOC_TRIPLET_MASKED;
+    if (!ok) {
+      bad = 1;
+    } else {
+      flags = EYOC_TRIPLET_VALID;
+      const unsigned long long key = (unsigned long long)ia + (unsigned long long)n * scale;
+      if (key_member(w.hc, key + 1ull)) {
+        flags |= EYOC_TRIPLET_MASKED;
+      } else {
+        const float4* src = reinterpret_cast<const float4*>(F0 + (size_t)ia * C);
+#pragma unroll
+        for (int q = 0; q < C / 4; ++q) {
+          const float4 v = src[q];
+          a[4 * q] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
+        }
+        pos = (float)sqrt(row_d2(a, F1 + (size_t)iq * C) + (double)1e-7f);
+        neg = (float)sqrt(row_d2(a, F1 + (size_t)n * C) + (double)1e-7f);
+        const float t = (pos + margin) - neg;
+        if (t > 0.0f) {
+          term = t;
+          flags |= EYOC_TRIPLET_ACTIVE;
+        }
+        kept = 1;
+        v0 = (double)term;
+        v1 = (double)neg;
+      }
+    }
+    w.rpos[r] = pos;
+    w.rneg[r] = neg;
+    w.rterm[r] = term;
+    w.rflags[r] = flags;
+  }
+  if (bad) atomicOr(&w.hc.ctl->status, EYOC_TRIPLET_BAD_INDEX);
+  v0 = wave_sum(v0);
+  v1 = wave_sum(v1);
+  v2 = wave_sum(v2);
+  kept = wave_sum_i(kept);
+  if (lane == 0) {
+    double* ps = w.part_sum + ((size_t)part * w.nblk + blockIdx.x) * 3;
+    ps[0] = v0; ps[1] = v1; ps[2] = v2;
+    w.part_cnt[(size_t)part * w.nblk + blockIdx.x] = kept;
+  }
+}
+
+__global__ __launch_bounds__(HC_THREADS) void tr_final_kernel(int n_pairs, int n_used, int n_rand, int hardest, TrWs w,
+                                                              eyoc_triplet_record* __restrict__ out) {
+#pragma clang fp contract(off)
+  __shared__ double red_d[HC_WAVES][9];
+  __shared__ int red_i[HC_WAVES][3];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double v[9];
+  int c[3] = {0, 0, 0};
+#pragma unroll
+  for (int k = 0; k < 9; ++k) v[k] = 0.0;
+  for (int b = threadIdx.x; b < w.nblk; b += HC_THREADS) {
+#pragma unroll
+    for (int part = 0; part < 3; ++part) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) v[3 * part + k] += w.part_sum[((size_t)part * w.nblk + b) * 3 + k];
+      c[part] += w.part_cnt[(size_t)part * w.nblk + b];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) v[k] = wave_sum(v[k]);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) c[k] = wave_sum_i(c[k]);
+  if (lane == 0) {
+    for (int k = 0; k < 9; ++k) red_d[wave][k] = v[k];
+    for (int k = 0; k < 3; ++k) red_i[wave][k] = c[k];
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double sum[9];
+  int cnt[3] = {0, 0, 0};
+  for (int k = 0; k < 9; ++k) sum[k] = 0.0;
+  for (int x = 0; x < HC_WAVES; ++x) {
+    for (int k = 0; k < 9; ++k) sum[k] += red_d[x][k];
+    for (int k = 0; k < 3; ++k) cnt[k] += red_i[x][k];
+  }
+  eyoc_triplet_record r;
+  r.sum01 = sum[0]; r.sum_pos_dist = sum[1]; r.sum_d01 = sum[2];
+  r.sum10 = sum[3]; r.sum_d10 = sum[5];
+  r.sum_rand = sum[6]; r.sum_rand_neg = sum[7];
+  r.n_used = n_used; r.n_rand = n_rand; r.k_rand = cnt[2]; r.k01 = cnt[0]; r.k10 = cnt[1];
+  r.status = w.hc.ctl->status;
+  r.reserved = 0;
+  const float nan = __builtin_nanf("");
+  const bool none = r.status != 0u || n_used == 0 || n_pairs == 0;
+  const double K = (double)(cnt[0] + cnt[1] + cnt[2]);
+  // a mean over nothing is 0 / 0 = NaN, the reference's value
+  r.loss = none ? nan : (float)(((r.sum_rand + r.sum01) + r.sum10) / K);
+  r.pos_dist_mean = none ? nan : (float)(r.sum_pos_dist / (double)n_used);
+  r.neg_dist_mean = none ? nan
+                         : (hardest ? (float)((r.sum_d01 / (double)n_used + r.sum_d10 / (double)n_used) / 2.0)
+                                    : (float)(r.sum_rand_neg / (double)cnt[2]));
+  *w.rec = r;
+  *out = r;
+}
+
+// one thread per term: its three contribution entries (anchor, positive, negative), or three empty ones
+__global__ __launch_bounds__(HC_THREADS) void tr_weights_kernel(const long long* __restrict__ pairs, int n_pairs,
+                                                                const long long* __restrict__ used, int n_used,
+                                                                const long long* __restrict__ sel0, int s0,
+                                                                const long long* __restrict__ sel1, int s1,
+                                                                const long long* __restrict__ rand_idx,
+                                                                const long long* __restrict__ negatives, int n_rand, int n0, int n1,
+                                                                const float* __restrict__ g, TrWs w) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * HC_THREADS + threadIdx.x;
+  if (t >= n_rand + 2 * n_used) return;
+  const eyoc_triplet_record rec = *w.rec;
+  const long long K = (long long)rec.k_rand + rec.k01 + rec.k10;
+  long long ra = -1, rq = -1, rn = -1;   // rows of the anchor, the positive and the negative
+  int mA = 0;                            // the anchor's matrix
+  float pos = 0.0f, neg = 0.0f;
+  bool emit = false;
+  if (t < n_rand) {
+    if (w.rflags[t] & EYOC_TRIPLET_ACTIVE) {
+      const long long u = rand_idx[t];
+      rn = negatives[t];
+      if (u >= 0 && u < n_pairs) {
+        ra = pairs[2 * (size_t)u];
+        rq = pairs[2 * (size_t)u + 1];
+      }
+      pos = w.rpos[t];
+      neg = w.rneg[t];
+      emit = ra >= 0 && ra < n0 && rq >= 0 && rq < n1 && rn >= 0 && rn < n1;
+    }
+  } else {
+    const int dir = t - n_rand >= n_used ? 1 : 0;
+    const int p = t - n_rand - dir * n_used;
+    if (w.hc.flags[(size_t)dir * n_used + p] & EYOC_TRIPLET_ACTIVE) {
+      const long long u = used ? used[p] : (long long)p;
+      long long i = -1, j = -1;
+      if (u >= 0 && u < n_pairs) {
+        i = pairs[2 * (size_t)u];
+        j = pairs[2 * (size_t)u + 1];
+      }
+      const int tt = w.hc.tstar[(size_t)dir * n_used + p];
+      const int s = dir ? s0 : s1;
+      if (tt >= 0 && tt < s) rn = dir ? sel0[tt] : sel1[tt];
+      mA = dir;
+      ra = dir ? j : i;
+      rq = dir ? i : j;
+      pos = w.pos_dist[p];
+      neg = w.hc.dist[(size_t)dir * n_used + p];
+      const int nA = dir ? n1 : n0, nO = dir ? n0 : n1;
+      emit = ra >= 0 && ra < nA && rq >= 0 && rq < nO && rn >= 0 && rn < nO;
+    }
+  }
+  emit = emit && K > 0 && n_used > 0 && n_pairs > 0;
+  unsigned int key[3] = {0u, 0u, 0u};
+  float wq = 0.0f, wn = 0.0f;
+  if (emit) {
+    const double gk = (double)*g / (double)K;
+    wq = (float)(gk / (double)pos);
+    wn = (float)(-gk / (double)neg);
+    key[0] = 2u * (unsigned int)ra + (unsigned int)mA + 1u;
+    key[1] = 2u * (unsigned int)rq + (unsigned int)(1 - mA) + 1u;
+    key[2] = 2u * (unsigned int)rn + (unsigned int)(1 - mA) + 1u;
+  }
+  const size_t e = 3 * (size_t)t;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    w.ckey[e + k] = key[k];
+    w.cidx[e + k] = (int)(e + k);
+  }
+  w.cwq[e] = wq;     w.cwn[e] = wn;       w.crq[e] = (int)rq;     w.crn[e] = (int)rn;
+  w.cwq[e + 1] = wq; w.cwn[e + 1] = 0.0f; w.crq[e + 1] = (int)ra; w.crn[e + 1] = 0;
+  w.cwq[e + 2] = wn; w.cwn[e + 2] = 0.0f; w.crq[e + 2] = (int)ra; w.crn[e + 2] = 0;
+}
+
+// One workgroup per position of the sorted list.  The first position of a run of equal destinations does the row: C lanes take one entry
+// (lane = channel), 256 / C entries side by side, entry k of the run goes to slot k mod (256 / C), the slots are added in order.  Every
+// other position leaves after two loads, so the list is read a bounded number of times however long a run is.
+template <int C>
+__global__ __launch_bounds__(HC_THREADS) void tr_rows_kernel(const float* __restrict__ F0, const float* __restrict__ F1, TrWs w,
+                                                             float* __restrict__ dF0, float* __restrict__ dF1) {
+#pragma clang fp contract(off)
+  constexpr int G = HC_THREADS / C;
+  __shared__ double slot_acc[HC_THREADS];
+  const int k = blockIdx.x;
+  const unsigned int key = w.ckey_s[k];
+  if (key == 0u) return;
+  if (k > 0 && w.ckey_s[k - 1] == key) return;
+  const int m = (int)((key - 1u) & 1u);
+  const size_t row = (size_t)((key - 1u) >> 1);
+  const int slot = threadIdx.x / C, ch = threadIdx.x % C;
+  const float* __restrict__ FO = m ? F0 : F1;   // the other matrix
+  const double own = (double)(m ? F1 : F0)[row * C + ch];
+  double acc = 0.0;
+  for (int q = slot; k + q < w.ncon && w.ckey_s[k + q] == key; q += G) {
+    const int e = w.cidx_s[k + q];
+    acc += (double)w.cwq[e] * (own - (double)FO[(size_t)w.crq[e] * C + ch]);
+    const float wn = w.cwn[e];
+    if (wn != 0.0f) acc += (double)wn * (own - (double)FO[(size_t)w.crn[e] * C + ch]);
+  }
+  slot_acc[threadIdx.x] = acc;
+  __syncthreads();
+  if (threadIdx.x >= C) return;
+  double total = 0.0;
+#pragma unroll
+  for (int g = 0; g < G; ++g) total += slot_acc[g * C + threadIdx.x];
+  float* __restrict__ dF = m ? dF1 : dF0;
+  dF[row * C + threadIdx.x] = w.rec->status ? __builtin_nanf("") : (float)total;
+}
+
+int tr_check_args(const char* what, const eyoc_ctx* ctx, const void* F0, int n0, const void* F1, int n1, int c, const void* pairs,
+                  int n_pairs, const void* used, int n_used, const void* sel0, int s0, const void* sel1, int s1, const void* rand_idx,
+                  const void* negatives, int n_rand, const void* ws, size_t ws_bytes) {
+  EYOC_REQUIRE(ctx, EYOC_ERR_INVALID, "%s: NULL ctx", what);
+  EYOC_REQUIRE(c == 16 || c == 32 || c == 64, EYOC_ERR_INVALID, "%s: feature dimension %d not supported (16/32/64)", what, c);
+  EYOC_REQUIRE(n0 >= 0 && n1 >= 0 && n_pairs >= 0 && n_used >= 0 && s0 >= 0 && s1 >= 0 && n_rand >= 0, EYOC_ERR_INVALID,
+               "%s: negative count", what);
+  EYOC_REQUIRE(n0 <= (1 << 30) && n1 <= (1 << 30), EYOC_ERR_INVALID, "%s: more than 2^30 rows", what);
+  EYOC_REQUIRE(n_pairs <= (1 << 28) && n_used <= (1 << 26) && n_rand <= (1 << 26), EYOC_ERR_INVALID,
+               "%s: more than 2^28 positives, 2^26 used positives or 2^26 random triplets", what);
+  EYOC_REQUIRE((s0 == 0) == (s1 == 0), EYOC_ERR_INVALID, "%s: s0 %d and s1 %d: both zero (no hardest parts) or both positive", what, s0, s1);
+  EYOC_REQUIRE(used || n_used == n_pairs || n_used == 0, EYOC_ERR_INVALID, "%s: used = NULL means all positives, n_used %d != n_pairs %d", what, n_used,
+               n_pairs);
+  EYOC_REQUIRE((F0 || n0 == 0) && (F1 || n1 == 0) && (pairs || n_pairs == 0) && (sel0 || s0 == 0) && (sel1 || s1 == 0) &&
+                   ((rand_idx && negatives) || n_rand == 0),
+               EYOC_ERR_INVALID, "%s: NULL argument", what);
+  EYOC_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, EYOC_ERR_INVALID, "%s: the workspace must be 256-byte aligned", what);
+  const size_t need = eyoc_triplet_workspace_bytes(n_pairs, n_used, s0, s1, n_rand, c);
+  EYOC_REQUIRE(ws_bytes >= need, EYOC_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", what, ws_bytes, need);
+  return EYOC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t eyoc_triplet_workspace_bytes(int n_pairs, int n_used, int s0, int s1, int n_rand, int c) {
+  (void)s0; (void)s1; (void)c;
+  if (n_pairs < 0 || n_used < 0 || n_rand < 0 || n_used > (1 << 26) || n_rand > (1 << 26)) return 0;
+  return tr_carve(nullptr, 0, n_pairs, n_used, n_rand).total;
+}
+
+int eyoc_triplet_workspace_layout(int n_pairs, int n_used, int s0, int s1, int n_rand, int c, eyoc_triplet_layout* out) {
+  EYOC_REQUIRE(out && n_pairs >= 0 && n_used >= 0 && s0 >= 0 && s1 >= 0 && n_rand >= 0 && n_used <= (1 << 26) && n_rand <= (1 << 26),
+               EYOC_ERR_INVALID, "eyoc_triplet_workspace_layout: invalid argument");
+  EYOC_REQUIRE(c == 16 || c == 32 || c == 64, EYOC_ERR_INVALID, "eyoc_triplet_workspace_layout: feature dimension %d not supported", c);
+  char* const base = (char*)(uintptr_t)4096;   // (a stand-in base, never dereferenced)
+  const TrWs w = tr_carve(base, 0, n_pairs, n_used, n_rand);
+  out->anchors = HC_A;
+  out->tile = HC_T;
+  out->n_used = n_used;
+  out->n_rand = n_rand;
+  out->table_slots = (int32_t)(w.hc.mask + 1);
+  out->n_contrib = w.ncon;
+  out->total = w.total;
+  out->off_record = (uint64_t)((char*)w.rec - base);
+  out->off_tstar = (uint64_t)((char*)w.hc.tstar - base);
+  out->off_dist = (uint64_t)((char*)w.hc.dist - base);
+  out->off_pos_dist = (uint64_t)((char*)w.pos_dist - base);
+  out->off_term = (uint64_t)((char*)w.term - base);
+  out->off_flags = (uint64_t)((char*)w.hc.flags - base);
+  out->off_rand_pos = (uint64_t)((char*)w.rpos - base);
+  out->off_rand_neg = (uint64_t)((char*)w.rneg - base);
+  out->off_rand_term = (uint64_t)((char*)w.rterm - base);
+  out->off_rand_flags = (uint64_t)((char*)w.rflags - base);
+  out->off_contrib_key = (uint64_t)((char*)w.ckey - base);
+  return EYOC_OK;
+}
+
+int eyoc_triplet_forward(eyoc_ctx* ctx, const float* F0, int n0, const float* F1, int n1, int c, const int64_t* pairs, int n_pairs,
+                         const int64_t* used, int n_used, const int64_t* sel0, int s0, const int64_t* sel1, int s1,
+                         const int64_t* rand_idx, const int64_t* negatives, int n_rand, float margin, eyoc_triplet_record* record_out,
+                         void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = tr_check_args("eyoc_triplet_forward", ctx, F0, n0, F1, n1, c, pairs, n_pairs, used, n_used, sel0, s0, sel1, s1, rand_idx,
+                             negatives, n_rand, ws, ws_bytes))
+    return rc;
+  EYOC_REQUIRE(record_out, EYOC_ERR_INVALID, "eyoc_triplet_forward: NULL record");
+  hipStream_t st = (hipStream_t)stream;
+  const TrWs w = tr_carve(ws, ws_bytes, n_pairs, n_used, n_rand);
+  const long long* P = (const long long*)pairs;
+  const long long* U = (const long long*)used;
+  const long long* S0 = (const long long*)sel0;
+  const long long* S1 = (const long long*)sel1;
+  const long long* RI = (const long long*)rand_idx;
+  const long long* NG = (const long long*)negatives;
+  // (rand_idx and negatives are checked by the terms kernel, the only reader of both)
+  if (int rc = launch_prep_search(F0, n0, F1, n1, c, P, n_pairs, U, n_used, S0, s0, S1, s1, w.hc, st)) return rc;
+  const dim3 grid_terms(w.nblk, 3);
+#define TR_TERMS(CC)                                                                                                                   \
+  hipLaunchKernelGGL((tr_terms_kernel<CC>), grid_terms, dim3(64), 0, st, F0, n0, F1, n1, P, n_pairs, U, n_used, S0, s0, S1, s1, RI, NG, n_rand, \
+                     margin, w)
+  if (c == 16) TR_TERMS(16);
+  else if (c == 32) TR_TERMS(32);
+  else TR_TERMS(64);
+#undef TR_TERMS
+  hipLaunchKernelGGL(tr_final_kernel, dim3(1), dim3(HC_THREADS), 0, st, n_pairs, n_used, n_rand, s1 > 0 ? 1 : 0, w, record_out);
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
+int eyoc_triplet_backward(eyoc_ctx* ctx, const float* F0, int n0, const float* F1, int n1, int c, const int64_t* pairs, int n_pairs,
+                          const int64_t* used, int n_used, const int64_t* sel0, int s0, const int64_t* sel1, int s1,
+                          const int64_t* rand_idx, const int64_t* negatives, int n_rand, float margin, const float* g, float* dF0,
+                          float* dF1, void* ws, size_t ws_bytes, void* stream) {
+  (void)margin;
+  if (int rc = tr_check_args("eyoc_triplet_backward", ctx, F0, n0, F1, n1, c, pairs, n_pairs, used, n_used, sel0, s0, sel1, s1, rand_idx,
+                             negatives, n_rand, ws, ws_bytes))
+    return rc;
+  EYOC_REQUIRE(g && (dF0 || n0 == 0) && (dF1 || n1 == 0), EYOC_ERR_INVALID, "eyoc_triplet_backward: NULL argument");
+  hipStream_t st = (hipStream_t)stream;
+  const TrWs w = tr_carve(ws, ws_bytes, n_pairs, n_used, n_rand);
+  if (n0 > 0) EYOC_CHECK_HIP(hipMemsetAsync(dF0, 0, (size_t)n0 * c * sizeof(float), st));
+  if (n1 > 0) EYOC_CHECK_HIP(hipMemsetAsync(dF1, 0, (size_t)n1 * c * sizeof(float), st));
+  if (n_used == 0 || n_pairs == 0) return EYOC_OK;   // no term, no contribution
+  hipLaunchKernelGGL(tr_weights_kernel, dim3(cdiv(n_rand + 2 * n_used, HC_THREADS)), dim3(HC_THREADS), 0, st, (const long long*)pairs,
+                     n_pairs, (const long long*)used, n_used, (const long long*)sel0, s0, (const long long*)sel1, s1,
+                     (const long long*)rand_idx, (const long long*)negatives, n_rand, n0, n1, g, w);
+  // keys are 2 row + matrix + 1 <= 2 max(n0, n1): that many bits; equal keys keep their entry order (a radix sort is stable)
+  const unsigned long long top = 2ull * (unsigned long long)(n0 > n1 ? n0 : n1);
+  int bits = 1;
+  while ((1ull << bits) <= top) ++bits;
+  if (int rc = sort_rows_by_key(w.sort_tmp, w.sort_bytes, w.ckey, w.ckey_s, w.cidx, w.cidx_s, w.ncon, bits, st)) return rc;
+#define TR_ROWS(CC) hipLaunchKernelGGL((tr_rows_kernel<CC>), dim3(w.ncon), dim3(HC_THREADS), 0, st, F0, F1, w, dF0, dF1)
+  if (c == 16) TR_ROWS(16);
+  else if (c == 32) TR_ROWS(32);
+  else TR_ROWS(64);
+#undef TR_ROWS
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
 }

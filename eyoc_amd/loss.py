@@ -4,7 +4,10 @@
 node on ``eyoc_hcloss_forward`` / ``eyoc_hcloss_backward`` (csrc/loss.hip): the positives may be a device tensor and then never leave
 the device (the label stages produce them there), the three host draws go up in one asynchronous copy, nothing is read back, the
 number of launches is fixed (5 + 4) and the gradient rows are summed in a fixed order without floating-point atomics - their bytes do
-not change from run to run.  The existing function stays; this route is opt-in."""
+not change from run to run.  The existing function stays; this route is opt-in.
+
+``triplet_loss`` / ``hardest_triplet_loss`` (second half of the file) are the losses of the reference's other two trainers
+(lib/trainer.py:567-621, :701-782) on ``eyoc_triplet_forward`` / ``eyoc_triplet_backward``, built the same way."""
 from __future__ import annotations
 
 import ctypes as C
@@ -134,3 +137,164 @@ def hardest_contrastive_loss(F0, F1, positive_pairs, num_pos=5192, num_hn_sample
     used = None if keep is None else draws[s0 + s1:]
     return _HardestContrastive.apply(F0.contiguous(), F1.contiguous(), pairs, used, draws[:s0], draws[s0:s0 + s1], float(pos_thresh),
                                      float(neg_thresh))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Triplet and hardest-triplet loss (lib/trainer.py:567-621 and :701-782) on eyoc_triplet_forward / eyoc_triplet_backward: one autograd
+# node, 5 launches forward, 4 and one radix sort backward; the gradient rows are summed per destination row from a sorted contribution
+# list (linear in the number of contributions), in a fixed order, without floating-point atomics.
+TRIPLET_BAD_INDEX, TRIPLET_MASKED, TRIPLET_VALID, TRIPLET_ACTIVE = 1, 1, 2, 4
+_TRIPLET_FLOATS = C.sizeof(_lib.TripletRecord) // 4
+_TRIPLET_LOSS = _lib.TripletRecord.loss.offset // 4          # loss, pos_dist_mean, neg_dist_mean follow each other
+
+
+def triplet_layout(n_pairs, n_used, s0, s1, n_rand, c):
+    out = _lib.TripletLayout()
+    _lib.check(_lib.load().eyoc_triplet_workspace_layout(n_pairs, n_used, s0, s1, n_rand, c, C.byref(out)), "eyoc_triplet_workspace_layout")
+    return out
+
+
+def _triplet_args(F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, margin):
+    n_used = pairs.shape[0] if used is None else used.shape[0]
+    return (_lib.ctx(F0.device.index), _lib.ptr(F0), F0.shape[0], _lib.ptr(F1), F1.shape[0], F0.shape[1], _lib.ptr(pairs), pairs.shape[0],
+            _lib.ptr(used), n_used, _lib.ptr(sel0), sel0.shape[0], _lib.ptr(sel1), sel1.shape[0], _lib.ptr(rand_idx), _lib.ptr(negatives),
+            rand_idx.shape[0], float(margin))
+
+
+def check_triplet_lengths(n_pairs, n1, num_rand_triplet):
+    """The reference adds the random triplets' anchors and negatives element-wise (``_hash``) and raises a broadcast ``ValueError``
+    unless both draws have one length; so does this, before anything is drawn or enqueued."""
+    a, b = min(n_pairs, num_rand_triplet), min(n1, num_rand_triplet)
+    if a != b:
+        raise ValueError(f"triplet loss: {a} random (anchor, positive) pairs = min(n_pairs {n_pairs}, num_rand_triplet {num_rand_triplet}) "
+                         f"but {b} random negatives = min(N1 {n1}, num_rand_triplet): the reference cannot broadcast them either")
+
+
+def draw_triplet_samples(rng, n0, n1, n_pairs, num_hn_samples, num_pos, num_rand_triplet):
+    """The reference's draws in the reference's order -> ``(sel0, sel1, used, rand_idx, negatives)``: the two candidate sets only with
+    ``num_hn_samples`` (HardestTripletLossTrainer, :715-716; ``None``: empty), the positive sub-sample only if ``n_pairs > num_pos``
+    (``None`` otherwise), then the random triplets' pairs and negatives."""
+    check_triplet_lengths(n_pairs, n1, num_rand_triplet)
+    empty = np.zeros(0, np.int64)
+    sel0 = sel1 = empty
+    if num_hn_samples is not None:
+        sel0 = rng.choice(n0, min(n0, num_hn_samples), replace=False)
+        sel1 = rng.choice(n1, min(n1, num_hn_samples), replace=False)
+    used = rng.choice(n_pairs, num_pos, replace=False) if n_pairs > num_pos else None
+    rand_idx = rng.choice(n_pairs, min(n_pairs, num_rand_triplet), replace=False)
+    negatives = rng.choice(n1, min(n1, num_rand_triplet), replace=False)
+    return sel0, sel1, used, rand_idx, negatives
+
+
+def triplet_raw_forward(F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, margin=1.4):
+    """``eyoc_triplet_forward`` on device tensors -> ``(record, workspace)``: ``record`` a float32 view of the 96-byte
+    ``eyoc_triplet_record`` (``read_triplet_record`` decodes it), ``workspace`` what ``triplet_raw_backward`` and ``triplet_results``
+    read.  ``used = None`` takes every positive; empty ``sel0`` and ``sel1`` give the plain variant."""
+    _check_inputs(F0, F1, pairs, used, sel0, sel1)
+    _check_inputs(F0, F1, pairs, None, rand_idx, negatives)
+    if rand_idx.shape[0] != negatives.shape[0]:
+        raise ValueError(f"triplet loss: {rand_idx.shape[0]} random pairs, {negatives.shape[0]} random negatives")
+    lib = _lib.load()
+    n_used = pairs.shape[0] if used is None else used.shape[0]
+    with _lib.on_device(F0.device):
+        ws = _lib.workspace(lib.eyoc_triplet_workspace_bytes(pairs.shape[0], n_used, sel0.shape[0], sel1.shape[0], rand_idx.shape[0],
+                                                             F0.shape[1]), F0.device)
+        rec = torch.empty(_TRIPLET_FLOATS, dtype=torch.float32, device=F0.device)
+        _lib.check(lib.eyoc_triplet_forward(*_triplet_args(F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, margin), _lib.ptr(rec),
+                                            _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "eyoc_triplet_forward")
+    return rec, ws
+
+
+def triplet_raw_backward(F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, margin, g, ws):
+    """``eyoc_triplet_backward`` -> ``(dF0, dF1)``; ``g`` a float32 device scalar, ``ws`` from ``triplet_raw_forward`` on the same arguments."""
+    lib = _lib.load()
+    dF0, dF1 = torch.empty_like(F0), torch.empty_like(F1)
+    with _lib.on_device(F0.device):
+        _lib.check(lib.eyoc_triplet_backward(*_triplet_args(F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, margin), _lib.ptr(g),
+                                             _lib.ptr(dF0), _lib.ptr(dF1), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   "eyoc_triplet_backward")
+    return dF0, dF1
+
+
+def read_triplet_record(rec) -> _lib.TripletRecord:
+    """The record on the host (tests, logging): this READS BACK, the loss itself never does."""
+    return _lib.TripletRecord.from_buffer_copy(rec.detach().cpu().numpy().tobytes())
+
+
+def triplet_results(ws, n_pairs, n_used, s0, s1, n_rand, c):
+    """The per-term results the forward left in its workspace, as device views: ``tstar`` int32 [2, n_used] (-1: none), ``dist`` (d01,
+    d10), ``term`` float32 [2, n_used], ``pos_dist`` float32 [n_used], ``flags`` int32 [2, n_used] (``TRIPLET_MASKED`` / ``_VALID`` /
+    ``_ACTIVE``; row 0 is direction 01); ``rand_pos``, ``rand_neg``, ``rand_term`` float32 [n_rand], ``rand_flags`` int32 [n_rand];
+    ``contrib_key`` int32 [3 (n_rand + 2 n_used)], written by the backward (2 row + matrix + 1, 0 = empty)."""
+    lay = triplet_layout(n_pairs, n_used, s0, s1, n_rand, c)
+
+    def view(off, count, dtype):
+        return ws[off:off + 4 * count].view(dtype)
+    out = {"tstar": view(lay.off_tstar, 2 * n_used, torch.int32).view(2, n_used),
+           "dist": view(lay.off_dist, 2 * n_used, torch.float32).view(2, n_used),
+           "term": view(lay.off_term, 2 * n_used, torch.float32).view(2, n_used),
+           "pos_dist": view(lay.off_pos_dist, n_used, torch.float32),
+           "flags": view(lay.off_flags, 2 * n_used, torch.int32).view(2, n_used),
+           "rand_flags": view(lay.off_rand_flags, n_rand, torch.int32),
+           "contrib_key": view(lay.off_contrib_key, lay.n_contrib, torch.int32)}
+    for k in ("pos", "neg", "term"):
+        out["rand_" + k] = view(getattr(lay, "off_rand_" + k), n_rand, torch.float32)
+    return out
+
+
+class _Triplet(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, margin):
+        rec, ws = triplet_raw_forward(F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, margin)
+        ctx.save_for_backward(F0, F1)
+        ctx.idx, ctx.margin, ctx.ws = (pairs, used, sel0, sel1, rand_idx, negatives), margin, ws
+        loss, pos, neg = rec[_TRIPLET_LOSS], rec[_TRIPLET_LOSS + 1], rec[_TRIPLET_LOSS + 2]
+        ctx.mark_non_differentiable(pos, neg)
+        return loss, pos, neg
+
+    @staticmethod
+    def backward(ctx, g, _g_pos, _g_neg):
+        F0, F1 = ctx.saved_tensors
+        if g is None:                                   # a missing gradient is zero
+            g = torch.zeros((), dtype=torch.float32, device=F0.device)
+        dF0, dF1 = triplet_raw_backward(F0, F1, *ctx.idx, ctx.margin, g.to(torch.float32).contiguous(), ctx.ws)
+        return dF0, dF1, None, None, None, None, None, None, None
+
+
+def _triplet(F0, F1, positive_pairs, num_pos, num_hn_samples, num_rand_triplet, neg_thresh, rng):
+    dev = F0.device
+    if isinstance(positive_pairs, torch.Tensor):
+        pairs = positive_pairs
+    else:
+        pairs = torch.from_numpy(np.ascontiguousarray(np.asarray(positive_pairs), dtype=np.int64))
+    pairs = pairs.reshape(-1, 2).to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
+    n0, n1, n_pairs = F0.shape[0], F1.shape[0], pairs.shape[0]
+    sel0, sel1, used, rand_idx, negatives = draw_triplet_samples(np.random if rng is None else rng, n0, n1, n_pairs, num_hn_samples,
+                                                                 num_pos, num_rand_triplet)
+    parts = [sel0, sel1, rand_idx, negatives] + ([] if used is None else [used])
+    # the draws: one pinned staging buffer, one asynchronous copy
+    stage = torch.empty(sum(len(p) for p in parts), dtype=torch.int64, pin_memory=True)
+    host, bounds, at = stage.numpy(), [], 0
+    for p in parts:
+        host[at:at + len(p)] = p
+        bounds.append((at, at + len(p)))
+        at += len(p)
+    draws = stage.to(dev, non_blocking=True)
+    d = [draws[a:b] for a, b in bounds]
+    return _Triplet.apply(F0.contiguous(), F1.contiguous(), pairs, None if used is None else d[4], d[0], d[1], d[2], d[3], float(neg_thresh))
+
+
+def triplet_loss(F0, F1, positive_pairs, num_pos=1024, num_hn_samples=None, num_rand_triplet=1024, neg_thresh=1.4, rng=None):
+    """``TripletLossTrainer.triplet_loss`` (lib/trainer.py:567-621) -> ``(loss, pos_dist_mean, neg_dist_mean)``: ``loss`` a 0-dim tensor
+    with grad, the monitors 0-dim device tensors without (``neg_dist_mean``: the kept random triplets' mean negative distance).  The
+    draws are the reference's, in its order, from ``rng`` (default: the global ``np.random``); ``num_hn_samples`` is not read, as in the
+    reference.  ``positive_pairs`` on the device stays there; nothing is read back.  Raises ``ValueError`` where the reference does:
+    ``min(n_pairs, num_rand_triplet) != min(N1, num_rand_triplet)``.  No double backward; ``c`` in {16, 32, 64}."""
+    return _triplet(F0, F1, positive_pairs, num_pos, None, num_rand_triplet, neg_thresh, rng)
+
+
+def hardest_triplet_loss(F0, F1, positive_pairs, num_pos=1024, num_hn_samples=512, num_rand_triplet=1024, neg_thresh=1.4, rng=None):
+    """``HardestTripletLossTrainer.triplet_loss`` (lib/trainer.py:701-782): the random triplets plus, per used positive, its hardest
+    negative among ``num_hn_samples`` candidates in both directions -> ``(loss, pos_dist_mean, neg_dist_mean)`` as ``triplet_loss``;
+    ``neg_dist_mean`` is ``(D01min.mean() + D10min.mean()) / 2`` as a device tensor (the reference's ``.item()`` is the caller's)."""
+    return _triplet(F0, F1, positive_pairs, num_pos, int(num_hn_samples), num_rand_triplet, neg_thresh, rng)

@@ -1040,6 +1040,84 @@ int eyoc_hcloss_backward(eyoc_ctx* ctx, const float* F0_dev, int n0, const float
                          int s1, float pos_thresh, float neg_thresh, const float* g_pos_dev, const float* g_neg_dev, float* dF0_dev,
                          float* dF1_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * triplet and hardest-triplet loss (lib/trainer.py:567-621 and :701-782) and their gradient.  Added after 111 without a bump, additive
+ * only.  The arguments of eyoc_hcloss_* plus:
+ *   rand_idx    int64 [n_rand] indices into pairs: the random triplets' (anchor, positive) = pairs[rand_idx[r]]
+ *   negatives   int64 [n_rand] rows of F1: the random triplets' negatives
+ *   margin      the reference's neg_thresh
+ *   s0 == s1 == 0 switches the two hardest parts off (the plain TripletLossTrainer); one of them zero alone is EYOC_ERR_INVALID.
+ * dist(x, y) = f32(sqrt(sum_c (x_c - y_c)^2 + 1e-7f)) with the sum and the root in fp64: every distance that enters a term or a monitor
+ * is rounded to fp32 once.  Keys are i + j * max(n0, n1) in the table of eyoc_hcloss_* (membership does not depend on the order of pairs).
+ *   random r:   (a, q) = pairs[rand_idx[r]], n = negatives[r]; dropped when key (a, n) is known, else
+ *               term = max((dist(F0[a], F1[q]) + margin) - dist(F0[a], F1[n]), 0) in fp32, in that order
+ *   hardest 01: per used positive p = (i, j): t* as in eyoc_hcloss_forward (the search kernel is the same one: eyoc_knn1(dist_type 1)'s
+ *               fp32 arithmetic and answer), d01 = dist(F0[i], F1[sel1[t*]]); dropped when key (i, sel1[t*]) is known, else
+ *               term = max((dist(F0[i], F1[j]) + margin) - d01, 0)
+ *   hardest 10: the mirror, F1[j] against F0[sel0[t]], key (sel0[t*], j), the same positive distance.
+ * A term is ACTIVE when kept and (pos + margin) - neg > 0, strictly.  Sums are fp64 sums of the fp32 values in a fixed order: lane -> wave
+ * (one workgroup of EYOC_HCLOSS_ANCHORS terms), then the workgroups in order in a final pass.  K = k_rand + k01 + k10 and
+ *   loss = f32(((sum_rand + sum01) + sum10) / K), pos_dist_mean = f32(sum_pos_dist / n_used),
+ *   neg_dist_mean = f32(sum_rand_neg / k_rand) without the hardest parts (the kept random triplets' negative distances), else
+ *                   f32((sum_d01 / n_used + sum_d10 / n_used) / 2) over ALL used positives, dropped or not;
+ * a mean over nothing is NaN.  Every index of pairs, used, sel0, sel1, rand_idx and negatives is checked before a feature is read through
+ * it: a bad one is skipped, sets EYOC_TRIPLET_BAD_INDEX and makes the three values (and, in the backward, every row that receives a
+ * contribution) NaN.  n_used == 0 or n_pairs == 0: the three values are NaN, the gradients exactly +0.0f.
+ *
+ * Backward.  Every active term (anchor x_a, positive x_q, negative x_n, distances pos, neg; w = g / K) makes three contributions:
+ *   anchor row:    (w / pos) (x_a - x_q) + (-w / neg) (x_a - x_n)
+ *   positive row:  (w / pos) (x_q - x_a)
+ *   negative row:  (-w / neg) (x_n - x_a)
+ * with the two factors rounded to fp32.  Term t (random triplets by r, then direction 01 by p, then direction 10 by p) owns the entries
+ * 3 t (anchor), 3 t + 1 (positive), 3 t + 2 (negative) of the contribution list: the entry number is the sequence number.  Dropped and
+ * inactive terms leave their entries empty and read nothing.  The list is grouped by destination (row, matrix) with one stable radix sort
+ * (rocPRIM, its temporary storage carved from the workspace), and the first entry of every run adds the run in list order: C lanes per
+ * entry, 256 / c entries side by side, entry k of the run to slot k mod (256 / c), fp64 accumulators, the slots added in order, rounded
+ * once.  The work is linear in the number of contributions; no floating-point atomics.  A row's bytes depend on its own list only; rows
+ * nothing touches are +0.0f; dF0 [n0, c] and dF1 [n1, c] are written completely.
+ *
+ * Launches: forward 5 (one fill, table build and index check, search, terms, final pass); backward 4 of this library (two fills, weights,
+ * row sums), whatever the sizes, plus those of the one rocPRIM sort, which chooses its passes by the length of the list (8 at 18 432
+ * entries: a block sort and merge passes).  Stream-ordered: no synchronisation, no allocation, no
+ * environment variable, no floating-point atomics, nothing read back; caller-owned 256-byte aligned workspace, which the backward reads as
+ * the forward of the SAME arguments left it.
+ * --------------------------------------------------------------------------------------------- */
+#define EYOC_TRIPLET_BAD_INDEX 1u
+#define EYOC_TRIPLET_MASKED 1u      /* flags: dropped (the negative is a known positive, or there is no candidate) */
+#define EYOC_TRIPLET_VALID 2u       /* flags: the term's own indices were in range */
+#define EYOC_TRIPLET_ACTIVE 4u      /* flags: kept and (pos + margin) - neg > 0 */
+
+typedef struct eyoc_triplet_record {
+  double sum_rand, sum01, sum10;                          /* the kept terms of the three parts */
+  double sum_pos_dist, sum_rand_neg, sum_d01, sum_d10;    /* the monitors' sums */
+  int32_t n_used, n_rand, k_rand, k01, k10;
+  uint32_t status;
+  float loss, pos_dist_mean, neg_dist_mean;
+  int32_t reserved;
+} eyoc_triplet_record;              /* 96 bytes */
+
+/* byte offsets into the workspace: record (eyoc_triplet_record), tstar int32 [2][n_used] (-1: none), dist f32 [2][n_used] (d01, d10),
+ * pos_dist f32 [n_used], term f32 [2][n_used], flags uint32 [2][n_used] ([0] is direction 01, [1] direction 10); rand_pos, rand_neg,
+ * rand_term f32 [n_rand], rand_flags uint32 [n_rand]; after the backward: contrib_key uint32 [n_contrib], n_contrib = 3 (n_rand + 2 n_used): the
+ * destination of each entry as 2 row + matrix + 1 (matrix 0 = dF0, 1 = dF1), 0 = empty */
+typedef struct eyoc_triplet_layout {
+  int32_t anchors, tile, n_used, n_rand, table_slots, n_contrib;
+  uint64_t total, off_record, off_tstar, off_dist, off_pos_dist, off_term, off_flags, off_rand_pos, off_rand_neg, off_rand_term,
+      off_rand_flags, off_contrib_key;
+} eyoc_triplet_layout;
+
+size_t eyoc_triplet_workspace_bytes(int n_pairs, int n_used, int s0, int s1, int n_rand, int c);
+int eyoc_triplet_workspace_layout(int n_pairs, int n_used, int s0, int s1, int n_rand, int c, eyoc_triplet_layout* out);
+int eyoc_triplet_forward(eyoc_ctx* ctx, const float* F0_dev, int n0, const float* F1_dev, int n1, int c, const int64_t* pairs_dev,
+                         int n_pairs, const int64_t* used_dev, int n_used, const int64_t* sel0_dev, int s0, const int64_t* sel1_dev,
+                         int s1, const int64_t* rand_idx_dev, const int64_t* negatives_dev, int n_rand, float margin,
+                         eyoc_triplet_record* record_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int eyoc_triplet_backward(eyoc_ctx* ctx, const float* F0_dev, int n0, const float* F1_dev, int n1, int c, const int64_t* pairs_dev,
+                          int n_pairs, const int64_t* used_dev, int n_used, const int64_t* sel0_dev, int s0, const int64_t* sel1_dev,
+                          int s1, const int64_t* rand_idx_dev, const int64_t* negatives_dev, int n_rand, float margin,
+                          const float* g_dev, float* dF0_dev, float* dF1_dev, void* workspace_dev, size_t workspace_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
