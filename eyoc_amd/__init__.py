@@ -10,7 +10,8 @@ brief, ``find_correspondences`` and ``estimate_transform``.  All compute happens
 from ._lib import EyocError, LIB_PATH  # noqa: F401
 from .sparse_tensor import SparseTensor, CoordinateManager  # noqa: F401
 from .model import (load_model, ResUNet2, ResUNetBN2, ResUNetBN2B, ResUNetBN2C, ResUNetBN2D,  # noqa: F401
-                    ResUNetBN2E, ResUNetFatBN, MODELS)
+                    ResUNetBN2E, ResUNetFatBN, MODELS, ResUNetIN2, ResUNetIN2B, ResUNetIN2C, ResUNetIN2D, ResUNetIN2E,
+                    IN_MODELS)
 from .eval import find_nn_gpu, pdist, find_corr, find_correspondences, random_sample, knn1_segmented  # noqa: F401
 from .transform_estimation import (est_quad_linear_robust, estimate_transform, pose_estimation,  # noqa: F401
                                    rigid_transform_3d, transform, integrate_trans, est_quad_linear_robust_batched)

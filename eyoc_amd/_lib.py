@@ -195,6 +195,14 @@ PROTOTYPES = {
     "eyoc_bn_train_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, C.c_float, _i, _vp, _i, _vp, _vp, _sz, _vp]),
     "eyoc_bn_train_forward_running": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, C.c_float, _i, _vp, _i, _vp, _vp, _vp, C.c_float, _vp, _sz, _vp]),
     "eyoc_bn_train_backward": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "eyoc_in_chunk_rows": (_i, []),
+    "eyoc_in_plan_bytes": (_sz, [_i, _i]),
+    "eyoc_in_plan_layout": (_i, [_i, _i, C.POINTER(C.c_int64)]),
+    "eyoc_in_plan_build": (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "eyoc_in_workspace_bytes": (_sz, [_i, _i, _i]),
+    "eyoc_in_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, C.c_float, _i, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "eyoc_in_backward": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz,
+                              _vp]),
     "eyoc_maps_gather_window": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "eyoc_maps_gather_window_internal": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "eyoc_knn_prefilter": (_i, [_vp, _i]),

@@ -47,15 +47,29 @@ class _Norm(nn.Module):
         self.bn = nn.BatchNorm1d(c, momentum=momentum)
 
 
-class _Block(nn.Module):
-    """``BasicBlockBN`` (model/residual_block.py:9-35): conv1, norm1, conv2, norm2."""
+class _InstNorm(nn.Module):
+    """``ME.MinkowskiInstanceNorm`` (model/common.py:7-8): ``weight`` and ``bias`` ``[1, c]`` held directly (no ``.bn``), no running
+    statistics, no buffers - eval mode equals training mode.  eps = 1e-8."""
+    eps = 1e-8
 
-    def __init__(self, c, momentum):
+    def __init__(self, c):
         super().__init__()
+        self.num_features = c
+        self.weight = nn.Parameter(torch.ones(1, c))
+        self.bias = nn.Parameter(torch.zeros(1, c))
+
+
+class _Block(nn.Module):
+    """``BasicBlockBN`` / ``BasicBlockIN`` (model/residual_block.py:9-35, 56-61): conv1, norm1, conv2, norm2; ``norm_type`` is the
+    block's ``NORM_TYPE``."""
+
+    def __init__(self, c, momentum, norm_type='BN'):
+        super().__init__()
+        norm = (lambda: _Norm(c, momentum)) if norm_type == 'BN' else (lambda: _InstNorm(c))
         self.conv1 = _Conv(27, c, c)
-        self.norm1 = _Norm(c, momentum)
+        self.norm1 = norm()
         self.conv2 = _Conv(27, c, c)
-        self.norm2 = _Norm(c, momentum)
+        self.norm2 = norm()
 
 
 class ResUNet2(nn.Module):
@@ -70,10 +84,9 @@ class ResUNet2(nn.Module):
         super().__init__()
         if D != 3:
             raise ValueError("only D=3 is supported")
-        if self.NORM_TYPE != 'BN' or self.BLOCK_NORM_TYPE != 'BN':
-            # ResUNet2 itself has NORM_TYPE None (get_norm would raise in the reference too);
-            # the IN variants need instance norm, which is outside the hot path
-            raise NotImplementedError(f"{type(self).__name__}: only batch-norm variants are implemented")
+        if self.NORM_TYPE != 'BN' or self.BLOCK_NORM_TYPE not in ('BN', 'IN'):
+            # ResUNet2 itself has NORM_TYPE None (get_norm would raise in the reference too)
+            raise NotImplementedError(f"{type(self).__name__}: only batch-norm stage norms with BN or IN blocks are implemented")
         if conv1_kernel_size is None:
             raise ValueError("conv1_kernel_size is required (config.py:84 default is 5)")
         Cn, T = self.CHANNELS, self.TR_CHANNELS
@@ -81,18 +94,19 @@ class ResUNet2(nn.Module):
         self.conv1_kernel_size = conv1_kernel_size
         self.normalize_feature = normalize_feature
         m = bn_momentum
+        bt = self.BLOCK_NORM_TYPE
         self.conv1 = _Conv(conv1_kernel_size ** 3, in_channels, Cn[1]); self.norm1 = _Norm(Cn[1], m)
-        self.block1 = _Block(Cn[1], m)
-        self.conv2 = _Conv(27, Cn[1], Cn[2]); self.norm2 = _Norm(Cn[2], m); self.block2 = _Block(Cn[2], m)
-        self.conv3 = _Conv(27, Cn[2], Cn[3]); self.norm3 = _Norm(Cn[3], m); self.block3 = _Block(Cn[3], m)
-        self.conv4 = _Conv(27, Cn[3], Cn[4]); self.norm4 = _Norm(Cn[4], m); self.block4 = _Block(Cn[4], m)
-        self.conv4_tr = _Conv(27, Cn[4], T[4]); self.norm4_tr = _Norm(T[4], m); self.block4_tr = _Block(T[4], m)
-        self.conv3_tr = _Conv(27, Cn[3] + T[4], T[3]); self.norm3_tr = _Norm(T[3], m); self.block3_tr = _Block(T[3], m)
-        self.conv2_tr = _Conv(27, Cn[2] + T[3], T[2]); self.norm2_tr = _Norm(T[2], m); self.block2_tr = _Block(T[2], m)
+        self.block1 = _Block(Cn[1], m, bt)
+        self.conv2 = _Conv(27, Cn[1], Cn[2]); self.norm2 = _Norm(Cn[2], m); self.block2 = _Block(Cn[2], m, bt)
+        self.conv3 = _Conv(27, Cn[2], Cn[3]); self.norm3 = _Norm(Cn[3], m); self.block3 = _Block(Cn[3], m, bt)
+        self.conv4 = _Conv(27, Cn[3], Cn[4]); self.norm4 = _Norm(Cn[4], m); self.block4 = _Block(Cn[4], m, bt)
+        self.conv4_tr = _Conv(27, Cn[4], T[4]); self.norm4_tr = _Norm(T[4], m); self.block4_tr = _Block(T[4], m, bt)
+        self.conv3_tr = _Conv(27, Cn[3] + T[4], T[3]); self.norm3_tr = _Norm(T[3], m); self.block3_tr = _Block(T[3], m, bt)
+        self.conv2_tr = _Conv(27, Cn[2] + T[3], T[2]); self.norm2_tr = _Norm(T[2], m); self.block2_tr = _Block(T[2], m, bt)
         if self.EXPANDED:            # ResUNetExpanded (model/resunet.py:254-425): a second norm + block per stage
             for i, c in (("1", Cn[1]), ("2", Cn[2]), ("3", Cn[3]), ("4", Cn[4]), ("4_tr", T[4]), ("3_tr", T[3]), ("2_tr", T[2])):
                 setattr(self, f"norm{i}_2", _Norm(c, m))
-                setattr(self, f"block{i}_2", _Block(c, m))
+                setattr(self, f"block{i}_2", _Block(c, m, bt))
         self.conv1_tr = _Conv(1, Cn[1] + T[2], T[1])
         self.final = _Conv(1, T[1], out_channels, bias=True)
         self._handle = None      # eyoc_model*
@@ -111,6 +125,16 @@ class ResUNet2(nn.Module):
         self.last_max_activation = None
 
     # ------------------------------------------------------------------ packing
+    @property
+    def instance_norm(self) -> bool:
+        """The blocks use instance norm (the ``ResUNetIN2`` family): no packed eval plan - every forward runs layer by layer
+        (``eyoc_amd/train.py``), the block norms through ``eyoc_in_forward`` / ``_backward``."""
+        return self.BLOCK_NORM_TYPE == 'IN'
+
+    def _bn_only(self):
+        if self.instance_norm:
+            raise NotImplementedError("packed plan: batch-norm models only")
+
     def _desc(self):
         d = _lib.ModelDesc()
         d.in_channels, d.out_channels = self.in_channels, self.out_channels
@@ -224,6 +248,7 @@ class ResUNet2(nn.Module):
     def repack(self):
         """Fold and upload the current parameters again.  ``forward`` does this on its own when ``_weights_version``
         changed; it is MANDATORY after edits that fingerprint cannot see (``p.data`` edits, writes through views)."""
+        self._bn_only()
         return self._repack(self._packed_device)
 
     def _repack(self, device):
@@ -242,6 +267,7 @@ class ResUNet2(nn.Module):
         events, math / probe settings - stays.  The blob is byte for byte what ``pack_host()`` gives.  Needs a packed model
         (``pack()``, also ``pack(from_blob=True)``) and the parameters on the blob's device.  A forward of this model on ANOTHER
         stream must be ordered against the call by the caller."""
+        self._bn_only()
         if self._handle is None:
             raise _lib.EyocError("repack_device: no packed model on the device - call pack() first")
         lib = _lib.load()
@@ -265,6 +291,7 @@ class ResUNet2(nn.Module):
     def pack_host(self) -> torch.Tensor:
         """The packed blob as a CPU tensor (``eyoc_model_pack_host``: batch norms folded, fp32 fragment order + split16
         packing) - byte for byte what ``pack()`` uploads.  Needs the shared library but no GPU."""
+        self._bn_only()
         lib = _lib.load()
         blob = torch.zeros(self.blob_floats(), dtype=torch.float32)
         d = self._desc()
@@ -276,6 +303,7 @@ class ResUNet2(nn.Module):
     def pack(self, device=None, blob: torch.Tensor | None = None, from_blob=False):
         """(Re)create the device-side model.  ``from_blob=True`` adopts an already packed blob (the
         receiving side of the weight broadcast) instead of packing this module's parameters."""
+        self._bn_only()
         lib = _lib.load()
         device = torch.device(device) if device is not None else self.final.kernel.device
         if device.type != "cuda":
@@ -313,6 +341,7 @@ class ResUNet2(nn.Module):
 
     @property
     def weight_blob(self):
+        self._bn_only()
         if self._handle is None:
             self.pack()
         return self._blob
@@ -333,6 +362,14 @@ class ResUNet2(nn.Module):
             # training mode: batch statistics + autograd (lib/trainer.py:1655-1676), layer by layer
             from .train import forward_layers
             return forward_layers(self, x)
+        if self.instance_norm:
+            # no packed plan: the layer-by-layer forward under the caller's grad mode (fp32 MFMA convolutions, the stage norms as
+            # running-statistics affines, the block norms through eyoc_in_forward)
+            from .train import forward_layers
+            out = forward_layers(self, x)
+            if rows is not None:
+                return out.F.index_select(0, rows.to(x.device, torch.int64).reshape(-1))
+            return out
         dev = x.device
         if self._handle is None or self._packed_device != dev:
             self.pack(dev)
@@ -415,6 +452,7 @@ class ResUNet2(nn.Module):
         """Enqueue a copy of the range guard's four device words into ``words`` (pinned ``int32[4]``) on the current stream, without
         synchronising: called right behind a forward, ``words[0] != 0`` - once an event recorded behind it has fired - says that THIS
         forward overflowed.  For callers that pipeline steps (``check_range`` reads behind everything enqueued since)."""
+        self._bn_only()
         assert words.is_pinned() and words.dtype == torch.int32 and words.numel() >= 4
         if self._handle is None:
             words.zero_()
@@ -442,6 +480,7 @@ class ResUNet2(nn.Module):
 
     @spconv_math.setter
     def spconv_math(self, mode: str):
+        self._bn_only()
         if mode not in self._MATH:
             raise ValueError(f"spconv_math must be one of {sorted(self._MATH)}")
         self._math = self._MATH[mode]
@@ -526,6 +565,33 @@ class ResUNetBN2E(ResUNet2):
     TR_CHANNELS = [None, 64, 128, 128, 128]
 
 
+class ResUNetIN2(ResUNet2):
+    """model/resunet.py:229-232: batch norm behind the stage convolutions, ``MinkowskiInstanceNorm`` inside every residual block
+    (model/residual_block.py:60-61).  No packed eval plan: ``model.eval()(x)`` runs layer by layer."""
+    NORM_TYPE = 'BN'
+    BLOCK_NORM_TYPE = 'IN'
+
+
+class ResUNetIN2B(ResUNetBN2B):
+    NORM_TYPE = 'BN'
+    BLOCK_NORM_TYPE = 'IN'
+
+
+class ResUNetIN2C(ResUNetBN2C):
+    NORM_TYPE = 'BN'
+    BLOCK_NORM_TYPE = 'IN'
+
+
+class ResUNetIN2D(ResUNetBN2D):
+    NORM_TYPE = 'BN'
+    BLOCK_NORM_TYPE = 'IN'
+
+
+class ResUNetIN2E(ResUNetBN2E):
+    NORM_TYPE = 'BN'
+    BLOCK_NORM_TYPE = 'IN'
+
+
 class ResUNetFatBN(ResUNet2):
     NORM_TYPE = 'BN'
     CHANNELS = [None, 32, 64, 128, 256]
@@ -547,14 +613,16 @@ class ResUNetExpBN2C(ResUNetExpanded):
 
 
 MODELS = [ResUNet2, ResUNetBN2, ResUNetBN2B, ResUNetBN2C, ResUNetBN2D, ResUNetBN2E, ResUNetFatBN, ResUNetExpanded, ResUNetExpBN2C]
+# the instance-norm family (model/resunet.py:229-251); a list of its own: tests and scripts iterate MODELS for the packed eval plan
+IN_MODELS = [ResUNetIN2, ResUNetIN2B, ResUNetIN2C, ResUNetIN2D, ResUNetIN2E]
 
 
 def load_model(name):
     """model/__init__.py:16-30 - class lookup by name; ``None`` (and a log line) if unknown."""
-    mdict = {m.__name__: m for m in MODELS}
+    mdict = {m.__name__: m for m in MODELS + IN_MODELS}
     if name not in mdict:
         logging.info(f'Invalid model index. You put {name}. Options are:')
-        for m in MODELS:
+        for m in MODELS + IN_MODELS:
             logging.info('\t* {}'.format(m.__name__))
         return None
     return mdict[name]

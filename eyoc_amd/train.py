@@ -11,6 +11,9 @@
     kernel (a library GEMM; its weight gradient is the transposed product);
   * batch normalisation with batch statistics = ``eyoc_bn_train_forward / _backward`` (fp64 sums in a fixed order), the ReLU that
     follows a norm fused into it; running statistics updated like ``nn.BatchNorm1d`` (momentum, unbiased variance);
+  * instance normalisation (the blocks of the ``ResUNetIN2`` family: ``MinkowskiInstanceNorm``, model/common.py:7-8,
+    model/residual_block.py:60-61) = ``eyoc_in_forward / _backward`` over the level's instance plan, the block's residual add and
+    ReLU fused into the second norm; the same nodes serve eval mode (instance norm has no running statistics);
   * the two 1x1 layers at the end are plain ``[N, C] x [C, C']`` products (library GEMMs); residual adds, concatenations and
     the final row normalisation are element-wise torch ops.
 
@@ -25,6 +28,7 @@ import torch
 from . import _lib
 from . import autograd as _ag
 from .autograd import sparse_conv
+from .model import _InstNorm
 from .sparse_tensor import SparseTensor
 
 MAP_S1, MAP_DOWN, MAP_UP = 0, 1, 2
@@ -163,6 +167,128 @@ def batch_norm_train(x: torch.Tensor, bn: torch.nn.BatchNorm1d, relu: bool = Fal
     return y
 
 
+def instance_plans(cm, internal: bool = False):
+    """``(n_inst, [plan of level 0 .. 3])`` of a coordinate manager: the instance plans ``eyoc_in_forward`` reads (rows grouped by batch
+    index, ``eyoc_in_plan_build``), from ``cm.level_coordinates(l, internal=internal)``; built once and cached on the manager.  One
+    read-back for ``n_inst`` (the largest batch index + 1); each build reads its header back once; nothing per norm."""
+    cache = cm.__dict__.setdefault("_in_plans", {})
+    key = bool(internal)
+    if key not in cache:
+        lib = _lib.load()
+        dev = cm.device
+        n_inst = int(cm.coordinates[:, 0].max().item()) + 1
+        plans = []
+        for lvl in range(4):
+            coords = cm.level_coordinates(lvl, internal=internal)
+            n = coords.shape[0]
+            plan = torch.empty(max(int(lib.eyoc_in_plan_bytes(n, n_inst)), 16) // 4, dtype=torch.int32, device=dev)
+            with _lib.on_device(dev):
+                _lib.check(lib.eyoc_in_plan_build(_lib.ctx(dev.index), _lib.ptr(coords), n, n_inst, _lib.ptr(plan), plan.numel() * 4,
+                                                  _lib.stream_ptr()), "eyoc_in_plan_build")
+            plans.append(plan)
+        cache[key] = (n_inst, plans)
+    return cache[key]
+
+
+def _in_forward(x, plan, n_inst, weight, bias, eps, relu, residual):
+    n, c = x.shape
+    lib = _lib.load()
+    y = torch.empty_like(x)
+    stats = torch.empty((n_inst, 2 * c), dtype=torch.float32, device=x.device)
+    with _lib.on_device(x.device):
+        ws = _lib.scratch(lib.eyoc_in_workspace_bytes(n, c, n_inst), x.device)
+        _lib.check(lib.eyoc_in_forward(_lib.ctx(x.device.index), _lib.ptr(x), n, c, x.stride(0), _lib.ptr(plan), n_inst, _lib.ptr(weight),
+                                       _lib.ptr(bias), float(eps), 1 if relu else 0, _lib.ptr(residual),
+                                       0 if residual is None else residual.stride(0), _lib.ptr(y), y.stride(0), _lib.ptr(stats), _lib.ptr(ws),
+                                       ws.numel(), _lib.stream_ptr()), "eyoc_in_forward")
+    return y, stats
+
+
+def _in_backward(x, y, dy, plan, n_inst, weight, stats, eps, want_dres):
+    """-> ``dx, dres (or None), dweight [1, c], dbias [1, c]``; ``y``: the forward's output when a ReLU was fused, else None."""
+    n, c = x.shape
+    lib = _lib.load()
+    dx = torch.empty_like(x)
+    dres = torch.empty_like(x) if want_dres else None
+    dweight = torch.empty((1, c), dtype=torch.float32, device=x.device)
+    dbias = torch.empty((1, c), dtype=torch.float32, device=x.device)
+    with _lib.on_device(x.device):
+        ws = _lib.scratch(lib.eyoc_in_workspace_bytes(n, c, n_inst), x.device)
+        _lib.check(lib.eyoc_in_backward(_lib.ctx(x.device.index), _lib.ptr(x), x.stride(0), _lib.ptr(y), 0 if y is None else y.stride(0),
+                                        _lib.ptr(dy), dy.stride(0), n, c, _lib.ptr(plan), n_inst, _lib.ptr(weight), _lib.ptr(stats), float(eps),
+                                        _lib.ptr(dx), dx.stride(0), _lib.ptr(dres), 0 if dres is None else dres.stride(0), _lib.ptr(dweight),
+                                        _lib.ptr(dbias), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "eyoc_in_backward")
+    return dx, dres, dweight, dbias
+
+
+class _InstanceNorm(torch.autograd.Function):
+    """``MinkowskiInstanceNorm`` alone: ``y = [relu](norm(x) [+ residual])`` over the level's instance plan."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, plan, n_inst, eps, relu, residual):
+        x = x.contiguous()
+        weight, bias = weight.contiguous(), bias.contiguous()
+        if residual is not None:
+            residual = residual.contiguous()
+        y, stats = _in_forward(x, plan, n_inst, weight, bias, eps, relu, residual)
+        ctx.save_for_backward(x, y if relu else None, weight, stats, plan)
+        ctx.n_inst, ctx.eps, ctx.has_res = n_inst, float(eps), residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, weight, stats, plan = ctx.saved_tensors
+        dx, dres, dw, db = _in_backward(x, y, dy.contiguous(), plan, ctx.n_inst, weight, stats, ctx.eps, ctx.has_res and ctx.needs_input_grad[7])
+        return dx, dw, db, None, None, None, None, dres
+
+
+class _ConvInstanceNorm(torch.autograd.Function):
+    """One sparse convolution, the instance norm behind it, the block's residual add and the ReLU as ONE autograd node (built like
+    ``_ConvNormTrain``, for its reason): ``y = [relu](norm(conv(x)) [+ residual])``."""
+
+    @staticmethod
+    def forward(ctx, x, kernel, weight, bias, table, table_t, mirror, n_out, plan, n_inst, eps, relu, residual, packed):
+        x = x.contiguous()
+        if residual is not None:
+            residual = residual.contiguous()
+        K, cin, cout = kernel.shape
+        z = _ag._run(table, n_out, x, _ag._pack(kernel, False, False) if packed is None else packed[0], cin, cout)
+        ctx.packed_t = None if packed is None else packed[1]
+        y, stats = _in_forward(z, plan, n_inst, weight, bias, eps, relu, residual)
+        ctx.save_for_backward(x, kernel, z, y if relu else None, weight, stats, plan)
+        ctx.table, ctx.table_t, ctx.mirror, ctx.n_in = table, table_t, mirror, x.shape[0]
+        ctx.n_inst, ctx.eps, ctx.has_res = n_inst, float(eps), residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, kernel, z, y, weight, stats, plan = ctx.saved_tensors
+        dz, dres, dw, db = _in_backward(z, y, dy.contiguous(), plan, ctx.n_inst, weight, stats, ctx.eps, ctx.has_res and ctx.needs_input_grad[12])
+        dx = _ag.input_gradient(dz, kernel, ctx.table_t, ctx.mirror, ctx.n_in, ctx.packed_t) if ctx.needs_input_grad[0] else None
+        dk = _ag.weight_gradient(x, dz, kernel, ctx.table) if ctx.needs_input_grad[1] else None
+        return dx, dk, dw, db, None, None, None, None, None, None, None, None, dres, None
+
+
+def _in_params_ok(norm, device):
+    return all(t.dtype == torch.float32 and t.is_contiguous() and t.device == device for t in (norm.weight, norm.bias))
+
+
+def instance_norm(x: torch.Tensor, norm, plan, n_inst: int, relu: bool = False, residual: torch.Tensor | None = None) -> torch.Tensor:
+    """``[relu](norm(x) [+ residual])`` for an ``_InstNorm`` module (weight / bias ``[1, c]``)."""
+    return _InstanceNorm.apply(x, norm.weight, norm.bias, plan, n_inst, norm.eps, relu, residual)
+
+
+def conv_instance_norm(x: torch.Tensor, kernel: torch.Tensor, norm, table, plan, n_inst: int, table_t=None, relu: bool = False,
+                       residual: torch.Tensor | None = None, packed=None) -> torch.Tensor:
+    """``[relu](norm(conv(x)) [+ residual])``: the fused node when the norm's parameters are plain contiguous fp32 on the device, the
+    two separate ones otherwise (the same library calls either way)."""
+    if not _in_params_ok(norm, x.device) or table is None:
+        return instance_norm(sparse_conv(x, kernel, table, table_t), norm, plan, n_inst, relu, residual)
+    mirror = table_t is None
+    return _ConvInstanceNorm.apply(x, kernel, norm.weight, norm.bias, table, table if mirror else table_t, mirror, table.shape[1], plan,
+                                   n_inst, norm.eps, relu, residual, packed)
+
+
 def gather_window(cm, feats: torch.Tensor, ks: int, internal: bool = False) -> torch.Tensor:
     """``[N, ks^3 * C_in]``: every row's ``ks^3`` window of input features (zeros where no voxel is), caller's row order
     (``internal=True``: ``feats`` and the result in the rows of the forward's own - possibly Z-ordered - maps)."""
@@ -202,7 +328,8 @@ def forward_layers(model, x: SparseTensor, taps: dict | None = None) -> SparseTe
     """The network layer by layer through the autograd Functions above - ``ResUNet2`` (model/resunet.py:142-193) and
     ``ResUNetExpanded`` (:254-484: every stage runs a second norm + block, ``norm<i>_2`` / ``block<i>_2``).  In training mode
     every norm uses batch statistics; in eval mode its running statistics (a per-channel affine, element-wise) - ``model(x)`` in eval
-    mode does not come here (it runs the packed plan, csrc/model.hip); tests call this under ``no_grad`` to have the same network twice."""
+    mode does not come here (it runs the packed plan, csrc/model.hip); tests call this under ``no_grad`` to have the same network twice.
+    The ``ResUNetIN2`` family has no packed plan: its eval forward IS this function, under the caller's grad mode."""
     cm = x.coordinate_manager
     # The layers run in the rows of the forward's own maps: from 8192 rows on those are Z-ordered (eyoc_maps_build_ordered(-1): one
     # sort + top-down derivation, two host synchronisations) - a second set of maps in the caller's order is the hash-table build with a
@@ -246,7 +373,9 @@ def forward_layers(model, x: SparseTensor, taps: dict | None = None) -> SparseTe
 
     # every kernel of the fused nodes packed (forward + transposed) by one gather
     packs = {}
-    if model.training:
+    in_blocks = bool(getattr(model, "instance_norm", False))
+    n_inst, plans = instance_plans(cm, internal) if in_blocks else (0, None)
+    if model.training or in_blocks:
         stages = ("1", "2", "3", "4", "4_tr", "3_tr", "2_tr")
         blocks = [getattr(model, "block" + n) for n in stages] + ([getattr(model, f"block{n}_2") for n in stages] if expanded else [])
         kernels = [(getattr(model, "conv" + n).kernel, False) for n in stages[1:]]
@@ -262,7 +391,13 @@ def forward_layers(model, x: SparseTensor, taps: dict | None = None) -> SparseTe
         return norm(sparse_conv(t, kernel, table, table_t), n, relu)
 
     def block(t, blk, table, name, lvl):
-        """BasicBlockBN (model/residual_block.py:37-53): relu(bn2(conv2(relu(bn1(conv1(x))))) + x)"""
+        """BasicBlockBN (model/residual_block.py:37-53): relu(bn2(conv2(relu(bn1(conv1(x))))) + x); BasicBlockIN (:60-61) the same with
+        instance norms, its tail relu(norm2(conv2(.)) + x) inside the second node"""
+        if isinstance(blk.norm1, _InstNorm):
+            out = tap(name + ".conv1", conv_instance_norm(t, blk.conv1.kernel, blk.norm1, table, plans[lvl], n_inst, relu=True,
+                                                          packed=packs.get(id(blk.conv1.kernel))), lvl)
+            return tap(name + ".conv2", conv_instance_norm(out, blk.conv2.kernel, blk.norm2, table, plans[lvl], n_inst, relu=True, residual=t,
+                                                           packed=packs.get(id(blk.conv2.kernel))), lvl)
         out = tap(name + ".conv1", conv_norm(t, blk.conv1.kernel, blk.norm1, table, relu=True), lvl)
         out = conv_norm(out, blk.conv2.kernel, blk.norm2, table)
         return tap(name + ".conv2", torch.relu(out + t), lvl)
@@ -329,6 +464,8 @@ def ema_sync(labeler, model, decay: float, debias: float, full_sync: bool = Fals
             new = (decay * torch.cat([l.reshape(-1) for l in lg]) + (1 - decay) * torch.cat([m.reshape(-1) for m in mg])) / debias
             parts = new.to(dt).split([l.numel() for l in lg])              # (float -> int64 truncates, as ``copy_`` does)
             torch._foreach_copy_(lg, [p.view(l.shape) for p, l in zip(parts, lg)])
+    if getattr(labeler, "instance_norm", False):          # no packed plan to refresh (ResUNetIN2 family)
+        return None
     if labeler._handle is None:
         return labeler.pack()
     return labeler.repack_device()

@@ -668,6 +668,43 @@ int eyoc_bn_train_forward_running(eyoc_ctx* ctx, const float* x_dev, int n, int 
 int eyoc_bn_train_backward(eyoc_ctx* ctx, const float* x_dev, int ld_x, const float* y_dev, int ld_y, const float* dy_dev, int ld_dy, int n,
                            int c, const float* gamma_dev, const float* mean_var_dev, float eps, float* dx_dev, int ld_dx,
                            float* dgamma_dev, float* dbeta_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* replaces: MinkowskiInstanceNorm (model/common.py:7-8; the norm inside every residual block of the ResUNetIN2 family,
+ * model/residual_block.py:60-61).  Additive to EYOC_VERSION 111.  For x f32 [n, c] whose row r belongs to instance b(r) = column 0 of
+ * the level's coordinates, n_b rows in instance b:  mean[b] = sum_{r in b} x / n_b, var[b] = sum_{r in b} (x - mean[b])^2 / n_b (biased),
+ * y = (x - mean[b]) / sqrt(var[b] + eps) * weight + bias.  No running statistics: eval mode equals training mode.  An instance of one
+ * row gives y = bias; an instance id without rows touches nothing.
+ *
+ * The PLAN of a level groups its rows by instance: eyoc_in_plan_build writes, into caller-owned device memory of
+ * eyoc_in_plan_bytes(n, n_inst) bytes, int32 words: a header {identity, n, n_inst, 0}, seg [n_inst + 1] (prefix sums of the row counts)
+ * and perm [n] (the rows grouped by instance, ascending row number inside an instance: a stable counting sort), plus internal arrays.
+ * eyoc_in_plan_layout gives the byte offsets {header, seg, perm, instance of every row}.  identity = 1: the ids never step down (every
+ * collated batch in the caller's order), perm is 0, 1, 2 ... and is not read.  n_inst <= 1024.  The build synchronises the stream once
+ * (it reads the header back): an id outside [0, n_inst) is refused with EYOC_ERR_INVALID.
+ *
+ * eyoc_in_forward: stats f32 [n_inst][2 c] = {mean, biased variance} per instance; with `residual` y = [relu](norm(x) + residual), the
+ * tail of a residual block in one pass.  eyoc_in_backward: g = dy where y > 0 (y = the forward's output when a ReLU was fused, else
+ * NULL); dx = weight invstd[b] (g - mean_b(g) - xhat mean_b(g xhat)); dres (or NULL) = g, the residual's gradient; dweight = sum g xhat
+ * and dbias = sum g over ALL rows.  c must divide 256 (as eyoc_bn_*); every leading dimension a multiple of 4 and >= c, tensors 16-byte
+ * aligned; workspace eyoc_in_workspace_bytes(n, c, n_inst), caller-owned.  Three launches forward, four backward, whatever n_inst; no
+ * host synchronisation, no floating-point atomics.
+ *
+ * Batch invariance: sums are fp64 about the instance's first row (plan order), over chunks of eyoc_in_chunk_rows() rows of the
+ * instance, added in an order that depends on the instance's row count alone.  The bytes of an instance's stats, y and dx rows do not
+ * depend on the other instances, on how the rows interleave, on the grid or on timing; a call on one instance alone (n_inst = 1, its
+ * rows in the same relative order) gives the same bytes.  dweight / dbias add the instances in ascending id. */
+int eyoc_in_chunk_rows(void);
+size_t eyoc_in_plan_bytes(int n, int n_inst);
+int eyoc_in_plan_layout(int n, int n_inst, int64_t* offsets_out /* [4] bytes: header, seg, perm, instance of every row */);
+int eyoc_in_plan_build(eyoc_ctx* ctx, const int32_t* coords_dev /* [n,4] */, int n, int n_inst, void* plan_dev, size_t plan_bytes,
+                       void* stream);
+size_t eyoc_in_workspace_bytes(int n, int c, int n_inst);
+int eyoc_in_forward(eyoc_ctx* ctx, const float* x_dev, int n, int c, int ld_x, const void* plan_dev, int n_inst, const float* weight_dev,
+                    const float* bias_dev, float eps, int relu, const float* residual_dev /* or NULL */, int ld_res, float* y_dev, int ld_y,
+                    float* stats_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int eyoc_in_backward(eyoc_ctx* ctx, const float* x_dev, int ld_x, const float* y_dev /* or NULL */, int ld_y, const float* dy_dev, int ld_dy,
+                     int n, int c, const void* plan_dev, int n_inst, const float* weight_dev, const float* stats_dev, float eps,
+                     float* dx_dev, int ld_dx, float* dres_dev /* or NULL */, int ld_dres, float* dweight_dev, float* dbias_dev,
+                     void* workspace_dev, size_t workspace_bytes, void* stream);
 /* The first convolution's window as a dense matrix (model/resunet.py:31-38, C_in = 1 in production, K = ks^3):
  * out f32 [n, ks^3 * cin], out[row][k * cin + c] = feats[voxel at window offset k of row][c] or 0 (offsets x fastest, like every
  * rulebook) - the convolution and its weight gradient are then plain [n, K cin] x [K cin, C_out] products.  Builds the level-0 hash
