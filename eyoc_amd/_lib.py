@@ -163,6 +163,8 @@ PROTOTYPES = {
     "eyoc_spconv_local_rulebook_bytes": (_sz, [_i]),
     "eyoc_spconv_build_local_rulebook": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "eyoc_spconv_staged": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "eyoc_spconv_build_local_rulebook128": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "eyoc_spconv_staged128": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "eyoc_split16_encode": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "eyoc_split16_decode": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "eyoc_model_set_math": (_i, [_vp, _i]),

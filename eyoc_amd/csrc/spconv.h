@@ -146,7 +146,8 @@ __device__ inline bool split16_poisoned(const unsigned int* range) { return rang
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Tile builders hash a tile's distinct input rows into an LDS table (linear probing, atomicCAS) and number the occupied slots
-// in slot order.  Which key of a probe cluster landed in which of its slots depends on the order the CAS loops ran in; the SET
+// in slot order.  Which key of a probe cluster landed in which of its slots depends on the order the CAS loops ran in (spconv_up.hip;
+// spconv_st.hip and spconv_upc.hip insert by ordered probing now, where it does not, and keep these numbers for their two-pass tiles); the SET
 // of occupied slots and the keys of a cluster (a maximal circular run of occupied slots) do not.  canonical_slot_id gives the
 // r-th smallest key of a cluster the number of the cluster's r-th slot: the numbering - and with it WHICH PASS stages a row, i.e.
 // the order in which a multi-pass tile's products are summed - is the same in every run (bit-reproducible outputs).

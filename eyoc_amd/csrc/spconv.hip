@@ -1262,6 +1262,28 @@ int eyoc_spconv_staged(eyoc_ctx* ctx, const int32_t* nbr_dev, const void* local_
   return launch_spconv(a, (hipStream_t)stream);
 }
 
+// the same two on 128-row tiles (build_local_rulebook128 / launch_spconv_st128, the strided tables' kernel family); the records of
+// n_out rows take eyoc_spconv_local_rulebook_bytes(2 * n_out): cdiv(n, 128) = cdiv(2 n, 256)
+int eyoc_spconv_build_local_rulebook128(eyoc_ctx* ctx, const int32_t* nbr_dev, int K, int n_out, void* out_dev, int32_t* overflow_dev,
+                                        void* stream) {
+  EYOC_REQUIRE(ctx && nbr_dev && out_dev && overflow_dev && K >= 1 && K <= 27 && n_out >= 0, EYOC_ERR_INVALID,
+               "eyoc_spconv_build_local_rulebook128: bad argument");
+  EYOC_CHECK_HIP(hipMemsetAsync(overflow_dev, 0, 4, (hipStream_t)stream));
+  return build_local_rulebook128(nbr_dev, K, n_out, (unsigned char*)out_dev, overflow_dev, (hipStream_t)stream, ctx->knobs.st_group);
+}
+
+int eyoc_spconv_staged128(eyoc_ctx* ctx, const int32_t* nbr_dev, const void* local_dev, int n_out, int n_in, const float* in_dev, int ld_in,
+                          int cin, const float* wpacked_dev, int cout, const float* bias_dev, const float* res_dev, int ld_res, int relu,
+                          float* out_dev, int ld_out, int out_split, const float* out_scale_dev, void* stream) {
+  EYOC_REQUIRE(ctx && nbr_dev && local_dev, EYOC_ERR_INVALID, "eyoc_spconv_staged128: NULL argument");
+  SpconvArgs a;
+  a.nbr = nbr_dev; a.K = 27; a.n_out = n_out; a.n_in = n_in; a.in = in_dev; a.ld_in = ld_in; a.cin = cin; a.w = wpacked_dev;
+  a.cout = cout; a.bias = bias_dev; a.res = res_dev; a.ld_res = ld_res; a.relu = relu; a.l2norm = 0;
+  a.out = out_dev; a.ld_out = ld_out; a.math = 1; a.out_split = out_split; a.out_scale = out_scale_dev;
+  a.local_down = (const unsigned char*)local_dev; a.ctx = ctx;
+  return launch_spconv(a, (hipStream_t)stream);
+}
+
 // the setters below return the previous value (-1: NULL ctx) and leave the switch alone for an out-of-range argument, so
 // f(ctx, -1) reads it
 int eyoc_spconv_st_group_rows(eyoc_ctx* ctx, int on) {

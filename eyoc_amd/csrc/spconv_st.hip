@@ -98,7 +98,7 @@ __global__ __launch_bounds__(NWB * 64) void k_local_rulebook(const int32_t* __re
   for (int i = threadIdx.x; i < HS; i += TR) hk[i] = -1;
   if (threadIdx.x == 0) too_many = 0;
   __syncthreads();
-  // 1. insert every valid entry (linear probing; duplicates meet their own key); the slot found stays in a register
+  // 1. insert every valid entry (ordered linear probing; duplicates meet their own key); the slot found stays in a register
   unsigned short slot[27];
   int idxs[27];                                                      // all 27 loads first: behind the CAS loops each would wait alone
   if constexpr (DERIVE) {                                            // no table in memory: the row's window through the octree (derive.h)
@@ -127,12 +127,20 @@ __global__ __launch_bounds__(NWB * 64) void k_local_rulebook(const int32_t* __re
     const int idx = idxs[k];
     unsigned int s = 0xFFFFu;
     if (idx >= 0) {
-      s = ((unsigned)idx * 2654435761u) >> HSHIFT;
-      int probes = 0;
+      // ORDERED linear probing: the larger key keeps a slot, the smaller one is carried on to the next.  Along a key's way from its
+      // home slot every slot then holds a larger key, and the table that satisfies this is unique: the same keys in the same slots
+      // whatever order the atomics ran in (with a compare-and-swap for empty slots only, which key of a probe cluster took which slot
+      // changed from build to build, and with it the record of a one-pass tile).  The set of occupied slots is that of plain linear
+      // probing - every insertion still ends in the first empty slot behind its home.
+      unsigned int p = ((unsigned)idx * 2654435761u) >> HSHIFT;
+      int carried = idx, probes = 0;
+      bool own = true;                                                 // still carrying the row's own key
       while (true) {
-        const int prev = atomicCAS(&hk[s], -1, idx);
-        if (prev == -1 || prev == idx) break;
-        s = (s + 1) & (HS - 1);
+        const int prev = atomicMax(&hk[p], carried);
+        if (own && prev <= carried) { s = p; own = false; }            // the own key sits at p now (it may be moved further on later: fixed up below)
+        if (prev == -1 || prev == carried) break;
+        if (prev < carried) carried = prev;
+        p = (p + 1) & (HS - 1);
         if (++probes >= HS) { too_many = 1; s = 0xFFFFu; break; }   // the table is full: more distinct rows than it has slots
       }
     }
@@ -166,6 +174,19 @@ __global__ __launch_bounds__(NWB * 64) void k_local_rulebook(const int32_t* __re
     }
     return;
   }
+  // the table is final now; a key that a larger one pushed on after this thread had placed it sits further along (never before)
+  {
+    int cur[27];
+#pragma unroll
+    for (int k = 0; k < 27; ++k) cur[k] = hk[slot[k] & (HS - 1)];      // all 27 reads first; few keys have moved
+#pragma unroll
+    for (int k = 0; k < 27; ++k) {
+      if (slot[k] == 0xFFFFu || cur[k] == idxs[k]) continue;
+      unsigned int p = slot[k];
+      for (int probes = 0; probes < HS && hk[p] != idxs[k]; ++probes) p = (p + 1) & (HS - 1);
+      srow[k][threadIdx.x] = (unsigned short)p;
+    }
+  }
   // 2. number the occupied slots in slot order (deterministic): every wave owns a quarter of the table
   constexpr int PER_WAVE = HS / NWB;
   int cnt = 0;
@@ -188,7 +209,8 @@ __global__ __launch_bounds__(NWB * 64) void k_local_rulebook(const int32_t* __re
       }
       base += __popcll(m);
     }
-  } else {                                                              // two passes: a numbering that does not depend on the order the CAS loops ran in (canonical_slot_id, spconv.h)
+  } else {                                                              // two passes: canonical_slot_id's numbering (spconv.h).  Slot order is reproducible too since the table is ordered, but it
+    // would stage other rows in the second pass: the sums' last bits would change
     // (hid holds the slot-order positions first and the canonical numbers after - a second 8 KB array would cost the kernel its
     // fourth workgroup per CU)
     for (int i0 = 0; i0 < PER_WAVE; i0 += 64) {

@@ -258,11 +258,17 @@ __global__ __launch_bounds__(256) void k_upc_records(const int32_t* __restrict__
     unsigned int s = 0xFFFFu;
     if (idx >= 0) {
       pattern |= 1u << i;
-      s = ((unsigned)idx * 2654435761u) >> 20;
-      while (true) {                                                   // at most 2048 distinct keys in 4096 slots: always ends
-        const int prev = atomicCAS(&hk[s], -1, idx);
-        if (prev == -1 || prev == idx) break;
-        s = (s + 1) & (HSLOTS - 1);
+      // ordered linear probing (see k_local_rulebook, spconv_st.hip): the larger key keeps a slot, the smaller one is carried on - the
+      // same keys in the same slots in every build
+      unsigned int p = ((unsigned)idx * 2654435761u) >> 20;
+      int carried = idx;
+      bool own = true;
+      for (int probes = 0; probes < HSLOTS; ++probes) {                // at most 2048 distinct keys in 4096 slots: ends at an empty slot long before
+        const int prev = atomicMax(&hk[p], carried);
+        if (own && prev <= carried) { s = p; own = false; }            // the own key sits at p now (it may be moved further on later: fixed up below)
+        if (prev == -1 || prev == carried) break;
+        if (prev < carried) carried = prev;
+        p = (p + 1) & (HSLOTS - 1);
       }
     }
     srow[i][threadIdx.x] = (unsigned short)s;
@@ -270,6 +276,15 @@ __global__ __launch_bounds__(256) void k_upc_records(const int32_t* __restrict__
   // rows with the same existing parents next to each other (padding rows - no parent at all - first)
   key[threadIdx.x] = (pattern << 8) | threadIdx.x;
   __syncthreads();
+  // the table is final now; a key that a larger one pushed on after this thread had placed it sits further along (never before)
+#pragma unroll
+  for (int i = 0; i < KC; ++i) {
+    if (idxs[i] < 0) continue;
+    unsigned int p = srow[i][threadIdx.x];
+    if (p == 0xFFFFu || hk[p] == idxs[i]) continue;
+    for (int probes = 0; probes < HSLOTS && hk[p] != idxs[i]; ++probes) p = (p + 1) & (HSLOTS - 1);
+    srow[i][threadIdx.x] = (unsigned short)p;
+  }
   constexpr int PER_WAVE = HSLOTS / NW;
   int cnt = 0;
   for (int i0 = 0; i0 < PER_WAVE; i0 += 64) cnt += __popcll(__ballot(hk[wave * PER_WAVE + i0 + lane] >= 0));
@@ -291,7 +306,8 @@ __global__ __launch_bounds__(256) void k_upc_records(const int32_t* __restrict__
       }
       base += __popcll(m);
     }
-  } else {                                                              // several passes: a numbering that does not depend on the order the CAS loops ran in (canonical_slot_id, spconv.h)
+  } else {                                                              // two passes: canonical_slot_id's numbering (spconv.h).  Slot order is reproducible too since the table is ordered, but it
+    // would stage other rows in the second pass: the sums' last bits would change
     for (int i0 = 0; i0 < PER_WAVE; i0 += 64) {
       const int s = wave * PER_WAVE + i0 + lane;
       const unsigned long long m = __ballot(hk[s] >= 0);

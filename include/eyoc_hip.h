@@ -320,6 +320,15 @@ int eyoc_spconv_build_local_rulebook(eyoc_ctx* ctx, const int32_t* nbr_dev, int 
 int eyoc_spconv_staged(eyoc_ctx* ctx, const int32_t* nbr_dev, const void* local_dev, int n_out, int n_in, const float* in_dev,
                        int ld_in, int cin, const float* wpacked_dev, int cout, const float* bias_dev, const float* res_dev,
                        int ld_res, int relu, float* out_dev, int ld_out, int out_split, const float* out_scale_dev, void* stream);
+/* The same two on 128-row tiles - the records and the kernel family of the strided layers and of the wide (>= 128-channel) workgroups -
+ * for tests and profiling; arguments as above.  The records of n_out rows take eyoc_spconv_local_rulebook_bytes(2 * n_out) bytes: one
+ * record per 128 rows, and cdiv(n, 128) = cdiv(2 n, 256).  eyoc_spconv_select_down_kernel(2 / 3) picks 64- / 128-channel workgroups
+ * for layers with >= 128 output channels. */
+int eyoc_spconv_build_local_rulebook128(eyoc_ctx* ctx, const int32_t* nbr_dev, int K, int n_out, void* out_dev,
+                                        int32_t* overflow_dev, void* stream);
+int eyoc_spconv_staged128(eyoc_ctx* ctx, const int32_t* nbr_dev, const void* local_dev, int n_out, int n_in, const float* in_dev,
+                          int ld_in, int cin, const float* wpacked_dev, int cout, const float* bias_dev, const float* res_dev,
+                          int ld_res, int relu, float* out_dev, int ld_out, int out_split, const float* out_scale_dev, void* stream);
 int eyoc_spconv_pack_weights_split16(const float* w_host, const float* scale_host, int K, int cin, int cout,
                                      float* packed_host, float* out_scale_host);
 int eyoc_spconv_ex(eyoc_ctx* ctx, const int32_t* nbr_dev, int K, int n_out, int n_in, const float* in_dev, int ld_in, int cin,

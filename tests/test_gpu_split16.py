@@ -419,8 +419,9 @@ def test_staged_kernel_vs_fp64(morton_maps, cin, cout, level):
 
 def test_local_rulebook_counts_tiles_it_cannot_stage_instead_of_hanging():
     """Rows in NO spatial order: a 256-row tile of a dense grid then references up to 256 x 27 distinct rows - more than the
-    1278 the stage takes in two passes, and more than the builder's 4096-slot LDS hash holds.  The builder gives up on such a
-    tile (n_unique = -1), counts it in *overflow and terminates; tiles of the same cloud in Morton order build cleanly."""
+    1278 the stage takes in two passes, and more than the builder's 2048-slot LDS hash holds (the assertion below asks for more than
+    4096, twice that).  The builder gives up on such a tile (n_unique = -1), counts it in *overflow and terminates; tiles of the same
+    cloud in Morton order build cleanly.  (The edges themselves - 1278 | 1279, 2048 | 2049 - are in tests/test_gpu_tile_boundaries.py.)"""
     from oracle import coords as oc
     L, lib = _lib()
     g = np.stack(np.meshgrid(np.arange(26), np.arange(26), np.arange(26), indexing="ij"), -1).reshape(-1, 3)
