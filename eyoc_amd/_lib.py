@@ -99,6 +99,16 @@ class TripletLayout(C.Structure):
                                            "off_rand_pos", "off_rand_neg", "off_rand_term", "off_rand_flags", "off_contrib_key")])
 
 
+class ClossRecord(C.Structure):
+    _fields_ = ([(k, C.c_double) for k in ("sum_pos", "sum_neg")] + [(k, C.c_int32) for k in ("n_pairs", "n_neg", "k_neg", "n_active")] +
+                [("status", C.c_uint32), ("pos_loss", C.c_float), ("neg_loss", C.c_float), ("reserved", C.c_int32)])
+
+
+class ClossLayout(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("anchors", "n_pairs", "n_neg", "table_slots", "n_contrib", "reserved")] +
+                [(k, C.c_uint64) for k in ("total", "off_record", "off_pos_d2", "off_dist", "off_term", "off_flags", "off_contrib_key")])
+
+
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 # name -> (restype, argtypes); every symbol include/eyoc_hip.h declares
 PROTOTYPES = {
@@ -274,6 +284,10 @@ PROTOTYPES = {
                                   _vp]),
     "eyoc_triplet_backward": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, C.c_float, _vp, _vp, _vp,
                                    _vp, _sz, _vp]),
+    "eyoc_closs_workspace_bytes": (_sz, [_i, _i, _i]),
+    "eyoc_closs_workspace_layout": (_i, [_i, _i, _i, C.POINTER(ClossLayout)]),
+    "eyoc_closs_forward": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, C.c_float, _vp, _vp, _sz, _vp]),
+    "eyoc_closs_backward": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, C.c_float, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -14,7 +14,8 @@
 // in fp32, channels in order, no contraction, sqrtf(acc + 1e-7f) - so t* is eyoc_knn1's.  The two values of a positive that enter the
 // loss (pos_d2, and dist of the chosen candidate) are then evaluated once more with an fp64 accumulator and rounded to fp32 once:
 // an fp32 chain over 64 channels is up to 8 ulp from the exact value, and the stage tests hold these values to one ulp of fp64.
-// The triplet losses of the reference's other two trainers follow below the hardest-contrastive entry points, on the same table and search.
+// The triplet losses of the reference's other two trainers follow below the hardest-contrastive entry points, on the same table and search;
+// the random-negative contrastive loss of the base trainer comes last, on the same table.
 #include "pose_math.h"
 
 using namespace eyoc;
@@ -1115,6 +1116,359 @@ int eyoc_triplet_backward(eyoc_ctx* ctx, const float* F0, int n0, const float* F
   else if (c == 32) TR_ROWS(32);
   else TR_ROWS(64);
 #undef TR_ROWS
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Random-negative contrastive loss of the reference's base trainer (lib/trainer.py:201-221 and :262-286; include/eyoc_hip.h has the
+// contract).  The workspace starts with an HcWs of (n_pairs, 0 used positives): hc_prep_kernel runs on it unchanged (key table, index check
+// of the positives).  Forward, 4 launches: the fill (control block + key table), hc_prep_kernel, cl_terms_kernel (grid.y = positives,
+// candidate negatives; lane = term), cl_final_kernel.  Backward: two fills, cl_weights_kernel (two contribution entries per term, entry
+// number = sequence number), one stable sort of (destination, entry number) by rocPRIM's radix_sort_pairs, cl_rows_kernel (tr_rows_kernel's
+// scheme with one factor per entry: the first position of a run of equal destinations adds the run in order, every other one leaves after
+// two loads).
+namespace {
+
+static_assert(sizeof(eyoc_closs_record) == 48, "eyoc_closs_record is 48 bytes");
+static_assert(EYOC_CLOSS_BAD_INDEX == EYOC_HCLOSS_BAD_INDEX, "hc_prep_kernel sets the shared status word");
+
+struct ClWs {
+  HcWs hc;                     // ctl (status) and the key table; nothing else of it is used
+  eyoc_closs_record* rec;
+  float* pos_d2;               // [n_pairs]
+  float *dist, *term;          // [n_neg]
+  unsigned int* flags;         // [n_neg]
+  int nblk;                    // workgroups of the terms kernel per part (>= 1)
+  double* part_sum;            // [2][nblk]: positives, kept candidates
+  int* part_cnt;               // [2][nblk]: kept, active
+  int ncon;                    // 2 (n_pairs + n_neg) contribution entries
+  unsigned int *ckey, *ckey_s; // destination 2 row + matrix + 1, 0 = empty; sorted
+  int *cidx, *cidx_s;          // entry numbers; sorted along
+  float* cw;                   // the factor of an entry
+  int* cr;                     // the row of the OTHER matrix it scales the difference to
+  void* sort_tmp;
+  size_t sort_bytes;
+  size_t total;
+};
+
+ClWs cl_carve(void* base, size_t bytes, int n_pairs, int n_neg) {
+  ClWs w;
+  w.hc = carve(base, bytes, n_pairs, 0);
+  Carver cv(base ? (char*)base + w.hc.total : nullptr, bytes > w.hc.total ? bytes - w.hc.total : 0);
+  const size_t np = (size_t)n_pairs, nn = (size_t)n_neg;
+  w.rec = (eyoc_closs_record*)cv.take<char>(256);
+  w.pos_d2 = cv.take<float>(np);
+  w.dist = cv.take<float>(nn);
+  w.term = cv.take<float>(nn);
+  w.flags = cv.take<unsigned int>(nn);
+  const int most = n_pairs > n_neg ? n_pairs : n_neg;
+  w.nblk = most > 0 ? cdiv(most, HC_A) : 1;
+  w.part_sum = cv.take<double>(2 * (size_t)w.nblk);
+  w.part_cnt = cv.take<int>(2 * (size_t)w.nblk);
+  w.ncon = 2 * (n_pairs + n_neg);
+  const size_t nc = (size_t)w.ncon;
+  w.ckey = cv.take<unsigned int>(nc);
+  w.ckey_s = cv.take<unsigned int>(nc);
+  w.cidx = cv.take<int>(nc);
+  w.cidx_s = cv.take<int>(nc);
+  w.cw = cv.take<float>(nc);
+  w.cr = cv.take<int>(nc);
+  w.sort_bytes = align_up(sort_rows_tmp_bytes(w.ncon, 32));
+  w.sort_tmp = cv.take<char>(w.sort_bytes);
+  w.total = w.hc.total + align_up(cv.off);
+  return w;
+}
+
+bool cl_counts_ok(int n_pairs, int n_neg) {
+  return n_pairs >= 0 && n_neg >= 0 && (long long)n_pairs + (long long)n_neg < (1ll << 30);
+}
+
+// grid (workgroups of 64 terms, part): part 0 = positives (lane = p), part 1 = candidate negatives (lane = q)
+template <int C>
+__global__ __launch_bounds__(64) void cl_terms_kernel(const float* __restrict__ F0, int n0, const float* __restrict__ F1, int n1,
+                                                      const long long* __restrict__ pairs, int n_pairs,
+                                                      const long long* __restrict__ neg, int n_neg, float neg_thresh, ClWs w) {
+#pragma clang fp contract(off)
+  const int part = blockIdx.y;
+  const int lane = threadIdx.x;
+  const int e = blockIdx.x * HC_A + lane;
+  const int count = part ? n_neg : n_pairs;
+  double v = 0.0;
+  int kept = 0, active = 0, bad = 0;
+  if (e < count) {
+    const long long* __restrict__ src = part ? neg : pairs;
+    const long long i = src[2 * (size_t)e], j = src[2 * (size_t)e + 1];
+    const bool ok = i >= 0 && i < n0 && j >= 0 && j < n1;   // checked before either becomes an address
+    bool member = false;
+    if (ok && part) {
+      const unsigned long long scale = (unsigned long long)(n0 > n1 ? n0 : n1);
+      member = key_member(w.hc, (unsigned long long)i + (unsigned long long)j * scale + 1ull);
+    }
+    double d2 = 0.0;
+    if (ok && !member) {
+      float a[C];
+      const float4* row = reinterpret_cast<const float4*>(F0 + (size_t)i * C);
+#pragma unroll
+      for (int q = 0; q < C / 4; ++q) {
+        const float4 x = row[q];
+        a[4 * q] = x.x; a[4 * q + 1] = x.y; a[4 * q + 2] = x.z; a[4 * q + 3] = x.w;
+      }
+      d2 = row_d2(a, F1 + (size_t)j * C);
+    }
+    bad = ok ? 0 : 1;
+    if (part == 0) {
+      const float acc = ok ? (float)d2 : 0.0f;   // a positive with a bad index: nothing read, nothing added
+      w.pos_d2[e] = acc;
+      v = (double)acc;
+    } else {
+      unsigned int flags = ok ? EYOC_CLOSS_VALID : EYOC_CLOSS_MASKED;
+      float dist = 0.0f, term = 0.0f;
+      if (ok && member) flags |= EYOC_CLOSS_MASKED;
+      if (ok && !member) {
+        kept = 1;
+        dist = (float)sqrt(d2 + (double)1e-4f);
+        const float h = neg_thresh - dist;
+        if (h > 0.0f) {
+          term = h * h;
+          flags |= EYOC_CLOSS_ACTIVE;
+          active = 1;
+        }
+        v = (double)term;
+      }
+      w.dist[e] = dist;
+      w.term[e] = term;
+      w.flags[e] = flags;
+    }
+  }
+  if (bad) atomicOr(&w.hc.ctl->status, EYOC_CLOSS_BAD_INDEX);
+  v = wave_sum(v);
+  kept = wave_sum_i(kept);
+  active = wave_sum_i(active);
+  if (lane == 0) {
+    w.part_sum[(size_t)part * w.nblk + blockIdx.x] = v;
+    if (part) {
+      w.part_cnt[blockIdx.x] = kept;
+      w.part_cnt[(size_t)w.nblk + blockIdx.x] = active;
+    }
+  }
+}
+
+__global__ __launch_bounds__(HC_THREADS) void cl_final_kernel(int n_pairs, int n_neg, ClWs w, eyoc_closs_record* __restrict__ out) {
+#pragma clang fp contract(off)
+  __shared__ double red_d[HC_WAVES][2];
+  __shared__ int red_i[HC_WAVES][2];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double v[2] = {0.0, 0.0};
+  int c[2] = {0, 0};
+  for (int b = threadIdx.x; b < w.nblk; b += HC_THREADS) {   // (a workgroup past the end of its part wrote zeros)
+    v[0] += w.part_sum[b];
+    v[1] += w.part_sum[(size_t)w.nblk + b];
+    c[0] += w.part_cnt[b];
+    c[1] += w.part_cnt[(size_t)w.nblk + b];
+  }
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    v[k] = wave_sum(v[k]);
+    c[k] = wave_sum_i(c[k]);
+  }
+  if (lane == 0) {
+    for (int k = 0; k < 2; ++k) {
+      red_d[wave][k] = v[k];
+      red_i[wave][k] = c[k];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double sum[2] = {0.0, 0.0};
+  int cnt[2] = {0, 0};
+  for (int x = 0; x < HC_WAVES; ++x) {
+    for (int k = 0; k < 2; ++k) {
+      sum[k] += red_d[x][k];
+      cnt[k] += red_i[x][k];
+    }
+  }
+  eyoc_closs_record r;
+  r.sum_pos = sum[0]; r.sum_neg = sum[1];
+  r.n_pairs = n_pairs; r.n_neg = n_neg; r.k_neg = cnt[0]; r.n_active = cnt[1];
+  r.status = w.hc.ctl->status;
+  r.reserved = 0;
+  const float nan = __builtin_nanf("");
+  const bool none = r.status != 0u || n_pairs == 0;
+  // a mean over nothing is 0 / 0 = NaN, the reference's value
+  r.pos_loss = none ? nan : (float)(sum[0] / (double)n_pairs);
+  r.neg_loss = none ? nan : (float)(sum[1] / (double)cnt[0]);
+  *w.rec = r;
+  *out = r;
+}
+
+// one thread per term (positives by p, then candidates by q): its two contribution entries (dF0 row, dF1 row), or two empty ones
+__global__ __launch_bounds__(HC_THREADS) void cl_weights_kernel(const long long* __restrict__ pairs, int n_pairs,
+                                                                const long long* __restrict__ neg, int n_neg, int n0, int n1,
+                                                                float neg_thresh, const float* __restrict__ g_pos,
+                                                                const float* __restrict__ g_neg, ClWs w) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * HC_THREADS + threadIdx.x;
+  if (t >= n_pairs + n_neg) return;
+  const eyoc_closs_record rec = *w.rec;
+  long long i = -1, j = -1;
+  float f = 0.0f;
+  bool emit = false;
+  if (t < n_pairs) {
+    i = pairs[2 * (size_t)t];
+    j = pairs[2 * (size_t)t + 1];
+    emit = true;
+    f = (float)(2.0 * (double)*g_pos / (double)n_pairs);
+  } else {
+    const int q = t - n_pairs;
+    if ((w.flags[q] & EYOC_CLOSS_ACTIVE) && rec.k_neg > 0) {
+      i = neg[2 * (size_t)q];
+      j = neg[2 * (size_t)q + 1];
+      emit = true;
+      const float d = w.dist[q];
+      const float h = neg_thresh - d;
+      f = (float)(-2.0 * ((double)*g_neg / (double)rec.k_neg) * (double)h / (double)d);
+    }
+  }
+  emit = emit && i >= 0 && i < n0 && j >= 0 && j < n1;
+  const size_t e = 2 * (size_t)t;
+  w.ckey[e] = emit ? 2u * (unsigned int)i + 1u : 0u;
+  w.ckey[e + 1] = emit ? 2u * (unsigned int)j + 2u : 0u;
+  w.cidx[e] = (int)e;
+  w.cidx[e + 1] = (int)(e + 1);
+  w.cw[e] = emit ? f : 0.0f;
+  w.cw[e + 1] = emit ? f : 0.0f;
+  w.cr[e] = emit ? (int)j : 0;
+  w.cr[e + 1] = emit ? (int)i : 0;
+}
+
+// One workgroup per position of the sorted list; tr_rows_kernel's scheme: the first position of a run of equal destinations does the row,
+// C lanes take one entry (lane = channel), 256 / C entries side by side, entry k of the run goes to slot k mod (256 / C), fp64
+// accumulators, the slots added in order, rounded once.
+template <int C>
+__global__ __launch_bounds__(HC_THREADS) void cl_rows_kernel(const float* __restrict__ F0, const float* __restrict__ F1, ClWs w,
+                                                             float* __restrict__ dF0, float* __restrict__ dF1) {
+#pragma clang fp contract(off)
+  constexpr int G = HC_THREADS / C;
+  __shared__ double slot_acc[HC_THREADS];
+  const int k = blockIdx.x;
+  const unsigned int key = w.ckey_s[k];
+  if (key == 0u) return;
+  if (k > 0 && w.ckey_s[k - 1] == key) return;
+  const int m = (int)((key - 1u) & 1u);
+  const size_t row = (size_t)((key - 1u) >> 1);
+  const int slot = threadIdx.x / C, ch = threadIdx.x % C;
+  const float* __restrict__ FO = m ? F0 : F1;   // the other matrix
+  const double own = (double)(m ? F1 : F0)[row * C + ch];
+  double acc = 0.0;
+  for (int q = slot; q < w.ncon - k && w.ckey_s[k + q] == key; q += G) {
+    const int e = w.cidx_s[k + q];
+    acc += (double)w.cw[e] * (own - (double)FO[(size_t)w.cr[e] * C + ch]);
+  }
+  slot_acc[threadIdx.x] = acc;
+  __syncthreads();
+  if (threadIdx.x >= C) return;
+  double total = 0.0;
+#pragma unroll
+  for (int g = 0; g < G; ++g) total += slot_acc[g * C + threadIdx.x];
+  float* __restrict__ dF = m ? dF1 : dF0;
+  dF[row * C + threadIdx.x] = w.rec->status ? __builtin_nanf("") : (float)total;
+}
+
+int cl_check_args(const char* what, const eyoc_ctx* ctx, const void* F0, int n0, const void* F1, int n1, int c, const void* pairs,
+                  int n_pairs, const void* neg, int n_neg, const void* ws, size_t ws_bytes) {
+  EYOC_REQUIRE(ctx, EYOC_ERR_INVALID, "%s: NULL ctx", what);
+  EYOC_REQUIRE(c == 16 || c == 32 || c == 64, EYOC_ERR_INVALID, "%s: feature dimension %d not supported (16/32/64)", what, c);
+  EYOC_REQUIRE(n0 >= 0 && n1 >= 0 && n_pairs >= 0 && n_neg >= 0, EYOC_ERR_INVALID, "%s: negative count", what);
+  EYOC_REQUIRE(n0 <= (1 << 30) && n1 <= (1 << 30), EYOC_ERR_INVALID, "%s: more than 2^30 rows", what);
+  EYOC_REQUIRE(cl_counts_ok(n_pairs, n_neg), EYOC_ERR_INVALID, "%s: n_pairs %d + n_neg %d must stay below 2^30", what, n_pairs, n_neg);
+  EYOC_REQUIRE((F0 || n0 == 0) && (F1 || n1 == 0) && (pairs || n_pairs == 0) && (neg || n_neg == 0), EYOC_ERR_INVALID, "%s: NULL argument", what);
+  EYOC_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, EYOC_ERR_INVALID, "%s: the workspace must be 256-byte aligned", what);
+  const size_t need = eyoc_closs_workspace_bytes(n_pairs, n_neg, c);
+  EYOC_REQUIRE(ws_bytes >= need, EYOC_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", what, ws_bytes, need);
+  return EYOC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t eyoc_closs_workspace_bytes(int n_pairs, int n_neg, int c) {
+  (void)c;
+  if (!cl_counts_ok(n_pairs, n_neg)) return 0;
+  return cl_carve(nullptr, 0, n_pairs, n_neg).total;
+}
+
+int eyoc_closs_workspace_layout(int n_pairs, int n_neg, int c, eyoc_closs_layout* out) {
+  EYOC_REQUIRE(out && cl_counts_ok(n_pairs, n_neg), EYOC_ERR_INVALID, "eyoc_closs_workspace_layout: invalid argument");
+  EYOC_REQUIRE(c == 16 || c == 32 || c == 64, EYOC_ERR_INVALID, "eyoc_closs_workspace_layout: feature dimension %d not supported", c);
+  char* const base = (char*)(uintptr_t)4096;   // (a stand-in base, never dereferenced)
+  const ClWs w = cl_carve(base, 0, n_pairs, n_neg);
+  out->anchors = HC_A;
+  out->n_pairs = n_pairs;
+  out->n_neg = n_neg;
+  out->table_slots = (int32_t)(w.hc.mask + 1);
+  out->n_contrib = w.ncon;
+  out->reserved = 0;
+  out->total = w.total;
+  out->off_record = (uint64_t)((char*)w.rec - base);
+  out->off_pos_d2 = (uint64_t)((char*)w.pos_d2 - base);
+  out->off_dist = (uint64_t)((char*)w.dist - base);
+  out->off_term = (uint64_t)((char*)w.term - base);
+  out->off_flags = (uint64_t)((char*)w.flags - base);
+  out->off_contrib_key = (uint64_t)((char*)w.ckey - base);
+  return EYOC_OK;
+}
+
+int eyoc_closs_forward(eyoc_ctx* ctx, const float* F0, int n0, const float* F1, int n1, int c, const int64_t* pairs, int n_pairs,
+                       const int64_t* neg, int n_neg, float neg_thresh, eyoc_closs_record* record_out, void* ws, size_t ws_bytes,
+                       void* stream) {
+  if (int rc = cl_check_args("eyoc_closs_forward", ctx, F0, n0, F1, n1, c, pairs, n_pairs, neg, n_neg, ws, ws_bytes)) return rc;
+  EYOC_REQUIRE(record_out, EYOC_ERR_INVALID, "eyoc_closs_forward: NULL record");
+  hipStream_t st = (hipStream_t)stream;
+  const ClWs w = cl_carve(ws, ws_bytes, n_pairs, n_neg);
+  const long long* P = (const long long*)pairs;
+  const long long* N = (const long long*)neg;
+  EYOC_CHECK_HIP(hipMemsetAsync(w.hc.ctl, 0, w.hc.fill_bytes, st));
+  int pg = cdiv(n_pairs, HC_THREADS);
+  pg = pg < 1 ? 1 : (pg > 4096 ? 4096 : pg);
+  hipLaunchKernelGGL(hc_prep_kernel, dim3(pg), dim3(HC_THREADS), 0, st, P, n_pairs, (const long long*)nullptr, 0, (const long long*)nullptr, 0,
+                     (const long long*)nullptr, 0, n0, n1, n_pairs, w.hc);
+  const dim3 grid_terms(w.nblk, 2);
+#define CL_TERMS(CC) hipLaunchKernelGGL((cl_terms_kernel<CC>), grid_terms, dim3(64), 0, st, F0, n0, F1, n1, P, n_pairs, N, n_neg, neg_thresh, w)
+  if (c == 16) CL_TERMS(16);
+  else if (c == 32) CL_TERMS(32);
+  else CL_TERMS(64);
+#undef CL_TERMS
+  hipLaunchKernelGGL(cl_final_kernel, dim3(1), dim3(HC_THREADS), 0, st, n_pairs, n_neg, w, record_out);
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
+int eyoc_closs_backward(eyoc_ctx* ctx, const float* F0, int n0, const float* F1, int n1, int c, const int64_t* pairs, int n_pairs,
+                        const int64_t* neg, int n_neg, float neg_thresh, const float* g_pos, const float* g_neg, float* dF0, float* dF1,
+                        void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = cl_check_args("eyoc_closs_backward", ctx, F0, n0, F1, n1, c, pairs, n_pairs, neg, n_neg, ws, ws_bytes)) return rc;
+  EYOC_REQUIRE(g_pos && g_neg && (dF0 || n0 == 0) && (dF1 || n1 == 0), EYOC_ERR_INVALID, "eyoc_closs_backward: NULL argument");
+  hipStream_t st = (hipStream_t)stream;
+  const ClWs w = cl_carve(ws, ws_bytes, n_pairs, n_neg);
+  if (n0 > 0) EYOC_CHECK_HIP(hipMemsetAsync(dF0, 0, (size_t)n0 * c * sizeof(float), st));
+  if (n1 > 0) EYOC_CHECK_HIP(hipMemsetAsync(dF1, 0, (size_t)n1 * c * sizeof(float), st));
+  if (n_pairs == 0) return EYOC_OK;   // both values are NaN by definition: no contribution
+  hipLaunchKernelGGL(cl_weights_kernel, dim3(cdiv(n_pairs + n_neg, HC_THREADS)), dim3(HC_THREADS), 0, st, (const long long*)pairs, n_pairs,
+                     (const long long*)neg, n_neg, n0, n1, neg_thresh, g_pos, g_neg, w);
+  // keys are 2 row + matrix + 1 <= 2 max(n0, n1): that many bits; equal keys keep their entry order (a radix sort is stable)
+  const unsigned long long top = 2ull * (unsigned long long)(n0 > n1 ? n0 : n1);
+  int bits = 1;
+  while ((1ull << bits) <= top) ++bits;
+  if (int rc = sort_rows_by_key(w.sort_tmp, w.sort_bytes, w.ckey, w.ckey_s, w.cidx, w.cidx_s, w.ncon, bits, st)) return rc;
+#define CL_ROWS(CC) hipLaunchKernelGGL((cl_rows_kernel<CC>), dim3(w.ncon), dim3(HC_THREADS), 0, st, F0, F1, w, dF0, dF1)
+  if (c == 16) CL_ROWS(16);
+  else if (c == 32) CL_ROWS(32);
+  else CL_ROWS(64);
+#undef CL_ROWS
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
 }

@@ -7,7 +7,10 @@ number of launches is fixed (5 + 4) and the gradient rows are summed in a fixed 
 not change from run to run.  The existing function stays; this route is opt-in.
 
 ``triplet_loss`` / ``hardest_triplet_loss`` (second half of the file) are the losses of the reference's other two trainers
-(lib/trainer.py:567-621, :701-782) on ``eyoc_triplet_forward`` / ``eyoc_triplet_backward``, built the same way."""
+(lib/trainer.py:567-621, :701-782) on ``eyoc_triplet_forward`` / ``eyoc_triplet_backward``, built the same way.
+
+``contrastive_loss`` (last part) is the loss of the base trainer, ``ContrastiveLossTrainer`` (lib/trainer.py:201-221, :262-286): all
+positives against random negatives, on ``eyoc_closs_forward`` / ``eyoc_closs_backward``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -298,3 +301,146 @@ def hardest_triplet_loss(F0, F1, positive_pairs, num_pos=1024, num_hn_samples=51
     negative among ``num_hn_samples`` candidates in both directions -> ``(loss, pos_dist_mean, neg_dist_mean)`` as ``triplet_loss``;
     ``neg_dist_mean`` is ``(D01min.mean() + D10min.mean()) / 2`` as a device tensor (the reference's ``.item()`` is the caller's)."""
     return _triplet(F0, F1, positive_pairs, num_pos, int(num_hn_samples), num_rand_triplet, neg_thresh, rng)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Random-negative contrastive loss of the base trainer (lib/trainer.py:201-221 and :262-286) on eyoc_closs_forward / eyoc_closs_backward:
+# one autograd node, 4 launches forward, 4 and one radix sort backward.  Every positive of the batch is used; the candidate negatives are
+# tested against the positives' key table on the device and keep their places (flags, nothing compacted); the gradient rows are summed per
+# destination row from a sorted contribution list, in a fixed order, without floating-point atomics.
+CLOSS_BAD_INDEX, CLOSS_MASKED, CLOSS_VALID, CLOSS_ACTIVE = 1, 1, 2, 4
+_CLOSS_FLOATS = C.sizeof(_lib.ClossRecord) // 4
+_CLOSS_POS = _lib.ClossRecord.pos_loss.offset // 4            # pos_loss, neg_loss follow each other
+
+
+def contrastive_layout(n_pairs, n_neg, c):
+    out = _lib.ClossLayout()
+    _lib.check(_lib.load().eyoc_closs_workspace_layout(n_pairs, n_neg, c, C.byref(out)), "eyoc_closs_workspace_layout")
+    return out
+
+
+def draw_negative_pairs(rng, n_pairs, n0, n1, n_neg=0):
+    """The reference's draw (lib/trainer.py:212-218) -> int64 ``[N, 2]`` on the host: ``floor(rand(N, 2) * [[n0, n1]])`` from ONE call,
+    row-major, ``N = 2 n_pairs`` when ``n_neg < 1``.  ``rng``: ``np.random`` or a ``RandomState``, as the other losses accept."""
+    n = int(n_neg) if n_neg >= 1 else 2 * int(n_pairs)
+    return np.floor(rng.rand(n, 2) * np.array([[n0, n1]])).astype(np.int64)
+
+
+def _contrastive_args(F0, F1, pairs, neg, neg_thresh):
+    return (_lib.ctx(F0.device.index), _lib.ptr(F0), F0.shape[0], _lib.ptr(F1), F1.shape[0], F0.shape[1], _lib.ptr(pairs), pairs.shape[0],
+            _lib.ptr(neg), neg.shape[0], float(neg_thresh))
+
+
+def contrastive_raw_forward(F0, F1, pairs, neg, neg_thresh=1.4):
+    """``eyoc_closs_forward`` on device tensors -> ``(record, workspace)``: ``record`` a float32 view of the 48-byte
+    ``eyoc_closs_record`` (``read_contrastive_record`` decodes it), ``workspace`` what ``contrastive_raw_backward`` and
+    ``contrastive_results`` read.  ``pairs`` int64 ``[n_pairs, 2]``: all positives; ``neg`` int64 ``[n_neg, 2]``: the raw candidates."""
+    _check_inputs(F0, F1, pairs, None, None, None)
+    _check_inputs(F0, F1, neg, None, None, None)
+    lib = _lib.load()
+    with _lib.on_device(F0.device):
+        ws = _lib.workspace(lib.eyoc_closs_workspace_bytes(pairs.shape[0], neg.shape[0], F0.shape[1]), F0.device)
+        rec = torch.empty(_CLOSS_FLOATS, dtype=torch.float32, device=F0.device)
+        _lib.check(lib.eyoc_closs_forward(*_contrastive_args(F0, F1, pairs, neg, neg_thresh), _lib.ptr(rec), _lib.ptr(ws), ws.numel(),
+                                          _lib.stream_ptr()), "eyoc_closs_forward")
+    return rec, ws
+
+
+def contrastive_raw_backward(F0, F1, pairs, neg, neg_thresh, g_pos, g_neg, ws):
+    """``eyoc_closs_backward`` -> ``(dF0, dF1)``; ``g_pos`` / ``g_neg`` float32 device scalars, ``ws`` from ``contrastive_raw_forward``
+    on the same arguments."""
+    lib = _lib.load()
+    dF0, dF1 = torch.empty_like(F0), torch.empty_like(F1)
+    with _lib.on_device(F0.device):
+        _lib.check(lib.eyoc_closs_backward(*_contrastive_args(F0, F1, pairs, neg, neg_thresh), _lib.ptr(g_pos), _lib.ptr(g_neg),
+                                           _lib.ptr(dF0), _lib.ptr(dF1), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   "eyoc_closs_backward")
+    return dF0, dF1
+
+
+def read_contrastive_record(rec) -> _lib.ClossRecord:
+    """The record on the host (tests, logging): this READS BACK, the loss itself never does."""
+    return _lib.ClossRecord.from_buffer_copy(rec.detach().cpu().numpy().tobytes())
+
+
+def contrastive_results(ws, n_pairs, n_neg, c):
+    """The per-term results the forward left in its workspace, as device views: ``pos_d2`` float32 [n_pairs]; ``dist``, ``term`` float32
+    [n_neg], ``flags`` int32 [n_neg] (``CLOSS_MASKED`` / ``_VALID`` / ``_ACTIVE``); ``contrib_key`` int32 [2 (n_pairs + n_neg)], written
+    by the backward (2 row + matrix + 1, 0 = empty)."""
+    lay = contrastive_layout(n_pairs, n_neg, c)
+
+    def view(off, count, dtype):
+        return ws[off:off + 4 * count].view(dtype)
+    return {"pos_d2": view(lay.off_pos_d2, n_pairs, torch.float32), "dist": view(lay.off_dist, n_neg, torch.float32),
+            "term": view(lay.off_term, n_neg, torch.float32), "flags": view(lay.off_flags, n_neg, torch.int32),
+            "contrib_key": view(lay.off_contrib_key, lay.n_contrib, torch.int32)}
+
+
+class _Contrastive(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, F0, F1, pairs, neg, neg_thresh):
+        rec, ws = contrastive_raw_forward(F0, F1, pairs, neg, neg_thresh)
+        ctx.save_for_backward(F0, F1)
+        ctx.idx, ctx.thresh, ctx.ws = (pairs, neg), neg_thresh, ws
+        return rec[_CLOSS_POS], rec[_CLOSS_POS + 1]
+
+    @staticmethod
+    def backward(ctx, g_pos, g_neg):
+        F0, F1 = ctx.saved_tensors
+
+        def scalar(g):                                  # a missing gradient is zero
+            if g is None:
+                return torch.zeros((), dtype=torch.float32, device=F0.device)
+            return g.to(torch.float32).contiguous()
+        dF0, dF1 = contrastive_raw_backward(F0, F1, *ctx.idx, ctx.thresh, scalar(g_pos), scalar(g_neg), ctx.ws)
+        return dF0, dF1, None, None, None
+
+
+def _device_pairs(positive_pairs, dev):
+    if isinstance(positive_pairs, torch.Tensor):
+        pairs = positive_pairs
+    else:
+        pairs = torch.from_numpy(np.ascontiguousarray(np.asarray(positive_pairs), dtype=np.int64))
+    return pairs.reshape(-1, 2).to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
+
+
+def _upload_negatives(neg, dev):
+    """One pinned staging buffer, one asynchronous copy."""
+    stage = torch.empty((neg.shape[0], 2), dtype=torch.int64, pin_memory=True)
+    stage.numpy()[...] = neg
+    return stage.to(dev, non_blocking=True)
+
+
+def contrastive_loss(F0, F1, positive_pairs, neg_thresh=1.4, n_neg=0, rng=None):
+    """``ContrastiveLossTrainer``'s loss (lib/trainer.py:262-286 with the negatives of :201-221) -> ``(pos_loss, neg_loss)``, 0-dim
+    tensors with grad: ``pos_loss`` the mean squared distance over ALL positives, ``neg_loss`` the mean of
+    ``relu(neg_thresh - sqrt(d2 + 1e-4))^2`` over the random candidates that are no known positive (``2 n_pairs`` candidates when
+    ``n_neg < 1``; the draw is the reference's, from ``rng``, default the global ``np.random``).  The caller forms
+    ``pos_loss + neg_weight * neg_loss`` and the ``/ iter_size``.
+
+    ``positive_pairs``: a DEVICE int64 ``[n, 2]`` tensor stays on the device; a host tensor or ndarray costs one upload.  The candidates
+    go up in one asynchronous copy and are tested against the positives on the device; nothing is read back.  A mean over nothing is
+    NaN (no positive: both values).  No double backward; ``c`` in {16, 32, 64}."""
+    dev = F0.device
+    pairs = _device_pairs(positive_pairs, dev)
+    neg = draw_negative_pairs(np.random if rng is None else rng, pairs.shape[0], F0.shape[0], F1.shape[0], n_neg)
+    return _Contrastive.apply(F0.contiguous(), F1.contiguous(), pairs, _upload_negatives(neg, dev), float(neg_thresh))
+
+
+def generate_rand_negative_pairs(positive_pairs, hash_seed, N0, N1, N_neg=0, rng=None):
+    """``ContrastiveLossTrainer.generate_rand_negative_pairs`` (lib/trainer.py:201-221) -> the kept negatives in draw order, a device
+    int64 ``[k, 2]`` tensor.  For callers that want the list (``contrastive_loss`` never forms it): the membership flags come from
+    ``eyoc_closs_forward`` on zero features, and the compaction READS BACK once, for the count.  ``hash_seed`` must be
+    ``max(N0, N1)``, the reference's only call and the only value for which the key is exact pair membership."""
+    if int(hash_seed) != max(int(N0), int(N1)):
+        raise ValueError(f"generate_rand_negative_pairs: hash_seed {hash_seed} != max(N0, N1) = {max(int(N0), int(N1))}")
+    on_dev = isinstance(positive_pairs, torch.Tensor) and positive_pairs.is_cuda
+    dev = positive_pairs.device if on_dev else torch.device("cuda", torch.cuda.current_device())
+    pairs = _device_pairs(positive_pairs, dev)
+    host = draw_negative_pairs(np.random if rng is None else rng, pairs.shape[0], int(N0), int(N1), N_neg)
+    neg = _upload_negatives(host, dev)
+    Z0 = torch.zeros((int(N0), 16), dtype=torch.float32, device=dev)
+    Z1 = torch.zeros((int(N1), 16), dtype=torch.float32, device=dev)
+    _, ws = contrastive_raw_forward(Z0, Z1, pairs, neg, 0.0)
+    flags = contrastive_results(ws, pairs.shape[0], neg.shape[0], 16)["flags"]
+    return neg[(flags & CLOSS_MASKED) == 0]

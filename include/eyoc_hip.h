@@ -1164,6 +1164,76 @@ int eyoc_triplet_backward(eyoc_ctx* ctx, const float* F0_dev, int n0, const floa
                           const float* g_dev, float* dF0_dev, float* dF1_dev, void* workspace_dev, size_t workspace_bytes,
                           void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * random-negative contrastive loss of the base trainer (lib/trainer.py:201-221 generate_rand_negative_pairs and :262-286, the loss in
+ * _train_epoch) and its gradient.  Added after 111 without a bump, additive only.
+ *   F0, F1      f32 [n0, c], [n1, c], c in {16, 32, 64}; n0, n1 <= 2^30
+ *   pairs       int64 [n_pairs, 2] on the device: ALL positives, each counted as often as it occurs
+ *   neg         int64 [n_neg, 2] on the device: the raw candidate negatives (row of F0, row of F1), before the membership test
+ *   n_pairs + n_neg < 2^30, anything else is EYOC_ERR_INVALID
+ * Membership: candidate q = (a, b) is dropped (MASKED) exactly when a + b * max(n0, n1) is one of the keys pairs[:,0] + pairs[:,1] *
+ * max(n0, n1) of the in-range positives - the table of eyoc_hcloss_* (integer compare-and-swaps: membership does not depend on the
+ * order of pairs); since a < max(n0, n1) this is exact pair membership, the reference's np.isin on _hash(., max(N0, N1)).  Nothing is
+ * compacted: candidate q keeps its place and gets a flag word; k_neg, the number of kept candidates, is counted on the device.
+ * No contraction anywhere:
+ *   positive p = (i, j):   pos_d2[p] = f32(sum_c (F0[i]_c - F1[j]_c)^2), the sum in fp64, rounded once
+ *   kept candidate (a, b): dist[q] = f32(sqrt(sum_c (F0[a]_c - F1[b]_c)^2 + (double)1e-4f)), sum and root in fp64, rounded once;
+ *                          h = neg_thresh - dist in fp32; ACTIVE when h > 0 strictly, then term[q] = h * h in fp32, else term[q] = +0
+ *   dropped candidates and candidates with a bad index store dist = term = +0.
+ * Sums are fp64 sums of the stored fp32 values in a fixed order: lane -> wave (one workgroup of EYOC_HCLOSS_ANCHORS terms), then the
+ * workgroups in order in a final pass.  pos_loss = f32(sum_pos / n_pairs), neg_loss = f32(sum_neg / k_neg); a mean over nothing is NaN
+ * (all candidates dropped: neg_loss is NaN, pos_loss is not).  n_pairs == 0: both values are NaN, the gradients exactly +0.0f.  Every
+ * index of pairs and neg is checked before a feature is read through it: a bad one is skipped, sets EYOC_CLOSS_BAD_INDEX and makes both
+ * values (and, in the backward, every row that receives a contribution) NaN.
+ *
+ * Backward, g_pos and g_neg f32 device scalars.  Positive p = (i, j): w = f32(2 g_pos / n_pairs); active candidate q = (a, b):
+ * w = f32(-2 (g_neg / k_neg) (neg_thresh - dist) / dist), the difference in fp32 as in the forward, the rest in fp64.  A term with rows
+ * (r0, r1) contributes w (F0[r0] - F1[r1]) to dF0[r0] and w (F1[r1] - F0[r0]) to dF1[r1].  Terms are numbered positives by p, then
+ * candidates by q; term t owns entry 2 t (its dF0 row) and 2 t + 1 (its dF1 row) of ONE contribution list: the entry number is the
+ * sequence number.  Dropped, inactive and bad terms leave their entries empty and read nothing.  The list is grouped by destination
+ * (row, matrix) with one stable radix sort (rocPRIM, its temporary storage carved from the workspace), and the first entry of every run
+ * adds the run in list order exactly as eyoc_triplet_backward does: C lanes per entry, 256 / c entries side by side, entry k of the run to
+ * slot k mod (256 / c), fp64 accumulators (factor times difference, both widened), the slots added in order, rounded once.  The work is
+ * linear in the number of contributions; no floating-point atomics.  A row's bytes depend on its own entries in list order only; rows
+ * nothing touches are +0.0f; dF0 [n0, c] and dF1 [n1, c] are written completely.
+ *
+ * Launches: forward 4 (one fill, table build and index check of the positives, terms, final pass); backward 4 of this library (two fills,
+ * weights, row sums; the two fills alone when n_pairs == 0), whatever the sizes, plus those of the one rocPRIM sort, which chooses its
+ * passes by the length of the list.  Stream-ordered: no synchronisation, no allocation, no environment variable, no floating-point
+ * atomics, nothing read back; caller-owned 256-byte aligned workspace, which the backward reads as the forward of the SAME arguments
+ * left it.
+ * --------------------------------------------------------------------------------------------- */
+#define EYOC_CLOSS_BAD_INDEX 1u
+#define EYOC_CLOSS_MASKED 1u        /* flags: dropped (the candidate is a known positive, or one of its indices is out of range) */
+#define EYOC_CLOSS_VALID 2u         /* flags: the candidate's own indices were in range */
+#define EYOC_CLOSS_ACTIVE 4u        /* flags: kept and neg_thresh - dist > 0 */
+
+typedef struct eyoc_closs_record {
+  double sum_pos, sum_neg;           /* the positives' squared distances; the kept candidates' terms */
+  int32_t n_pairs, n_neg, k_neg, n_active;
+  uint32_t status;
+  float pos_loss, neg_loss;
+  int32_t reserved;
+} eyoc_closs_record;                /* 48 bytes */
+
+/* byte offsets into the workspace: record (eyoc_closs_record), pos_d2 f32 [n_pairs], dist f32 [n_neg], term f32 [n_neg], flags uint32
+ * [n_neg]; after the backward: contrib_key uint32 [n_contrib], n_contrib = 2 (n_pairs + n_neg): the destination of each entry as
+ * 2 row + matrix + 1 (matrix 0 = dF0, 1 = dF1), 0 = empty */
+typedef struct eyoc_closs_layout {
+  int32_t anchors, n_pairs, n_neg, table_slots, n_contrib, reserved;
+  uint64_t total, off_record, off_pos_d2, off_dist, off_term, off_flags, off_contrib_key;
+} eyoc_closs_layout;
+
+size_t eyoc_closs_workspace_bytes(int n_pairs, int n_neg, int c);
+int eyoc_closs_workspace_layout(int n_pairs, int n_neg, int c, eyoc_closs_layout* out);
+int eyoc_closs_forward(eyoc_ctx* ctx, const float* F0_dev, int n0, const float* F1_dev, int n1, int c, const int64_t* pairs_dev,
+                       int n_pairs, const int64_t* neg_dev, int n_neg, float neg_thresh, eyoc_closs_record* record_out_dev,
+                       void* workspace_dev, size_t workspace_bytes, void* stream);
+int eyoc_closs_backward(eyoc_ctx* ctx, const float* F0_dev, int n0, const float* F1_dev, int n1, int c, const int64_t* pairs_dev,
+                        int n_pairs, const int64_t* neg_dev, int n_neg, float neg_thresh, const float* g_pos_dev,
+                        const float* g_neg_dev, float* dF0_dev, float* dF1_dev, void* workspace_dev, size_t workspace_bytes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,18 @@ from eyoc_amd.harness import DeviceBatch, RegistrationConfig, RegistrationPipeli
 
 if os.environ.get("LOSS_ROUTE", "existing") == "device":      # the device-side loss (eyoc_amd/loss.py) instead of the torch-op route
     from eyoc_amd.loss import hardest_contrastive_loss as contrastive_hardest_negative_loss  # noqa: E402,F811
+elif os.environ.get("LOSS_ROUTE") == "contrastive":           # the base trainer's loss: all positives, random negatives (neg_weight 1)
+    def contrastive_hardest_negative_loss(F0, F1, pp, num_pos, num_hn_samples):  # noqa: F811
+        from eyoc_amd.loss import contrastive_loss
+        return contrastive_loss(F0, F1, pp)
+elif os.environ.get("LOSS_ROUTE") in ("triplet", "hardest-triplet"):   # the triplet trainers' losses; the "neg" column stays zero
+    def contrastive_hardest_negative_loss(F0, F1, pp, num_pos, num_hn_samples):  # noqa: F811
+        from eyoc_amd.loss import hardest_triplet_loss, triplet_loss
+        if os.environ["LOSS_ROUTE"] == "triplet":
+            loss = triplet_loss(F0, F1, pp, num_pos=num_pos, num_rand_triplet=1024)[0]
+        else:
+            loss = hardest_triplet_loss(F0, F1, pp, num_pos=num_pos, num_hn_samples=num_hn_samples, num_rand_triplet=1024)[0]
+        return loss, torch.zeros_like(loss)
 ITERS = int(os.environ.get("ITERS", "400"))
 N_TRAIN = int(os.environ.get("N_TRAIN", "24"))
 BEAMS, AZ = int(os.environ.get("BEAMS", "32")), int(os.environ.get("AZ", "1000"))
