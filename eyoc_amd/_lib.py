@@ -188,6 +188,9 @@ PROTOTYPES = {
     "eyoc_model_blob_floats": (_sz, [C.POINTER(ModelDesc)]),
     "eyoc_model_pack_host": (_i, [C.POINTER(ModelDesc), C.POINTER(LayerParams), _i, _vp, _sz]),
     "eyoc_model_create": (_i, [_vp, C.POINTER(ModelDesc), C.POINTER(LayerParams), _i, _vp, _sz, C.POINTER(_vp)]),
+    "eyoc_model_blob_floats_in": (_sz, [C.POINTER(ModelDesc), _i]),
+    "eyoc_model_pack_host_in": (_i, [C.POINTER(ModelDesc), C.POINTER(LayerParams), _i, _vp, _sz, _i]),
+    "eyoc_model_create_in": (_i, [_vp, C.POINTER(ModelDesc), C.POINTER(LayerParams), _i, _vp, _sz, _i, C.POINTER(_vp)]),
     "eyoc_model_destroy": (_i, [_vp]),
     "eyoc_model_repack_workspace_bytes": (_sz, [_vp]),
     "eyoc_model_repack_device": (_i, [_vp, _vp, C.POINTER(LayerParams), _i, _vp, _sz, _vp]),
@@ -213,6 +216,7 @@ PROTOTYPES = {
     "eyoc_in_plan_build": (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp]),
     "eyoc_in_workspace_bytes": (_sz, [_i, _i, _i]),
     "eyoc_in_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, C.c_float, _i, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "eyoc_in_forward_split16": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, C.c_float, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "eyoc_in_backward": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz,
                               _vp]),
     "eyoc_maps_gather_window": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),

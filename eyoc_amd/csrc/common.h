@@ -218,6 +218,12 @@ struct eyoc_maps {
   hipEvent_t s1_ev[EYOC_MAX_LEVELS] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t up_ev[EYOC_MAX_LEVELS] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t table0_ev = nullptr;
+  // Instance plans of the packed instance-norm layers (inorm.hip; one per level, in the maps' internal row order): their memory is
+  // reserved by the build (the end of the workspace), eyoc::maps_ensure_in_plan fills one on the first forward that needs it - the same
+  // discipline as the lazy tables: flag and event are set there only, every reader's stream waits for the event.
+  void* in_plan[EYOC_MAX_LEVELS] = {nullptr, nullptr, nullptr, nullptr};
+  bool in_ready[EYOC_MAX_LEVELS] = {false, false, false, false};
+  hipEvent_t in_ev[EYOC_MAX_LEVELS] = {nullptr, nullptr, nullptr, nullptr};
   eyoc_maps() = default;
   eyoc_maps(const eyoc_maps&) = delete;
   eyoc_maps& operator=(const eyoc_maps&) = delete;
@@ -230,6 +236,8 @@ int maps_build_table0(eyoc_maps* maps, hipStream_t st);
 // fills a lazily skipped [27][n] table (kind: EYOC_MAP_S1 / EYOC_MAP_UP; anything else is always there) on `st`; when it was filled
 // before, `st` waits for that fill instead.  Every reader of nbr_s1[0], nbr_up[l] comes through here.
 int maps_ensure_table(eyoc_maps* maps, int kind, int level, hipStream_t st);
+// builds the level's instance plan (eyoc_maps::in_plan) on `st` on first use, without a read-back; afterwards `st` waits for that build
+int maps_ensure_in_plan(eyoc_maps* maps, int level, hipStream_t st);
 size_t sort_rows64_tmp_bytes(int n);
 int sort_rows_by_key64(void* tmp, size_t tmp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out, const int* vals_in,
                        int* vals_out, int n, int bits, hipStream_t st);

@@ -1261,7 +1261,15 @@ struct MapBuild {
 
   int finish() {
     EYOC_CHECK_HIP(hipGetLastError());
-    return fits();                          // the backstop: every stage has checked its own takes
+    // memory of the instance plans (common.h eyoc_maps::in_plan): reserved behind everything else, written by the first forward of
+    // an instance-norm model that reads these maps (maps_ensure_in_plan) - a batch-norm forward never touches it
+    for (int l = 0; l < m->n_levels; ++l)
+      if (m->rows[l] > 0) m->in_plan[l] = cv.take<unsigned char>(in_plan_bytes_nosync(m->rows[l]));
+    if (int rc = fits()) {                  // the backstop: every stage has checked its own takes
+      for (int l = 0; l < EYOC_MAX_LEVELS; ++l) m->in_plan[l] = nullptr;
+      return rc;
+    }
+    return EYOC_OK;
   }
 };
 
@@ -1288,6 +1296,7 @@ size_t eyoc_maps_workspace_bytes(int n_rows) {
   b += 2 * (align_up(upc_kept_bytes(n_rows)) + align_up(upc_scratch_bytes(n_rows))) + EYOC_MAX_LEVELS * (align_up(upc_kept_bytes(1)) + align_up(upc_scratch_bytes(1)) + 512);   // class-major transposed records + their builder's scratch
   b += 4 * (align_up(local_rulebook128_bytes(n_rows)) + 256);        // strided tables (3) and the coarsest stride-1 table in 128-row tiles (a level has at most n rows)
   b += 4096;                                                         // counters
+  b += EYOC_MAX_LEVELS * align_up(in_plan_bytes_nosync(n_rows > 0 ? n_rows : 1));   // instance plans (inorm.hip; a level has at most n rows)
   return b + 96 * 256;
 }
 
@@ -1613,6 +1622,19 @@ int eyoc::maps_ensure_table(eyoc_maps* m, int kind, int level, hipStream_t st) {
   return EYOC_OK;
 }
 
+// the level's instance plan on demand (the packed instance-norm layers, model.hip): count, scan, place - no read-back
+int eyoc::maps_ensure_in_plan(eyoc_maps* m, int level, hipStream_t st) {
+  EYOC_REQUIRE(level >= 0 && level < m->n_levels && m->in_plan[level], EYOC_ERR_INVALID, "maps: no instance plan memory for level %d", level);
+  if (m->in_ready[level]) {                                             // built before, maybe on another stream
+    if (m->in_ev[level]) EYOC_CHECK_HIP(hipStreamWaitEvent(st, m->in_ev[level], 0));
+    return EYOC_OK;
+  }
+  if (int rc = in_plan_build_nosync(m->coords[level], m->rows[level], m->in_plan[level], st)) return rc;
+  if (int rc = publish_fill(m->in_ev[level], st)) return rc;
+  m->in_ready[level] = true;
+  return EYOC_OK;
+}
+
 // level-0 hash table on demand (only the hash-probing first-convolution fallback, the window gather and eyoc_maps_info read it)
 int eyoc::maps_build_table0(eyoc_maps* m, hipStream_t st) {
   if (m->table0_built) {                                                // built before, maybe on another stream
@@ -1633,7 +1655,8 @@ int eyoc::maps_build_table0(eyoc_maps* m, hipStream_t st) {
 
 eyoc_maps::~eyoc_maps() {
   // a fill still pending on some stream writes into the workspace, which the caller may reuse once the maps are freed
-  for (hipEvent_t* ev : {&table0_ev, s1_ev + 0, s1_ev + 1, s1_ev + 2, s1_ev + 3, up_ev + 0, up_ev + 1, up_ev + 2, up_ev + 3})
+  for (hipEvent_t* ev : {&table0_ev, s1_ev + 0, s1_ev + 1, s1_ev + 2, s1_ev + 3, up_ev + 0, up_ev + 1, up_ev + 2, up_ev + 3, in_ev + 0, in_ev + 1,
+                         in_ev + 2, in_ev + 3})
     if (*ev) {
       (void)hipEventSynchronize(*ev);
       (void)hipEventDestroy(*ev);

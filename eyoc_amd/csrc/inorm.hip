@@ -13,7 +13,7 @@
 // (sub, ch) takes the chunk's rows sub, sub + 256 / c, ...; the subs meet in ascending order), and the chunks of an instance meet in
 // the order k_in_final walks them, which depends on their number alone.  So the bytes of an instance's statistics, y and dx rows are a
 // function of that instance's rows and of nothing else: not of the other instances, of how the rows interleave, of the grid or of timing.
-#include "common.h"
+#include "spconv.h"
 
 using namespace eyoc;
 
@@ -82,8 +82,20 @@ __global__ __launch_bounds__(1024) void k_in_plan_scan(int32_t* __restrict__ cou
   __shared__ int total[IN_MAX_INST];
   const int i = threadIdx.x;
   if (i < n_inst) {
-    int run = 0;
-    for (int b = 0; b < blocks; ++b) {
+    // eight loads in flight per step: one load, one store at a time is a memory latency per row block, 2 ms for the 3737 + ... row
+    // blocks of a 64-pair batch's four levels (a thread owns its column, so the order of its loads and stores is free)
+    int run = 0, b = 0;
+    for (; b + 8 <= blocks; b += 8) {
+      int v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = counts[(size_t)(b + j) * n_inst + i];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        counts[(size_t)(b + j) * n_inst + i] = run;
+        run += v[j];
+      }
+    }
+    for (; b < blocks; ++b) {
       const int v = counts[(size_t)b * n_inst + i];
       counts[(size_t)b * n_inst + i] = run;
       run += v;
@@ -109,9 +121,12 @@ __global__ __launch_bounds__(1024) void k_in_plan_scan(int32_t* __restrict__ cou
 }
 
 // Pass 3: perm[seg[id] + rows of id in earlier blocks + rows of id EARLIER IN THIS BLOCK] = row - the slot is computed, not claimed.
+// `hdr` (optional): the build that never reads the header back (in_plan_build_nosync) launches this pass always and leaves the identity
+// decision to it - an identity plan's perm is not read, so it stays unwritten.
 __global__ __launch_bounds__(256) void k_in_plan_place(const int32_t* __restrict__ inst, int n, int n_inst, const int32_t* __restrict__ counts,
-                                                       const int32_t* __restrict__ seg, int32_t* __restrict__ perm) {
+                                                       const int32_t* __restrict__ seg, int32_t* __restrict__ perm, const int32_t* __restrict__ hdr) {
   __shared__ int ids[IN_PLAN_ROWS];
+  if (hdr && hdr[0]) return;
   const int r0 = blockIdx.x * IN_PLAN_ROWS, m = min(n - r0, IN_PLAN_ROWS);
   for (int i = threadIdx.x; i < m; i += 256) ids[i] = inst[r0 + i];
   __syncthreads();
@@ -148,9 +163,19 @@ __device__ inline bool chunk_of(const PlanView& P, int n, int n_inst, int& b, in
   return p0 >= 0 && p1 <= n;
 }
 
+// one channel of a row: fp32 rows, or SPLIT16 rows (spconv.h: hi + lo, the value split16_decode4 gives - so the sums below are, bit
+// for bit, those of the fp32 kernel on the decoded rows).  One channel per lane keeps the summation order of the fp32 pass; a wave's 32
+// lanes of a channel block read the block's 64 contiguous hi bytes, then its 64 lo bytes: whole 128-byte lines either way.
+template <bool SPLIT>
+__device__ inline float ld1(const float* row, int ch) {
+  if (!SPLIT) return row[ch];
+  const char* p = reinterpret_cast<const char*>(row) + (ch >> 5) * 128 + (ch & 31) * 2;
+  return (float)*reinterpret_cast<const _Float16*>(p) + (float)*reinterpret_cast<const _Float16*>(p + SPLIT16_LO);
+}
+
 // partial[chunk][0..c) = sum of a, [c..2c) = sum of b over the chunk's rows.  MODE 0: a = x - s, b = (x - s)^2, s = the instance's
 // first row in plan order.  MODE 1: a = g, b = g * xhat (g = dy where y > 0 when `y` is given).
-template <int MODE>
+template <int MODE, bool SPLIT = false>
 __global__ __launch_bounds__(256) void k_in_partial(const float* __restrict__ x, int ld_x, const float* __restrict__ y, int ld_y,
                                                     const float* __restrict__ dy, int ld_dy, int n, int c, PlanView P, int n_inst,
                                                     const float* __restrict__ stats, float eps, double* __restrict__ partial) {
@@ -163,7 +188,7 @@ __global__ __launch_bounds__(256) void k_in_partial(const float* __restrict__ x,
   float mean = 0.f, invstd = 0.f;
   if (MODE == 0) {
     const int first = ident ? P.seg[b] : P.perm[P.seg[b]];
-    shift = (unsigned)first < (unsigned)n ? (double)x[(size_t)first * ld_x + ch] : 0.0;
+    shift = (unsigned)first < (unsigned)n ? (double)ld1<SPLIT>(x + (size_t)first * ld_x, ch) : 0.0;
   } else {
     mean = stats[(size_t)b * 2 * c + ch];
     invstd = 1.0f / sqrtf(stats[(size_t)b * 2 * c + c + ch] + eps);
@@ -171,7 +196,7 @@ __global__ __launch_bounds__(256) void k_in_partial(const float* __restrict__ x,
   for (int p = p0 + sub; p < p1; p += nsub) {
     const int r = ident ? p : P.perm[p];
     if ((unsigned)r >= (unsigned)n) continue;
-    const float xv = x[(size_t)r * ld_x + ch];
+    const float xv = ld1<SPLIT>(x + (size_t)r * ld_x, ch);
     if (MODE == 0) {
       const double d = (double)xv - shift;
       a += d;
@@ -197,41 +222,45 @@ __global__ __launch_bounds__(256) void k_in_partial(const float* __restrict__ x,
 // t >> 2, t >> 2 + 64, ... in ascending order, the 64 sums meet in a fixed tree.  MODE 0: stats[b] = {mean, biased variance}.
 // MODE 1: isum[b] = {sum g, sum g xhat} (fp64: k_in_param_grads adds them over the instances; the apply pass rounds them to fp32).
 // An instance without rows writes nothing.
-template <int MODE>
+template <int MODE, bool SPLIT = false>
 __global__ __launch_bounds__(256) void k_in_final(const double* __restrict__ partial, const float* __restrict__ x, int ld_x, int n, int c, PlanView P,
                                                   int n_inst, float* __restrict__ stats, double* __restrict__ isum) {
   __shared__ double red[256];
   if (P.hdr[1] != n || P.hdr[2] != n_inst || P.hdr[3]) return;
-  const int b = blockIdx.y;
-  const int nb = P.seg[b + 1] - P.seg[b];
-  if (nb <= 0) return;
-  const int k0 = P.cseg[b], k1 = P.cseg[b + 1];
   const int col = threadIdx.x & 3, sub = threadIdx.x >> 2;
   const int ch = blockIdx.x * 2 + (col >> 1), ab = col & 1;
-  double s = 0.0;
-  if (ch < c)
-    for (int k = k0 + sub; k < k1; k += 64) s += partial[(size_t)k * 2 * c + ab * c + ch];
-  red[threadIdx.x] = s;
-  __syncthreads();
-#pragma unroll
-  for (int w = 32; w >= 1; w >>= 1) {
-    if (sub < w) red[threadIdx.x] += red[threadIdx.x + 4 * w];
+  // gridDim.y == n_inst: one instance per workgroup.  The packed plan (launch_in_layer) does not know how many of its IN_MAX_INST ids
+  // have rows and walks them with a small grid; an instance's arithmetic does not depend on which workgroup does it.
+  for (int b = blockIdx.y; b < n_inst; b += gridDim.y) {
+    const int nb = P.seg[b + 1] - P.seg[b];
+    if (nb <= 0) continue;
+    const int k0 = P.cseg[b], k1 = P.cseg[b + 1];
+    double s = 0.0;
+    if (ch < c)
+      for (int k = k0 + sub; k < k1; k += 64) s += partial[(size_t)k * 2 * c + ab * c + ch];
+    red[threadIdx.x] = s;
     __syncthreads();
-  }
-  if (threadIdx.x < 4 && ab == 0 && ch < c) {
-    const double a = red[threadIdx.x], bb = red[threadIdx.x + 1];
-    if (MODE == 0) {
-      const int first = P.hdr[0] ? P.seg[b] : P.perm[P.seg[b]];
-      const double x0 = (unsigned)first < (unsigned)n ? (double)x[(size_t)first * ld_x + ch] : 0.0;
-      const double ms = a / nb;
-      double v = bb / nb - ms * ms;
-      if (v < 0.0) v = 0.0;
-      stats[(size_t)b * 2 * c + ch] = (float)(x0 + ms);
-      stats[(size_t)b * 2 * c + c + ch] = (float)v;
-    } else {
-      isum[(size_t)b * 2 * c + ch] = a;
-      isum[(size_t)b * 2 * c + c + ch] = bb;
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1) {
+      if (sub < w) red[threadIdx.x] += red[threadIdx.x + 4 * w];
+      __syncthreads();
     }
+    if (threadIdx.x < 4 && ab == 0 && ch < c) {
+      const double a = red[threadIdx.x], bb = red[threadIdx.x + 1];
+      if (MODE == 0) {
+        const int first = P.hdr[0] ? P.seg[b] : P.perm[P.seg[b]];
+        const double x0 = (unsigned)first < (unsigned)n ? (double)ld1<SPLIT>(x + (size_t)first * ld_x, ch) : 0.0;
+        const double ms = a / nb;
+        double v = bb / nb - ms * ms;
+        if (v < 0.0) v = 0.0;
+        stats[(size_t)b * 2 * c + ch] = (float)(x0 + ms);
+        stats[(size_t)b * 2 * c + c + ch] = (float)v;
+      } else {
+        isum[(size_t)b * 2 * c + ch] = a;
+        isum[(size_t)b * 2 * c + c + ch] = bb;
+      }
+    }
+    __syncthreads();                                                      // red is free for the next instance
   }
 }
 
@@ -249,30 +278,42 @@ __global__ __launch_bounds__(256) void k_in_param_grads(const double* __restrict
 // ---------------------------------------------------------------------------------------------- the element-wise passes
 __device__ inline float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
-// y = (x - mean_b) * invstd_b * weight + bias [+ residual] [ReLU]; the arithmetic of k_bn_apply per element
-__global__ __launch_bounds__(256) void k_in_apply(const float* __restrict__ x, int ld_x, int n, int c, PlanView P, int n_inst,
+// y = (x - mean_b) * invstd_b * weight + bias [+ residual] [ReLU]; the arithmetic of k_bn_apply per element.  SPLIT: x, residual and y
+// are SPLIT16 rows (8 bytes of hi halves + 8 bytes of lo halves per lane, the lanes of a channel block side by side) - decode, the same
+// arithmetic, encode; like every writer of SPLIT16 rows it feeds the range guard (spconv.h split16_guard).  In place (y == x) is fine:
+// a thread reads its four channels before it writes them.
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void k_in_apply(const float* x, int ld_x, int n, int c, PlanView P, int n_inst,
                                                   const float* __restrict__ stats, const float* __restrict__ weight, const float* __restrict__ bias,
-                                                  float eps, int relu, const float* __restrict__ res, int ld_res, float* __restrict__ y, int ld_y) {
+                                                  float eps, int relu, const float* res, int ld_res, float* y, int ld_y, unsigned int* range) {
   const int c4 = c / 4;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long long)n * c4 || P.hdr[1] != n || P.hdr[2] != n_inst || P.hdr[3]) return;
-  const int r = (int)(i / c4), q = (int)(i % c4) * 4;
-  const int b = P.inst[r];
-  if ((unsigned)b >= (unsigned)n_inst) return;
-  const float4 v = ld4(x + (size_t)r * ld_x + q);
-  const float4 m = ld4(stats + (size_t)b * 2 * c + q), va = ld4(stats + (size_t)b * 2 * c + c + q);
-  const float4 g = ld4(weight + q), be = ld4(bias + q);
-  float4 o;
-  o.x = (v.x - m.x) * (1.0f / sqrtf(va.x + eps)) * g.x + be.x;
-  o.y = (v.y - m.y) * (1.0f / sqrtf(va.y + eps)) * g.y + be.y;
-  o.z = (v.z - m.z) * (1.0f / sqrtf(va.z + eps)) * g.z + be.z;
-  o.w = (v.w - m.w) * (1.0f / sqrtf(va.w + eps)) * g.w + be.w;
-  if (res) {
-    const float4 t = ld4(res + (size_t)r * ld_res + q);
-    o.x += t.x; o.y += t.y; o.z += t.z; o.w += t.w;
+  bool live = i < (long long)n * c4 && P.hdr[1] == n && P.hdr[2] == n_inst && !P.hdr[3];
+  const int r = live ? (int)(i / c4) : 0, q = live ? (int)(i % c4) * 4 : 0;
+  const int b = live ? P.inst[r] : 0;
+  live = live && (unsigned)b < (unsigned)n_inst;
+  float mx = 0.0f;
+  if (live) {
+    const float4 v = SPLIT ? split16_load4(x + (size_t)r * ld_x, q) : ld4(x + (size_t)r * ld_x + q);
+    const float4 m = ld4(stats + (size_t)b * 2 * c + q), va = ld4(stats + (size_t)b * 2 * c + c + q);
+    const float4 g = ld4(weight + q), be = ld4(bias + q);
+    float4 o;
+    o.x = (v.x - m.x) * (1.0f / sqrtf(va.x + eps)) * g.x + be.x;
+    o.y = (v.y - m.y) * (1.0f / sqrtf(va.y + eps)) * g.y + be.y;
+    o.z = (v.z - m.z) * (1.0f / sqrtf(va.z + eps)) * g.z + be.z;
+    o.w = (v.w - m.w) * (1.0f / sqrtf(va.w + eps)) * g.w + be.w;
+    if (res) {
+      const float4 t = SPLIT ? split16_load4(res + (size_t)r * ld_res, q) : ld4(res + (size_t)r * ld_res + q);
+      o.x += t.x; o.y += t.y; o.z += t.z; o.w += t.w;
+    }
+    if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+    if (SPLIT) { split16_track(mx, o); split16_store4(y + (size_t)r * ld_y, q, o); }
+    else *reinterpret_cast<float4*>(y + (size_t)r * ld_y + q) = o;
   }
-  if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
-  *reinterpret_cast<float4*>(y + (size_t)r * ld_y + q) = o;
+  if (SPLIT) {
+    for (int o = 32; o; o >>= 1) mx = split16_merge(mx, __shfl_xor(mx, o));
+    if ((threadIdx.x & 63) == 0) split16_report(range, mx);
+  }
 }
 
 __device__ inline float in_dx(float x, float g, float mean, float var, float eps, float w, float sa, float sb, float inv_n) {
@@ -330,6 +371,21 @@ InWorkspace in_workspace(void* ws, int n, int c, int n_inst) {
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// eyoc_in_forward on fp32 rows (SPLIT = false) or SPLIT16 rows: the three launches
+template <bool SPLIT>
+int in_forward_launch(const float* x_dev, int n, int c, int ld_x, const PlanView& P, int n_inst, int final_rows, const float* weight_dev,
+                             const float* bias_dev, float eps, int relu, const float* residual_dev, int ld_res, float* y_dev, int ld_y,
+                             float* stats_dev, double* partial, unsigned int* range, hipStream_t st) {
+  hipLaunchKernelGGL((k_in_partial<0, SPLIT>), dim3(in_max_chunks(n, n_inst)), dim3(256), 0, st, x_dev, ld_x, (const float*)nullptr, 0,
+                     (const float*)nullptr, 0, n, c, P, n_inst, (const float*)nullptr, eps, partial);
+  hipLaunchKernelGGL((k_in_final<0, SPLIT>), dim3(cdiv(c, 2), final_rows), dim3(256), 0, st, (const double*)partial, x_dev, ld_x, n, c, P, n_inst,
+                     stats_dev, (double*)nullptr);
+  hipLaunchKernelGGL(k_in_apply<SPLIT>, dim3(cdiv((long long)n * (c / 4), 256)), dim3(256), 0, st, x_dev, ld_x, n, c, P, n_inst,
+                     (const float*)stats_dev, weight_dev, bias_dev, eps, relu, residual_dev, ld_res, y_dev, ld_y, range);
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -374,7 +430,8 @@ int eyoc_in_plan_build(eyoc_ctx* ctx, const int32_t* coords_dev, int n, int n_in
   if (hdr[0])
     hipLaunchKernelGGL(k_in_plan_iota, dim3(cdiv(n, 256)), dim3(256), 0, st, p + L.perm, n);
   else
-    hipLaunchKernelGGL(k_in_plan_place, dim3(blocks), dim3(256), 0, st, p + L.inst, n, n_inst, p + L.counts, p + L.seg, p + L.perm);
+    hipLaunchKernelGGL(k_in_plan_place, dim3(blocks), dim3(256), 0, st, p + L.inst, n, n_inst, p + L.counts, p + L.seg, p + L.perm,
+                       (const int32_t*)nullptr);
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
 }
@@ -383,29 +440,41 @@ size_t eyoc_in_workspace_bytes(int n, int c, int n_inst) {
   return in_shape_ok(n, c) && in_inst_ok(n_inst) ? in_workspace(nullptr, n, c, n_inst).bytes : 0;
 }
 
-int eyoc_in_forward(eyoc_ctx* ctx, const float* x_dev, int n, int c, int ld_x, const void* plan_dev, int n_inst, const float* weight_dev,
-                    const float* bias_dev, float eps, int relu, const float* residual_dev, int ld_res, float* y_dev, int ld_y,
-                    float* stats_dev, void* ws_dev, size_t ws_bytes, void* stream) {
-  EYOC_REQUIRE(ctx && x_dev && plan_dev && weight_dev && bias_dev && y_dev && stats_dev && ws_dev, EYOC_ERR_INVALID, "eyoc_in_forward: NULL argument");
-  EYOC_REQUIRE(in_shape_ok(n, c) && in_inst_ok(n_inst), EYOC_ERR_INVALID, "eyoc_in_forward: n %d, c %d (a divisor of 256, >= 4), n_inst %d (1 .. %d)", n,
+static int in_forward_checked(const char* who, bool split, eyoc_ctx* ctx, const float* x_dev, int n, int c, int ld_x, const void* plan_dev, int n_inst,
+                              const float* weight_dev, const float* bias_dev, float eps, int relu, const float* residual_dev, int ld_res, float* y_dev,
+                              int ld_y, float* stats_dev, unsigned int* range_dev, void* ws_dev, size_t ws_bytes, void* stream) {
+  EYOC_REQUIRE(ctx && x_dev && plan_dev && weight_dev && bias_dev && y_dev && stats_dev && ws_dev, EYOC_ERR_INVALID, "%s: NULL argument", who);
+  EYOC_REQUIRE(in_shape_ok(n, c) && in_inst_ok(n_inst), EYOC_ERR_INVALID, "%s: n %d, c %d (a divisor of 256, >= 4), n_inst %d (1 .. %d)", who, n,
                c, n_inst, IN_MAX_INST);
-  EYOC_REQUIRE(ld_x >= c && ld_y >= c && ld_x % 4 == 0 && ld_y % 4 == 0 && (!residual_dev || (ld_res >= c && ld_res % 4 == 0)), EYOC_ERR_INVALID,
-               "eyoc_in_forward: leading dimensions %d / %d / %d (multiples of 4, >= c = %d)", ld_x, ld_y, ld_res, c);
+  const int q = split ? 32 : 4;                 // SPLIT16 rows: whole 32-channel blocks
+  EYOC_REQUIRE(c % q == 0 && ld_x >= c && ld_y >= c && ld_x % q == 0 && ld_y % q == 0 && (!residual_dev || (ld_res >= c && ld_res % q == 0)),
+               EYOC_ERR_INVALID, "%s: leading dimensions %d / %d / %d (multiples of %d, >= c = %d)", who, ld_x, ld_y, ld_res, q, c);
   EYOC_REQUIRE(aligned16(x_dev) && aligned16(y_dev) && aligned16(residual_dev) && aligned16(stats_dev) && aligned16(weight_dev) && aligned16(bias_dev),
-               EYOC_ERR_INVALID, "eyoc_in_forward: tensors must be 16-byte aligned");
-  EYOC_REQUIRE(ws_bytes >= eyoc_in_workspace_bytes(n, c, n_inst), EYOC_ERR_WORKSPACE, "eyoc_in_forward: workspace %zu < %zu bytes", ws_bytes,
+               EYOC_ERR_INVALID, "%s: tensors must be 16-byte aligned", who);
+  EYOC_REQUIRE(ws_bytes >= eyoc_in_workspace_bytes(n, c, n_inst), EYOC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes,
                eyoc_in_workspace_bytes(n, c, n_inst));
   hipStream_t st = (hipStream_t)stream;
   const PlanView P = plan_view(plan_dev, n, n_inst);
   const InWorkspace W = in_workspace(ws_dev, n, c, n_inst);
-  hipLaunchKernelGGL(k_in_partial<0>, dim3(in_max_chunks(n, n_inst)), dim3(256), 0, st, x_dev, ld_x, (const float*)nullptr, 0, (const float*)nullptr, 0, n,
-                     c, P, n_inst, (const float*)nullptr, eps, W.partial);
-  hipLaunchKernelGGL(k_in_final<0>, dim3(cdiv(c, 2), n_inst), dim3(256), 0, st, (const double*)W.partial, x_dev, ld_x, n, c, P, n_inst, stats_dev,
-                     (double*)nullptr);
-  hipLaunchKernelGGL(k_in_apply, dim3(cdiv((long long)n * (c / 4), 256)), dim3(256), 0, st, x_dev, ld_x, n, c, P, n_inst, (const float*)stats_dev,
-                     weight_dev, bias_dev, eps, relu, residual_dev, ld_res, y_dev, ld_y);
-  EYOC_CHECK_HIP(hipGetLastError());
-  return EYOC_OK;
+  if (split)
+    return in_forward_launch<true>(x_dev, n, c, ld_x, P, n_inst, n_inst, weight_dev, bias_dev, eps, relu, residual_dev, ld_res, y_dev, ld_y, stats_dev,
+                                   W.partial, range_dev, st);
+  return in_forward_launch<false>(x_dev, n, c, ld_x, P, n_inst, n_inst, weight_dev, bias_dev, eps, relu, residual_dev, ld_res, y_dev, ld_y, stats_dev,
+                                  W.partial, nullptr, st);
+}
+
+int eyoc_in_forward(eyoc_ctx* ctx, const float* x_dev, int n, int c, int ld_x, const void* plan_dev, int n_inst, const float* weight_dev,
+                    const float* bias_dev, float eps, int relu, const float* residual_dev, int ld_res, float* y_dev, int ld_y,
+                    float* stats_dev, void* ws_dev, size_t ws_bytes, void* stream) {
+  return in_forward_checked("eyoc_in_forward", false, ctx, x_dev, n, c, ld_x, plan_dev, n_inst, weight_dev, bias_dev, eps, relu, residual_dev, ld_res,
+                            y_dev, ld_y, stats_dev, nullptr, ws_dev, ws_bytes, stream);
+}
+
+int eyoc_in_forward_split16(eyoc_ctx* ctx, const float* x_dev, int n, int c, int ld_x, const void* plan_dev, int n_inst, const float* weight_dev,
+                            const float* bias_dev, float eps, int relu, const float* residual_dev, int ld_res, float* y_dev, int ld_y,
+                            float* stats_dev, unsigned int* range_dev, void* ws_dev, size_t ws_bytes, void* stream) {
+  return in_forward_checked("eyoc_in_forward_split16", true, ctx, x_dev, n, c, ld_x, plan_dev, n_inst, weight_dev, bias_dev, eps, relu, residual_dev,
+                            ld_res, y_dev, ld_y, stats_dev, range_dev, ws_dev, ws_bytes, stream);
 }
 
 int eyoc_in_backward(eyoc_ctx* ctx, const float* x_dev, int ld_x, const float* y_dev, int ld_y, const float* dy_dev, int ld_dy, int n, int c,
@@ -439,3 +508,48 @@ int eyoc_in_backward(eyoc_ctx* ctx, const float* x_dev, int ld_x, const float* y
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- the packed plan's side (model.hip)
+// The forward knows neither how many instances a batch holds nor may it read anything back, so its plans are built for IN_MAX_INST ids
+// (the maps' own batch limit: eyoc_maps_build refuses larger indices, an id outside the plan cannot occur): ids without rows cost a
+// seg entry each, k_in_final walks them with IN_FINAL_ROWS workgroups per channel pair.
+namespace eyoc {
+
+constexpr int IN_FINAL_ROWS = 32;
+
+size_t in_plan_bytes_nosync(int n) { return eyoc_in_plan_bytes(n, IN_MAX_INST); }
+
+// eyoc_in_plan_build without its read-back: count, scan, place - the placement decides on the device whether it has anything to do
+int in_plan_build_nosync(const int32_t* coords_dev, int n, void* plan_dev, hipStream_t st) {
+  const PlanLayout L = plan_layout(n, IN_MAX_INST);
+  int32_t* p = (int32_t*)plan_dev;
+  const int blocks = cdiv(n, IN_PLAN_ROWS);
+  EYOC_CHECK_HIP(hipMemsetAsync(p + L.flags, 0, 4 * sizeof(int32_t), st));
+  hipLaunchKernelGGL(k_in_plan_count, dim3(blocks), dim3(256), 0, st, coords_dev, n, IN_MAX_INST, p + L.inst, p + L.counts, p + L.flags);
+  hipLaunchKernelGGL(k_in_plan_scan, dim3(1), dim3(1024), 0, st, p + L.counts, blocks, n, IN_MAX_INST, p + L.flags, p, p + L.seg, p + L.cseg);
+  hipLaunchKernelGGL(k_in_plan_place, dim3(blocks), dim3(256), 0, st, p + L.inst, n, IN_MAX_INST, p + L.counts, p + L.seg, p + L.perm,
+                     (const int32_t*)p);
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
+// workspace of one instance-norm layer of the plan: the partial sums and the statistics [IN_MAX_INST][2 c]
+size_t in_layer_workspace_bytes(int n, int c) {
+  if (!in_shape_ok(n, c)) return 0;
+  return in_workspace(nullptr, n, c, IN_MAX_INST).bytes + align_up((size_t)IN_MAX_INST * 2 * c * sizeof(float));
+}
+
+int launch_in_layer(const float* x, int ld_x, int n, int c, const void* plan, const float* weight, const float* bias, float eps, int relu,
+                    const float* res, int ld_res, float* y, int ld_y, bool split, unsigned int* range, void* ws, hipStream_t st) {
+  const int q = split ? 32 : 4;
+  EYOC_REQUIRE(in_shape_ok(n, c) && c % q == 0 && ld_x % q == 0 && ld_y % q == 0 && (!res || ld_res % q == 0) && aligned16(x) && aligned16(y) &&
+                   aligned16(res), EYOC_ERR_INVALID, "model: instance norm over %d rows of %d channels (rows of %d -> %d floats)", n, c, ld_x, ld_y);
+  const PlanView P = plan_view(plan, n, IN_MAX_INST);
+  const InWorkspace W = in_workspace(ws, n, c, IN_MAX_INST);
+  float* stats = (float*)((char*)ws + W.bytes);
+  if (split)
+    return in_forward_launch<true>(x, n, c, ld_x, P, IN_MAX_INST, IN_FINAL_ROWS, weight, bias, eps, relu, res, ld_res, y, ld_y, stats, W.partial, range, st);
+  return in_forward_launch<false>(x, n, c, ld_x, P, IN_MAX_INST, IN_FINAL_ROWS, weight, bias, eps, relu, res, ld_res, y, ld_y, stats, W.partial, nullptr, st);
+}
+
+}  // namespace eyoc

@@ -2,6 +2,10 @@
 // Mirrors ResUNet2.__init__/forward (model/resunet.py:18-193) and BasicBlockBase.forward
 // (model/residual_block.py:37-53) with every batch norm folded into the convolution before it
 // (eval mode, model/common.py:4-6) and every ReLU / residual add / concat fused into a conv epilogue.
+// The ResUNetIN2 family (model/resunet.py:229-251; eyoc_model_create_in, block_norm 1) keeps the stage norms folded; inside the residual
+// blocks (model/residual_block.py:60-61) every convolution writes its raw sums and the instance norm behind it is a layer of its own
+// (M_INORM: statistics per instance and channel, then normalise + weight / bias [+ residual] + ReLU in place - inorm.hip), on the plan's
+// own row formats (fp32 / SPLIT16): 37 layers instead of 23, no new activation buffer.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -12,7 +16,10 @@ using namespace eyoc;
 
 namespace {
 
-enum MapSel { M_CONV1, M_S1, M_DOWN, M_UP, M_IDENT, M_AFFINE };   // M_AFFINE: a batch norm that stands alone (ResUNetExpanded's norm<i>_2): y = x * scale + shift per channel
+enum MapSel { M_CONV1, M_S1, M_DOWN, M_UP, M_IDENT, M_AFFINE, M_INORM };   // M_AFFINE: a batch norm that stands alone (ResUNetExpanded's norm<i>_2): y = x * scale + shift per channel
+// M_INORM: an instance norm (the blocks of the ResUNetIN2 family, model/residual_block.py:60-61): its statistics belong to the input, so it
+// folds into nothing - one layer behind the raw convolution, in place, with the block's ReLU / residual (inorm.hip launch_in_layer)
+constexpr float IN_EPS = 1e-8f;      // MinkowskiInstanceNorm's (model/common.py:7-8)
 
 struct LayerPlan {
   std::string name;      // conv name in the state_dict ("block2.conv1")
@@ -36,11 +43,13 @@ enum Buf { B_IN = 0, B_X1, B_T1, B_CAT1, B_X2, B_T2, B_CAT2, B_X4, B_T4, B_CAT4,
 struct BufPlan { int level, width; };
 
 size_t pad64(size_t v) { return (v + 63) / 64 * 64; }
+bool is_norm_layer(MapSel m) { return m == M_AFFINE || m == M_INORM; }   // no products: per-channel parameters at w_off / b_off only
 
 }  // namespace
 
 struct eyoc_model {
   eyoc_model_desc desc;
+  int block_norm = 0;      // 0: batch norm inside the residual blocks (folded), 1: instance norm (M_INORM layers); eyoc_model_create_in
   std::vector<LayerPlan> layers;
   BufPlan bufs[B_COUNT];
   float* blob = nullptr;
@@ -62,7 +71,7 @@ struct eyoc_model {
 
 namespace {
 
-void build_plan(const eyoc_model_desc& d, std::vector<LayerPlan>& L, BufPlan* bufs) {
+void build_plan(const eyoc_model_desc& d, int block_norm, std::vector<LayerPlan>& L, BufPlan* bufs) {
   const int* C = d.channels;
   const int* T = d.tr_channels;
   const int K1 = d.conv1_kernel_size * d.conv1_kernel_size * d.conv1_kernel_size;
@@ -89,6 +98,15 @@ void build_plan(const eyoc_model_desc& d, std::vector<LayerPlan>& L, BufPlan* bu
     L.push_back(p);
   };
   auto block1 = [&](const std::string& name, int c, int level, int x_buf, int t_buf, int out_buf, int out_col) {
+    if (block_norm == 1) {
+      // BasicBlockIN: the convolution writes its raw sums (scale 1, shift 0), the norm runs in place behind it - conv1 -> t, norm1 + ReLU
+      // on t; conv2 -> the block's destination (a column range of a concat buffer), norm2 + residual x + ReLU there.  No new buffer.
+      conv((name + ".conv1").c_str(), "", 27, c, c, M_S1, level, level, x_buf, 0, t_buf, 0, -1, 0);
+      conv((name + ".norm1").c_str(), (name + ".norm1").c_str(), 0, c, c, M_INORM, level, level, t_buf, 0, t_buf, 0, -1, 1);
+      conv((name + ".conv2").c_str(), "", 27, c, c, M_S1, level, level, t_buf, 0, out_buf, out_col, -1, 0);
+      conv((name + ".norm2").c_str(), (name + ".norm2").c_str(), 0, c, c, M_INORM, level, level, out_buf, out_col, out_buf, out_col, x_buf, 1);
+      return;
+    }
     conv((name + ".conv1").c_str(), (name + ".norm1").c_str(), 27, c, c, M_S1, level, level, x_buf, 0, t_buf, 0, -1, 1);
     conv((name + ".conv2").c_str(), (name + ".norm2").c_str(), 27, c, c, M_S1, level, level, t_buf, 0, out_buf, out_col,
          x_buf, 1);
@@ -126,13 +144,13 @@ void build_plan(const eyoc_model_desc& d, std::vector<LayerPlan>& L, BufPlan* bu
   size_t off = 0;
   for (auto& p : L) {
     p.w_off = off;
-    off += p.map == M_AFFINE ? pad64((size_t)p.cout) : pad64((size_t)p.K * p.cin * p.cout);    // a stand-alone norm: its scale per channel
+    off += is_norm_layer(p.map) ? pad64((size_t)p.cout) : pad64((size_t)p.K * p.cin * p.cout);    // a stand-alone norm: its scale (an instance norm: its weight) per channel
     p.b_off = off;
     off += pad64((size_t)p.cout);
   }
   // second half of the blob: the SPLIT16 packing of every sparse-conv layer (spconv_wave.hip, MATH = 1)
   for (auto& p : L) {
-    if (p.map == M_AFFINE) continue;
+    if (is_norm_layer(p.map)) continue;
     if (p.map != M_CONV1) {
       p.w16_off = off;
       off += pad64((size_t)p.K * p.cin * p.cout);
@@ -181,7 +199,7 @@ size_t plan_blob_floats(const std::vector<LayerPlan>& L) {
   size_t end = 0;
   for (auto& p : L) {
     end = std::max(end, p.b_off + pad64(p.cout));
-    if (p.map != M_AFFINE) end = std::max(end, p.s_off + 64);
+    if (!is_norm_layer(p.map)) end = std::max(end, p.s_off + 64);
   }
   return end;
 }
@@ -209,6 +227,22 @@ int check_desc(const eyoc_model_desc* d) {
   return EYOC_OK;
 }
 
+int check_block_norm(const eyoc_model_desc* d, int block_norm) {
+  EYOC_REQUIRE(block_norm == 0 || block_norm == 1, EYOC_ERR_INVALID, "model: block_norm %d not in {0 (batch norm), 1 (instance norm)}", block_norm);
+  EYOC_REQUIRE(!(block_norm == 1 && d->expanded), EYOC_ERR_INVALID, "model: no instance-norm plan for the expanded network");
+  return EYOC_OK;
+}
+
+// an instance norm's parameters as eyoc_layer_params carries them: weight and bias, no statistics
+const eyoc_layer_params* find_inorm(const eyoc_layer_params* layers, int n, const LayerPlan& p) {
+  const eyoc_layer_params* nm = find_layer(layers, n, p.norm);
+  if (!(nm && nm->bn_weight && nm->bn_bias && !nm->bn_mean && !nm->bn_var && nm->cout == p.cout)) {
+    set_error("eyoc_model_create: instance norm '%s' missing or wrong width (weight and bias of %d channels, no statistics)", p.norm.c_str(), p.cout);
+    return nullptr;
+  }
+  return nm;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Device-side re-pack (eyoc_model_repack_device): the arithmetic of eyoc_model_pack_host, eyoc_spconv_pack_weights and
 // eyoc_spconv_pack_weights_split16 restated as four launches over ALL layers of the plan - fold, fp32 pack + layer maximum, layer
@@ -221,7 +255,7 @@ constexpr int RP_CH = 256;         // channels of the widest layer (check_desc)
 struct RpFoldLayer {
   const float *g, *b, *m, *v, *bias;   // the norm folded into the layer (all NULL: none), the convolution's bias (NULL: none)
   uint32_t b_off, w_off;               // float offsets into the blob: shifts; M_AFFINE's scales
-  uint32_t cout, affine;
+  uint32_t cout, affine;               // affine 1: M_AFFINE (the folded scale goes to w_off); 2: M_INORM (weight -> w_off, bias -> b_off, as they are)
 };
 struct RpFoldArgs { RpFoldLayer L[RP_MAXL]; };
 
@@ -302,7 +336,10 @@ __global__ void __launch_bounds__(RP_CH) k_repack_fold(RpFoldArgs a, float eps, 
   if (c >= pc) return;
   float s = 1.0f, sh = 0.0f;
   if (c < (int)L.cout) {
-    if (L.g) {
+    if (L.affine == 2) {
+      s = L.g[c];
+      sh = L.b[c];
+    } else if (L.g) {
       const float var = L.v[c], g = L.g[c], mu = L.m[c], be = L.b[c];
       const float ve = rp_nan(var + eps, var, eps);
       float rt = sqrtf(ve);
@@ -459,9 +496,15 @@ int eyoc_model_repack_device(eyoc_ctx* ctx, eyoc_model* m, const eyoc_layer_para
     RpPackLayer& P = p32.L[li];
     p32.blk[li] = b32;
     blk16[li] = b16;
-    F.b_off = (uint32_t)p.b_off; F.w_off = (uint32_t)p.w_off; F.cout = (uint32_t)p.cout; F.affine = p.map == M_AFFINE;
+    F.b_off = (uint32_t)p.b_off; F.w_off = (uint32_t)p.w_off; F.cout = (uint32_t)p.cout; F.affine = p.map == M_AFFINE ? 1 : p.map == M_INORM ? 2 : 0;
     EYOC_REQUIRE(p.cout <= RP_CH, EYOC_ERR_INVALID, "eyoc_model_repack_device: layer '%s' has %d channels", p.name.c_str(), p.cout);
     const eyoc_layer_params* cv = nullptr;
+    if (p.map == M_INORM) {
+      const eyoc_layer_params* nm = find_inorm(layers, n_layers, p);
+      if (!nm) return EYOC_ERR_INVALID;
+      F.g = nm->bn_weight; F.b = nm->bn_bias;
+      continue;
+    }
     if (p.map != M_AFFINE) {
       cv = find_layer(layers, n_layers, p.name);
       EYOC_REQUIRE(cv && cv->kernel && cv->K == p.K && cv->cin == p.cin && cv->cout == p.cout, EYOC_ERR_INVALID,
@@ -499,28 +542,45 @@ int eyoc_model_repack_device(eyoc_ctx* ctx, eyoc_model* m, const eyoc_layer_para
   return EYOC_OK;
 }
 
-size_t eyoc_model_blob_floats(const eyoc_model_desc* desc) {
-  if (check_desc(desc) != EYOC_OK) return 0;
+size_t eyoc_model_blob_floats_in(const eyoc_model_desc* desc, int block_norm) {
+  if (check_desc(desc) != EYOC_OK || check_block_norm(desc, block_norm) != EYOC_OK) return 0;
   std::vector<LayerPlan> L;
   BufPlan bufs[B_COUNT];
-  build_plan(*desc, L, bufs);
+  build_plan(*desc, block_norm, L, bufs);
   return plan_blob_floats(L);
 }
+
+size_t eyoc_model_blob_floats(const eyoc_model_desc* desc) { return eyoc_model_blob_floats_in(desc, 0); }
 
 // Folds batch norm into every convolution and writes the packed blob (fp32 fragment order + split16 packing + shifts) into
 // HOST memory.  Pure host code: no device is touched, so a rank can build (or verify) the blob it broadcasts without a GPU.
 int eyoc_model_pack_host(const eyoc_model_desc* desc, const eyoc_layer_params* layers, int n_layers, float* blob_host,
                          size_t blob_floats) {
+  return eyoc_model_pack_host_in(desc, layers, n_layers, blob_host, blob_floats, 0);
+}
+
+// block_norm 1: the residual blocks' convolutions are packed as they are (scale 1, shift 0), every block norm is a layer of its own
+// holding its weight at w_off and its bias at b_off
+int eyoc_model_pack_host_in(const eyoc_model_desc* desc, const eyoc_layer_params* layers, int n_layers, float* blob_host,
+                            size_t blob_floats, int block_norm) {
   EYOC_REQUIRE(layers && blob_host, EYOC_ERR_INVALID, "eyoc_model_pack_host: NULL argument");
   int rc = check_desc(desc);
+  if (!rc) rc = check_block_norm(desc, block_norm);
   if (rc) return rc;
   std::vector<LayerPlan> plan;
   BufPlan bufs[B_COUNT];
-  build_plan(*desc, plan, bufs);
+  build_plan(*desc, block_norm, plan, bufs);
   const size_t need = plan_blob_floats(plan);
   EYOC_REQUIRE(blob_floats >= need, EYOC_ERR_INVALID, "eyoc_model_pack_host: blob of %zu floats required, got %zu", need, blob_floats);
   std::fill(blob_host, blob_host + need, 0.0f);
   for (auto& p : plan) {
+    if (p.map == M_INORM) {
+      const eyoc_layer_params* nm = find_inorm(layers, n_layers, p);
+      if (!nm) return EYOC_ERR_INVALID;
+      memcpy(blob_host + p.w_off, nm->bn_weight, p.cout * sizeof(float));
+      memcpy(blob_host + p.b_off, nm->bn_bias, p.cout * sizeof(float));
+      continue;
+    }
     if (p.map == M_AFFINE) {                                            // scale / shift of a norm that stands alone (the same fold as below)
       const eyoc_layer_params* bn = find_layer(layers, n_layers, p.norm);
       EYOC_REQUIRE(bn && bn->bn_weight && bn->bn_bias && bn->bn_mean && bn->bn_var && bn->cout == p.cout, EYOC_ERR_INVALID,
@@ -574,12 +634,19 @@ int eyoc_model_pack_host(const eyoc_model_desc* desc, const eyoc_layer_params* l
 
 int eyoc_model_create(eyoc_ctx* ctx, const eyoc_model_desc* desc, const eyoc_layer_params* layers, int n_layers,
                       float* blob_dev, size_t blob_floats, eyoc_model** out) {
+  return eyoc_model_create_in(ctx, desc, layers, n_layers, blob_dev, blob_floats, 0, out);
+}
+
+int eyoc_model_create_in(eyoc_ctx* ctx, const eyoc_model_desc* desc, const eyoc_layer_params* layers, int n_layers,
+                         float* blob_dev, size_t blob_floats, int block_norm, eyoc_model** out) {
   EYOC_REQUIRE(ctx && out && blob_dev, EYOC_ERR_INVALID, "eyoc_model_create: NULL argument");
   int rc = check_desc(desc);
+  if (!rc) rc = check_block_norm(desc, block_norm);
   if (rc) return rc;
   eyoc_model* m = new eyoc_model();
   m->desc = *desc;
-  build_plan(*desc, m->layers, m->bufs);
+  m->block_norm = block_norm;
+  build_plan(*desc, block_norm, m->layers, m->bufs);
   m->blob = blob_dev;
   m->blob_floats = plan_blob_floats(m->layers);
   if (blob_floats < m->blob_floats || ((uintptr_t)blob_dev & 255) != 0) {
@@ -590,7 +657,7 @@ int eyoc_model_create(eyoc_ctx* ctx, const eyoc_model_desc* desc, const eyoc_lay
   }
   if (layers) {
     std::vector<float> host(m->blob_floats, 0.0f);
-    rc = eyoc_model_pack_host(desc, layers, n_layers, host.data(), host.size());
+    rc = eyoc_model_pack_host_in(desc, layers, n_layers, host.data(), host.size(), block_norm);
     if (rc) { delete m; return rc; }
     hipError_t e = hipMemcpy(blob_dev, host.data(), m->blob_floats * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
@@ -672,11 +739,20 @@ static size_t ks_part_bytes(const eyoc_model* m, const eyoc_maps* maps) {
   return 0;
 }
 
+// the instance-norm layers' scratch (partial sums, statistics): the largest layer's, shared by all of them; 0 for a batch-norm model
+static size_t in_ws_bytes(const eyoc_model* m, const eyoc_maps* maps) {
+  size_t b = 0;
+  for (const LayerPlan& p : m->layers)
+    if (p.map == M_INORM && maps->rows[p.out_level] > 0) b = std::max(b, in_layer_workspace_bytes(maps->rows[p.out_level], p.cout));
+  return b;
+}
+
 size_t eyoc_model_workspace_bytes(const eyoc_model* m, const eyoc_maps* maps) {
   if (!m || !maps) return 0;
   size_t b = 0;
   for (int i = B_X1; i < B_OUT; ++i) b += align_up((size_t)maps->rows[m->bufs[i].level] * m->bufs[i].width * sizeof(float));
   b += align_up(ks_part_bytes(m, maps));
+  b += align_up(in_ws_bytes(m, maps));
   return b + 256;
 }
 
@@ -757,6 +833,8 @@ static int forward_impl(eyoc_ctx* ctx, const eyoc_model* mc, const eyoc_maps* ma
   for (int i = B_X1; i < B_OUT; ++i) buf[i] = cv.take<float>((size_t)maps->rows[m->bufs[i].level] * m->bufs[i].width);
   const size_t ks_bytes = ks_part_bytes(m, maps);
   float* ks_part = ks_bytes ? cv.take<float>(ks_bytes / 4) : nullptr;
+  const size_t in_bytes = in_ws_bytes(m, maps);
+  void* in_ws = in_bytes ? cv.take<unsigned char>(in_bytes) : nullptr;
   float* rows_region = nullptr;        // the compact rows / the full output of a forward with a row list
   void* rows_scratch = nullptr;
   if (rows_dev) {
@@ -793,7 +871,15 @@ static int forward_impl(eyoc_ctx* ctx, const eyoc_model* mc, const eyoc_maps* ma
       EYOC_CHECK_HIP(hipEventRecord(m->progress_event, st));
       progress_recorded = true;
     }
-    if (p.map == M_AFFINE) {
+    if (p.map == M_INORM) {
+      // the level's instance plan: built on the first instance-norm forward over these maps, without a read-back (maps_ensure_in_plan)
+      if ((rc = maps_ensure_in_plan(const_cast<eyoc_maps*>(maps), p.out_level, st))) return rc;
+      rc = n_out ? launch_in_layer(buf[p.in_buf] + p.in_col, m->bufs[p.in_buf].width, n_out, p.cout, maps->in_plan[p.out_level], m->blob + p.w_off,
+                                   m->blob + p.b_off, IN_EPS, p.relu, p.res_buf >= 0 ? buf[p.res_buf] : nullptr,
+                                   p.res_buf >= 0 ? m->bufs[p.res_buf].width : 0, buf[p.out_buf] + p.out_col, m->bufs[p.out_buf].width, split,
+                                   split ? m->range : nullptr, in_ws, st)
+                 : EYOC_OK;
+    } else if (p.map == M_AFFINE) {
       rc = launch_affine(buf[p.in_buf] + p.in_col, m->bufs[p.in_buf].width, n_out, p.cout, m->blob + p.w_off, m->blob + p.b_off,
                          buf[p.out_buf] + p.out_col, m->bufs[p.out_buf].width, split, split ? m->range : nullptr, st);
     } else if (p.map == M_CONV1) {
@@ -988,8 +1074,9 @@ int eyoc_model_layer_work(eyoc_ctx* ctx, const eyoc_model* m, const eyoc_maps* m
       case M_UP: pr = (double)info.pairs_up[p.level]; n_in = maps->rows[p.level + 1]; break;
       case M_IDENT: pr = n_out; break;
       case M_AFFINE: break;
+      case M_INORM: break;
     }
-    if (p.map == M_AFFINE) {                                             // no products: one read and one write of the rows
+    if (is_norm_layer(p.map)) {                                             // no products: one read and one write of the rows
       if (names) names[li] = p.name.c_str();
       if (pairs) pairs[li] = 0;
       if (flops) flops[li] = 2.0 * n_out * p.cout;

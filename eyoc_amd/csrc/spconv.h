@@ -249,6 +249,14 @@ struct Conv1Args {
 };
 // layout of a local rulebook record (spconv_st.hip owns it; conv1_bf_kernel in spconv.hip reads the row list and the entries)
 constexpr int ST_TILE = 256, ST_UMAX = 639, ST_UCAP = 1280, ST_NPASS = 2, ST_LOC_OFF = 16 + ST_UCAP * 4, ST_INV_OFF = 33152, ST_LR_BYTES = 33408;
+// Instance norm as a layer of the packed plan (inorm.hip): y = [relu]((x - mean_b) / sqrt(var_b + eps) * weight + bias [+ res]) on fp32 or
+// SPLIT16 rows, in place allowed, over the level's instance plan (maps_ensure_in_plan: built for the maps' batch limit, never read back);
+// `ws`: in_layer_workspace_bytes(n, c).  SPLIT16 rows feed `range` like every other writer.
+size_t in_plan_bytes_nosync(int n);
+int in_plan_build_nosync(const int32_t* coords_dev, int n, void* plan_dev, hipStream_t st);
+size_t in_layer_workspace_bytes(int n, int c);
+int launch_in_layer(const float* x, int ld_x, int n, int c, const void* plan, const float* weight, const float* bias, float eps, int relu,
+                    const float* res, int ld_res, float* y, int ld_y, bool split, unsigned int* range, void* ws, hipStream_t st);
 int launch_conv1(const Conv1Args& a, hipStream_t st);
 bool conv1_walks_octree(const Conv1Args& a);   // false: launch_conv1 will probe a.table (it must be built)
 

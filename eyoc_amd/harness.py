@@ -444,9 +444,12 @@ class RegistrationPipeline:
         # the split16 range check is deferred to where ``register`` synchronises anyway (no host wait after the forward)
         return self._features(batch, maps)[0]
 
+    @torch.no_grad()
     def _features(self, batch, maps, sampled=False):
         """``features`` -> (the features, the batch they belong to): under ``isolate_failures`` that is ``batch`` without the pairs a
-        failed map build named - dropped here, or by ``prepare_maps``, whose handle then carries the reduced batch.
+        failed map build named - dropped here, or by ``prepare_maps``, whose handle then carries the reduced batch.  Without a graph
+        on every route (``enqueue`` and ``validate`` come here outside ``no_grad``): the packed plan never builds one, and an opted-in
+        ``ResUNetIN2`` model takes that plan only where no gradient can be asked for (``model._runs_packed``).
 
         ``sampled`` (the step): only the rows matching reads, ``model(x, rows=cat(sel0, sel1))`` of the batch the forward runs on -
         a dense ``[2 P n, C]`` tensor, ``sel0``'s rows first, bit for bit ``model(x).F[rows]``."""

@@ -123,17 +123,32 @@ class ResUNet2(nn.Module):
         self.device_repack = False
         self._probe = False
         self.last_max_activation = None
+        # ResUNetIN2 family only: True = the eval forward and everything that lives on the packed blob (pack, repack, weight_blob,
+        # spconv_math, the registration pipeline, dist.broadcast_model ...) use the instance-norm plan (csrc/model.hip M_INORM);
+        # False (default) = no packed plan, every forward runs layer by layer.  Set it before the first pack.
+        self.packed_in = False
 
     # ------------------------------------------------------------------ packing
     @property
     def instance_norm(self) -> bool:
-        """The blocks use instance norm (the ``ResUNetIN2`` family): no packed eval plan - every forward runs layer by layer
-        (``eyoc_amd/train.py``), the block norms through ``eyoc_in_forward`` / ``_backward``."""
+        """The blocks use instance norm (the ``ResUNetIN2`` family).  Unless ``packed_in`` is set there is no packed eval plan - every
+        forward runs layer by layer (``eyoc_amd/train.py``), the block norms through ``eyoc_in_forward`` / ``_backward``."""
         return self.BLOCK_NORM_TYPE == 'IN'
 
     def _bn_only(self):
-        if self.instance_norm:
+        if self.instance_norm and not self.packed_in:
             raise NotImplementedError("packed plan: batch-norm models only")
+
+    def _packed_block_norm(self) -> int:
+        """``block_norm`` of the ``eyoc_model_*_in`` entry points: 1 = the instance-norm plan (an opted-in IN model), 0 = the batch-norm one."""
+        return 1 if self.instance_norm and self.packed_in else 0
+
+    def _runs_packed(self) -> bool:
+        """The eval forward takes the packed plan: always for a batch-norm model; an opted-in IN model wherever no gradient can be asked
+        for (the plan has no backward: under ``enable_grad`` with parameters that require grad the layer-by-layer route stays)."""
+        if not self.instance_norm:
+            return True
+        return self.packed_in and not (torch.is_grad_enabled() and any(t.requires_grad for t in self._tensor_list()))
 
     def _desc(self):
         d = _lib.ModelDesc()
@@ -200,6 +215,9 @@ class ResUNet2(nn.Module):
 
     def blob_floats(self) -> int:
         d = self._desc()
+        bn = self._packed_block_norm()
+        if bn:
+            return int(_lib.load().eyoc_model_blob_floats_in(C.byref(d), bn))
         return int(_lib.load().eyoc_model_blob_floats(C.byref(d)))
 
     def _layer_params(self, device=False):
@@ -242,6 +260,12 @@ class ResUNet2(nn.Module):
                 lp.cout = mod.bn.num_features
                 lp.bn_weight, lp.bn_bias = fptr(arr(mod.bn.weight)), fptr(arr(mod.bn.bias))
                 lp.bn_mean, lp.bn_var = fptr(arr(mod.bn.running_mean)), fptr(arr(mod.bn.running_var))
+                items.append(lp)
+            elif isinstance(mod, _InstNorm):                   # weight and bias, no statistics (bn_mean / bn_var stay NULL)
+                lp = _lib.LayerParams()
+                lp.name = name.encode()
+                lp.cout = mod.num_features
+                lp.bn_weight, lp.bn_bias = fptr(arr(mod.weight.reshape(-1))), fptr(arr(mod.bias.reshape(-1)))
                 items.append(lp)
         return (_lib.LayerParams * len(items))(*items), len(items), keep
 
@@ -296,7 +320,12 @@ class ResUNet2(nn.Module):
         blob = torch.zeros(self.blob_floats(), dtype=torch.float32)
         d = self._desc()
         layers, nl, keep = self._layer_params()
-        _lib.check(lib.eyoc_model_pack_host(C.byref(d), layers, nl, C.c_void_p(blob.data_ptr()), blob.numel()), "eyoc_model_pack_host")
+        bn = self._packed_block_norm()
+        if bn:
+            rc = lib.eyoc_model_pack_host_in(C.byref(d), layers, nl, C.c_void_p(blob.data_ptr()), blob.numel(), bn)
+        else:
+            rc = lib.eyoc_model_pack_host(C.byref(d), layers, nl, C.c_void_p(blob.data_ptr()), blob.numel())
+        _lib.check(rc, "eyoc_model_pack_host")
         del keep
         return blob
 
@@ -317,14 +346,14 @@ class ResUNet2(nn.Module):
         d = self._desc()
         h = C.c_void_p()
         on_device = not from_blob and self.device_repack and self._params_on(device)   # a handle over the zeroed blob, filled below
+        bn = self._packed_block_norm()
         with torch.cuda.device(device):
-            if from_blob or on_device:
-                rc = lib.eyoc_model_create(_lib.ctx(device.index), C.byref(d), None, 0, _lib.ptr(blob), blob.numel(),
-                                           C.byref(h))
+            layers, nl, keep = (None, 0, None) if from_blob or on_device else self._layer_params()
+            if bn:
+                rc = lib.eyoc_model_create_in(_lib.ctx(device.index), C.byref(d), layers, nl, _lib.ptr(blob), blob.numel(), bn, C.byref(h))
             else:
-                layers, nl, keep = self._layer_params()
-                rc = lib.eyoc_model_create(_lib.ctx(device.index), C.byref(d), layers, nl, _lib.ptr(blob),
-                                           blob.numel(), C.byref(h))
+                rc = lib.eyoc_model_create(_lib.ctx(device.index), C.byref(d), layers, nl, _lib.ptr(blob), blob.numel(), C.byref(h))
+            del keep
         _lib.check(rc, "eyoc_model_create")
         self._handle, self._blob, self._packed_device = h, blob, device
         self._packed_version = None if from_blob else self._weights_version()
@@ -362,9 +391,9 @@ class ResUNet2(nn.Module):
             # training mode: batch statistics + autograd (lib/trainer.py:1655-1676), layer by layer
             from .train import forward_layers
             return forward_layers(self, x)
-        if self.instance_norm:
-            # no packed plan: the layer-by-layer forward under the caller's grad mode (fp32 MFMA convolutions, the stage norms as
-            # running-statistics affines, the block norms through eyoc_in_forward)
+        if not self._runs_packed():
+            # no packed plan (or a gradient may be asked for): the layer-by-layer forward under the caller's grad mode (fp32 MFMA
+            # convolutions, the stage norms as running-statistics affines, the block norms through eyoc_in_forward)
             from .train import forward_layers
             out = forward_layers(self, x)
             if rows is not None:
@@ -567,7 +596,8 @@ class ResUNetBN2E(ResUNet2):
 
 class ResUNetIN2(ResUNet2):
     """model/resunet.py:229-232: batch norm behind the stage convolutions, ``MinkowskiInstanceNorm`` inside every residual block
-    (model/residual_block.py:60-61).  No packed eval plan: ``model.eval()(x)`` runs layer by layer."""
+    (model/residual_block.py:60-61).  ``model.eval()(x)`` runs layer by layer unless ``model.packed_in = True`` opts into the packed
+    plan (every block norm one layer of it, on fp32 or split16 rows; no backward, so a forward that may need one stays layer by layer)."""
     NORM_TYPE = 'BN'
     BLOCK_NORM_TYPE = 'IN'
 

@@ -464,7 +464,7 @@ def ema_sync(labeler, model, decay: float, debias: float, full_sync: bool = Fals
             new = (decay * torch.cat([l.reshape(-1) for l in lg]) + (1 - decay) * torch.cat([m.reshape(-1) for m in mg])) / debias
             parts = new.to(dt).split([l.numel() for l in lg])              # (float -> int64 truncates, as ``copy_`` does)
             torch._foreach_copy_(lg, [p.view(l.shape) for p, l in zip(parts, lg)])
-    if getattr(labeler, "instance_norm", False):          # no packed plan to refresh (ResUNetIN2 family)
+    if getattr(labeler, "instance_norm", False) and not getattr(labeler, "packed_in", False):   # no packed plan to refresh (ResUNetIN2 family, not opted in)
         return None
     if labeler._handle is None:
         return labeler.pack()

@@ -405,6 +405,21 @@ int eyoc_model_pack_host(const eyoc_model_desc* desc, const eyoc_layer_params* l
 int eyoc_model_create(eyoc_ctx* ctx, const eyoc_model_desc* desc, const eyoc_layer_params* layers,
                       int n_layers, float* blob_dev, size_t blob_floats, eyoc_model** out);
 int eyoc_model_destroy(eyoc_model* model);
+/* The ResUNetIN2 family (model/resunet.py:229-251: batch norm behind the stage convolutions, MinkowskiInstanceNorm inside every
+ * residual block, model/residual_block.py:60-61) as a packed plan; additive to EYOC_VERSION 111, the descriptor is unchanged.  The
+ * three calls are their siblings above plus `block_norm`: 0 = batch norm inside the blocks (exactly the sibling), 1 = instance norm.
+ * With 1 every "block<i>.norm1" / ".norm2" entry of `layers` carries bn_weight / bn_bias (weight, bias [c]) and NULL bn_mean / bn_var
+ * (anything else is refused, naming the layer), and the plan holds two layers per block convolution: the convolution with nothing
+ * folded in (packed with scale 1, shift 0, in both the fp32 and the split16 packing) and the instance norm behind it, which keeps its
+ * weight and its bias in the blob (pad64(c) floats each) and carries the block's ReLU / residual.  eps = 1e-8 (model/common.py:7-8).
+ * The stage convolutions keep their folded batch norm.  eyoc_model_forward then runs eyoc_in_forward's arithmetic per norm on the
+ * plan's own rows (fp32 or split16), over instance plans it builds once per maps object without a read-back; eyoc_model_forward_rows
+ * computes the full output and takes its rows (an instance norm needs every row).  expanded = 1 is refused. */
+size_t eyoc_model_blob_floats_in(const eyoc_model_desc* desc, int block_norm);
+int eyoc_model_pack_host_in(const eyoc_model_desc* desc, const eyoc_layer_params* layers, int n_layers,
+                            float* blob_host, size_t blob_floats, int block_norm);
+int eyoc_model_create_in(eyoc_ctx* ctx, const eyoc_model_desc* desc, const eyoc_layer_params* layers,
+                         int n_layers, float* blob_dev, size_t blob_floats, int block_norm, eyoc_model** out);
 /* Re-pack on the device (additive to EYOC_VERSION 111): folds and packs `layers` - the same struct and the same name matching as
  * eyoc_model_create, but EVERY pointer is a device pointer to contiguous fp32 on the model's device - into the model's existing
  * blob, in place, on `stream`.  The blob afterwards is byte for byte what eyoc_model_pack_host writes for the same parameters
@@ -710,6 +725,13 @@ size_t eyoc_in_workspace_bytes(int n, int c, int n_inst);
 int eyoc_in_forward(eyoc_ctx* ctx, const float* x_dev, int n, int c, int ld_x, const void* plan_dev, int n_inst, const float* weight_dev,
                     const float* bias_dev, float eps, int relu, const float* residual_dev /* or NULL */, int ld_res, float* y_dev, int ld_y,
                     float* stats_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* eyoc_in_forward on SPLIT16 rows (the packed plan's second row format: per 32 channels 32 fp16 hi halves, then 32 fp16 lo halves, the
+ * same 4 bytes per channel): x, residual and y are such rows, c and every leading dimension multiples of 32.  The result is, bit for
+ * bit, the SPLIT16 encoding of what eyoc_in_forward gives on the decoded rows (the kernels are the same templates); stats as there.
+ * range_dev (or NULL): the four range-guard words of eyoc_model_range_snapshot - words 0 and 3 are raised when a stored |y| reaches 6e4. */
+int eyoc_in_forward_split16(eyoc_ctx* ctx, const float* x_dev, int n, int c, int ld_x, const void* plan_dev, int n_inst, const float* weight_dev,
+                            const float* bias_dev, float eps, int relu, const float* residual_dev /* or NULL */, int ld_res, float* y_dev, int ld_y,
+                            float* stats_dev, uint32_t* range_dev /* or NULL */, void* workspace_dev, size_t workspace_bytes, void* stream);
 int eyoc_in_backward(eyoc_ctx* ctx, const float* x_dev, int ld_x, const float* y_dev /* or NULL */, int ld_y, const float* dy_dev, int ld_dy,
                      int n, int c, const void* plan_dev, int n_inst, const float* weight_dev, const float* stats_dev, float eps,
                      float* dx_dev, int ld_dx, float* dres_dev /* or NULL */, int ld_dres, float* dweight_dev, float* dbias_dev,
