@@ -26,5 +26,6 @@ from .validate import (valid_metrics_batched, decode_valid_records, ValidMeters,
 from .autograd import sparse_conv, contrastive_hardest_negative_loss  # noqa: F401,E402
 from .loss import hardest_contrastive_loss, triplet_loss, hardest_triplet_loss  # noqa: F401,E402
 from .loss import contrastive_loss, generate_rand_negative_pairs  # noqa: F401,E402
+from .draws import DeviceDraws  # noqa: F401,E402
 from .matches import (matching_indices_batched, get_matching_indices, compute_overlap_ratio, overlap_ratio_batched)  # noqa: F401,E402
 from .trainbatch import TrainBatch, draw_augmentation  # noqa: F401,E402

@@ -292,6 +292,9 @@ PROTOTYPES = {
     "eyoc_closs_workspace_layout": (_i, [_i, _i, _i, C.POINTER(ClossLayout)]),
     "eyoc_closs_forward": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, C.c_float, _vp, _vp, _sz, _vp]),
     "eyoc_closs_backward": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, C.c_float, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "eyoc_draw_workspace_bytes": (_sz, [_i]),
+    "eyoc_draw_subsets": (_i, [_vp, C.c_uint64, C.c_uint64, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _vp, _vp, _sz, _vp]),
+    "eyoc_draw_pairs": (_i, [_vp, C.c_uint64, C.c_uint64, _i, _i, _i, _i, _vp, _vp]),
 }
 
 

@@ -6,6 +6,11 @@ the device (the label stages produce them there), the three host draws go up in 
 number of launches is fixed (5 + 4) and the gradient rows are summed in a fixed order without floating-point atomics - their bytes do
 not change from run to run.  The existing function stays; this route is opt-in.
 
+Every loss here takes ``rng=DeviceDraws(seed)`` (eyoc_amd/draws.py) beside ``None``, a ``RandomState`` or a ``Generator``: the draws are
+then made on the device by a counter-based generator, in the reference's order of slots, and handed straight to the same autograd
+nodes - no host permutation, no staging buffer, one ``subsets`` or one ``pairs`` call per loss call.  With any other ``rng`` nothing
+changes.
+
 ``triplet_loss`` / ``hardest_triplet_loss`` (second half of the file) are the losses of the reference's other two trainers
 (lib/trainer.py:567-621, :701-782) on ``eyoc_triplet_forward`` / ``eyoc_triplet_backward``, built the same way.
 
@@ -20,6 +25,7 @@ import torch
 
 from . import _lib
 from .autograd import _draw_loss_samples
+from .draws import DeviceDraws
 
 BAD_INDEX, MASKED, VALID = 1, 1, 2        # record status bit; per-direction flag bits (include/eyoc_hip.h)
 _RECORD_FLOATS = C.sizeof(_lib.HclossRecord) // 4
@@ -128,6 +134,12 @@ def hardest_contrastive_loss(F0, F1, positive_pairs, num_pos=5192, num_hn_sample
         pairs = torch.from_numpy(np.ascontiguousarray(np.asarray(positive_pairs), dtype=np.int64))
     pairs = pairs.reshape(-1, 2).to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
     n0, n1, n_pairs = F0.shape[0], F1.shape[0], pairs.shape[0]
+    if isinstance(rng, DeviceDraws):
+        # slots in the reference's order: candidates of cloud 0, of cloud 1, the positive sub-sample (an empty slot when all are kept)
+        sel0, sel1, used = rng.subsets([(n0, min(n0, num_hn_samples)), (n1, min(n1, num_hn_samples)),
+                                        (n_pairs, num_pos) if n_pairs > num_pos else (0, 0)], device=dev)
+        return _HardestContrastive.apply(F0.contiguous(), F1.contiguous(), pairs, used if n_pairs > num_pos else None, sel0, sel1,
+                                         float(pos_thresh), float(neg_thresh))
     cand0, cand1, keep = _draw_loss_samples(np.random if rng is None else rng, n0, n1, n_pairs, num_hn_samples, num_pos)
     s0, s1, n_keep = len(cand0), len(cand1), 0 if keep is None else len(keep)
     # the draws: one pinned staging buffer, one asynchronous copy
@@ -272,6 +284,16 @@ def _triplet(F0, F1, positive_pairs, num_pos, num_hn_samples, num_rand_triplet, 
         pairs = torch.from_numpy(np.ascontiguousarray(np.asarray(positive_pairs), dtype=np.int64))
     pairs = pairs.reshape(-1, 2).to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
     n0, n1, n_pairs = F0.shape[0], F1.shape[0], pairs.shape[0]
+    if isinstance(rng, DeviceDraws):
+        check_triplet_lengths(n_pairs, n1, num_rand_triplet)           # before anything is drawn or enqueued, as on the host route
+        hn = 0 if num_hn_samples is None else num_hn_samples
+        # slots in the reference's order (draw_triplet_samples); a draw the variant does not make keeps its slot, empty
+        sel0, sel1, used, rand_idx, negatives = rng.subsets([(n0, min(n0, hn)), (n1, min(n1, hn)),
+                                                             (n_pairs, num_pos) if n_pairs > num_pos else (0, 0),
+                                                             (n_pairs, min(n_pairs, num_rand_triplet)), (n1, min(n1, num_rand_triplet))],
+                                                            device=dev)
+        return _Triplet.apply(F0.contiguous(), F1.contiguous(), pairs, used if n_pairs > num_pos else None, sel0, sel1, rand_idx, negatives,
+                              float(neg_thresh))
     sel0, sel1, used, rand_idx, negatives = draw_triplet_samples(np.random if rng is None else rng, n0, n1, n_pairs, num_hn_samples,
                                                                  num_pos, num_rand_triplet)
     parts = [sel0, sel1, rand_idx, negatives] + ([] if used is None else [used])
@@ -411,6 +433,13 @@ def _upload_negatives(neg, dev):
     return stage.to(dev, non_blocking=True)
 
 
+def _candidate_negatives(rng, n_pairs, n0, n1, n_neg, dev):
+    """The candidate negatives on the device: drawn there by a ``DeviceDraws`` (one launch), else the reference's host draw, uploaded."""
+    if isinstance(rng, DeviceDraws):
+        return rng.pairs(int(n_neg) if n_neg >= 1 else 2 * int(n_pairs), n0, n1, device=dev)
+    return _upload_negatives(draw_negative_pairs(np.random if rng is None else rng, n_pairs, n0, n1, n_neg), dev)
+
+
 def contrastive_loss(F0, F1, positive_pairs, neg_thresh=1.4, n_neg=0, rng=None):
     """``ContrastiveLossTrainer``'s loss (lib/trainer.py:262-286 with the negatives of :201-221) -> ``(pos_loss, neg_loss)``, 0-dim
     tensors with grad: ``pos_loss`` the mean squared distance over ALL positives, ``neg_loss`` the mean of
@@ -423,8 +452,8 @@ def contrastive_loss(F0, F1, positive_pairs, neg_thresh=1.4, n_neg=0, rng=None):
     NaN (no positive: both values).  No double backward; ``c`` in {16, 32, 64}."""
     dev = F0.device
     pairs = _device_pairs(positive_pairs, dev)
-    neg = draw_negative_pairs(np.random if rng is None else rng, pairs.shape[0], F0.shape[0], F1.shape[0], n_neg)
-    return _Contrastive.apply(F0.contiguous(), F1.contiguous(), pairs, _upload_negatives(neg, dev), float(neg_thresh))
+    neg = _candidate_negatives(rng, pairs.shape[0], F0.shape[0], F1.shape[0], n_neg, dev)
+    return _Contrastive.apply(F0.contiguous(), F1.contiguous(), pairs, neg, float(neg_thresh))
 
 
 def generate_rand_negative_pairs(positive_pairs, hash_seed, N0, N1, N_neg=0, rng=None):
@@ -437,8 +466,7 @@ def generate_rand_negative_pairs(positive_pairs, hash_seed, N0, N1, N_neg=0, rng
     on_dev = isinstance(positive_pairs, torch.Tensor) and positive_pairs.is_cuda
     dev = positive_pairs.device if on_dev else torch.device("cuda", torch.cuda.current_device())
     pairs = _device_pairs(positive_pairs, dev)
-    host = draw_negative_pairs(np.random if rng is None else rng, pairs.shape[0], int(N0), int(N1), N_neg)
-    neg = _upload_negatives(host, dev)
+    neg = _candidate_negatives(rng, pairs.shape[0], int(N0), int(N1), N_neg, dev)
     Z0 = torch.zeros((int(N0), 16), dtype=torch.float32, device=dev)
     Z1 = torch.zeros((int(N1), 16), dtype=torch.float32, device=dev)
     _, ws = contrastive_raw_forward(Z0, Z1, pairs, neg, 0.0)

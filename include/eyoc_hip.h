@@ -1256,6 +1256,52 @@ int eyoc_closs_backward(eyoc_ctx* ctx, const float* F0_dev, int n0, const float*
                         const float* g_neg_dev, float* dF0_dev, float* dF1_dev, void* workspace_dev, size_t workspace_bytes,
                         void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * device-side draws for the training losses: a counter-based generator and the two draw primitives of the reference's trainers.
+ * Added after 111 without a bump, additive only.  The index arrays these calls write are what eyoc_hcloss_*, eyoc_triplet_* and
+ * eyoc_closs_* take as sel0 / sel1 / used / rand_idx / negatives / neg.
+ *
+ * Generator: Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11) - ten rounds, multipliers 0xD2511F53 (word 0) and 0xCD9E8D57 (word 2),
+ * Weyl increments 0x9E3779B9 and 0xBB67AE85 of the two key words.  Key and counter of the 128-bit block of element `index` of draw
+ * `slot` of call `call` under `seed`:
+ *   key     k0 = seed[31:0]    k1 = seed[63:32]
+ *   counter c0 = index[31:0]   c1 = index[63:32]   c2 = call[31:0]   c3 = call[59:32] | slot << 28
+ * call < 2^60 and slot < 8 (anything else: EYOC_ERR_INVALID).  The block's four output words are x0 .. x3.  Every number is a pure
+ * function of (seed, call, slot, index): no device state, no atomics, the same on any grid, stream, device or host - a host program
+ * that evaluates Philox4x32-10 on this layout gets the same bits.
+ *
+ * eyoc_draw_subsets: np.random.choice(n, k, replace=False) as a distribution (lib/trainer.py:445-449, :715-719, :754-760, :946-955):
+ * a uniformly random k-subset of [0, n) in uniformly random order, for up to EYOC_DRAW_MAX_SLOTS independent draws in one call.  The
+ * position in n[] / k[] IS the slot number.  Element i of slot s gets the 64-bit key
+ *   (s << 61) | ((x1 << 32 | x0) >> 3)            x0, x1 of the block (seed, call, s, i)
+ * all keys of the call are ordered with ONE stable radix sort (rocPRIM, the wrapper of the map build, all 64 bits) together with
+ * their i, and the first k[s] values of slot s's run are its draw, written as int64; k == n is a full permutation.  The outputs lie back
+ * to back in out_idx in slot order (slot s starts at k[0] + ... + k[s - 1]).  Two elements of one slot whose 61 generator bits collide
+ * are ordered by i (the sort is stable): the outcome is deterministic, and the departure from a uniform permutation is bounded by the
+ * collision probability, n^2 / 2^62 - below 1e-8 for a cloud of 2^17 rows.  A slot's result depends on (seed, call, s, n[s], k[s]) only,
+ * not on which other slots share the call.  n[] and k[] are HOST arrays of n_slots entries.
+ *   k > n, a negative size, n_slots outside [0, EYOC_DRAW_MAX_SLOTS], call >= 2^60, more than 2^31 - 1 elements in one call:
+ *   EYOC_ERR_INVALID before any launch, nothing written.  A slot with k == 0 or n == 0 is legal, puts no keys into the sort and writes
+ *   nothing; a call whose slots are all empty launches nothing (out_idx and the workspace may be NULL then).
+ * Workspace: eyoc_draw_workspace_bytes(total_n), total_n = the sum of n[s] over the slots with k[s] > 0 (0 for total_n <= 0); caller-owned,
+ * 256-byte aligned, needed until the call's kernels have run; a smaller one is EYOC_ERR_WORKSPACE before any launch.
+ * Launches: one that writes keys, the rocPRIM sort (which chooses its passes by the length), one that writes out_idx.
+ *
+ * eyoc_draw_pairs: floor(rand(N, 2) * [n0, n1]) as a distribution (lib/trainer.py:212-218): out int64 [n_rows][2], row-major, in one
+ * launch.  Row r: out[r][0] = mulhi64(x1 << 32 | x0, n0), out[r][1] = mulhi64(x3 << 32 | x2, n1) with x0 .. x3 of the block (seed,
+ * call, slot, r) and mulhi64(x, n) = floor(x n / 2^64), always < n.  The probability of every index differs from 1 / n by less than
+ * 2^-64 (a relative departure of n / 2^64 < 2^-33 for n < 2^31); no floating point anywhere.  n_rows == 0 launches
+ * nothing; a negative size, slot outside [0, 8), call >= 2^60, or n_rows > 0 with n0 == 0 or n1 == 0: EYOC_ERR_INVALID before any launch.
+ *
+ * Both: stream-ordered, no synchronisation, no allocation, no environment variable, no atomics, nothing read back.
+ * --------------------------------------------------------------------------------------------- */
+#define EYOC_DRAW_MAX_SLOTS 8
+
+size_t eyoc_draw_workspace_bytes(int total_n);
+int eyoc_draw_subsets(eyoc_ctx* ctx, uint64_t seed, uint64_t call, int n_slots, const int* n, const int* k, int64_t* out_idx_dev,
+                      void* workspace_dev, size_t workspace_bytes, void* stream);
+int eyoc_draw_pairs(eyoc_ctx* ctx, uint64_t seed, uint64_t call, int slot, int n_rows, int n0, int n1, int64_t* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

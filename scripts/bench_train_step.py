@@ -20,8 +20,14 @@ d, j = cKDTree(p["xyz1"].astype(np.float64)).query(p["xyz0"].astype(np.float64) 
 i = np.nonzero(d < 0.3)[0]
 pos = torch.from_numpy(np.stack([i, j[i]], 1))
 if os.environ.get("LOSS_ROUTE", "existing") == "device":      # the device-side loss (eyoc_amd/loss.py) on device-resident positives
-    from eyoc_amd.loss import hardest_contrastive_loss as contrastive_hardest_negative_loss
+    from eyoc_amd.loss import hardest_contrastive_loss
     pos = pos.to(dev)
+    # LOSS_DRAWS=device: the three draws on the device too (eyoc_amd/draws.py) instead of np.random on the host
+    draws = eyoc_amd.DeviceDraws(0) if os.environ.get("LOSS_DRAWS", "host") == "device" else None
+    def contrastive_hardest_negative_loss(F0, F1, pp, num_pos, num_hn_samples):
+        return hardest_contrastive_loss(F0, F1, pp, num_pos=num_pos, num_hn_samples=num_hn_samples, rng=draws)
+elif os.environ.get("LOSS_DRAWS", "host") == "device":
+    raise SystemExit("LOSS_DRAWS=device needs LOSS_ROUTE=device")
 model = eyoc_amd.load_model("ResUNetBN2C")(1, 32, bn_momentum=0.05, conv1_kernel_size=5, normalize_feature=True).to(dev).train()
 opt = torch.optim.SGD(model.parameters(), lr=0.1, momentum=0.8, weight_decay=1e-4)
 coords = torch.from_numpy(syn.batch_coords([p["coords0"], p["coords1"]])).to(dev)

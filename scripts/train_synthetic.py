@@ -17,19 +17,26 @@ from eyoc_amd import synthetic as syn  # noqa: E402
 from eyoc_amd.autograd import contrastive_hardest_negative_loss  # noqa: E402
 from eyoc_amd.harness import DeviceBatch, RegistrationConfig, RegistrationPipeline  # noqa: E402
 
+# LOSS_DRAWS=device (with a LOSS_ROUTE of eyoc_amd/loss.py): the losses' draws come from a seeded generator on the device
+# (eyoc_amd/draws.py) instead of np.random; a step's draws are then a function of (seed 0, the step's call number) alone
+DRAWS = eyoc_amd.DeviceDraws(0) if os.environ.get("LOSS_DRAWS", "host") == "device" else None
+if DRAWS is not None and os.environ.get("LOSS_ROUTE", "existing") == "existing":
+    raise SystemExit("LOSS_DRAWS=device needs LOSS_ROUTE=device, contrastive, triplet or hardest-triplet")
 if os.environ.get("LOSS_ROUTE", "existing") == "device":      # the device-side loss (eyoc_amd/loss.py) instead of the torch-op route
-    from eyoc_amd.loss import hardest_contrastive_loss as contrastive_hardest_negative_loss  # noqa: E402,F811
+    def contrastive_hardest_negative_loss(F0, F1, pp, num_pos, num_hn_samples):  # noqa: F811
+        from eyoc_amd.loss import hardest_contrastive_loss
+        return hardest_contrastive_loss(F0, F1, pp, num_pos=num_pos, num_hn_samples=num_hn_samples, rng=DRAWS)
 elif os.environ.get("LOSS_ROUTE") == "contrastive":           # the base trainer's loss: all positives, random negatives (neg_weight 1)
     def contrastive_hardest_negative_loss(F0, F1, pp, num_pos, num_hn_samples):  # noqa: F811
         from eyoc_amd.loss import contrastive_loss
-        return contrastive_loss(F0, F1, pp)
+        return contrastive_loss(F0, F1, pp, rng=DRAWS)
 elif os.environ.get("LOSS_ROUTE") in ("triplet", "hardest-triplet"):   # the triplet trainers' losses; the "neg" column stays zero
     def contrastive_hardest_negative_loss(F0, F1, pp, num_pos, num_hn_samples):  # noqa: F811
         from eyoc_amd.loss import hardest_triplet_loss, triplet_loss
         if os.environ["LOSS_ROUTE"] == "triplet":
-            loss = triplet_loss(F0, F1, pp, num_pos=num_pos, num_rand_triplet=1024)[0]
+            loss = triplet_loss(F0, F1, pp, num_pos=num_pos, num_rand_triplet=1024, rng=DRAWS)[0]
         else:
-            loss = hardest_triplet_loss(F0, F1, pp, num_pos=num_pos, num_hn_samples=num_hn_samples, num_rand_triplet=1024)[0]
+            loss = hardest_triplet_loss(F0, F1, pp, num_pos=num_pos, num_hn_samples=num_hn_samples, num_rand_triplet=1024, rng=DRAWS)[0]
         return loss, torch.zeros_like(loss)
 ITERS = int(os.environ.get("ITERS", "400"))
 N_TRAIN = int(os.environ.get("N_TRAIN", "24"))
