@@ -77,6 +77,8 @@ struct eyoc_ctx {
   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: remembered per ctx, not per process
   bool ransac_attr_set = false, sc2_attr_set = false;
   bool up_attr_set[2] = {false, false};   // spconv_up_kernel<64> / <32>
+  bool conv1p_attr_set = false;           // conv1_bfp_kernel
+  int n_cus = 0;                          // compute units of `device` (0: not asked yet; the persistent first convolution's grid)
   // Z-order sort of eyoc_maps_build: how many bits the Morton key needs is SPECULATED from the previous build of this ctx
   // (coordinates within +-2^zorder_kbits, batch index below 2^zorder_bbits); a build whose rows do not fit redoes its sort with
   // the full 18 + 10 bits.  The permutation is the same either way (the bias is order-preserving); only the number of radix passes differs.
@@ -105,7 +107,8 @@ struct eyoc_ctx {
     int st128_wide = 1;                // (diagnostics, eyoc_spconv_select_down_kernel(2 / 3)): 128-row strided tiles of >= 128-channel layers as 128-channel workgroups
     int down_kernel = 1;               // eyoc_spconv_select_down_kernel: 1 staged on 128-row tiles (Z-ordered maps of >= upc_min_rows rows), 0 the gathering kernel
     int upc_min_rows = 1 << 17;        // eyoc_spconv_upc_min_rows: maps with fewer level-0 rows keep spconv_up.hip under mode 2
-    int conv1_kernel = 1;              // eyoc_spconv_select_conv1_kernel: 1 conv1_bf_kernel (block feature vectors), 0 conv1_mfma_kernel, 2 the exact-fp32 octree walker
+    int conv1_kernel = 3;              // eyoc_spconv_select_conv1_kernel: 3 conv1_bfp_kernel (block feature vectors, persistent workgroups), 1 conv1_bf_kernel (the same products from one workgroup per tile, bit-identical; kept for A/B), 0 conv1_mfma_kernel, 2 the exact-fp32 octree walker
+    int conv1_workgroups = 0;          // eyoc_spconv_conv1_workgroups: grid of conv1_bfp_kernel, 0 = one workgroup per CU (tests make one workgroup walk many tiles)
     int st_group = 1;                  // eyoc_spconv_st_group_rows: the staged kernel's tiles sorted by neighbour pattern
     int st_variant = 1;                // eyoc_spconv_select_st_kernel
     int st_split_below = 1024;         // eyoc_spconv_st_split_below

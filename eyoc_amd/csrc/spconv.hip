@@ -1104,6 +1104,264 @@ __global__ __launch_bounds__(256, 2) void conv1_bf_kernel(Conv1Args a) {
   if (a.out_split) split16_report(a.range, mx);
 }
 
+// ---- the same first convolution from PERSISTENT workgroups (eyoc_spconv_select_conv1_kernel(3)).  conv1_bf_kernel's workgroups live for
+// one tile (~600 fine rows) and each of them rebuilds ktab, re-reads and re-splits the kernel, gathers two class weight matrices and
+// sits through three dependent rounds of global loads before its first MFMA.  None of the weight work depends on the tile.  Here one
+// 512-thread workgroup per CU walks tiles blockIdx.x, blockIdx.x + gridDim.x, ... (static order, no atomics; every output row still
+// belongs to exactly one wave); wave q IS parity class q and keeps the class's [224 x 32] hi / lo weight fragments in 112 registers
+// for its whole life; and the tile record lives in one of TWO LDS buffers: while the waves multiply a tile out of one, the next
+// tile's loads are in flight in registers - its row numbers U were asked for a whole tile earlier, its child links go out at the top
+// of the tile, its child features between the two halves of the wave's chunks - and at the end of the tile they are converted into
+// the other buffer, where the eight ballots of the next tile's class compaction run as well (two barriers per tile).  All loads are
+// unconditional on clamped indices (a load inside a branch is waited for on the spot), past the last tile they re-read it.
+// Same products in the same order as conv1_bf_kernel (k-steps 0..6, hh / hl / lh), same slot lookup, same epilogue: bit-identical
+// output rows and range-guard words (tests/test_gpu_conv1_persistent.py).
+struct alignas(16) Conv1Tile {
+  static constexpr int NSLOT = ST_NPASS * ST_UMAX + 1;
+  _Float16 cfh[NSLOT][8], cfl[NSLOT][8];       // block vectors of the staged level-1 rows; slot NSLOT - 1 = zeros
+  unsigned short ent[27 * 64 * 4];             // pass-0 rulebook entries
+  unsigned short lrow[8][ST_TILE];             // fine rows of class q (minus f0)
+  unsigned char lpar[8][ST_TILE];              // ... and their parents (local index)
+  unsigned char inv[ST_TILE];
+  int ctot[8];
+  int f0, pad[3];
+};
+struct alignas(16) Conv1Shared {
+  Conv1Tile tile[2];
+  _Float16 w5h[128][32], w5l[128][32];         // the kernel, scaled and split; row 127 = zeros (read once, at kernel start)
+  signed char ktab[8][216];
+  float bias[32];
+  int ccnt[8][4], f0h[2], pad[2];
+};
+static_assert(sizeof(Conv1Shared) <= 160 * 1024, "conv1_bfp_kernel: one workgroup per CU, within its LDS");
+extern __shared__ __attribute__((aligned(16))) unsigned char conv1p_smem[];
+
+__global__ __launch_bounds__(512, 1) void conv1_bfp_kernel(Conv1Args a, int n_tiles) {
+  constexpr int COUT = 32, NT = COUT / 16, NS7 = 7;
+  constexpr int NSLOT = Conv1Tile::NSLOT, ZSLOT = NSLOT - 1;
+  constexpr int NS = (NSLOT + 511) / 512;                // staged rows per thread
+  constexpr int NENT = 27 * 64 * 4 * 2 / 16;             // 16-byte pieces of a tile's pass-0 entries
+  Conv1Shared& S = *reinterpret_cast<Conv1Shared*>(conv1p_smem);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = lane & 15, g = lane >> 4;
+  const int K = a.ks * a.ks * a.ks, r = a.ks / 2;
+  const int G = gridDim.x;
+  const int4* __restrict__ child4 = reinterpret_cast<const int4*>(a.children);
+  const float* __restrict__ fin = a.in;
+  // row numbers of the first tile's stage: in flight under the weight work
+  int tn = blockIdx.x;                                   // the tile being staged (< n_tiles: the grid is at most n_tiles)
+  int nu_n, un[NS];
+  {
+    const unsigned char* lr = a.local1 + (size_t)tn * ST_LR_BYTES;
+    nu_n = *reinterpret_cast<const int*>(lr);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) un[i] = reinterpret_cast<const int*>(lr + 16)[min(tid + 512 * i, ST_UCAP - 1)];
+  }
+  for (int e = tid; e < 8 * 216; e += 512) {
+    const int cls = e / 216, kc = (e % 216) / 8, cs = e % 8;
+    const int dx = 2 * (kc % 3 - 1) + (cs & 1) - (cls & 1), dy = 2 * ((kc / 3) % 3 - 1) + ((cs >> 1) & 1) - ((cls >> 1) & 1),
+              dz = 2 * (kc / 9 - 1) + (cs >> 2) - (cls >> 2);
+    const bool in = dx >= -r && dx <= r && dy >= -r && dy <= r && dz >= -r && dz <= r;
+    S.ktab[cls][kc * 8 + cs] = (signed char)(in ? (dx + r) + a.ks * (dy + r) + a.ks * a.ks * (dz + r) : 127);
+  }
+  {   // the kernel: W * 2^sh split into fp16 halves (2^sh lifts the layer's largest weight into [256, 512))
+    const float wsc = a.wscale ? a.wscale[0] : 256.0f;
+    for (int e = tid; e < 128 * COUT; e += 512) {
+      const int k = e / COUT;
+      const float w = k < K ? a.w[e] * wsc : 0.0f;
+      const _Float16 h = (_Float16)w;
+      (&S.w5h[0][0])[e] = h;
+      (&S.w5l[0][0])[e] = (_Float16)(w - (float)h);
+    }
+  }
+  if (tid < 32) {                                        // the zero vector of both buffers: written once, no stage touches it
+    const int b = tid >> 4, e = tid & 15;
+    (e < 8 ? S.tile[b].cfh[ZSLOT][e] : S.tile[b].cfl[ZSLOT][e - 8]) = (_Float16)0.f;
+  }
+  if (tid >= 64 && tid < 64 + COUT) S.bias[tid - 64] = a.bias[tid - 64];
+  __syncthreads();
+  // this wave's class = its index; lane (g, j) of k-step t holds W[window position of (block 4 t + g, child i)][channel 16 tt + j], i = 0..7
+  half8_t wh[NS7][NT], wl[NS7][NT];
+#pragma unroll
+  for (int t = 0; t < NS7; ++t) {
+    const int kc = 4 * t + g;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int kp = kc < 27 ? (int)S.ktab[wave][kc * 8 + i] : 127;
+#pragma unroll
+      for (int tt = 0; tt < NT; ++tt) {
+        wh[t][tt][i] = S.w5h[kp][16 * tt + j];
+        wl[t][tt][i] = S.w5l[kp][16 * tt + j];
+      }
+    }
+  }
+  const float iwsc = a.wscale ? a.wscale[1] : 1.0f / 256.0f;
+  float mx = 0.f;
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  int tc = -1, nu_c = 0;                                 // the tile being multiplied (none yet) and its distinct rows
+  for (int it = 0;; ++it) {
+    const Conv1Tile& B = S.tile[it & 1];                 // multiplied now (filled during the previous tile)
+    Conv1Tile& N = S.tile[(it & 1) ^ 1];                 // filled now (last read during the previous tile)
+    // ---- loads for tile tn.  Round 2: the child links of its staged rows (their numbers arrived during the previous tile)
+    const unsigned char* lrn = a.local1 + (size_t)min(tn, n_tiles - 1) * ST_LR_BYTES;
+    int4 c0[NS], c1[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const int u = tid + 512 * i < nu_n ? min(max(un[i], 0), a.nc - 1) : 0;
+      c0[i] = child4[2 * (size_t)u];
+      c1[i] = child4[2 * (size_t)u + 1];
+    }
+    // ... its pass-0 entries and its inverse map
+    const uint4* esrc = reinterpret_cast<const uint4*>(lrn + ST_LOC_OFF);
+    const uint4 en0 = esrc[tid], en1 = esrc[min(tid + 512, NENT - 1)];
+    const unsigned int invw = reinterpret_cast<const unsigned int*>(lrn + ST_INV_OFF)[lane];
+    // ---- tile tc: this wave's class, 16 rows at a time
+    const int nq = tc >= 0 ? B.ctot[wave] : 0;
+    const int f0 = B.f0;
+    const int n_pass = nu_c > ST_UMAX ? 2 : 1;
+    const unsigned short* __restrict__ loc = reinterpret_cast<const unsigned short*>(a.local1 + (size_t)max(tc, 0) * ST_LR_BYTES + ST_LOC_OFF);
+    auto chunk = [&](const int c0r) __attribute__((always_inline)) {
+      const int idx = c0r + j;
+      const bool ok = idx < nq;
+      const int pl = B.lpar[wave][ok ? idx : 0];
+      const int o = f0 + (int)B.lrow[wave][ok ? idx : 0];
+      const int sl = B.inv[pl];
+      const int ew = (sl >> 6) * 16 + (sl & 15), ec = (sl >> 4) & 3;
+      f32x4 acc[NT];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      // the seven slots first (independent LDS reads; conv1_bf_kernel's lookup, with the rare second-pass branch made wave-uniform
+      // and taken once per chunk instead of splitting every k-step off behind its own dependent read)
+      int slot[NS7];
+#pragma unroll
+      for (int t = 0; t < NS7; ++t) {
+        const int kc = min(4 * t + g, 26);
+        const int e0 = B.ent[(kc * 64 + ew) * 4 + ec] >> 6;                             // entry = 64 l + swizzle
+        slot[t] = 4 * t + g < 27 ? e0 : -1;                                             // -1: no such block; ST_UMAX: not in pass 0
+      }
+      if (n_pass > 1) {                                                                 // rare: neighbours may sit in the second pass
+#pragma unroll
+        for (int t = 0; t < NS7; ++t) {
+          const int e1 = loc[((27 + min(4 * t + g, 26)) * 64 + ew) * 4 + ec] >> 6;
+          slot[t] = slot[t] != ST_UMAX ? slot[t] : e1 != ST_UMAX ? ST_UMAX + e1 : -1;
+        }
+      } else {
+#pragma unroll
+        for (int t = 0; t < NS7; ++t) slot[t] = slot[t] == ST_UMAX ? -1 : slot[t];
+      }
+#pragma unroll
+      for (int t = 0; t < NS7; ++t) {
+        const int sl_t = slot[t] < 0 ? ZSLOT : slot[t];
+        const half8_t vh = *reinterpret_cast<const half8_t*>(&B.cfh[sl_t][0]);
+        const half8_t vl = *reinterpret_cast<const half8_t*>(&B.cfl[sl_t][0]);
+#pragma unroll
+        for (int tt = 0; tt < NT; ++tt) {
+          acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t][tt], vh, acc[tt], 0, 0, 0);
+          acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t][tt], vl, acc[tt], 0, 0, 0);
+          acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[t][tt], vh, acc[tt], 0, 0, 0);
+        }
+      }
+      if (ok) {
+        float* dst = a.out + (size_t)o * a.ld_out;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          const int ch0 = 16 * t + 4 * g;
+          const float4 b4 = *reinterpret_cast<const float4*>(&S.bias[ch0]);
+          const float4 v = make_float4(acc[t][0] * iwsc + b4.x, acc[t][1] * iwsc + b4.y, acc[t][2] * iwsc + b4.z, acc[t][3] * iwsc + b4.w);
+          split16_track(mx, v);
+          if (a.out_split) split16_store4(dst, ch0, v);
+          else *reinterpret_cast<float4*>(dst + ch0) = v;
+        }
+      }
+    };
+    const int nch = (nq + 15) >> 4, nch0 = (nch + 1) >> 1;
+    for (int c = 0; c < nch0; ++c) chunk(16 * c);
+    // ---- the entries and the inverse map go to the other buffer (nothing reads it during this tile), then round 3 for tile tn: the
+    // child features (the links arrived under the first half), half of one of its own parents' child links per thread, and round 1 of
+    // the tile after it
+    reinterpret_cast<uint4*>(N.ent)[tid] = en0;
+    if (tid + 512 < NENT) reinterpret_cast<uint4*>(N.ent)[tid + 512] = en1;
+    if (tid < 64) reinterpret_cast<unsigned int*>(N.inv)[tid] = invw;
+    float f[NS][8];
+    unsigned int vmask = 0;                              // bit 8 i + q: child q of staged row i exists
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const int v[8] = {c0[i].x, c0[i].y, c0[i].z, c0[i].w, c1[i].x, c1[i].y, c1[i].z, c1[i].w};
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        f[i][q] = fin[max(v[q], 0)];
+        vmask |= v[q] >= 0 ? 1u << (8 * i + q) : 0u;                // (the links die here: 24 registers less under the second half)
+      }
+    }
+    const int pl_own = tid & 255, hf = tid >> 8;
+    const int prow = min(tn, n_tiles - 1) * ST_TILE + pl_own;
+    const int4 own = child4[2 * (size_t)min(prow, a.nc - 1) + hf];
+    int nu_2, un2[NS];
+    {
+      const unsigned char* lr2 = a.local1 + (size_t)min(tn + G, n_tiles - 1) * ST_LR_BYTES;
+      nu_2 = *reinterpret_cast<const int*>(lr2);
+#pragma unroll
+      for (int i = 0; i < NS; ++i) un2[i] = reinterpret_cast<const int*>(lr2 + 16)[min(tid + 512 * i, ST_UCAP - 1)];
+    }
+    for (int c = nch0; c < nch; ++c) chunk(16 * c);
+    // ---- tile tn into the other buffer
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const int s = tid + 512 * i;
+      if (s < nu_n) {
+        half8_t h8, l8;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const float x = (vmask >> (8 * i + q)) & 1u ? f[i][q] : 0.f;
+          h8[q] = (_Float16)x;
+          l8[q] = (_Float16)(x - (float)h8[q]);
+        }
+        *reinterpret_cast<half8_t*>(&N.cfh[s][0]) = h8;
+        *reinterpret_cast<half8_t*>(&N.cfl[s][0]) = l8;
+      }
+    }
+    // its fine rows by class: thread (hf, p) holds children 4 hf .. 4 hf + 3 of parent p; wave w counts parents 64 (w & 3) ...
+    int v[4] = {own.x, own.y, own.z, own.w};
+    if (prow >= a.nc) v[0] = v[1] = v[2] = v[3] = -1;
+    if (pl_own == 0) {                                   // the tile's first fine row: the first child of its first parent (Z-order)
+      int m = a.n;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) if (v[q] >= 0 && v[q] < m) m = v[q];
+      S.f0h[hf] = m;
+    }
+    unsigned long long bm[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      bm[q] = __ballot(v[q] >= 0);
+      if (lane == 0) S.ccnt[4 * hf + q][wave & 3] = __popcll(bm[q]);
+    }
+    lds_barrier();
+    const int f0n = min(S.f0h[0], S.f0h[1]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int cls = 4 * hf + q;
+      int base = 0;
+      for (int w = 0; w < (wave & 3); ++w) base += S.ccnt[cls][w];
+      if (v[q] >= 0) {
+        const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(bm[q] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)bm[q], 0u));   // set bits below this lane
+        N.lrow[cls][pos] = (unsigned short)(v[q] - f0n);
+        N.lpar[cls][pos] = (unsigned char)pl_own;
+      }
+    }
+    if (tid < 8) N.ctot[tid] = S.ccnt[tid][0] + S.ccnt[tid][1] + S.ccnt[tid][2] + S.ccnt[tid][3];
+    if (tid == 0) N.f0 = f0n;
+    lds_barrier();
+    tc = tn;
+    nu_c = nu_n;
+    if (tc >= n_tiles) break;
+    tn += G;
+    nu_n = nu_2;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) un[i] = un2[i];
+  }
+  if (a.out_split) split16_report(a.range, mx);
+}
+
 int launch_conv1(const Conv1Args& a, hipStream_t st) {
   EYOC_REQUIRE(a.ks == 1 || a.ks == 3 || a.ks == 5 || a.ks == 7, EYOC_ERR_INVALID, "conv1: kernel size %d", a.ks);
   EYOC_REQUIRE(a.cin >= 1 && a.cin * a.cout <= 8192, EYOC_ERR_INVALID, "conv1: C_in %d x C_out %d too large", a.cin, a.cout);
@@ -1115,6 +1373,25 @@ int launch_conv1(const Conv1Args& a, hipStream_t st) {
     // C_in = 1, 32 output channels, split16 activations downstream (the large-batch path): the MFMA formulation.  Its
     // products carry 22-bit significands like every split16 layer; fp32 consumers keep the exact-fp32 walker
     if (knobs_of(a.ctx).conv1_kernel != 2 && a.cin == 1 && a.cout == 32 && a.out_split && a.ks * a.ks * a.ks < 128 && !a.in_perm) {
+      if (a.local1 && knobs_of(a.ctx).conv1_kernel == 3) {                               // ... from persistent workgroups, one per CU
+        eyoc_ctx* ctx = const_cast<eyoc_ctx*>(a.ctx);
+        int cus = ctx ? ctx->n_cus : 0;
+        if (cus <= 0) {
+          int dev = 0;
+          EYOC_CHECK_HIP(hipGetDevice(&dev));
+          EYOC_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+          EYOC_REQUIRE(cus > 0, EYOC_ERR_INVALID, "conv1: device reports %d compute units", cus);
+          if (ctx) ctx->n_cus = cus;
+        }
+        if (!ctx || !ctx->conv1p_attr_set) {
+          EYOC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_bfp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Conv1Shared)));
+          if (ctx) ctx->conv1p_attr_set = true;
+        }
+        const int n_tiles = cdiv(a.nc, ST_TILE), want = knobs_of(a.ctx).conv1_workgroups > 0 ? knobs_of(a.ctx).conv1_workgroups : cus;
+        hipLaunchKernelGGL(conv1_bfp_kernel, dim3(n_tiles < want ? n_tiles : want), dim3(512), sizeof(Conv1Shared), st, a, n_tiles);
+        EYOC_CHECK_HIP(hipGetLastError());
+        return EYOC_OK;
+      }
       if (a.local1 && knobs_of(a.ctx).conv1_kernel == 1) {                               // Z-ordered maps: block vectors staged per 256-parent tile
         hipLaunchKernelGGL(conv1_bf_kernel, dim3(cdiv(a.nc, ST_TILE)), dim3(256), 0, st, a);
         EYOC_CHECK_HIP(hipGetLastError());
@@ -1344,7 +1621,14 @@ int eyoc_spconv_upc(eyoc_ctx* ctx, const int32_t* nbr_dev, const void* ws_dev, i
 int eyoc_spconv_select_conv1_kernel(eyoc_ctx* ctx, int on) {
   if (!ctx) return -1;
   const int prev = ctx->knobs.conv1_kernel;
-  if (on >= 0 && on <= 2) ctx->knobs.conv1_kernel = on;
+  if (on >= 0 && on <= 3) ctx->knobs.conv1_kernel = on;
+  return prev;
+}
+
+int eyoc_spconv_conv1_workgroups(eyoc_ctx* ctx, int workgroups) {
+  if (!ctx) return -1;
+  const int prev = ctx->knobs.conv1_workgroups;
+  if (workgroups >= 0) ctx->knobs.conv1_workgroups = workgroups;
   return prev;
 }
 

@@ -285,11 +285,17 @@ int eyoc_spconv_upc_build(eyoc_ctx* ctx, const int32_t* nbr_dev, int n_out, void
 int eyoc_spconv_upc(eyoc_ctx* ctx, const int32_t* nbr_dev, const void* ws_dev, int n_out, int n_in, const float* in_dev, int ld_in,
                     int cin, const float* wpacked_dev, int cout, const float* bias_dev, int relu, float* out_dev, int ld_out,
                     int out_split, const float* out_scale_dev, void* stream);
-/* First convolution (C_in = 1, 32 output channels) of split16 forwards on Z-ordered maps: 1 (default) = conv1_bf_kernel - the block
+/* First convolution (C_in = 1, 32 output channels) of split16 forwards on Z-ordered maps (default 3): 1 = conv1_bf_kernel - the block
  * feature vectors (8 child features per level-1 row) of a 256-parent tile's neighbourhood staged in LDS through the level-1 tile
  * rulebook, the tile's fine rows grouped by parity class, a K = 27 product over blocks; 0 = conv1_mfma_kernel, which probes
- * the octree per fine row; 2 = the exact-fp32 octree walker (conv1_tree_kernel) even in front of split16 consumers.  Other values only query.  Returns the previous state; per ctx, for tests and profiling. */
+ * the octree per fine row; 2 = the exact-fp32 octree walker (conv1_tree_kernel) even in front of split16 consumers; 3 =
+ * conv1_bfp_kernel - the products of 1 in the same order (bit-identical rows and range words) from one persistent 512-thread
+ * workgroup per CU: wave = parity class with its weights resident in registers, two tile buffers in LDS, the next tile's loads in
+ * flight under the current tile's MFMAs.  Other values only query.  Returns the previous state; per ctx, for tests and profiling. */
 int eyoc_spconv_select_conv1_kernel(eyoc_ctx* ctx, int on);
+/* Grid of conv1_bfp_kernel: 0 (default) = one workgroup per compute unit, n > 0 = n workgroups (never more than the level-1 tiles;
+ * tests make one workgroup walk many tiles with it); negative only queries.  Results do not depend on it.  Returns the previous value; per ctx. */
+int eyoc_spconv_conv1_workgroups(eyoc_ctx* ctx, int workgroups);
 /* Stride-1 (3^3) split16 layers with a tile-local input stage (spconv_st.hip): per 256-row tile the distinct input rows are
  * copied to LDS once per 32-channel block and all 27 offsets run from there.  Needs the table's per-tile "local
  * rulebooks" (built once per table; *overflow_dev counts 256-row tiles with more than 1278 distinct input rows - the staged
