@@ -29,3 +29,4 @@ from .loss import contrastive_loss, generate_rand_negative_pairs  # noqa: F401,E
 from .draws import DeviceDraws  # noqa: F401,E402
 from .matches import (matching_indices_batched, get_matching_indices, compute_overlap_ratio, overlap_ratio_batched)  # noqa: F401,E402
 from .trainbatch import TrainBatch, draw_augmentation  # noqa: F401,E402
+from .icp import (estimate_normals, estimate_normals_batched, icp_plane_batched, registration_icp_point_to_plane)  # noqa: F401,E402

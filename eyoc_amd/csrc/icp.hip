@@ -22,6 +22,10 @@
 // 3. POSED NEAREST NEIGHBOUR (eyoc_posed_nn_grid): k_pnn_init, k_pnn_keys, build_grid, k_pnn_search - fp32 arithmetic, see its section.
 // 4. RADIUS MATCHES (eyoc_radius_matches_count / _fill): EVERY target inside the gate, fp64; a count pass, a scan and a fill pass over grids
 //    that stay in the workspace between the two calls, see its section.
+// 5. NORMALS (eyoc_normals_batched): the clouds are targets and queries of their own grid; every neighbour inside the radius, the first
+//    max_nn by (d2, row) kept in a lane-strided list in LDS, covariance in list order, smallest eigenvector - fp64, see its section.
+// 6. POINT-TO-PLANE ICP (eyoc_icp_plane_batched): section 2's kernels with PLANE = true - the same evaluation, 29 sums instead of 17,
+//    a 6 x 6 LDL^T solve instead of Kabsch, see its section.
 // The users differ in what they do with a candidate (the functor handed to probe_cells), in the query half of their key kernel and in
 // their own arrays; everything else about the grid exists once, here.
 #include <cmath>
@@ -267,6 +271,7 @@ int for_each_chunk(int n_pairs, Chunk&& chunk) {
 // 2. ICP: the queries are the source rows under the pair's current pose, fp64
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int ICP_SUMS = 17;       // count, sum d2, sum p (3), sum q (3), sum p q^T (9)
+constexpr int PLANE_SUMS = 29;     // point-to-plane (section 6): count, sum d2, sum J J^T (upper triangle, 21), sum J r (6)
 
 __global__ void k_icp_init(IcpSegs s, const double* __restrict__ init, eyoc_icp_result* __restrict__ res, int* __restrict__ done) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -286,18 +291,31 @@ __global__ void k_icp_init(IcpSegs s, const double* __restrict__ init, eyoc_icp_
   done[b] = r.status != 0;
 }
 
+// PLANE (section 6): the target rows also carry a normal - checked here (a non-finite one is RANGE), stored once as 16 bytes in the
+// target's own row order so that the evaluation reads the winner's normal with one load
+template <bool PLANE>
 __global__ __launch_bounds__(ICP_BLOCK) void k_icp_keys(IcpSegs s, const float* __restrict__ src, const float* __restrict__ tgt, double edge,
                                                         eyoc_icp_result* __restrict__ res, int* __restrict__ done,
                                                         unsigned long long* __restrict__ tkey, int* __restrict__ trow,
                                                         unsigned long long* __restrict__ skey, int* __restrict__ srow,
-                                                        int32_t* __restrict__ corr, double* __restrict__ d2) {
+                                                        int32_t* __restrict__ corr, double* __restrict__ d2,
+                                                        const float* __restrict__ nrm, float4* __restrict__ nrm4) {
   const int n_tgt = s.tgt[s.n_pairs], n_src = s.src[s.n_pairs];
   int i = blockIdx.x * ICP_BLOCK + threadIdx.x;
   if (i < n_tgt) {
     const int b = pair_of(s.tgt, s.n_pairs, i);
     bool ok;
     trow[i] = i;
-    tkey[i] = target_key(tgt, i, b, edge, res[b].status & EYOC_ICP_BAD_INIT, &ok);
+    const bool bad_init = res[b].status & EYOC_ICP_BAD_INIT;
+    tkey[i] = target_key(tgt, i, b, edge, bad_init, &ok);
+    if constexpr (PLANE) {
+      float4 n4 = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (!bad_init) {
+        n4 = make_float4(nrm[(size_t)i * 3], nrm[(size_t)i * 3 + 1], nrm[(size_t)i * 3 + 2], 0.f);
+        ok = ok && isfinite(n4.x) && isfinite(n4.y) && isfinite(n4.z);
+      }
+      nrm4[i] = n4;
+    }
     if (!ok) { atomicOr(&res[b].status, EYOC_ICP_RANGE); done[b] = 1; }
     return;
   }
@@ -326,10 +344,14 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_keys(IcpSegs s, const float* 
 }
 
 #pragma clang fp contract(off)
+// PLANE (section 6): the search and the outputs are the same; what a correspondence adds to the sums differs
+template <bool PLANE>
 __global__ __launch_bounds__(ICP_BLOCK) void k_icp_eval(IcpSegs s, const float* __restrict__ src, const int* __restrict__ srow_sorted, IcpGrid g,
                                                         double edge, double r2, const eyoc_icp_result* __restrict__ res,
                                                         const int* __restrict__ done, double* __restrict__ partial,
-                                                        int32_t* __restrict__ corr, double* __restrict__ d2_out) {
+                                                        int32_t* __restrict__ corr, double* __restrict__ d2_out,
+                                                        const float4* __restrict__ nrm4) {
+  constexpr int ICP_SUMS = PLANE ? PLANE_SUMS : eyoc::ICP_SUMS;     // (shadows the file's constant: the lines below are the point-to-point kernel's own)
   __shared__ int sb;
   __shared__ double red[ICP_BLOCK / 64][ICP_SUMS];
   if (threadIdx.x == 0) sb = pair_of(s.wg, s.n_pairs, blockIdx.x);
@@ -368,11 +390,26 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_eval(IcpSegs s, const float* 
     if (hit) {
       const double q[3] = {(double)best_q.x, (double)best_q.y, (double)best_q.z};
       v[0] = 1.0; v[1] = best;
+      if constexpr (PLANE) {
+        // r = (p - q) . n, J = (p x n, n): A = J J^T (upper triangle, row by row), g = J r
+        const float4 nf = nrm4[s.tgt[b] + best_row];
+        const double n[3] = {(double)nf.x, (double)nf.y, (double)nf.z};
+        const double r = ((p[0] - q[0]) * n[0] + (p[1] - q[1]) * n[1]) + (p[2] - q[2]) * n[2];
+        const double J[6] = {p[1] * n[2] - p[2] * n[1], p[2] * n[0] - p[0] * n[2], p[0] * n[1] - p[1] * n[0], n[0], n[1], n[2]};
+        int at = 2;
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        v[2 + k] = p[k]; v[5 + k] = q[k];
+        for (int k = 0; k < 6; ++k)
 #pragma unroll
-        for (int l = 0; l < 3; ++l) v[8 + 3 * k + l] = p[k] * q[l];
+          for (int l = k; l < 6; ++l) v[at++] = J[k] * J[l];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) v[23 + k] = J[k] * r;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          v[2 + k] = p[k]; v[5 + k] = q[k];
+#pragma unroll
+          for (int l = 0; l < 3; ++l) v[8 + 3 * k + l] = p[k] * q[l];
+        }
       }
     }
   }
@@ -391,9 +428,52 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_eval(IcpSegs s, const float* 
   }
 }
 
+// The point-to-plane step (section 6): A xi = -g from the sums S[2 .. 22] (upper triangle of A, row by row) and S[23 .. 28] (g), by
+// LDL^T without pivoting.  false: a pivot d_k is not above 2^-30 A_kk (A_kk before elimination - a scale-free test per variable; a NaN
+// pivot fails it too), xi is then meaningless.  Every loop has constant bounds: the 6 x 6 arrays stay in registers.
+__device__ inline bool plane_step(const double* S, double* xi) {
+  double A[6][6], L[6][6], d[6], y[6];
+  int at = 2;
+#pragma unroll
+  for (int k = 0; k < 6; ++k)
+#pragma unroll
+    for (int l = k; l < 6; ++l) A[k][l] = S[at++];
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    double dk = A[k][k];
+#pragma unroll
+    for (int m = 0; m < k; ++m) dk -= L[k][m] * L[k][m] * d[m];
+    ok = ok && dk > 0x1p-30 * A[k][k];
+    d[k] = dk;
+#pragma unroll
+    for (int i = k + 1; i < 6; ++i) {
+      double v = A[k][i];
+#pragma unroll
+      for (int m = 0; m < k; ++m) v -= L[i][m] * L[k][m] * d[m];
+      L[i][k] = v / dk;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {           // L y = -g
+    y[k] = -S[23 + k];
+#pragma unroll
+    for (int m = 0; m < k; ++m) y[k] -= L[k][m] * y[m];
+  }
+#pragma unroll
+  for (int k = 5; k >= 0; --k) {          // L^T xi = D^-1 y
+    xi[k] = y[k] / d[k];
+#pragma unroll
+    for (int m = k + 1; m < 6; ++m) xi[k] -= L[m][k] * xi[m];
+  }
+  return ok;
+}
+
 // evaluation `e` (0 = the one under the initial pose) of every pair that is still running
+template <bool PLANE>
 __global__ __launch_bounds__(64) void k_icp_solve(IcpSegs s, const double* __restrict__ partial, eyoc_icp_result* __restrict__ res,
                                                   int* __restrict__ done, int e, int max_iteration, double rel_fitness, double rel_rmse) {
+  constexpr int ICP_SUMS = PLANE ? PLANE_SUMS : eyoc::ICP_SUMS;
   const int b = blockIdx.x, lane = threadIdx.x;
   if (done[b]) return;
   // a fixed order that only depends on the pair's own workgroup count: lane l adds workgroups l, l + 64, ... in that order, then the
@@ -419,13 +499,27 @@ __global__ __launch_bounds__(64) void k_icp_solve(IcpSegs s, const double* __res
   if (n < 3.0) status |= EYOC_ICP_FEW;
   r.status = status;
   if (converged || n < 3.0 || e >= max_iteration) { done[b] = 1; return; }
-  double cp[3], cq[3], H[3][3], R[3][3];
-  for (int k = 0; k < 3; ++k) { cp[k] = S[2 + k] / n; cq[k] = S[5 + k] / n; }
-  for (int k = 0; k < 3; ++k)
-    for (int l = 0; l < 3; ++l) H[k][l] = S[8 + 3 * k + l] - n * cp[k] * cq[l];
-  kabsch_rotation(H, R);
-  double t[3], Tn[12];
-  for (int k = 0; k < 3; ++k) t[k] = cq[k] - (R[k][0] * cp[0] + R[k][1] * cp[1] + R[k][2] * cp[2]);
+  double R[3][3], t[3], Tn[12];
+  if constexpr (PLANE) {
+    double xi[6];
+    if (!plane_step(S, xi)) {       // a direction the correspondences do not constrain: the pair stops with its current T
+      r.status = status | EYOC_ICP_SINGULAR;
+      done[b] = 1;
+      return;
+    }
+    const double sa = sin(xi[0]), ca = cos(xi[0]), sb = sin(xi[1]), cb = cos(xi[1]), sg = sin(xi[2]), cg = cos(xi[2]);
+    R[0][0] = cb * cg; R[0][1] = sa * sb * cg - ca * sg; R[0][2] = ca * sb * cg + sa * sg;       // Rz(gamma) Ry(beta) Rx(alpha)
+    R[1][0] = cb * sg; R[1][1] = sa * sb * sg + ca * cg; R[1][2] = ca * sb * sg - sa * cg;
+    R[2][0] = -sb;     R[2][1] = sa * cb;                R[2][2] = ca * cb;
+    for (int k = 0; k < 3; ++k) t[k] = xi[3 + k];
+  } else {
+    double cp[3], cq[3], H[3][3];
+    for (int k = 0; k < 3; ++k) { cp[k] = S[2 + k] / n; cq[k] = S[5 + k] / n; }
+    for (int k = 0; k < 3; ++k)
+      for (int l = 0; l < 3; ++l) H[k][l] = S[8 + 3 * k + l] - n * cp[k] * cq[l];
+    kabsch_rotation(H, R);
+    for (int k = 0; k < 3; ++k) t[k] = cq[k] - (R[k][0] * cp[0] + R[k][1] * cp[1] + R[k][2] * cp[2]);
+  }
   for (int k = 0; k < 3; ++k) {
     for (int l = 0; l < 4; ++l) Tn[4 * k + l] = R[k][0] * r.T[l] + R[k][1] * r.T[4 + l] + R[k][2] * r.T[8 + l];
     Tn[4 * k + 3] += t[k];
@@ -437,27 +531,30 @@ struct IcpWorkspace {
   GridWorkspace grid;
   int* done;
   double* partial;
+  float4* nrm4;      // point-to-plane only: the target normals, 16 bytes per row
 };
 
-size_t carve(void* base, size_t bytes, int n_pairs, int total_src, int total_tgt, IcpWorkspace* w) {
+size_t carve(void* base, size_t bytes, int n_pairs, int total_src, int total_tgt, IcpWorkspace* w, bool plane = false) {
   Carver c(base, bytes);
   const int chunk = n_pairs < ICP_CHUNK ? n_pairs : ICP_CHUNK;
   carve_grid(c, total_src, total_tgt, 1, &w->grid);
   w->done = c.take<int>(chunk > 0 ? chunk : 1);
-  w->partial = c.take<double>(((size_t)cdiv(total_src, ICP_BLOCK) + chunk + 1) * ICP_SUMS);
+  w->partial = c.take<double>(((size_t)cdiv(total_src, ICP_BLOCK) + chunk + 1) * (plane ? PLANE_SUMS : ICP_SUMS));
+  w->nrm4 = plane ? c.take<float4>(total_tgt) : nullptr;
   return align_up(c.off);
 }
 
 // one chunk of <= ICP_CHUNK pairs; every pointer is already that of the chunk's first row
-int run_chunk(const float* src, const float* tgt, const int32_t* seg_src, const int32_t* seg_tgt, int n_pairs, const double* init,
+template <bool PLANE>
+int run_chunk(const float* src, const float* tgt, const float* nrm, const int32_t* seg_src, const int32_t* seg_tgt, int n_pairs, const double* init,
               const eyoc_icp_params& p, eyoc_icp_result* res, int32_t* corr, double* d2, const IcpWorkspace& w, hipStream_t st) {
   const IcpSegs s = make_segs(seg_src, seg_tgt, n_pairs);
   const int n_src = s.src[n_pairs], n_tgt = s.tgt[n_pairs], n_wg = s.wg[n_pairs];
   const double edge = p.max_distance, r2 = p.max_distance * p.max_distance;
   hipLaunchKernelGGL(k_icp_init, dim3(cdiv(n_pairs, 64)), dim3(64), 0, st, s, init, res, w.done);
   if (n_src + n_tgt > 0)
-    hipLaunchKernelGGL(k_icp_keys, dim3(cdiv((long long)n_src + n_tgt, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, s, src, tgt, edge, res, w.done,
-                       w.grid.tkey, w.grid.trow, w.grid.qkey, w.grid.qrow, corr, d2);
+    hipLaunchKernelGGL(k_icp_keys<PLANE>, dim3(cdiv((long long)n_src + n_tgt, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, s, src, tgt, edge, res, w.done,
+                       w.grid.tkey, w.grid.trow, w.grid.qkey, w.grid.qrow, corr, d2, nrm, w.nrm4);
   if (n_src == 0 || n_tgt == 0) {       // every pair has an empty segment: k_icp_init finished them all
     EYOC_CHECK_HIP(hipGetLastError());
     return EYOC_OK;
@@ -466,16 +563,19 @@ int run_chunk(const float* src, const float* tgt, const int32_t* seg_src, const 
   const int rc = build_grid(s, tgt, w.done, w.grid, st, &g);
   if (rc != EYOC_OK) return rc;
   for (int e = 0; e <= p.max_iteration; ++e) {
-    hipLaunchKernelGGL(k_icp_eval, dim3(n_wg), dim3(ICP_BLOCK), 0, st, s, src, w.grid.qrow_sorted, g, edge, r2, res, w.done, w.partial, corr, d2);
-    hipLaunchKernelGGL(k_icp_solve, dim3(n_pairs), dim3(64), 0, st, s, w.partial, res, w.done, e, p.max_iteration, p.relative_fitness,
+    hipLaunchKernelGGL(k_icp_eval<PLANE>, dim3(n_wg), dim3(ICP_BLOCK), 0, st, s, src, w.grid.qrow_sorted, g, edge, r2, res, w.done, w.partial, corr,
+                       d2, w.nrm4);
+    hipLaunchKernelGGL(k_icp_solve<PLANE>, dim3(n_pairs), dim3(64), 0, st, s, w.partial, res, w.done, e, p.max_iteration, p.relative_fitness,
                        p.relative_rmse);
   }
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
 }
 
+// `plane`: eyoc_icp_plane_batched (section 6), `nrm` its target normals; the point-to-point entry points pass false / nullptr
 int run(const char* what, eyoc_ctx* ctx, const float* src, const float* tgt, const int32_t* seg_src, const int32_t* seg_tgt, int n_pairs,
-        const double* init, const eyoc_icp_params& p, eyoc_icp_result* res, int32_t* corr, double* d2, void* ws, size_t ws_bytes, void* stream) {
+        const double* init, const eyoc_icp_params& p, eyoc_icp_result* res, int32_t* corr, double* d2, void* ws, size_t ws_bytes, void* stream,
+        bool plane = false, const float* nrm = nullptr) {
   int bad = check_grid_head(what, ctx && seg_src && seg_tgt && res && ws, n_pairs, ws);
   if (bad != EYOC_OK) return bad;
   EYOC_REQUIRE(std::isfinite(p.max_distance) && p.max_distance > 0.0, EYOC_ERR_INVALID, "%s: max_distance must be positive and finite", what);
@@ -484,15 +584,25 @@ int run(const char* what, eyoc_ctx* ctx, const float* src, const float* tgt, con
   bad = check_segments(what, n_pairs, {seg_src, seg_tgt});
   if (bad != EYOC_OK) return bad;
   EYOC_REQUIRE((seg_src[n_pairs] == 0 || src) && (seg_tgt[n_pairs] == 0 || tgt), EYOC_ERR_INVALID, "%s: NULL cloud", what);
+  EYOC_REQUIRE(!plane || seg_tgt[n_pairs] == 0 || nrm, EYOC_ERR_INVALID, "%s: NULL target normals", what);
   IcpWorkspace w;
-  const size_t need = carve(ws, ws_bytes, n_pairs, seg_src[n_pairs], seg_tgt[n_pairs], &w);
-  EYOC_REQUIRE(ws_bytes >= need, EYOC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (eyoc_icp_workspace_bytes)", what, ws_bytes, need);
+  const size_t need = carve(ws, ws_bytes, n_pairs, seg_src[n_pairs], seg_tgt[n_pairs], &w, plane);
+  EYOC_REQUIRE(ws_bytes >= need, EYOC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (%s)", what, ws_bytes, need,
+               plane ? "eyoc_icp_plane_workspace_bytes" : "eyoc_icp_workspace_bytes");
   EYOC_CHECK_HIP(hipSetDevice(ctx->device));
   return for_each_chunk(n_pairs, [&](int b0, int np) {
     const size_t so = (size_t)seg_src[b0], to = (size_t)seg_tgt[b0];
-    return run_chunk(src ? src + 3 * so : nullptr, tgt ? tgt + 3 * to : nullptr, seg_src + b0, seg_tgt + b0, np,
-                     init ? init + 16 * (size_t)b0 : nullptr, p, res + b0, corr ? corr + so : nullptr, d2 ? d2 + so : nullptr, w,
-                     (hipStream_t)stream);
+    const float* s0 = src ? src + 3 * so : nullptr;
+    const float* t0 = tgt ? tgt + 3 * to : nullptr;
+    const double* i0 = init ? init + 16 * (size_t)b0 : nullptr;
+    IcpWorkspace wc = w;
+    if (plane) {
+      wc.nrm4 += to;
+      return run_chunk<true>(s0, t0, nrm ? nrm + 3 * to : nullptr, seg_src + b0, seg_tgt + b0, np, i0, p, res + b0, corr ? corr + so : nullptr,
+                             d2 ? d2 + so : nullptr, wc, (hipStream_t)stream);
+    }
+    return run_chunk<false>(s0, t0, nullptr, seg_src + b0, seg_tgt + b0, np, i0, p, res + b0, corr ? corr + so : nullptr,
+                            d2 ? d2 + so : nullptr, wc, (hipStream_t)stream);
   });
 }
 
@@ -895,6 +1005,147 @@ int rm_run(const char* what, bool fill, eyoc_ctx* ctx, const float* src, const f
   return scan_offsets64(w.scan_tmp, w.scan_bytes, (long long*)offsets, total_src + 1, st);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// 5. Normals (eyoc_normals_batched): Open3D's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) restated for a batch of clouds.
+// The fourth user of the grid of section 1: a cloud is the target AND the query side of its own grid, the query's point is the row
+// itself (fp32, exact in fp64), so d = x_j - x_i is ONE rounding per axis and d2 = (dx dx + dy dy) + dz dz as in section 4.
+//   status = 0   one fill per chunk
+//   k_nrm_keys   one thread per row: target_key (RANGE for a non-finite point or a cell outside the key range), the same key on the
+//                query side, normal and count preset to 0
+//   build_grid
+//   k_nrm_search 64 cell-sorted rows of one cloud per workgroup (ONE wave: nothing is shared, no barrier), lane = row.  The lane keeps
+//                the first `cap` neighbours by (d2, j) in a list in LDS, inserted as in k_rm_fill: entry m of lane l is d2 at double
+//                [m * 64 + l] and j at int [m * 64 + l] behind the doubles - consecutive lanes on consecutive banks, 12 bytes per entry,
+//                cap * 768 bytes per workgroup, asked for at the launch (max_nn = 30: 22.5 KiB, 64: 48 KiB).  Then the offsets of the
+//                list's rows are read again in list order for S1 and S2.  max_nn = 0 (all neighbours): cap = 64 and further passes,
+//                each keeping the next 64 entries above the last one of the pass before, until a pass saw no more than 64.
+// Cell edge: fl(radius (1 + 2^-20)), section 4's derivation with p = x_i exact - the neighbours found are exactly those of the n x n sweep.
+// The sums are added in list order by one lane: a row's normal does not depend on the launch, on the slot placement or on another cloud.
+constexpr int NRM_BLOCK = 64;
+constexpr int NRM_MAX_NN = 64;
+
+__global__ __launch_bounds__(ICP_BLOCK) void k_nrm_keys(IcpSegs s, const float* __restrict__ pts, double edge, int* __restrict__ status,
+                                                        unsigned long long* __restrict__ tkey, int* __restrict__ trow,
+                                                        unsigned long long* __restrict__ qkey, int* __restrict__ qrow,
+                                                        float* __restrict__ normals, int* __restrict__ count) {
+  const int i = blockIdx.x * ICP_BLOCK + threadIdx.x;
+  if (i >= s.tgt[s.n_pairs]) return;
+  const int b = pair_of(s.tgt, s.n_pairs, i);
+  bool ok;
+  const unsigned long long key = target_key(pts, i, b, edge, false, &ok);
+  trow[i] = i; qrow[i] = i;
+  tkey[i] = key; qkey[i] = key;
+  if (!ok) atomicOr(&status[b], EYOC_ICP_RANGE);
+  normals[(size_t)i * 3] = 0.f; normals[(size_t)i * 3 + 1] = 0.f; normals[(size_t)i * 3 + 2] = 0.f;
+  if (count) count[i] = 0;
+}
+
+__global__ __launch_bounds__(NRM_BLOCK) void k_nrm_search(IcpSegs s, const float* __restrict__ pts, const int* __restrict__ qrow_sorted, IcpGrid g,
+                                                          double edge, double r2, int max_nn, int cap, const int* __restrict__ status,
+                                                          float* __restrict__ normals, int* __restrict__ count) {
+  extern __shared__ double nrm_list[];     // cap x 64 doubles (d2), then cap x 64 ints (j)
+  const int b = pair_of(s.wg, s.n_pairs, blockIdx.x);     // uniform: kernel arguments and the workgroup index
+  if (status[b]) return;                                  // the cloud keeps its zeros
+  const int local = (blockIdx.x - s.wg[b]) * NRM_BLOCK + threadIdx.x;
+  if (local >= s.src[b + 1] - s.src[b]) return;           // no barrier below
+  double* const dd = nrm_list + threadIdx.x;
+  int* const jj = reinterpret_cast<int*>(nrm_list + (size_t)cap * NRM_BLOCK) + threadIdx.x;
+  const int qi = qrow_sorted[s.src[b] + local];
+  const double x[3] = {(double)pts[(size_t)qi * 3], (double)pts[(size_t)qi * 3 + 1], (double)pts[(size_t)qi * 3 + 2]};
+  int c[3];
+  if (!(cell_of(x[0], edge, &c[0]) && cell_of(x[1], edge, &c[1]) && cell_of(x[2], edge, &c[2]))) return;   // (status 0: never)
+  double S1[3] = {0.0, 0.0, 0.0}, S2[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // S2: xx, xy, xz, yy, yz, zz
+  double last_d = -1.0;      // a pass takes the entries above (last_d, last_j); every d2 is >= 0
+  int last_j = -1, k = 0;
+  for (;;) {
+    int n = 0, above = 0;
+    probe_cells(g, b, c, [&](const float4 q) {
+      const double dx = (double)q.x - x[0], dy = (double)q.y - x[1], dz = (double)q.z - x[2];
+      const double d = (dx * dx + dy * dy) + dz * dz;
+      if (!(d < r2)) return;
+      const int j = __float_as_int(q.w);
+      if (!(d > last_d || (d == last_d && j > last_j))) return;
+      ++above;
+      int pos;
+      if (n < cap) pos = n++;
+      else {                              // full: the largest leaves if the new entry is smaller
+        pos = cap - 1;
+        const double dl = dd[pos * NRM_BLOCK];
+        if (!(d < dl || (d == dl && j < jj[pos * NRM_BLOCK]))) return;
+      }
+      for (; pos > 0; --pos) {            // entries above (d2, j) move up one place
+        const double dp = dd[(pos - 1) * NRM_BLOCK];
+        const int jp = jj[(pos - 1) * NRM_BLOCK];
+        if (dp < d || (dp == d && jp < j)) break;
+        dd[pos * NRM_BLOCK] = dp;
+        jj[pos * NRM_BLOCK] = jp;
+      }
+      dd[pos * NRM_BLOCK] = d;
+      jj[pos * NRM_BLOCK] = j;
+    });
+    for (int m = 0; m < n; ++m) {
+      const float* q = pts + 3 * ((size_t)s.tgt[b] + (size_t)jj[m * NRM_BLOCK]);
+      const double d[3] = {(double)q[0] - x[0], (double)q[1] - x[1], (double)q[2] - x[2]};
+      S1[0] += d[0]; S1[1] += d[1]; S1[2] += d[2];
+      S2[0] += d[0] * d[0]; S2[1] += d[0] * d[1]; S2[2] += d[0] * d[2];
+      S2[3] += d[1] * d[1]; S2[4] += d[1] * d[2]; S2[5] += d[2] * d[2];
+    }
+    k += n;
+    if (max_nn > 0 || above <= cap) break;
+    last_d = dd[(n - 1) * NRM_BLOCK];
+    last_j = jj[(n - 1) * NRM_BLOCK];
+  }
+  if (count) count[qi] = k;
+  if (k < 3) return;                       // the zero vector
+  const double kk = (double)k, m[3] = {S1[0] / kk, S1[1] / kk, S1[2] / kk};
+  double C[3][3], w[3], v[3][3];
+  C[0][0] = S2[0] / kk - m[0] * m[0]; C[0][1] = S2[1] / kk - m[0] * m[1]; C[0][2] = S2[2] / kk - m[0] * m[2];
+  C[1][1] = S2[3] / kk - m[1] * m[1]; C[1][2] = S2[4] / kk - m[1] * m[2]; C[2][2] = S2[5] / kk - m[2] * m[2];
+  C[1][0] = C[0][1]; C[2][0] = C[0][2]; C[2][1] = C[1][2];
+  jacobi_eig3(C, w, v);
+  double nv[3] = {v[2][0], v[2][1], v[2][2]};     // the smallest eigenvalue's vector
+  const double len = sqrt((nv[0] * nv[0] + nv[1] * nv[1]) + nv[2] * nv[2]);
+  const double dot = (nv[0] * x[0] + nv[1] * x[1]) + nv[2] * x[2];
+  const double first = nv[0] != 0.0 ? nv[0] : (nv[1] != 0.0 ? nv[1] : nv[2]);
+  const double sign = dot > 0.0 || (dot == 0.0 && first < 0.0) ? -1.0 : 1.0;       // towards the origin; undecided: first component positive
+#pragma unroll
+  for (int a = 0; a < 3; ++a) normals[(size_t)qi * 3 + a] = (float)(sign * (nv[a] / len));
+}
+
+size_t nrm_carve(void* base, size_t bytes, int total, GridWorkspace* w) {
+  Carver c(base, bytes);
+  carve_grid(c, total, total, 1, w);
+  return align_up(c.off);
+}
+
+// one chunk of <= ICP_CHUNK clouds; every pointer is already that of the chunk's first row / cloud
+int nrm_chunk(const float* pts, const int32_t* seg, int n_clouds, double radius, int max_nn, float* normals, int32_t* count, int32_t* status,
+              const GridWorkspace& w, hipStream_t st) {
+  IcpSegs s = make_segs(seg, seg, n_clouds);
+  for (int b = 0; b < n_clouds; ++b) s.wg[b + 1] = s.wg[b] + cdiv(s.src[b + 1] - s.src[b], NRM_BLOCK);     // 64 rows per workgroup here
+  const int n = s.tgt[n_clouds];
+  const double edge = radius * RM_EDGE_MARGIN, r2 = radius * radius;
+  const int cap = max_nn > 0 ? max_nn : NRM_MAX_NN;
+  EYOC_CHECK_HIP(hipMemsetAsync(status, 0, (size_t)n_clouds * sizeof(int32_t), st));
+  if (n == 0) return EYOC_OK;
+  hipLaunchKernelGGL(k_nrm_keys, dim3(cdiv(n, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, s, pts, edge, status, w.tkey, w.trow, w.qkey, w.qrow, normals,
+                     count);
+  IcpGrid g;
+  const int rc = build_grid(s, pts, status, w, st, &g);
+  if (rc != EYOC_OK) return rc;
+  hipLaunchKernelGGL(k_nrm_search, dim3(s.wg[n_clouds]), dim3(NRM_BLOCK), (size_t)cap * NRM_BLOCK * (sizeof(double) + sizeof(int)), st, s, pts,
+                     w.qrow_sorted, g, edge, r2, max_nn, cap, status, normals, count);
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// 6. Point-to-plane ICP (eyoc_icp_plane_batched): section 2 with PLANE = true.  The evaluation - search, gate, fitness, rmse, FEW,
+// convergence - is k_icp_eval's own code; a correspondence (p, q, n) adds r = (p - q) . n and J = (p x n, n) to A = sum J J^T and
+// g = sum J r instead of the Kabsch moments, reduced in the same fixed order; k_icp_solve solves A xi = -g (plane_step: LDL^T, a small
+// pivot is SINGULAR) and applies U = [Rz Ry Rx | t].  A target without a usable normal (the zero vector of section 5) adds zeros.
+// ---------------------------------------------------------------------------------------------------------------------
+
 }  // namespace
 }  // namespace eyoc
 
@@ -983,4 +1234,52 @@ extern "C" int eyoc_radius_matches_fill(eyoc_ctx* ctx, const float* src_dev, con
   return eyoc::rm_run("eyoc_radius_matches_fill", true, ctx, src_dev, tgt_dev, seg_src_host, seg_tgt_host, n_pairs, T_dev, radius, max_per_source,
                       const_cast<int64_t*>(offsets_dev), const_cast<int32_t*>(status_dev), total, pairs_out_dev, d2_out_dev, workspace_dev,
                       workspace_bytes, stream);
+}
+
+extern "C" size_t eyoc_normals_workspace_bytes(int n_clouds, int total) {
+  if (n_clouds < 1 || total < 0) return 0;
+  eyoc::GridWorkspace w;
+  return eyoc::nrm_carve(nullptr, 0, total, &w);
+}
+
+extern "C" int eyoc_normals_batched(eyoc_ctx* ctx, const float* pts_dev, const int32_t* seg_host, int n_clouds, double radius, int max_nn,
+                                    float* normals_dev, int32_t* count_dev, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes,
+                                    void* stream) {
+  using namespace eyoc;
+  const char* what = "eyoc_normals_batched";
+  int bad = check_grid_head(what, ctx && seg_host && status_dev && workspace_dev, n_clouds, workspace_dev);
+  if (bad != EYOC_OK) return bad;
+  EYOC_REQUIRE(std::isfinite(radius) && radius > 0.0, EYOC_ERR_INVALID, "%s: radius must be positive and finite", what);
+  EYOC_REQUIRE(max_nn >= 0 && max_nn <= NRM_MAX_NN, EYOC_ERR_INVALID, "%s: max_nn = %d is outside [0, %d] (0 = all)", what, max_nn, NRM_MAX_NN);
+  bad = check_segments(what, n_clouds, {seg_host});
+  if (bad != EYOC_OK) return bad;
+  const int total = seg_host[n_clouds];
+  EYOC_REQUIRE(total == 0 || (pts_dev && normals_dev), EYOC_ERR_INVALID, "%s: NULL cloud or output", what);
+  GridWorkspace w;
+  const size_t need = nrm_carve(workspace_dev, workspace_bytes, total, &w);
+  EYOC_REQUIRE(workspace_bytes >= need, EYOC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (eyoc_normals_workspace_bytes)", what, workspace_bytes,
+               need);
+  EYOC_CHECK_HIP(hipSetDevice(ctx->device));
+  return for_each_chunk(n_clouds, [&](int b0, int nc) {
+    const size_t o = (size_t)seg_host[b0];
+    return nrm_chunk(pts_dev ? pts_dev + 3 * o : nullptr, seg_host + b0, nc, radius, max_nn, normals_dev ? normals_dev + 3 * o : nullptr,
+                     count_dev ? count_dev + o : nullptr, status_dev + b0, w, (hipStream_t)stream);
+  });
+}
+
+extern "C" size_t eyoc_icp_plane_workspace_bytes(int n_pairs, int total_src, int total_tgt) {
+  if (n_pairs < 1 || total_src < 0 || total_tgt < 0) return 0;
+  eyoc::IcpWorkspace w;
+  return eyoc::carve(nullptr, 0, n_pairs, total_src, total_tgt, &w, true);
+}
+
+extern "C" int eyoc_icp_plane_batched(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const float* tgt_normals_dev,
+                                      const int32_t* seg_src_host, const int32_t* seg_tgt_host, int n_pairs, const double* init_dev,
+                                      const eyoc_icp_params* params, eyoc_icp_result* results_dev, int32_t* corr_dev, void* workspace_dev,
+                                      size_t workspace_bytes, void* stream) {
+  EYOC_REQUIRE(params, EYOC_ERR_INVALID, "eyoc_icp_plane_batched: NULL params");
+  EYOC_REQUIRE(std::isfinite(params->relative_fitness) && std::isfinite(params->relative_rmse), EYOC_ERR_INVALID,
+               "eyoc_icp_plane_batched: the convergence thresholds must be finite");
+  return eyoc::run("eyoc_icp_plane_batched", ctx, src_dev, tgt_dev, seg_src_host, seg_tgt_host, n_pairs, init_dev, *params, results_dev, corr_dev,
+                   nullptr, workspace_dev, workspace_bytes, stream, true, tgt_normals_dev);
 }

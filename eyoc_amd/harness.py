@@ -61,6 +61,16 @@ class RegistrationConfig:
     icp_refine: bool = False
     icp_max_correspondence_distance: float | None = None
     icp_max_iteration: int = 30
+    # the ICP's step: "point" (Kabsch over the correspondences) or "plane" (point-to-plane: the normals of the step's target sample sets
+    # are estimated on the device first, eyoc_amd.icp.estimate_normals_batched, inside icp_normal_radius - None: 5 x voxel_size - from at
+    # most icp_normal_max_nn neighbours).  Anything else raises here
+    icp_method: str = "point"
+    icp_normal_radius: float | None = None
+    icp_normal_max_nn: int = 30
+
+    def __post_init__(self):
+        if self.icp_method not in ("point", "plane"):
+            raise ValueError(f"icp_method = {self.icp_method!r}: \"point\" or \"plane\"")
 
 
 # ``RegistrationResult.status`` / ``PendingStep.status`` bit: the pair's step overflowed split16 and was registered again in fp32
@@ -624,8 +634,16 @@ class RegistrationPipeline:
         as they are on the device -> the refined poses, f32 ``[P, 16]`` (the fp64 result rounded once).  A pair without a pose (NaN:
         dropped, degenerate) keeps it and gets BAD_INIT, an empty segment FEW; the records stay in ``step.icp``."""
         batch, gate = step.batch, self.cfg.icp_max_correspondence_distance
-        step.icp = icp.icp_batched(batch.xyz0.reshape(-1, 3), batch.xyz1.reshape(-1, 3), batch.seg, batch.seg,
-                                   2.0 * self.cfg.voxel_size if gate is None else gate, T.to(torch.float64), self.cfg.icp_max_iteration)
+        gate = 2.0 * self.cfg.voxel_size if gate is None else gate
+        if self.cfg.icp_method == "plane":     # the same records from the point-to-plane step, normals from the target sample sets themselves
+            xyz1, radius = batch.xyz1.reshape(-1, 3), self.cfg.icp_normal_radius
+            normals, _ = icp.estimate_normals_batched(xyz1, batch.seg, 5.0 * self.cfg.voxel_size if radius is None else radius,
+                                                      self.cfg.icp_normal_max_nn)
+            step.icp = icp.icp_plane_batched(batch.xyz0.reshape(-1, 3), xyz1, normals, batch.seg, batch.seg, gate, T.to(torch.float64),
+                                             self.cfg.icp_max_iteration)
+        else:
+            step.icp = icp.icp_batched(batch.xyz0.reshape(-1, 3), batch.xyz1.reshape(-1, 3), batch.seg, batch.seg, gate,
+                                       T.to(torch.float64), self.cfg.icp_max_iteration)
         return step.icp.view(torch.float64)[:, :16].to(torch.float32)
 
     def _pinned_stage(self, slot, count):

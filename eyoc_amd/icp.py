@@ -1,11 +1,14 @@
-"""Point-to-point ICP refinement on the GPU (``eyoc_icp_batched``, csrc/icp.hip), with the reference's call surfaces.
+"""ICP refinement on the GPU - point-to-point (``eyoc_icp_batched``, csrc/icp.hip) with the reference's call surfaces, and point-to-plane.
 
 * ``registration_icp`` stands in for ``o3d.pipelines.registration.registration_icp(pcd0, pcd1, r, init,
   TransformationEstimationPointToPoint(), ICPConvergenceCriteria(max_iteration=200))`` at ``lib/data_loaders.py:485-515`` (through
   ``eyoc_amd.o3d`` those lines run unchanged);
 * ``icp_refine`` mirrors ``scripts/SC2_PCR/benchmark_utils.py:40-56``;
 * ``icp_batched`` refines a batch of pairs in one call and leaves the records on the device; ``correspondences`` is one
-  evaluation of the contract (nearest target row under a gate, fp64) on the same cell grid.
+  evaluation of the contract (nearest target row under a gate, fp64) on the same cell grid;
+* ``estimate_normals`` / ``estimate_normals_batched`` (``eyoc_normals_batched``) and ``registration_icp_point_to_plane`` /
+  ``icp_plane_batched`` (``eyoc_icp_plane_batched``) are Open3D's ``estimate_normals(KDTreeSearchParamHybrid(radius, max_nn))`` and
+  ``registration_icp`` with ``TransformationEstimationPointToPlane``, restated the same way; the reference has no call site for them.
 
 The algorithm is restated from Open3D's published source - parity unpinned, see DESIGN.md 4 - and documented in
 ``include/eyoc_hip.h``.
@@ -22,6 +25,7 @@ from .eval import _cuda_f32
 from .registration import RegistrationResult
 
 CONVERGED, BAD_INIT, FEW, RANGE = 1, 2, 4, 8      # eyoc_icp_result.status
+SINGULAR = 16                                     # ... of the point-to-plane runs only: the step's 6 x 6 system had a negligible pivot
 RECORD_BYTES = C.sizeof(_lib.IcpResult)           # 160
 
 
@@ -124,6 +128,83 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
     T0 = np.eye(4) if init is None else np.asarray(init, np.float64)
     res, corr = icp_batched(s, t, [0, s.shape[0]], [0, t.shape[0]], max_correspondence_distance, T0[None], it, rf, rr,
                             return_correspondences=True)
+    return decode_icp_result(res[0], corr)
+
+
+def estimate_normals_batched(pts, seg, radius, max_nn=30, return_count=False):
+    """Normals of a batch of clouds (``eyoc_normals_batched``; Open3D's ``estimate_normals(KDTreeSearchParamHybrid(radius, max_nn))``
+    restated, see ``include/eyoc_hip.h``): ``pts f32 [N, 3]`` holds the clouds back to back, cloud ``b`` = rows ``seg[b]:seg[b+1]``.
+    Returns ``(normals f32 [N, 3], status int32 [B])`` on the device - with ``return_count`` ``(normals, count int32 [N], status)``.  A
+    row with fewer than 3 neighbours gets the zero vector; a cloud whose status is ``RANGE`` gets zeros throughout.  ``max_nn = 0``
+    keeps every neighbour inside ``radius``, otherwise ``1 <= max_nn <= 64``."""
+    p = _cuda_f32(pts).reshape(-1, 3)
+    sc, seg_l = _segs(seg)
+    B = len(seg_l) - 1
+    if B < 1 or seg_l[-1] != p.shape[0]:
+        raise ValueError("estimate_normals_batched: the segments do not describe the clouds")
+    normals = torch.empty((p.shape[0], 3), dtype=torch.float32, device=p.device)
+    count = torch.empty(p.shape[0], dtype=torch.int32, device=p.device) if return_count else None
+    status = torch.empty(B, dtype=torch.int32, device=p.device)
+    lib = _lib.load()
+    with _lib.on_device(p.device):
+        ws = _lib.workspace(lib.eyoc_normals_workspace_bytes(B, p.shape[0]), p.device)
+        _lib.check(lib.eyoc_normals_batched(_lib.ctx(p.device.index), _lib.ptr(p), sc, B, float(radius), int(max_nn), _lib.ptr(normals),
+                                            _lib.ptr(count), _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   "eyoc_normals_batched")
+    return (normals, count, status) if return_count else (normals, status)
+
+
+def estimate_normals(points, radius, max_nn=30):
+    """One cloud: ``[n, 3]`` points (numpy, torch, or anything with a ``points`` attribute) -> ``f32 [n, 3]`` normals on the device,
+    pointing towards the origin.  Raises for a cloud the grid cannot hold (a non-finite point, a point beyond 2^17 cells)."""
+    if not torch.cuda.is_available():
+        raise _lib.EyocError("no GPU visible: normal estimation runs on MI355X only (no CPU fallback)")
+    p = _points(points)
+    normals, status = estimate_normals_batched(p, [0, p.shape[0]], radius, max_nn)
+    if int(status[0]) != 0:
+        raise _lib.EyocError("estimate_normals: a point is not finite or lies outside the grid's range", _lib.ERR_RANGE)
+    return normals
+
+
+def icp_plane_batched(src, tgt, tgt_normals, seg_src, seg_tgt, max_correspondence_distance, init=None, max_iteration=30,
+                      relative_fitness=1e-6, relative_rmse=1e-6, return_correspondences=False):
+    """``icp_batched`` with the point-to-plane step (``eyoc_icp_plane_batched``): ``tgt_normals f32 [M, 3]`` are the target rows' normals
+    (``estimate_normals_batched``).  Same records, same correspondences; a pair whose 6 x 6 system is singular stops with ``SINGULAR``."""
+    s, t, ss, st, P, res = _clouds("icp_plane_batched", src, tgt, seg_src, seg_tgt)
+    n = _cuda_f32(tgt_normals, s.device).reshape(-1, 3)
+    if n.shape[0] != t.shape[0]:
+        raise ValueError(f"icp_plane_batched: {n.shape[0]} normals for {t.shape[0]} target rows")
+    T0 = None if init is None else _poses(init, P, s.device)
+    p = _lib.IcpParams(float(max_correspondence_distance), float(relative_fitness), float(relative_rmse), int(max_iteration), 0)
+    corr = torch.empty(s.shape[0], dtype=torch.int32, device=s.device) if return_correspondences else None
+    lib = _lib.load()
+    with _lib.on_device(s.device):
+        ws = _lib.workspace(lib.eyoc_icp_plane_workspace_bytes(P, s.shape[0], t.shape[0]), s.device)
+        _lib.check(lib.eyoc_icp_plane_batched(_lib.ctx(s.device.index), _lib.ptr(s), _lib.ptr(t), _lib.ptr(n), ss, st, P, _lib.ptr(T0),
+                                              C.byref(p), _lib.ptr(res), _lib.ptr(corr), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   "eyoc_icp_plane_batched")
+    return (res, corr) if return_correspondences else res
+
+
+def registration_icp_point_to_plane(source, target, max_correspondence_distance, init=None, criteria=None, target_normals=None,
+                                    normal_radius=None, max_nn=30):
+    """Open3D's ``registration_icp(..., TransformationEstimationPointToPlane())`` for one pair: -> ``RegistrationResult`` like
+    ``registration_icp``.  ``target_normals [m, 3]``: the target's normals; ``None``: they are estimated on the device from the target
+    itself (``estimate_normals(target, normal_radius, max_nn)``), ``normal_radius`` is then mandatory."""
+    if not torch.cuda.is_available():
+        raise _lib.EyocError("no GPU visible: ICP runs on MI355X only (no CPU fallback)")
+    rf, rr, it = (1e-6, 1e-6, 30) if criteria is None else (criteria.relative_fitness, criteria.relative_rmse, criteria.max_iteration)
+    s, t = _points(source), _points(target)
+    if target_normals is None:
+        if normal_radius is None:
+            raise ValueError("registration_icp_point_to_plane: normal_radius is needed when no target_normals are given")
+        t = _cuda_f32(t).reshape(-1, 3)
+        target_normals, _ = estimate_normals_batched(t, [0, t.shape[0]], normal_radius, max_nn)    # a RANGE cloud is RANGE in the ICP too
+    elif not isinstance(target_normals, torch.Tensor):
+        target_normals = torch.from_numpy(np.ascontiguousarray(np.asarray(target_normals, np.float32)))
+    T0 = np.eye(4) if init is None else np.asarray(init, np.float64)
+    res, corr = icp_plane_batched(s, t, target_normals, [0, s.shape[0]], [0, t.shape[0]], max_correspondence_distance, T0[None], it, rf, rr,
+                                  return_correspondences=True)
     return decode_icp_result(res[0], corr)
 
 

@@ -16,7 +16,9 @@ touches exists here - this is not an Open3D re-implementation: other estimation 
 ``o3d.pipelines.registration.registration_icp(pcd0, pcd1, 0.2, np.eye(4), TransformationEstimationPointToPoint(),
 ICPConvergenceCriteria(max_iteration=200))`` and ``pcd0.transform(reg.transformation)`` (``lib/data_loaders.py:497-507``) and the legacy
 ``o3d.registration.registration_icp`` of ``scripts/SC2_PCR/benchmark_utils.py:52-54`` run unchanged as well (``eyoc_amd.icp``);
-``TransformationEstimationPointToPoint(with_scaling=True)`` and point-to-plane raise ``NotImplementedError``.
+``TransformationEstimationPointToPoint(with_scaling=True)`` and point-to-plane raise ``NotImplementedError``.  Point-to-plane ICP itself
+exists (``eyoc_amd.icp.registration_icp_point_to_plane``, with ``estimate_normals`` for the target's normals); this shim keeps refusing
+``TransformationEstimationPointToPlane`` because its ``PointCloud`` carries no normals to hand over.
 """
 from __future__ import annotations
 

@@ -914,7 +914,8 @@ enum {
   EYOC_ICP_CONVERGED = 1,
   EYOC_ICP_BAD_INIT = 2,   /* non-finite init: T is returned as given, nothing else of the pair is read */
   EYOC_ICP_FEW = 4,        /* an evaluation left fewer than 3 correspondences (or a segment is empty) */
-  EYOC_ICP_RANGE = 8       /* a non-finite source / target point or a target cell outside +-2^17 cells: T = init */
+  EYOC_ICP_RANGE = 8,      /* a non-finite source / target point or a target cell outside +-2^17 cells: T = init */
+  EYOC_ICP_SINGULAR = 16   /* eyoc_icp_plane_batched only: the correspondences leave a direction of the step unconstrained */
 };
 typedef struct {
   double max_distance, relative_fitness, relative_rmse;
@@ -936,6 +937,51 @@ int eyoc_icp_batched(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, 
 int eyoc_icp_correspondences(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int32_t* seg_src_host,
                              const int32_t* seg_tgt_host, int n_pairs, const double* T_dev, double max_distance, int32_t* corr_dev,
                              double* d2_dev, eyoc_icp_result* results_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* Normal estimation for a batch of clouds.  Added after 111 without a bump, additive only.
+ * Open3D's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) restated as a contract of this library (parity unpinned, like the
+ * ICP).  n_clouds <= 1024 clouds back to back: pts_dev f32 [total][3], cloud b owns rows [seg[b], seg[b+1]) (HOST array of n_clouds + 1
+ * ints from 0, empty clouds accepted).  For every row x_i of a cloud:
+ *   neighbours   the rows j of the SAME cloud, i itself included, with d2 = (dx dx + dy dy) + dz dz < radius * radius, d = x_j - x_i;
+ *                all of it fp64 from the fp32 values, every operation rounded on its own (no fused multiply-add), the product
+ *                radius * radius formed once; ordered by (d2, j) ascending and cut to the first max_nn.  max_nn = 0 keeps all,
+ *                1 <= max_nn <= 64 otherwise (a lane's list lives on chip).  EXACTLY the decision of the n x n sweep: the cell
+ *                edge is radius (1 + 2^-20), icp.hip derives the margin.
+ *   covariance   k neighbours with offsets d_m in list order: S1 = sum d_m, S2 = sum d_m d_m^T, C = S2 / k - (S1 / k)(S1 / k)^T, fp64,
+ *                summed in list order by one lane.
+ *   normal       the eigenvector of C's smallest eigenvalue (cyclic Jacobi, fp64), normalised, with the sign that makes n . x_i <= 0
+ *                (towards a sensor at the origin); n . x_i == 0: the first non-zero component is positive.  Rounded once to fp32.
+ *                k < 3: the zero vector - in eyoc_icp_plane_batched such a target adds nothing to the system.
+ * normals_dev f32 [total][3]; count_dev int32 [total] = k, or NULL; status_dev int32 [n_clouds]: 0, or EYOC_ICP_RANGE for a cloud with
+ * a non-finite point or a cell floor(v / edge) outside [-2^17, 2^17) - that cloud gets zero normals and count 0, nothing of it is
+ * searched.  EYOC_ERR_INVALID for a radius that is not positive and finite or max_nn outside [0, 64].
+ * Caller-owned 256-byte aligned workspace of eyoc_normals_workspace_bytes; no allocation, no read-back, no floating-point atomics;
+ * every 64-cloud chunk builds its own grid.  A cloud's bytes are the same from run to run, alone, and at any place in a batch. */
+size_t eyoc_normals_workspace_bytes(int n_clouds, int total);
+int eyoc_normals_batched(eyoc_ctx* ctx, const float* pts_dev, const int32_t* seg_host, int n_clouds, double radius, int max_nn,
+                         float* normals_dev, int32_t* count_dev, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes,
+                         void* stream);
+
+/* Point-to-plane ICP for a batch of pairs.  Added after 111 without a bump, additive only.
+ * Open3D's registration_icp with TransformationEstimationPointToPlane restated (parity unpinned).  Call shape, segments, params (flags
+ * 0), records, corr_dev and workspace rules are eyoc_icp_batched's; tgt_normals_dev f32 [total_tgt][3] is added (NULL only with no
+ * target rows) and the workspace is sized by eyoc_icp_plane_workspace_bytes.
+ *   eval(T)  is eyoc_icp_batched's: nearest target by (d2, row), gate d2 < max_distance^2, fitness, Euclidean inlier_rmse, FEW below 3
+ *            correspondences, convergence on fitness and rmse.
+ *   step     for every correspondence, p = T x in fp64, target q with normal n (fp32, exact in fp64):
+ *              r = ((p0 - q0) n0 + (p1 - q1) n1) + (p2 - q2) n2,  a = p x n,  J = (a, n),  A = sum J J^T,  g = sum J r
+ *            (21 + 6 sums, reduced lane -> wave -> workgroup -> pair in eyoc_icp_batched's fixed order, no fused multiply-add);
+ *            A xi = -g by LDL^T without pivoting in fp64.  A pivot d_k that is not above 2^-30 A_kk (A_kk before elimination) stops
+ *            the pair with its current T and EYOC_ICP_SINGULAR.  Otherwise xi = (alpha, beta, gamma, t),
+ *            U = [Rz(gamma) Ry(beta) Rx(alpha) | t], T = U T.
+ * A non-finite normal sets EYOC_ICP_RANGE for its pair (T = init, nothing searched); a zero normal adds nothing to A and g.
+ * Guarantees as eyoc_icp_batched: all max_iteration + 1 evaluations are enqueued, no floating-point atomics, results[b] is
+ * byte-identical from run to run and to a call on pair b alone. */
+size_t eyoc_icp_plane_workspace_bytes(int n_pairs, int total_src, int total_tgt);
+int eyoc_icp_plane_batched(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const float* tgt_normals_dev,
+                           const int32_t* seg_src_host, const int32_t* seg_tgt_host, int n_pairs, const double* init_dev,
+                           const eyoc_icp_params* params, eyoc_icp_result* results_dev, int32_t* corr_dev, void* workspace_dev,
+                           size_t workspace_bytes, void* stream);
 
 /* Posed nearest neighbour with a gate, for a batch of pairs (lib/trainer.py:1198-1211 without the [n0, n1] sweep).  Added after 111
  * without a bump, additive only.  For every query row of every pair: the target row (LOCAL to the pair) that eyoc_knn2(c = 4) returns for
