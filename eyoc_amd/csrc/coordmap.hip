@@ -488,11 +488,22 @@ __global__ void k_iota(int32_t* __restrict__ out, int n) {
   if (i < n) out[i] = i;
 }
 
+// one coordinate's cell, floor(x / voxel) in fp32; false (and cell 0) outside the key range k_insert accepts and for a NaN: the test is made
+// on the floored quotient, nothing is cast then (a float-to-int conversion makes 0 of a NaN and saturates +-inf)
+__device__ inline bool voxel_cell(float x, float voxel, int& c) {
+  constexpr float LIM = COORD_BIAS - 16;   // k_insert's test
+  const float f = floorf(x / voxel);
+  const bool in = f >= -LIM && f < LIM;
+  c = in ? (int)f : 0;
+  return in;
+}
+
 // voxel coordinates of raw points: floor(x / voxel) in fp32 (IEEE division, like torch / numpy on fp32 input)
 // Packed clouds: point i of cloud b (pt_off[b] <= i < pt_off[b+1]; not read for one cloud) gets batch index batch_base + b, so equal
 // voxels of different clouds never share a key.  The cloud of the workgroup's first point by one binary search, every point's by a
-// forward walk from there (empty clouds only lengthen the walk).  bad (atomicMax of n_clouds - b): the first cloud that holds a point
-// outside the key range k_insert accepts.
+// forward walk from there (empty clouds only lengthen the walk).  A fault is a point with a NaN / inf in x, y or z or with a cell outside
+// the key range (voxel_cell).  bad (atomicMax of n_clouds - b): the first cloud that holds a fault; the row's x
+// is INT_MAX, which k_insert_runs counts.
 // kIsolate: instead, faults[b][0] counts cloud b's finite points outside the key range and faults[b][1] its points with a NaN / inf in
 // x, y or z (atomics from faulty points only); such a point's row holds its cloud and zeros.
 template <bool kIsolate>
@@ -520,20 +531,19 @@ __global__ void k_quantize(const float* __restrict__ xyz, int n, int stride, flo
     while (pt_off[b + 1] <= i) ++b;
   }
   const float* p = xyz + (size_t)i * stride;
-  int4 c = make_int4(batch_base + b, (int)floorf(p[0] / voxel), (int)floorf(p[1] / voxel), (int)floorf(p[2] / voxel));
-  constexpr int LIM = COORD_BIAS - 16;   // k_insert's test
-  const bool out = c.y < -LIM || c.y >= LIM || c.z < -LIM || c.z >= LIM || c.w < -LIM || c.w >= LIM;
-  if constexpr (kIsolate) {
-    const bool finite = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
-    if (!finite || out) {
+  int4 c = make_int4(batch_base + b, 0, 0, 0);
+  const bool inx = voxel_cell(p[0], voxel, c.y), iny = voxel_cell(p[1], voxel, c.z), inz = voxel_cell(p[2], voxel, c.w);
+  if (!(inx && iny && inz)) {
+    if constexpr (kIsolate) {
+      const bool finite = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
       atomicAdd(&faults[2 * b + (finite ? 0 : 1)], 1);
       c = make_int4(batch_base + b, 0, 0, 0);
+    } else {
+      c.y = 0x7fffffff;
+      atomicMax(bad, n_clouds - b);
     }
-    reinterpret_cast<int4*>(coords)[i] = c;
-  } else {
-    reinterpret_cast<int4*>(coords)[i] = c;
-    if (out) atomicMax(bad, n_clouds - b);
   }
+  reinterpret_cast<int4*>(coords)[i] = c;
 }
 
 // k_quantize under the training loader's augmentation (eyoc_voxelize_batched_posed; lib/data_loaders.py:919-920, :931-932, :940-943,

@@ -20,7 +20,8 @@ def sparse_quantize(xyz, voxel_size: float, batch_index: int = 0):
     """First point of every occupied ``voxel_size`` voxel, in input order.
 
     ``xyz``: ``[N,3]`` (or ``[N,4]`` KITTI xyzr) float32, numpy or torch.  Returns device tensors
-    ``(coords int32 [M,4] = (batch, floor(p / voxel)), sel int64 [M])`` with ``sel`` ascending."""
+    ``(coords int32 [M,4] = (batch, floor(p / voxel)), sel int64 [M])`` with ``sel`` ascending.  A NaN or +-inf in x, y or z fails the
+    call with ``EYOC_ERR_RANGE`` (an ``EyocError``), like a point outside the key range."""
     t = xyz if isinstance(xyz, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(xyz, np.float32))
     if not t.is_cuda:
         if not torch.cuda.is_available():

@@ -48,6 +48,8 @@ typedef enum {
  *     eyoc_voxelize_batched_isolating(_workspace_bytes), again found by symbol; nothing that existed changes.
  *     Training batches from raw scans add eyoc_cloud_centroids(_workspace_bytes), eyoc_augment_poses and
  *     eyoc_voxelize_batched_posed(_workspace_bytes) the same way.
+ *     A fix without a new number: eyoc_voxelize and eyoc_voxelize_batched refuse a point with a NaN coordinate (EYOC_ERR_RANGE), which
+ *     earlier libraries of 111 took for cell 0 on that axis; no signature and no output for valid input changes.
  * 110 (round 6): the kernel-selection setters and eyoc_ransac_workspace_bytes take the ctx first (round 5), eyoc_maps_gather_window
  * refuses Z-ordered maps again and eyoc_maps_gather_window_internal exists, eyoc_model_workspace_bytes depends on the maps' size class */
 #define EYOC_VERSION 111
@@ -176,6 +178,7 @@ int eyoc_maps_info(eyoc_ctx* ctx, const eyoc_maps* maps, int conv1_kernel_size, 
  *   xyz f32 rows of `stride` floats (3 = xyz, 4 = KITTI .bin xyzr) -> sel int32 [n_out] = index of the
  *   first point of every occupied voxel, ascending; coords int32 [n_out,4] = (batch_index, floor(p / v)).
  *   Outputs need room for n rows.  Synchronises `stream` once (to return n_out).
+ *   A NaN or +-inf in x, y or z fails the call with EYOC_ERR_RANGE, like a point outside the key range (a fourth float is never read).
  * --------------------------------------------------------------------------------------------- */
 size_t eyoc_voxelize_workspace_bytes(int n_points);
 int eyoc_voxelize(eyoc_ctx* ctx, const float* xyz_dev, int n_points, int stride, float voxel_size, int batch_index,
@@ -196,7 +199,8 @@ int eyoc_voxelize(eyoc_ctx* ctx, const float* xyz_dev, int n_points, int stride,
  *   (batch_base + b, floor(p / v)), xyz_out f32 [.,3] = the kept points' xyz (or NULL: not written);
  *   voxel_offsets (HOST out, int64 [n_clouds+1]) = the clouds' row ranges of the outputs.  Outputs need room for
  *   n_points rows.  A point outside the key range fails the call (EYOC_ERR_RANGE; the message names the first cloud
- *   holding one).  Synchronises `stream` once per call; n_points = 0 launches nothing.
+ *   holding one).  A NaN or +-inf in x, y or z fails the call with EYOC_ERR_RANGE in the same way.  Synchronises `stream` once per
+ *   call; n_points = 0 launches nothing.
  * --------------------------------------------------------------------------------------------- */
 size_t eyoc_voxelize_batched_workspace_bytes(int n_points_total, int n_clouds);
 int eyoc_voxelize_batched(eyoc_ctx* ctx, const float* xyz_dev, int stride, const int64_t* point_offsets, int n_clouds,
