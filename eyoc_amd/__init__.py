@@ -13,6 +13,7 @@ from .model import (load_model, ResUNet2, ResUNetBN2, ResUNetBN2B, ResUNetBN2C, 
                     ResUNetBN2E, ResUNetFatBN, MODELS, ResUNetIN2, ResUNetIN2B, ResUNetIN2C, ResUNetIN2D, ResUNetIN2E,
                     IN_MODELS)
 from .eval import find_nn_gpu, pdist, find_corr, find_correspondences, random_sample, knn1_segmented  # noqa: F401
+from .eval import knn1_mutual_segmented, mutual_correspondences  # noqa: F401
 from .transform_estimation import (est_quad_linear_robust, estimate_transform, pose_estimation,  # noqa: F401
                                    rigid_transform_3d, transform, integrate_trans, est_quad_linear_robust_batched)
 from .registration import (Matcher, registration_ransac_based_on_feature_matching,  # noqa: F401

@@ -241,6 +241,9 @@ PROTOTYPES = {
     "eyoc_maps_select_orders": (_i, [_vp, _i, _i]),
     "eyoc_ransac_select_pruning": (_i, [_vp, _i]),
     "eyoc_ransac_select_generate": (_i, [_vp, _i]),
+    "eyoc_knn1_mutual": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _vp, _vp, _vp, _vp]),
+    "eyoc_knn_mutual_select": (_i, [_vp, _i]),
+    "eyoc_mutual_compact": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _i, _i, _vp, _vp, _vp, _vp]),
     "eyoc_knn_pack_targets": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _vp, _sz, _vp, _vp]),
     "eyoc_registration_accept_degenerate": (_i, [_vp, _i]),
     "eyoc_ransac_transform_store": (_i, [_vp, _i]),

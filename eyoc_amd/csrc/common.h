@@ -98,6 +98,7 @@ struct eyoc_ctx {
     int maps_internal_order = -1;      // eyoc_maps_internal_order: -1 automatic (Z-order from 8192 rows), 0 caller's order, 1 Z-order
     int maps_lazy_tables = 1, maps_fused_levels = 1;          // eyoc_maps_lazy_tables: big Z-ordered batches skip the tables only their record builders read (coordmap.hip)
     int knn_prefilter = 1;             // eyoc_knn_prefilter
+    int knn_mutual = -1;               // eyoc_knn_mutual_select: -1 automatic, 0 two one-way queries, 1 the fused sweep (knn1_mutual_kernel)
     int fuse_tail = 2;                 // eyoc_model_fuse_tail: 2 the 1x1 tail in the epilogue of the last staged layer where that layer allows it (spconv_st.hip TAILF), 1 in one kernel of its own (spconv_tail.hip), 0 two launches
     int sampled_tail = 1;              // eyoc_model_sampled_tail: eyoc_model_forward_rows computes the last 3^3 layer and the 1x1 tail for the listed rows only (0: full forward + row gather)
     int spconv_kernel = -1;            // eyoc_spconv_select_kernel: -1 automatic, 0 workgroup-tiled, 1 wave-private

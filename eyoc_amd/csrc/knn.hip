@@ -8,7 +8,7 @@
 //
 // Arithmetic contract (bit-exact with oracle/matching.py): d = a - b; s = d * d; acc = acc + s in
 // fp32, channels in order, no FMA contraction.
-#include "common.h"
+#include "scan.h"
 
 namespace {
 
@@ -37,6 +37,83 @@ __global__ void knn_transpose_targets(const float* __restrict__ B, SegArgs seg, 
   if (j < nb) v = *reinterpret_cast<const float4*>(B + (size_t)(b0 + j) * C + 4 * c4);
   float* dst = Bt + seg.bt_off[s] + (size_t)(4 * c4) * ld + j;
   dst[0] = v.x; dst[ld] = v.y; dst[2 * (size_t)ld] = v.z; dst[3 * (size_t)ld] = v.w;
+}
+
+// acc[k] = the contract's value for targets 2 k, 2 k + 1 of the group of TGROUP whose channel-major rows start at `col` (wave-uniform,
+// row length ld) against the lane's query `a`: the squared distance, or with DOT -<a, b>.  This is knn1_kernel's own group body, word for word: that kernel keeps its text (and with it the code it
+// was measured with - sharing the function changes its register allocation), knn1_mutual_kernel calls this copy.
+template <int C, bool DOT>
+__device__ __forceinline__ void knn_group_distances(const f32x2 (&a)[C], const float* col, int ld, f32x2 (&acc)[TGROUP / 2]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int k = 0; k < TGROUP / 2; ++k) acc[k] = f32x2{0.0f, 0.0f};
+  // Channels in batches of CB (eight SGPRs per channel).  Scalar loads return out of order, so a wait is always
+  // "all of them": the next batch is therefore issued right AFTER the wait for the current one (behind the first
+  // packed op that needs it) and its latency hides behind the rest of the current batch.
+  constexpr int CB = C >= 8 ? 4 : C / 2;
+  auto load_batch = [&](int cb, f32x2 (&b)[CB][TGROUP / 2]) {
+#pragma unroll
+    for (int c = 0; c < CB; ++c) {
+      const float4 lo = *reinterpret_cast<const float4*>(col + (size_t)(cb + c) * ld);
+      const float4 hi = *reinterpret_cast<const float4*>(col + (size_t)(cb + c) * ld + 4);
+      b[c][0] = f32x2{lo.x, lo.y}; b[c][1] = f32x2{lo.z, lo.w}; b[c][2] = f32x2{hi.x, hi.y}; b[c][3] = f32x2{hi.z, hi.w};
+    }
+  };
+  // the four target pairs side by side, so that dependent packed ops are never back to back (a wait state each)
+  auto channel = [&](int c, const f32x2 (&b)[TGROUP / 2]) {
+    if (DOT) {
+#pragma unroll
+      for (int k = 0; k < TGROUP / 2; ++k) acc[k] = __builtin_elementwise_fma(a[c], -b[k], acc[k]);
+      return;
+    }
+    f32x2 d[TGROUP / 2];
+#pragma unroll
+    for (int k = 0; k < TGROUP / 2; ++k) d[k] = a[c] - b[k];
+#pragma unroll
+    for (int k = 0; k < TGROUP / 2; ++k) d[k] = d[k] * d[k];
+#pragma unroll
+    for (int k = 0; k < TGROUP / 2; ++k) acc[k] = acc[k] + d[k];
+  };
+  f32x2 b0[CB][TGROUP / 2], b1[CB][TGROUP / 2];
+  load_batch(0, b0);
+#pragma unroll
+  for (int cb = 0; cb < C; cb += 2 * CB) {
+    __builtin_amdgcn_sched_barrier(0);
+    channel(cb, b0[0]);                               // forces the wait for batch b0
+    __builtin_amdgcn_sched_barrier(0);
+    load_batch(cb + CB, b1);                          // C is a multiple of 2 CB
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int c = 1; c < CB; ++c) channel(cb + c, b0[c]);
+    __builtin_amdgcn_sched_barrier(0);
+    channel(cb + CB, b1[0]);
+    __builtin_amdgcn_sched_barrier(0);
+    if (cb + 2 * CB < C) load_batch(cb + 2 * CB, b0);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int c = 1; c < CB; ++c) channel(cb + CB + c, b1[c]);
+  }
+}
+
+// what a (query, target) pair competes with: the contract's value of `knn_group_distances` after the mode's own steps
+template <int MODE>
+__device__ __forceinline__ float knn_candidate(float v, int dist_type) {
+#pragma clang fp contract(off)
+  v = dist_type == 1 ? sqrtf(v + 1e-7f) : v;
+  if (MODE == 2) {          // acc = -S exactly (the negated chain rounds symmetrically)
+    const float w = (2.0f - 2.0f * (-v)) + 1e-6f;
+    const float d = sqrtf(w);
+    v = d != d ? -1.0f : d;                                        // NaN first: below every distance
+  }
+  return v;
+}
+
+// the 32 bits above the index in a packed minimum: the value's bits, order-preserving for negative values too where there can be any
+template <bool DOT>
+__device__ __forceinline__ unsigned int knn_key(float v) {
+  unsigned int bits = __float_as_uint(v);
+  if (DOT) bits = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
+  return bits;
 }
 
 // Lane = query (C features in VGPRs); the targets are wave-uniform, so they come through the SCALAR cache
@@ -94,6 +171,8 @@ __global__ __launch_bounds__(256) void knn1_kernel(const float* __restrict__ A, 
   // the four waves of the block take interleaved groups of TGROUP targets
   const float* bt = Bt + seg.bt_off[s];
   for (int t = t_begin + wave * TGROUP; t < t_end; t += 4 * TGROUP) {
+    // (the group body below has a word-for-word COPY, knn_group_distances, which knn1_mutual_kernel calls: a change of the arithmetic
+    // contract here must be made there too - tests/test_gpu_mutual.py compares the two kernels' indices)
     f32x2 acc[TGROUP / 2];
 #pragma unroll
     for (int k = 0; k < TGROUP / 2; ++k) acc[k] = f32x2{0.0f, 0.0f};
@@ -201,11 +280,181 @@ __global__ __launch_bounds__(256) void knn1_kernel(const float* __restrict__ A, 
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Mutual nearest neighbours in one sweep (eyoc_knn1_mutual, route 1).  All three distance forms are symmetric bit for bit -
+// (a - b)^2 = (b - a)^2, and every term of the FMA chain of <a, b> commutes - so d(i, t), computed once as in knn1_kernel, serves
+// the row minimum of query i AND the column minimum of target t: what eyoc_knn1(B, A) would find for row t.  A wave owns 64
+// consecutive targets at a time (the four waves of a block interleave such chunks) and walks them in groups of TGROUP; per group
+// the 64 lanes' candidates (key << 32 | query row) of the eight targets are reduced by a butterfly that halves the targets a lane
+// holds while it doubles the lanes merged (4 + 2 + 1 exchanges, then three more over the upper lane bits: 10 instead of 48), lane
+// l ends with the wave's minimum for target l & 7 and the lanes of group g park theirs.  After eight groups lane l holds target
+// t0 + l, and ONE wave-wide atomicMin goes to 64 consecutive words of colbest (512 contiguous bytes).  Integer minima: the result
+// does not depend on how the grid splits the work, ties go to the lowest row.  A candidate enters the column minimum exactly where
+// the reverse query would have taken it: valid lane, valid target, value < +inf (a NaN compares false in modes 0 and 1; in mode 2
+// it is the -1 of knn_candidate, below every number, and the lowest row wins).
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long p, int d) {
+  const unsigned int lo = __shfl_xor((unsigned int)p, d, 64), hi = __shfl_xor((unsigned int)(p >> 32), d, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long min_u64(unsigned long long x, unsigned long long y) { return y < x ? y : x; }
+
+constexpr int MUT_CHUNK = 64;                    // targets a wave parks before its atomic
+constexpr int MUT_SPLIT_ALIGN = 4 * MUT_CHUNK;   // split boundaries: a whole chunk for each of the block's four waves
+
+template <int C, int MODE>
+__global__ __launch_bounds__(256) void knn1_mutual_kernel(const float* __restrict__ A, const float* __restrict__ Bt, SegArgs seg,
+                                                          int split_len, int dist_type, unsigned long long* __restrict__ best,
+                                                          unsigned long long* __restrict__ colbest) {
+#pragma clang fp contract(off)
+  constexpr bool DOT = MODE != 0;
+  const int s = blockIdx.z;
+  const int a0 = seg.a[s], na = seg.a[s + 1] - a0;
+  const int b0 = seg.b[s], nb = seg.b[s + 1] - b0, ld = seg.ld[s];
+  const int t_begin = blockIdx.y * split_len;
+  const int t_end = min(nb, t_begin + split_len);
+  const int q0 = blockIdx.x * 64;
+  if (t_begin >= t_end || q0 >= na) return;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int q = q0 + lane;
+  const bool q_ok = q < na;
+  f32x2 a[C];   // {a_c, a_c}: the query's feature in both halves of a packed operand
+  {
+    const float4* src = reinterpret_cast<const float4*>(A + (size_t)(a0 + (q_ok ? q : 0)) * C);
+#pragma unroll
+    for (int i = 0; i < C / 4; ++i) {
+      const float4 v = src[i];
+      a[4 * i] = f32x2{v.x, v.x}; a[4 * i + 1] = f32x2{v.y, v.y}; a[4 * i + 2] = f32x2{v.z, v.z}; a[4 * i + 3] = f32x2{v.w, v.w};
+    }
+  }
+  float best_d = __builtin_inff();
+  int best_j = 0x7FFFFFFF;
+  bool any = false;
+  const float* bt = Bt + seg.bt_off[s];
+  for (int t0 = t_begin + wave * MUT_CHUNK; t0 < t_end; t0 += 4 * MUT_CHUNK) {
+    unsigned long long parked = ~0ull;
+#pragma unroll 1
+    for (int g = 0; g < MUT_CHUNK / TGROUP; ++g) {
+      const int t = t0 + g * TGROUP;
+      if (t >= t_end) break;                                           // wave-uniform (ld covers the whole group)
+      f32x2 acc[TGROUP / 2];
+      knn_group_distances<C, DOT>(a, bt + t, ld, acc);
+      __builtin_amdgcn_sched_barrier(0);
+      unsigned long long p[TGROUP];
+#pragma unroll
+      for (int e = 0; e < TGROUP; ++e) {
+        const float v = knn_candidate<MODE>((e & 1) ? acc[e / 2].y : acc[e / 2].x, dist_type);
+        const bool valid = t + e < t_end;
+        const bool better = valid & (v < best_d);
+        best_d = better ? v : best_d;
+        best_j = better ? t + e : best_j;
+        any = any | better;
+        p[e] = (q_ok & valid & (v < __builtin_inff())) ? (((unsigned long long)knn_key<DOT>(v) << 32) | (unsigned)q) : ~0ull;
+      }
+      // w[k]: target 2 k + (lane & 1) over lane pairs; x[k]: target 4 k + (lane & 3) over lane quads; y: target lane & 7 over eight lanes
+      const bool l1 = lane & 1, l2 = lane & 2, l4 = lane & 4;
+      unsigned long long w[TGROUP / 2], x[TGROUP / 4];
+#pragma unroll
+      for (int k = 0; k < TGROUP / 2; ++k) w[k] = min_u64(l1 ? p[2 * k + 1] : p[2 * k], shfl_xor_u64(l1 ? p[2 * k] : p[2 * k + 1], 1));
+#pragma unroll
+      for (int k = 0; k < TGROUP / 4; ++k) x[k] = min_u64(l2 ? w[2 * k + 1] : w[2 * k], shfl_xor_u64(l2 ? w[2 * k] : w[2 * k + 1], 2));
+      unsigned long long y = min_u64(l4 ? x[1] : x[0], shfl_xor_u64(l4 ? x[0] : x[1], 4));
+      y = min_u64(y, shfl_xor_u64(y, 8));
+      y = min_u64(y, shfl_xor_u64(y, 16));
+      y = min_u64(y, shfl_xor_u64(y, 32));
+      parked = (lane >> 3) == g ? y : parked;                          // lane 8 g + e keeps target t0 + 8 g + e
+    }
+    const int tt = t0 + lane;
+    if (tt < t_end && parked != ~0ull) atomicMin(&colbest[b0 + tt], parked);
+  }
+  if (q_ok && any) atomicMin(&best[a0 + q], ((unsigned long long)knn_key<DOT>(best_d) << 32) | (unsigned)best_j);
+}
+
+// flags[i] of row i of segment s: bit 1 = the row has a neighbour j = idx_ab[i], bit 0 = mutual: j has a neighbour too and it is i
+__global__ void knn_mutual_flags(SegArgs seg, const long long* __restrict__ idx_ab, const long long* __restrict__ idx_ba,
+                                 const unsigned char* __restrict__ has_a, const unsigned char* __restrict__ has_b,
+                                 unsigned char* __restrict__ flags) {
+  const int s = blockIdx.z;
+  const int a0 = seg.a[s], na = seg.a[s + 1] - a0, b0 = seg.b[s];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= na) return;
+  unsigned char f = 0;
+  if (has_a[a0 + i]) {                                                 // (then the B segment is not empty and j is one of its rows)
+    const long long j = idx_ab[a0 + i];
+    f = 2 | (has_b[b0 + j] && idx_ba[b0 + j] == i ? 1 : 0);
+  }
+  flags[a0 + i] = f;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Stable per-segment compaction of the mutual rows (eyoc_mutual_compact): counts per segment, the flag scan of scan.h, a fill
+// pass.  No atomics: the output is the same bytes on every run.
+// cnt[s] = rows of segment s the compaction keeps - its mutual rows, or (fewer than min_keep of them) its rows with a neighbour;
+// fallback[s] says which.  One workgroup per segment.
+__global__ __launch_bounds__(SCAN_BLOCK) void k_mutual_count(SegArgs seg, const unsigned char* __restrict__ flags, int min_keep,
+                                                             int* __restrict__ cnt, int* __restrict__ fallback) {
+  const int s = blockIdx.x;
+  const int a0 = seg.a[s], na = seg.a[s + 1] - a0;
+  int m = 0, h = 0;
+  for (int i = threadIdx.x; i < na; i += SCAN_BLOCK) {
+    const unsigned char f = flags[a0 + i];
+    m += f & 1;
+    h += (f >> 1) & 1;
+  }
+  int mt, ht;
+  block_exclusive_scan(m, &mt);
+  block_exclusive_scan(h, &ht);
+  if (threadIdx.x == 0) {
+    const bool fb = mt < min_keep;
+    cnt[s] = fb ? ht : mt;
+    fallback[s] = fb;
+  }
+}
+
+// keep[i] = 1 iff row i stays, loc[i] = its row inside its segment; block (0, 0, 0) also writes seg_out = the running sum of cnt
+__global__ void k_mutual_keep(SegArgs seg, int nseg, const unsigned char* __restrict__ flags, const int* __restrict__ cnt,
+                              const int* __restrict__ fallback, int* __restrict__ keep, int* __restrict__ loc,
+                              int32_t* __restrict__ seg_out) {
+  const int s = blockIdx.z;
+  const int a0 = seg.a[s], na = seg.a[s + 1] - a0;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < na) {
+    const unsigned char f = flags[a0 + i];
+    keep[a0 + i] = fallback[s] ? (f >> 1) & 1 : f & 1;
+    loc[a0 + i] = i;
+  }
+  if (blockIdx.x == 0 && s == 0 && threadIdx.x == 0) {
+    int run = 0;
+    for (int k = 0; k < nseg; ++k) { seg_out[k] = run; run += cnt[k]; }
+    seg_out[nseg] = run;
+  }
+}
+
+// partial: the exclusive scan of the tiles' kept rows (k_scan_partials + k_scan_top, SCAN_ITEMS consecutive rows per thread)
+__global__ __launch_bounds__(SCAN_BLOCK) void k_mutual_fill(const int* __restrict__ keep, const int* __restrict__ loc,
+                                                            const int* __restrict__ partial, const long long* __restrict__ idx_ab,
+                                                            int n, long long* __restrict__ rows, long long* __restrict__ corr) {
+  const int base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
+  int k[SCAN_ITEMS], sum = 0;
+#pragma unroll
+  for (int j = 0; j < SCAN_ITEMS; ++j) { k[j] = base + j < n ? keep[base + j] : 0; sum += k[j]; }
+  int tot;
+  int pos = partial[blockIdx.x] + block_exclusive_scan(sum, &tot);
+#pragma unroll
+  for (int j = 0; j < SCAN_ITEMS; ++j)
+    if (k[j]) {
+      rows[pos] = loc[base + j];
+      corr[pos] = idx_ab[base + j];
+      ++pos;
+    }
+}
+
 __global__ void knn1_unpack(const unsigned long long* __restrict__ best, int n, long long* __restrict__ idx,
-                            float* __restrict__ dist, int dot) {
+                            float* __restrict__ dist, int dot, unsigned char* __restrict__ has = nullptr) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   unsigned long long p = best[i];
+  if (has) has[i] = p != ~0ull;   // (the mutual check: a row without a neighbour reads index 0 like a row whose neighbour is row 0)
   if (p == ~0ull) {  // every candidate compared false (NaN features) or the target set was empty
     if (idx) idx[i] = 0;
     if (dist) dist[i] = __builtin_nanf("");
@@ -601,7 +850,8 @@ extern "C" int eyoc_knn_pack_targets(eyoc_ctx* ctx, const float* B_dev, const in
 
 static int knn_run(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c, const int32_t* seg_a,
                    const int32_t* seg_b, int nseg, int dist_type, int64_t* idx_dev, float* dist_dev, float* second_dev,
-                   void* stream, bool dot = false) {
+                   void* stream, bool dot = false, size_t base = 0, unsigned char* has_dev = nullptr) {
+  // base (a multiple of 256): the first bytes of the ctx's scratch belong to the caller (eyoc_knn1_mutual); has_dev: see knn1_unpack
   EYOC_REQUIRE(ctx && A_dev && B_dev && seg_a && seg_b, EYOC_ERR_INVALID, "eyoc_knn1: NULL argument");
   EYOC_REQUIRE(nseg >= 1 && nseg <= MAX_SEG, EYOC_ERR_INVALID, "eyoc_knn1: nseg %d not in [1,%d]", nseg, MAX_SEG);
   EYOC_REQUIRE(dist_type >= 0 && dist_type <= 2, EYOC_ERR_INVALID, "eyoc_knn1: dist_type %d", dist_type);
@@ -641,14 +891,14 @@ static int knn_run(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c,
   }
   const bool prefilter = prefilter_env != 0 && !dot && !second_dev && !dist_dev && dist_type != 1 && c == 32 && max_nb > 0 &&
                          (waves >= 512 || prefilter_env == 2);   // (round 5: a single pair - 79 waves, each walking all 5000 targets - takes 0.15 ms here against 0.10 in the exact kernel)
-  const size_t off_bt = eyoc::align_up((size_t)n_total * sizeof(unsigned long long));
+  const size_t off_bt = eyoc::align_up(base + (size_t)n_total * sizeof(unsigned long long));
   const size_t off_bm = eyoc::align_up(off_bt + (size_t)bt_floats * sizeof(float) + 64);
   const size_t off_an = eyoc::align_up(off_bm + (prefilter ? (size_t)bm_floats * sizeof(float) : 0));
   const size_t off_fl = eyoc::align_up(off_an + (prefilter ? (size_t)n_total * sizeof(float) : 0));
   const size_t off_bx = eyoc::align_up(off_fl + (prefilter ? (size_t)n_total * sizeof(int) : 0));
   int rc = ctx->ensure_scratch(off_bx + 2 * MAX_SEG * sizeof(int) + 64, st);
   if (rc) return rc;
-  unsigned long long* best = (unsigned long long*)ctx->scratch;
+  unsigned long long* best = (unsigned long long*)((char*)ctx->scratch + base);
   float* Bt = (float*)((char*)ctx->scratch + off_bt);
   EYOC_CHECK_HIP(hipMemsetAsync(best, 0xFF, (size_t)n_total * sizeof(unsigned long long), st));
   const int *only = nullptr, *only_cnt = nullptr;
@@ -685,7 +935,7 @@ static int knn_run(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c,
     }
   }
   hipLaunchKernelGGL(knn1_unpack, dim3(eyoc::cdiv(n_total, 256)), dim3(256), 0, st, best, n_total,
-                     (long long*)idx_dev, dist_dev, dot ? 1 : dist_type == 2 ? 2 : 0);
+                     (long long*)idx_dev, dist_dev, dot ? 1 : dist_type == 2 ? 2 : 0, has_dev);
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
 }
@@ -694,6 +944,158 @@ extern "C" int eyoc_knn1(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, 
                          const int32_t* seg_b, int nseg, int dist_type, int64_t* idx_dev, float* dist_dev,
                          void* stream) {
   return knn_run(ctx, A_dev, B_dev, c, seg_a, seg_b, nseg, dist_type, idx_dev, dist_dev, nullptr, stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// mutual nearest neighbours
+extern "C" int eyoc_knn_mutual_select(eyoc_ctx* ctx, int mode) {
+  if (!ctx) return -1;
+  const int prev = ctx->knobs.knn_mutual;
+  if (mode >= -1 && mode <= 1) ctx->knobs.knn_mutual = mode;
+  return prev + 2;
+}
+
+// what knn_run carves behind `base` for n query rows against the targets seg_b, at most (pre-filter buffers included)
+static size_t knn_scratch_bound(int n, const int32_t* seg_b, int nseg, int c) {
+  long long bt = 0, bm = 0;
+  for (int s = 0; s < nseg; ++s) {
+    const int nb = seg_b[s + 1] - seg_b[s];
+    bt += (long long)((nb + TGROUP - 1) / TGROUP * TGROUP) * c;
+    bm += packed_target_floats(nb);
+  }
+  return eyoc::align_up((size_t)n * 8) + eyoc::align_up((size_t)bt * 4 + 64) + eyoc::align_up((size_t)bm * 4) + 2 * eyoc::align_up((size_t)n * 4) +
+         2 * MAX_SEG * sizeof(int) + 64 + 256;
+}
+
+template <int C>
+static void launch_knn_mutual(const float* A, const float* Bt, const SegArgs& seg, int nseg, int max_na, int max_nb, int dist_type,
+                              unsigned long long* best, unsigned long long* colbest, hipStream_t st) {
+  const int qtiles = eyoc::cdiv(max_na, 64);
+  int nsplit = 4096 / (qtiles * nseg);
+  const int max_splits = eyoc::cdiv(max_nb, MUT_SPLIT_ALIGN);
+  nsplit = nsplit < 1 ? 1 : nsplit > max_splits ? max_splits : nsplit;
+  const int split_len = eyoc::cdiv(eyoc::cdiv(max_nb, nsplit), MUT_SPLIT_ALIGN) * MUT_SPLIT_ALIGN;
+  const dim3 grid(qtiles, eyoc::cdiv(max_nb, split_len), nseg);
+  if (dist_type == 2) hipLaunchKernelGGL((knn1_mutual_kernel<C, 2>), grid, dim3(256), 0, st, A, Bt, seg, split_len, 0, best, colbest);
+  else hipLaunchKernelGGL((knn1_mutual_kernel<C, 0>), grid, dim3(256), 0, st, A, Bt, seg, split_len, dist_type, best, colbest);
+}
+
+extern "C" int eyoc_knn1_mutual(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c, const int32_t* seg_a, const int32_t* seg_b,
+                                int nseg, int dist_type, int64_t* idx_ab_dev, int64_t* idx_ba_dev, uint8_t* mutual_dev, void* stream) {
+  EYOC_REQUIRE(ctx && A_dev && B_dev && seg_a && seg_b, EYOC_ERR_INVALID, "eyoc_knn1_mutual: NULL argument");
+  EYOC_REQUIRE(nseg >= 1 && nseg <= MAX_SEG, EYOC_ERR_INVALID, "eyoc_knn1_mutual: nseg %d not in [1,%d]", nseg, MAX_SEG);
+  EYOC_REQUIRE(dist_type >= 0 && dist_type <= 2, EYOC_ERR_INVALID, "eyoc_knn1_mutual: dist_type %d", dist_type);
+  EYOC_REQUIRE(c == 4 || c == 16 || c == 32 || c == 64 || c == 128, EYOC_ERR_INVALID,
+               "eyoc_knn1_mutual: feature dimension %d not supported (4/16/32/64/128)", c);
+  EYOC_REQUIRE(seg_a[0] == 0 && seg_b[0] == 0, EYOC_ERR_INVALID, "eyoc_knn1_mutual: seg_a[0] and seg_b[0] must be 0");
+  hipStream_t st = (hipStream_t)stream;
+  SegArgs seg;
+  int max_na = 0, max_nb = 0, max_ld = 0;
+  long long bt_floats = 0;
+  for (int s = 0; s <= nseg; ++s) { seg.a[s] = seg_a[s]; seg.b[s] = seg_b[s]; }
+  for (int s = 0; s < nseg; ++s) {
+    const int na = seg_a[s + 1] - seg_a[s], nb = seg_b[s + 1] - seg_b[s];
+    EYOC_REQUIRE(na >= 0 && nb >= 0, EYOC_ERR_INVALID, "eyoc_knn1_mutual: negative segment length");
+    max_na = na > max_na ? na : max_na;
+    max_nb = nb > max_nb ? nb : max_nb;
+    seg.ld[s] = (nb + TGROUP - 1) / TGROUP * TGROUP;
+    seg.bt_off[s] = bt_floats;
+    bt_floats += (long long)seg.ld[s] * c;
+    max_ld = seg.ld[s] > max_ld ? seg.ld[s] : max_ld;
+  }
+  const int n_a = seg_a[nseg], n_b = seg_b[nseg];
+  if (n_a == 0 && (n_b == 0 || !idx_ba_dev)) return EYOC_OK;
+  EYOC_REQUIRE((n_a == 0 || (idx_ab_dev && mutual_dev)), EYOC_ERR_INVALID, "eyoc_knn1_mutual: NULL output");
+  // the ctx's scratch: [has_a | has_b | idx_ba when the caller wants none] in front, then either route's own buffers
+  const size_t off_hb = eyoc::align_up((size_t)n_a);
+  const size_t off_ba = eyoc::align_up(off_hb + (size_t)n_b);
+  const size_t base = eyoc::align_up(off_ba + (idx_ba_dev ? 0 : (size_t)n_b * sizeof(int64_t)));
+  const size_t need0 = knn_scratch_bound(n_a, seg_b, nseg, c), need1 = knn_scratch_bound(n_b, seg_a, nseg, c);
+  int rc = ctx->ensure_scratch(base + (need0 > need1 ? need0 : need1) + eyoc::align_up((size_t)n_b * 8), st);   // (no call below grows it: the front survives)
+  if (rc) return rc;
+  unsigned char* has_a = (unsigned char*)ctx->scratch;
+  unsigned char* has_b = has_a + off_hb;
+  long long* idx_ba = idx_ba_dev ? (long long*)idx_ba_dev : (long long*)((char*)ctx->scratch + off_ba);
+  // auto, as measured (EXPERIMENTS.md "Mutual nearest-neighbour filter"): the fused sweep for c = 32 queries that do not fill the chip in
+  // either direction (< 512 waves of MF_ROWS rows: eyoc_knn1 runs its exact kernel there, twice; a single 5000 x 5000 pair: 0.19 against
+  // 0.30 ms), two one-way queries where the MFMA pre-filter carries them (64 pairs: 1.4 against 4.6 ms) and for every shape class that
+  // was not measured (other widths, whose fused kernel spills)
+  long long waves_a = 0, waves_b = 0;
+  for (int s = 0; s < nseg; ++s) {
+    waves_a += eyoc::cdiv(seg_a[s + 1] - seg_a[s], MF_ROWS);
+    waves_b += eyoc::cdiv(seg_b[s + 1] - seg_b[s], MF_ROWS);
+  }
+  const int route = ctx->knobs.knn_mutual >= 0 ? ctx->knobs.knn_mutual : (c == 32 && waves_a < 512 && waves_b < 512) ? 1 : 0;
+  if (route == 0 || max_na == 0 || max_nb == 0) {
+    // both one-way queries as eyoc_knn1 runs them (a side without rows has nothing to write)
+    if (n_a) rc = knn_run(ctx, A_dev, B_dev, c, seg_a, seg_b, nseg, dist_type, idx_ab_dev, nullptr, nullptr, stream, false, base, has_a);
+    if (rc) return rc;
+    if (n_b) rc = knn_run(ctx, B_dev, A_dev, c, seg_b, seg_a, nseg, dist_type, (int64_t*)idx_ba, nullptr, nullptr, stream, false, base, has_b);
+    if (rc) return rc;
+  } else {
+    unsigned long long* best = (unsigned long long*)((char*)ctx->scratch + base);
+    unsigned long long* colbest = (unsigned long long*)((char*)ctx->scratch + eyoc::align_up(base + (size_t)n_a * 8));
+    float* Bt = (float*)((char*)ctx->scratch + eyoc::align_up(eyoc::align_up(base + (size_t)n_a * 8) + (size_t)n_b * 8));
+    EYOC_CHECK_HIP(hipMemsetAsync(best, 0xFF, (size_t)n_a * 8, st));
+    EYOC_CHECK_HIP(hipMemsetAsync(colbest, 0xFF, (size_t)n_b * 8, st));
+    hipLaunchKernelGGL(knn_transpose_targets, dim3(eyoc::cdiv((long long)max_ld * (c / 4), 256), 1, nseg), dim3(256), 0, st, B_dev, seg, c, Bt);
+    switch (c) {
+      case 4: launch_knn_mutual<4>(A_dev, Bt, seg, nseg, max_na, max_nb, dist_type, best, colbest, st); break;
+      case 16: launch_knn_mutual<16>(A_dev, Bt, seg, nseg, max_na, max_nb, dist_type, best, colbest, st); break;
+      case 32: launch_knn_mutual<32>(A_dev, Bt, seg, nseg, max_na, max_nb, dist_type, best, colbest, st); break;
+      case 64: launch_knn_mutual<64>(A_dev, Bt, seg, nseg, max_na, max_nb, dist_type, best, colbest, st); break;
+      default: launch_knn_mutual<128>(A_dev, Bt, seg, nseg, max_na, max_nb, dist_type, best, colbest, st); break;
+    }
+    hipLaunchKernelGGL(knn1_unpack, dim3(eyoc::cdiv(n_a, 256)), dim3(256), 0, st, best, n_a, (long long*)idx_ab_dev, (float*)nullptr, 0, has_a);
+    hipLaunchKernelGGL(knn1_unpack, dim3(eyoc::cdiv(n_b, 256)), dim3(256), 0, st, colbest, n_b, idx_ba, (float*)nullptr, 0, has_b);
+  }
+  if (n_a)
+    hipLaunchKernelGGL(knn_mutual_flags, dim3(eyoc::cdiv(max_na, 256), 1, nseg), dim3(256), 0, st, seg, (const long long*)idx_ab_dev,
+                       (const long long*)idx_ba, (const unsigned char*)has_a, (const unsigned char*)has_b, (unsigned char*)mutual_dev);
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
+extern "C" int eyoc_mutual_compact(eyoc_ctx* ctx, const int64_t* idx_ab_dev, const uint8_t* mutual_dev, const int32_t* seg_a, int nseg,
+                                   int min_keep, int64_t* rows_dev, int64_t* corr_dev, int32_t* seg_out_dev, void* stream) {
+  EYOC_REQUIRE(ctx && seg_a && seg_out_dev, EYOC_ERR_INVALID, "eyoc_mutual_compact: NULL argument");
+  EYOC_REQUIRE(nseg >= 1 && nseg <= MAX_SEG, EYOC_ERR_INVALID, "eyoc_mutual_compact: nseg %d not in [1,%d]", nseg, MAX_SEG);
+  EYOC_REQUIRE(min_keep >= 0 && seg_a[0] == 0, EYOC_ERR_INVALID, "eyoc_mutual_compact: min_keep %d, seg_a[0] %d", min_keep, seg_a[0]);
+  hipStream_t st = (hipStream_t)stream;
+  SegArgs seg = {};
+  int max_na = 0;
+  for (int s = 0; s <= nseg; ++s) seg.a[s] = seg_a[s];
+  for (int s = 0; s < nseg; ++s) {
+    const int na = seg_a[s + 1] - seg_a[s];
+    EYOC_REQUIRE(na >= 0, EYOC_ERR_INVALID, "eyoc_mutual_compact: negative segment length");
+    max_na = na > max_na ? na : max_na;
+  }
+  const int n = seg_a[nseg];
+  if (n == 0) {
+    EYOC_CHECK_HIP(hipMemsetAsync(seg_out_dev, 0, (size_t)(nseg + 1) * sizeof(int32_t), st));
+    return EYOC_OK;
+  }
+  EYOC_REQUIRE(idx_ab_dev && mutual_dev && rows_dev && corr_dev, EYOC_ERR_INVALID, "eyoc_mutual_compact: NULL argument");
+  const int tiles = eyoc::cdiv(n, SCAN_TILE);
+  const size_t off_keep = eyoc::align_up(2 * MAX_SEG * sizeof(int));
+  const size_t off_loc = eyoc::align_up(off_keep + (size_t)n * sizeof(int));
+  const size_t off_part = eyoc::align_up(off_loc + (size_t)n * sizeof(int));
+  int rc = ctx->ensure_scratch(off_part + (size_t)(tiles + 2) * sizeof(int), st);
+  if (rc) return rc;
+  int* cnt = (int*)ctx->scratch;
+  int* fallback = cnt + MAX_SEG;
+  int* keep = (int*)((char*)ctx->scratch + off_keep);
+  int* loc = (int*)((char*)ctx->scratch + off_loc);
+  int* partial = (int*)((char*)ctx->scratch + off_part);     // [tiles] + the total behind them
+  hipLaunchKernelGGL(k_mutual_count, dim3(nseg), dim3(SCAN_BLOCK), 0, st, seg, (const unsigned char*)mutual_dev, min_keep, cnt, fallback);
+  hipLaunchKernelGGL(k_mutual_keep, dim3(eyoc::cdiv(max_na, 256), 1, nseg), dim3(256), 0, st, seg, nseg, (const unsigned char*)mutual_dev,
+                     (const int*)cnt, (const int*)fallback, keep, loc, seg_out_dev);
+  hipLaunchKernelGGL(k_scan_partials, dim3(tiles), dim3(SCAN_BLOCK), 0, st, (const int*)keep, n, partial);
+  hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(SCAN_BLOCK), 0, st, partial, tiles, partial + tiles);
+  hipLaunchKernelGGL(k_mutual_fill, dim3(tiles), dim3(SCAN_BLOCK), 0, st, (const int*)keep, (const int*)loc, (const int*)partial,
+                     (const long long*)idx_ab_dev, n, (long long*)rows_dev, (long long*)corr_dev);
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
 }
 
 extern "C" int eyoc_dotmax(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c, const int32_t* seg_a,

@@ -11,6 +11,7 @@ materialised and ``nn_max_n`` (a memory knob that never changes the result) is a
 from __future__ import annotations
 
 import ctypes as C
+import threading
 
 import numpy as np
 import torch
@@ -70,6 +71,120 @@ def knn1_segmented(A: torch.Tensor, B: torch.Tensor, seg_a, seg_b, dist_type="Sq
                                              _lib.stream_ptr()),
                        "eyoc_knn1")
     return (idx, dist) if return_distance else idx
+
+
+def _mutual_chunks(seg_a, seg_b):
+    """``_segment_chunks`` for the mutual search, whose outputs are per A row AND per B row: yield ``(a0, b0, sa, sb, ns)`` per launch
+    with both ``sa`` and ``sb`` re-based to the chunk's first rows.  A chunk with an empty side has nothing to search (indices 0, no
+    flags - what the outputs are initialised to) and is skipped."""
+    nseg = len(seg_a) - 1
+    for s0 in range(0, nseg, MAX_SEGMENTS):
+        ns = min(MAX_SEGMENTS, nseg - s0)
+        a0, b0 = int(seg_a[s0]), int(seg_b[s0])
+        if int(seg_a[s0 + ns]) == a0 or int(seg_b[s0 + ns]) == b0:
+            continue
+        sa = (C.c_int32 * (ns + 1))(*[int(v) - a0 for v in seg_a[s0:s0 + ns + 1]])
+        sb = (C.c_int32 * (ns + 1))(*[int(v) - b0 for v in seg_b[s0:s0 + ns + 1]])
+        yield a0, b0, sa, sb, ns
+
+
+def _knn1_mutual_flags(A, B, seg_a, seg_b, dist_type, want_reverse):
+    """``eyoc_knn1_mutual`` over every chunk -> ``(A, idx_ab, flags uint8 [len(A)], idx_ba or None)``; ``flags`` as the library writes
+    them (bit 0 mutual, bit 1 the row has a neighbour - ``eyoc_mutual_compact``'s fallback reads it)."""
+    if dist_type not in _DIST:
+        raise NotImplementedError('Not implemented')
+    A = _cuda_f32(A)
+    B = _cuda_f32(B, A.device)
+    if A.shape[1] != B.shape[1]:
+        raise ValueError("feature dimensions differ")
+    if int(seg_a[-1]) != A.shape[0] or int(seg_b[-1]) != B.shape[0] or len(seg_a) != len(seg_b):
+        raise ValueError("seg_a / seg_b must cover A / B with the same number of segments")
+    idx_ab = torch.zeros(A.shape[0], dtype=torch.int64, device=A.device)
+    flags = torch.zeros(A.shape[0], dtype=torch.uint8, device=A.device)
+    idx_ba = torch.zeros(B.shape[0], dtype=torch.int64, device=A.device) if want_reverse else None
+    with torch.cuda.device(A.device):
+        for a0, b0, sa, sb, ns in _mutual_chunks(seg_a, seg_b):
+            _lib.check(_lib.load().eyoc_knn1_mutual(_lib.ctx(A.device.index), _lib.ptr(A[a0:]), _lib.ptr(B[b0:]), A.shape[1], sa, sb, ns,
+                                                    _DIST[dist_type], _lib.ptr(idx_ab[a0:]), _lib.ptr(idx_ba[b0:]) if want_reverse else None,
+                                                    _lib.ptr(flags[a0:]), _lib.stream_ptr()), "eyoc_knn1_mutual")
+    return A, idx_ab, flags, idx_ba
+
+
+def knn1_mutual_segmented(A, B, seg_a, seg_b, dist_type="SquareL2", return_reverse=False):
+    """``knn1_segmented`` with the reciprocity check, per segment, on the device: ``idx_ab int64 [len(A)]`` - exactly
+    ``knn1_segmented(A, B)``'s indices -, ``mutual bool [len(A)]`` - row ``i`` has a neighbour ``j = idx_ab[i]``, ``j`` has one among
+    the segment's A rows, and that is ``i`` (ties to the lowest index both ways; a row without a neighbour - empty B segment, NaN
+    features - reads index 0 and is never mutual) - and with ``return_reverse`` ``idx_ba int64 [len(B)]``, exactly
+    ``knn1_segmented(B, A, seg_b, seg_a)``'s.  One library call per 128 segments (``eyoc_knn1_mutual``)."""
+    _, idx_ab, flags, idx_ba = _knn1_mutual_flags(A, B, seg_a, seg_b, dist_type, return_reverse)
+    mutual = (flags & 1).to(torch.bool)
+    return (idx_ab, mutual, idx_ba) if return_reverse else (idx_ab, mutual)
+
+
+def mutual_compact_device(idx_ab, flags, seg_a, min_keep=0):
+    """``eyoc_mutual_compact`` on ``_knn1_mutual_flags``' outputs, nothing read back: ``(rows int64, corr int64, seg_out int32
+    [nseg + 1])`` on the device; only the first ``seg_out[-1]`` entries of ``rows`` / ``corr`` (both ``[len(A)]``) mean anything."""
+    n, nseg, dev = idx_ab.shape[0], len(seg_a) - 1, idx_ab.device
+    rows = torch.empty(n, dtype=torch.int64, device=dev)
+    corr = torch.empty(n, dtype=torch.int64, device=dev)
+    outs = []
+    with torch.cuda.device(dev):
+        for s0 in range(0, nseg, MAX_SEGMENTS):
+            ns = min(MAX_SEGMENTS, nseg - s0)
+            a0 = int(seg_a[s0])
+            sa = (C.c_int32 * (ns + 1))(*[int(v) - a0 for v in seg_a[s0:s0 + ns + 1]])
+            so = torch.empty(ns + 1, dtype=torch.int32, device=dev)
+            _lib.check(_lib.load().eyoc_mutual_compact(_lib.ctx(dev.index), _lib.ptr(idx_ab[a0:]), _lib.ptr(flags[a0:]), sa, ns, int(min_keep),
+                                                       _lib.ptr(rows[a0:]), _lib.ptr(corr[a0:]), _lib.ptr(so), _lib.stream_ptr()),
+                       "eyoc_mutual_compact")
+            outs.append((a0, so))
+    if len(outs) == 1:
+        return rows, corr, outs[0][1]
+    # several launches: every chunk's kept rows sit at the chunk's first A row; move them back to back (device-side, no counts on the host)
+    counts = torch.cat([so[1:] - so[:-1] for _, so in outs])
+    seg_out = torch.cat((counts.new_zeros(1), torch.cumsum(counts, 0).to(torch.int32)))
+    k = torch.arange(n, device=dev)
+    src = torch.zeros(n, dtype=torch.int64, device=dev)
+    for (a0, so), s0 in zip(outs, range(0, nseg, MAX_SEGMENTS)):
+        # output position p in [seg_out[s0], seg_out[s0] + so[-1]) reads the chunk's entry a0 + p - seg_out[s0]
+        lo = seg_out[s0].to(torch.int64)
+        inside = (k >= lo) & (k < lo + so[-1].to(torch.int64))
+        src = torch.where(inside, k - lo + a0, src)
+    return rows[src], corr[src], seg_out
+
+
+_PINNED_SEG: dict = {}
+
+
+def read_back_segments(seg_out_dev, buf=None):
+    """``seg_out`` on the host (a numpy copy): an asynchronous copy into pinned memory and an event wait - this stream only, no device
+    synchronisation.  ``buf``: the caller's own pinned ``int32`` staging (the pipeline keeps one per slot); without it a buffer cached
+    per (thread, device, length) - the copy and the read of it happen inside this call, so no two callers ever share one in flight."""
+    n = seg_out_dev.numel()
+    if buf is None:
+        key = (threading.get_ident(), seg_out_dev.device.index, n)
+        buf = _PINNED_SEG.get(key)
+        if buf is None:
+            buf = _PINNED_SEG[key] = torch.empty(n, dtype=torch.int32, pin_memory=True)
+    buf = buf[:n]
+    buf.copy_(seg_out_dev, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record()
+    ev.synchronize()
+    return buf.numpy().copy()
+
+
+def mutual_correspondences(A, B, seg_a, seg_b, dist_type="SquareL2", min_keep=0):
+    """The mutual nearest neighbours of every segment, compacted in order: ``rows int64 [m]`` (row inside its A segment), ``corr int64
+    [m]`` (its neighbour, inside the B segment) on the device and ``seg_out`` (numpy ``int32 [nseg + 1]``): segment ``s`` owns
+    ``[seg_out[s], seg_out[s + 1])``.  A segment with fewer than ``min_keep`` mutual rows keeps all of its rows that have a neighbour
+    (Open3D's fallback with ``min_keep = ransac_n``); 0: no fallback.  ``seg_out`` is the one read-back, and the only wait."""
+    A, idx_ab, flags, _ = _knn1_mutual_flags(A, B, seg_a, seg_b, dist_type, False)
+    with torch.cuda.device(A.device):
+        rows, corr, seg_dev = mutual_compact_device(idx_ab, flags, seg_a, min_keep)
+        seg_out = read_back_segments(seg_dev)
+    m = int(seg_out[-1])
+    return rows[:m], corr[:m], seg_out
 
 
 def gather_rows(F: torch.Tensor, sel: torch.Tensor, G: torch.Tensor | None = None, beta: float = 0.0) -> torch.Tensor:

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, icp
+from . import eval as ev
 from . import registration as reg
 from .eval import gather_rows, knn1_segmented
 from .isolate import batch_drop, remap_rows
@@ -67,10 +68,17 @@ class RegistrationConfig:
     icp_method: str = "point"
     icp_normal_radius: float | None = None
     icp_normal_max_nn: int = 30
+    # RANSAC route only: the reciprocity check of Open3D's ``mutual_filter`` between the feature search and the back-end - RANSAC runs on
+    # the source points whose neighbour's own nearest source point is them (all of a pair's correspondences when fewer than 4 are
+    # reciprocal); ``fitness`` is over the correspondences used.  One host wait per step for the kept counts (an event, not a device
+    # synchronisation).  SC2-PCR resamples to a fixed ``num_node``: a filter in front of it is a separate design, asking for it raises
+    mutual_filter: bool = False
 
     def __post_init__(self):
         if self.icp_method not in ("point", "plane"):
             raise ValueError(f"icp_method = {self.icp_method!r}: \"point\" or \"plane\"")
+        if self.mutual_filter and not self.use_RANSAC:
+            raise ValueError("mutual_filter is implemented for the RANSAC route only (use_RANSAC=True)")
 
 
 # ``RegistrationResult.status`` / ``PendingStep.status`` bit: the pair's step overflowed split16 and was registered again in fp32
@@ -365,13 +373,15 @@ class MapsHandle(NamedTuple):
 class _Step:
     """What ONE enqueued step produced (``RegistrationPipeline._step``).  Nothing of it is on the pipeline: ``_publish`` makes a step
     "the last step", a retry hands its step to whoever asked for it."""
-    __slots__ = ("slot", "timers", "batch", "F", "featured", "matched", "nn_idx", "result", "icp", "words", "host", "icp_host", "done")
+    __slots__ = ("slot", "timers", "batch", "F", "featured", "matched", "nn_idx", "kept_rows", "kept_seg", "result", "icp", "words", "host",
+                 "icp_host", "done")
 
     def __init__(self, slot, timers):
         self.slot, self.timers = slot, timers      # the buffer set the step uses; its four stage-timer events (None: not timed)
         self.batch = self.F = None                 # the batch the step actually ran on (isolate_failures: reduced) and its features
         self.featured = self.matched = None        # events: the forward is enqueued / forward and matching are enqueued
         self.nn_idx = None                         # RANSAC path: the feature correspondences on the device
+        self.kept_rows = self.kept_seg = None      # mutual_filter: the source rows RANSAC ran on (device, row inside its pair) and their segments (host, [P + 1])
         self.result = self.icp = None              # the back-end's records on the device; icp_refine: the ``eyoc_icp_result`` records
         self.words = self.host = self.icp_host = self.done = None    # the read-back, when it was enqueued with the step
 
@@ -691,8 +701,26 @@ class RegistrationPipeline:
         F0, F1 = self._sampled_halves(step)                        # the sampled rows (+ descriptor blend, if any)
         # isolate_failures: a dropped pair is an empty segment - for the neighbour search, which gives the live rows what the live
         # segments alone give (tests/test_gpu_isolate_batch.py), and for the back-end, where it keeps the pair's slot and every seed
-        step.nn_idx = knn1_segmented(F0, F1, batch.seg, batch.seg, "SquareL2", return_distance=False)
+        src, seg_src = batch.xyz0.reshape(-1, 3), batch.seg
+        if self.cfg.mutual_filter:
+            # nn_idx stays the full forward result; RANSAC gets the kept source rows, their neighbours and their segments
+            _, step.nn_idx, flags, _ = ev._knn1_mutual_flags(F0, F1, batch.seg, batch.seg, "SquareL2", False)
+            rows, corr, seg_dev = ev.mutual_compact_device(step.nn_idx, flags, batch.seg, min_keep=4)
+        else:
+            step.nn_idx = corr = knn1_segmented(F0, F1, batch.seg, batch.seg, "SquareL2", return_distance=False)
         self._matched(step)
+        if self.cfg.mutual_filter:
+            # the step's one extra host wait: this stream's event behind a copy into the slot's own pinned staging
+            step.kept_seg = seg_src = ev.read_back_segments(seg_dev, self._pinned_set(step.slot, seg_dev))
+            m = int(seg_src[-1])
+            counts = (seg_dev[1:] - seg_dev[:-1]).to(torch.int64)
+            # the pairs' first rows on the device: uploaded once per batch (keyed by the ``seg`` object, like ``_sel01``)
+            cached = batch.__dict__.get("_seg_first")
+            if cached is None or cached[0] is not batch.seg:
+                cached = batch.__dict__["_seg_first"] = (batch.seg, torch.as_tensor(np.asarray(batch.seg[:-1], np.int64)).to(F.device))
+            first = cached[1]
+            step.kept_rows, corr = rows[:m], corr[:m]
+            src = src[step.kept_rows + torch.repeat_interleave(first, counts, output_size=m)]
         # all pairs in one batched call (pair p samples with seed + p, exactly like a per-pair loop would)
         # (the scratch budget - a quarter of the free memory, a driver round trip - is asked for once per pipeline: any launch-chunk
         # size gives the same records)
@@ -700,7 +728,7 @@ class RegistrationPipeline:
             self._ransac_budget = reg._ransac_budget(F.device)
         with self._accept_degenerate(F.device):
             res = reg.ransac_batched_from_correspondences(
-                batch.xyz0.reshape(-1, 3), batch.xyz1.reshape(-1, 3), step.nn_idx, batch.seg, batch.seg,
+                src, batch.xyz1.reshape(-1, 3), corr, seg_src, batch.seg,
                 self.cfg.voxel_size * 1.0, self.cfg.ransac_max_iteration, seed=seed,
                 workspace_budget=self._ransac_budget)                                  # [P, 84] bytes on the device
         if self.cfg.icp_refine:
@@ -747,7 +775,8 @@ class RegistrationPipeline:
                 self.model.spconv_math = "fp32"
                 return self.register(batch, seed, False, maps)
         if self.cfg.use_RANSAC:
-            results = [reg.decode_ransac_result(host[p], batch.n_points) for p in range(batch.P)]
+            used = np.full(batch.P, batch.n_points) if step.kept_seg is None else np.diff(step.kept_seg)      # mutual_filter: fitness over the kept rows
+            results = [reg.decode_ransac_result(host[p], int(used[p])) for p in range(batch.P)]
         else:
             Th = host.numpy().astype(np.float64)
             results = [reg.RegistrationResult(Th[p], 0.0, 0.0) for p in range(batch.P)]

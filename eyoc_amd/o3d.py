@@ -10,8 +10,9 @@ CorrespondenceCheckerBasedOnDistance(d)], RANSACConvergenceCriteria(4000000, 100
     import eyoc_amd.o3d as o3d
 
 those lines run unchanged; the work happens in ``libeyoc_hip.so`` (``eyoc_amd.registration``).  Only what that call site
-touches exists here - this is not an Open3D re-implementation: other estimation methods, ``ransac_n != 4`` and
-``mutual_filter=True`` raise ``NotImplementedError``, unknown checkers raise ``TypeError``.
+touches exists here - this is not an Open3D re-implementation: other estimation methods and ``ransac_n != 4`` raise
+``NotImplementedError``, unknown checkers raise ``TypeError``.  ``mutual_filter=True`` (the reference passes False) keeps the reciprocal
+feature matches only, all of them when fewer than ``ransac_n`` are reciprocal, like Open3D.
 
 ``o3d.pipelines.registration.registration_icp(pcd0, pcd1, 0.2, np.eye(4), TransformationEstimationPointToPoint(),
 ICPConvergenceCriteria(max_iteration=200))`` and ``pcd0.transform(reg.transformation)`` (``lib/data_loaders.py:497-507``) and the legacy
@@ -114,7 +115,8 @@ RegistrationResult = _reg.RegistrationResult
 def registration_ransac_based_on_feature_matching(source, target, source_feature, target_feature, mutual_filter,
                                                   max_correspondence_distance, estimation_method=None, ransac_n=3, checkers=(),
                                                   criteria=None, seed=0):
-    """Positional layout of Open3D >= 0.12 (the 5th argument is ``mutual_filter``).  ``seed`` is an extension: Open3D draws
+    """Positional layout of Open3D >= 0.12 (the 5th argument is ``mutual_filter``: RANSAC over the reciprocal matches, ``fitness`` over
+    the correspondences used - ``eyoc_amd.registration``).  ``seed`` is an extension: Open3D draws
     from ``std::random_device``; here hypothesis ``h`` samples with the counter hash of ``oracle/ransac.py``."""
     if not isinstance(source, PointCloud) or not isinstance(target, PointCloud):
         raise TypeError("source / target must be eyoc_amd.o3d.geometry.PointCloud")

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .eval import _cuda_f32, knn1_segmented
+from .eval import _cuda_f32, knn1_segmented, mutual_correspondences
 from .transform_estimation import transform
 
 
@@ -101,17 +101,24 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
     ``source/target``: ``[n,3]`` points (numpy or torch); ``*_feature``: ``[n,C]`` rows (the layout of
     the model output - not Open3D's transposed ``[C,n]``).  ``criteria = (max_iteration, confidence)``:
     like Open3D >= 0.12 with the reference's ``confidence = 10000`` (clamped to 1), every iteration
-    runs.  Correspondences are the feature-space nearest neighbours of the source points."""
-    if mutual_filter:
-        raise NotImplementedError("mutual_filter=True is not used by the reference path")
+    runs.  Correspondences are the feature-space nearest neighbours of the source points.
+
+    ``mutual_filter=True`` (the reference passes False): only the source points whose neighbour's own nearest source point is
+    them keep their correspondence (``eval.mutual_correspondences``); with fewer than ``ransac_n`` of them every correspondence
+    stays, as in Open3D.  RANSAC then runs on the kept source rows alone, in their order, and ``fitness`` is inliers over the
+    correspondences actually used."""
     if ransac_n != 4:
         raise NotImplementedError("ransac_n must be 4 (scripts/test_kitti.py:174)")
     F0 = _cuda_f32(source_feature)
     F1 = _cuda_f32(target_feature, F0.device)
-    idx = knn1_segmented(F0, F1, [0, F0.shape[0]], [0, F1.shape[0]], "SquareL2", return_distance=False)
-    return ransac_from_correspondences(torch.as_tensor(np.asarray(source)) if not isinstance(source, torch.Tensor) else source,
-                                       torch.as_tensor(np.asarray(target)) if not isinstance(target, torch.Tensor) else target,
-                                       idx, max_correspondence_distance, int(criteria[0]), seed, edge_similarity)
+    source = torch.as_tensor(np.asarray(source)) if not isinstance(source, torch.Tensor) else source
+    target = torch.as_tensor(np.asarray(target)) if not isinstance(target, torch.Tensor) else target
+    if mutual_filter:
+        rows, idx, _ = mutual_correspondences(F0, F1, [0, F0.shape[0]], [0, F1.shape[0]], "SquareL2", min_keep=ransac_n)
+        source = _cuda_f32(source, F0.device)[rows]
+    else:
+        idx = knn1_segmented(F0, F1, [0, F0.shape[0]], [0, F1.shape[0]], "SquareL2", return_distance=False)
+    return ransac_from_correspondences(source, target, idx, max_correspondence_distance, int(criteria[0]), seed, edge_similarity)
 
 
 class Matcher:
@@ -140,9 +147,12 @@ class Matcher:
                                  float(self.nms_radius), int(self.num_iterations), int(self.max_points),
                                  int(self.k1), int(self.k2)), n_seed
 
-    def match_pair(self, src_keypts, tgt_keypts, src_features, tgt_features, rng=None):
+    def match_pair(self, src_keypts, tgt_keypts, src_features, tgt_features, rng=None, mutual=False):
         """:280-305.  ``rng`` replaces the reference's global ``np.random`` for the resampling to
-        ``num_node`` (with replacement).  The nearest neighbour is the reference's own quantity,
+        ``num_node`` (with replacement).  ``mutual=True`` (an extension, off by default) keeps only the reciprocal matches of the
+        same GemmL2 search, in source order, without a fallback - possibly none.  The constructor's ``use_mutual`` does NOT
+        switch it on: the reference stores that flag and never reads it (:23), its default is True, and honouring it would
+        change every result of this class; it stays inert here too.  The nearest neighbour is the reference's own quantity,
         ``argmin_j sqrt(2 - 2 <s_i,t_j> + 1e-6)`` (:296-298, ``eyoc_knn1`` dist_type 2): for descriptors that are not
         unit-norm that is an arg-max of the inner product, not an L2 neighbour, and a NaN (inner product above 1)
         wins the row at its first occurrence - both reproduced."""
@@ -157,6 +167,9 @@ class Matcher:
         tgt_desc = tgt_features[:, tgt_sel_ind, :]
         src_keypts = src_keypts[:, src_sel_ind, :]
         tgt_keypts = tgt_keypts[:, tgt_sel_ind, :]
+        if mutual:
+            rows, idx, _ = mutual_correspondences(src_desc[0], tgt_desc[0], [0, src_desc.shape[1]], [0, tgt_desc.shape[1]], "GemmL2")
+            return src_keypts[:, rows.to(src_keypts.device)], tgt_keypts[:, idx.to(tgt_keypts.device)]
         idx = knn1_segmented(src_desc[0], tgt_desc[0], [0, src_desc.shape[1]], [0, tgt_desc.shape[1]],
                              "GemmL2", return_distance=False)
         return src_keypts, tgt_keypts[:, idx.to(tgt_keypts.device)]
@@ -220,9 +233,9 @@ class Matcher:
         T, fit, n_seed = self.SC2_PCR_packed(src, tgt, np.concatenate([[0], np.cumsum(ns)]))
         return [(T[b], fit[b, :n_seed[b]]) for b in range(len(ns))]
 
-    def estimator(self, src_keypts, tgt_keypts, src_features, tgt_features, rng=None):
-        """:386-413 -> ``(T, labels, src_corr, tgt_corr, seedwise_fitness)``."""
-        src_corr, tgt_corr = self.match_pair(src_keypts, tgt_keypts, src_features, tgt_features, rng)
+    def estimator(self, src_keypts, tgt_keypts, src_features, tgt_features, rng=None, mutual=False):
+        """:386-413 -> ``(T, labels, src_corr, tgt_corr, seedwise_fitness)``.  ``mutual``: see ``match_pair``."""
+        src_corr, tgt_corr = self.match_pair(src_keypts, tgt_keypts, src_features, tgt_features, rng, mutual)
         pred_trans, fitness = self.SC2_PCR(src_corr, tgt_corr)
         warp = transform(src_corr, pred_trans.to(src_corr.device))
         distance = torch.sum((warp - tgt_corr) ** 2, dim=-1) ** 0.5

@@ -545,6 +545,34 @@ int eyoc_knn1(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c, cons
               const int32_t* seg_b, int nseg, int dist_type, int64_t* idx_dev, float* dist_dev,
               void* stream);
 
+/* Mutual nearest neighbours (additive to EYOC_VERSION 111; no counterpart in the reference, whose use_mutual is stored and never read,
+ * scripts/SC2_PCR/SC2_PCR.py:23 - this is the reciprocity check Open3D's registration_ransac_based_on_feature_matching applies with
+ * mutual_filter = true).  Same argument rules, arithmetic and tie rule as eyoc_knn1 (host seg arrays, nseg <= 128, c in
+ * {4, 16, 32, 64, 128}, dist_type 0 / 1 / 2, scratch on the ctx); seg_a[0] = seg_b[0] = 0.
+ *   idx_ab int64 [na]: byte for byte what eyoc_knn1(A, B) writes (local to the B segment);
+ *   idx_ba int64 [nb] (NULL: not wanted): byte for byte what eyoc_knn1(B, A) with the segments swapped writes (local to the A segment);
+ *   mutual uint8 [na]: bit 1 = row i has a neighbour at all (some comparison of its row succeeded: the B segment is not empty and, for
+ *     dist_type 0 / 1, some distance is a number below +inf), bit 0 = it is mutual: j = idx_ab[i] has a neighbour too and idx_ba[j] = i.
+ *     So 0 = no neighbour (its index reads 0 like a true neighbour 0, and it is never mutual), 2 = a neighbour that prefers another
+ *     row, 3 = mutual; eyoc_mutual_compact's fallback needs bit 1.
+ * All three distance forms are symmetric bit for bit, so the two routes give identical bytes: eyoc_knn_mutual_select mode 0 runs
+ * eyoc_knn1's machinery in both directions (its MFMA pre-filter included where eyoc_knn1 would use it), 1 one fused sweep that takes the
+ * row and the column minima from every distance it computes (knn.hip knn1_mutual_kernel), -1 (default) picks as measured - the fused sweep for c = 32
+ * queries below 512 waves of 64 rows in both directions (a single pair), two one-way queries for everything else
+ * (EXPERIMENTS.md "Mutual nearest-neighbour filter").  Any other mode only queries; returns the previous mode + 2 (1, 2 or 3), -1 without a
+ * ctx.  Per ctx; for tests and profiling. */
+int eyoc_knn1_mutual(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c, const int32_t* seg_a, const int32_t* seg_b,
+                     int nseg, int dist_type, int64_t* idx_ab_dev, int64_t* idx_ba_dev, uint8_t* mutual_dev, void* stream);
+int eyoc_knn_mutual_select(eyoc_ctx* ctx, int mode);
+/* Stable per-segment compaction of eyoc_knn1_mutual's result: the mutual rows of every segment in their order, back to back -
+ * rows int64 (the row INSIDE its A segment), corr int64 (its idx_ab, local to the B segment), both [na] of which the first
+ * seg_out[nseg] entries are written; seg_out int32 [nseg + 1] on the DEVICE: segment s owns [seg_out[s], seg_out[s + 1]).  A segment with
+ * fewer than min_keep mutual rows keeps all of its rows that have a neighbour instead (Open3D: fewer than ransac_n correspondences
+ * survive the mutual filter -> the original set); min_keep 0: no fallback.  A count pass, a flag scan and a fill pass: no atomics, no
+ * read-back, the same bytes on every run.  seg_a: host array, seg_a[0] = 0, nseg <= 128; scratch on the ctx. */
+int eyoc_mutual_compact(eyoc_ctx* ctx, const int64_t* idx_ab_dev, const uint8_t* mutual_dev, const int32_t* seg_a, int nseg,
+                        int min_keep, int64_t* rows_dev, int64_t* corr_dev, int32_t* seg_out_dev, void* stream);
+
 /* Row gather: out[i,:] = F[sel[i], 0:c] (F rows are `ld` floats apart) - the `F[inds]` of
  * scripts/test_kitti.py:30-35,159-160 and of Matcher.match_pair (scripts/SC2_PCR/SC2_PCR.py:291-294).
  * With G_dev != NULL (f32 [n,c]) the gathered row is blended and re-normalised,
