@@ -269,6 +269,8 @@ PROTOTYPES = {
                                       _vp, _vp, _sz, _vp]),
     "eyoc_normals_workspace_bytes": (_sz, [_i, _i]),
     "eyoc_normals_batched": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, C.c_double, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "eyoc_fpfh_workspace_bytes": (_sz, [_i, _i, _i]),
+    "eyoc_fpfh_batched": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _i, C.c_double, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "eyoc_icp_plane_workspace_bytes": (_sz, [_i, _i, _i]),
     "eyoc_icp_plane_batched": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _vp, C.POINTER(IcpParams), _vp,
                                     _vp, _vp, _sz, _vp]),

@@ -19,7 +19,13 @@ ICPConvergenceCriteria(max_iteration=200))`` and ``pcd0.transform(reg.transforma
 ``o3d.registration.registration_icp`` of ``scripts/SC2_PCR/benchmark_utils.py:52-54`` run unchanged as well (``eyoc_amd.icp``);
 ``TransformationEstimationPointToPoint(with_scaling=True)`` and point-to-plane raise ``NotImplementedError``.  Point-to-plane ICP itself
 exists (``eyoc_amd.icp.registration_icp_point_to_plane``, with ``estimate_normals`` for the target's normals); this shim keeps refusing
-``TransformationEstimationPointToPlane`` because its ``PointCloud`` carries no normals to hand over.
+``TransformationEstimationPointToPlane``: its ``PointCloud`` carries normals for the FPFH route below only.
+
+The hand-crafted descriptor of ``scripts/SC2_PCR/dataset.py:66-74`` runs as written too: ``pcd.estimate_normals(
+o3d.geometry.KDTreeSearchParamHybrid(radius, max_nn))`` and ``o3d.pipelines.registration.compute_fpfh_feature(pcd,
+o3d.geometry.KDTreeSearchParamHybrid(radius, max_nn))`` (``eyoc_amd.fpfh``; the result is a ``Feature`` with ``[33, n]`` float64 ``data``).
+The normals point to the origin (Open3D leaves the sign to the eigen-solver), and FPFH depends on that sign.  Only the hybrid search
+parameter exists.
 """
 from __future__ import annotations
 
@@ -44,15 +50,38 @@ class PointCloud:
     def __init__(self, points=None):
         self.points = np.zeros((0, 3)) if points is None else _vector3d(points)
         self.colors = np.zeros((0, 3))
+        self.normals = np.zeros((0, 3))
+
+    def has_normals(self):
+        return len(self.normals) == len(self.points) and len(self.points) > 0
+
+    def estimate_normals(self, search_param=None):
+        """``normals`` <- ``eyoc_amd.icp.estimate_normals`` (float64 ``[n, 3]``, towards the origin); the hybrid search parameter only."""
+        from . import icp as _icp
+        if not isinstance(search_param, KDTreeSearchParamHybrid):
+            raise NotImplementedError("estimate_normals needs a KDTreeSearchParamHybrid(radius, max_nn)")
+        n = _icp.estimate_normals(np.asarray(self.points, np.float32), search_param.radius, search_param.max_nn)
+        self.normals = n.cpu().numpy().astype(np.float64)
+        return self
 
     def __len__(self):
         return len(self.points)
 
     def transform(self, T):
-        """In place, like Open3D: ``points <- R points + t``."""
+        """In place, like Open3D: ``points <- R points + t``, ``normals <- R normals`` (where the cloud carries normals)."""
         T = np.asarray(T, np.float64)
         self.points = self.points @ T[:3, :3].T + T[:3, 3]
+        if len(self.normals):
+            self.normals = np.asarray(self.normals, np.float64) @ T[:3, :3].T
         return self
+
+
+class KDTreeSearchParamHybrid:
+    """``o3d.geometry.KDTreeSearchParamHybrid``: the neighbours inside ``radius``, at most the ``max_nn`` nearest."""
+
+    def __init__(self, radius, max_nn):
+        self.radius = float(radius)
+        self.max_nn = int(max_nn)
 
 
 class Feature:
@@ -112,6 +141,32 @@ class RANSACConvergenceCriteria:
 RegistrationResult = _reg.RegistrationResult
 
 
+def compute_fpfh_feature(input, search_param):
+    """``o3d.pipelines.registration.compute_fpfh_feature``: the cloud must carry normals (``estimate_normals``) -> ``Feature`` with
+    ``data`` ``[33, n]`` float64, the fp32 rows of ``eyoc_amd.fpfh.compute_fpfh_feature`` widened."""
+    from . import fpfh as _fpfh
+    if not isinstance(input, PointCloud):
+        raise TypeError("input must be eyoc_amd.o3d.geometry.PointCloud")
+    if not isinstance(search_param, KDTreeSearchParamHybrid):
+        raise NotImplementedError("compute_fpfh_feature needs a KDTreeSearchParamHybrid(radius, max_nn)")
+    if not input.has_normals():
+        raise RuntimeError("compute_fpfh_feature: the cloud has no normals (call estimate_normals first)")
+    rows = _fpfh.compute_fpfh_feature(np.asarray(input.points, np.float32), search_param.radius, search_param.max_nn,
+                                      normals=np.asarray(input.normals, np.float32))
+    f = Feature()
+    f.data = np.ascontiguousarray(rows.cpu().numpy().astype(np.float64).T)
+    return f
+
+
+def _knn_rows(feature):
+    """``[dim, n]`` float64 -> ``[n, dim]`` float32 rows; FPFH's 33 columns are padded with zeros to 64, a width the neighbour search takes
+    (zero columns change no distance)."""
+    rows = np.ascontiguousarray(feature.data.T, np.float32)
+    if rows.shape[1] == 33:
+        rows = np.concatenate([rows, np.zeros((rows.shape[0], 31), np.float32)], 1)
+    return rows
+
+
 def registration_ransac_based_on_feature_matching(source, target, source_feature, target_feature, mutual_filter,
                                                   max_correspondence_distance, estimation_method=None, ransac_n=3, checkers=(),
                                                   criteria=None, seed=0):
@@ -145,7 +200,7 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
         raise ValueError("features and points disagree in length")
     return _reg.registration_ransac_based_on_feature_matching(
         np.asarray(source.points, np.float32), np.asarray(target.points, np.float32),
-        np.ascontiguousarray(source_feature.data.T, np.float32), np.ascontiguousarray(target_feature.data.T, np.float32),
+        _knn_rows(source_feature), _knn_rows(target_feature),
         mutual_filter, float(max_correspondence_distance), None, ransac_n, None, (criteria.max_iteration, criteria.confidence),
         seed=seed, edge_similarity=edge)
 
@@ -169,7 +224,7 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
                                  float(max_correspondence_distance), np.eye(4) if init is None else init, estimation_method, criteria)
 
 
-geometry = types.SimpleNamespace(PointCloud=PointCloud)
+geometry = types.SimpleNamespace(PointCloud=PointCloud, KDTreeSearchParamHybrid=KDTreeSearchParamHybrid)
 utility = types.SimpleNamespace(Vector3dVector=_vector3d)
 pipelines = types.SimpleNamespace(registration=types.SimpleNamespace(
     Feature=Feature, TransformationEstimationPointToPoint=TransformationEstimationPointToPoint,
@@ -178,5 +233,5 @@ pipelines = types.SimpleNamespace(registration=types.SimpleNamespace(
     RANSACConvergenceCriteria=RANSACConvergenceCriteria, RegistrationResult=RegistrationResult,
     registration_ransac_based_on_feature_matching=registration_ransac_based_on_feature_matching,
     TransformationEstimationPointToPlane=TransformationEstimationPointToPlane, ICPConvergenceCriteria=ICPConvergenceCriteria,
-    registration_icp=registration_icp))
+    registration_icp=registration_icp, compute_fpfh_feature=compute_fpfh_feature))
 registration = pipelines.registration      # the pre-0.10 module path scripts/SC2_PCR/benchmark_utils.py:52-54 uses

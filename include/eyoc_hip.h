@@ -994,6 +994,42 @@ int eyoc_normals_batched(eyoc_ctx* ctx, const float* pts_dev, const int32_t* seg
                          float* normals_dev, int32_t* count_dev, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes,
                          void* stream);
 
+/* FPFH descriptors for a batch of clouds.  Added after 111 without a bump, additive only.
+ * Open3D's compute_fpfh_feature(pcd, KDTreeSearchParamHybrid(radius, max_nn)) restated as a contract of this library (parity unpinned:
+ * Open3D is not part of any build here; tests/fpfh_restatement.py is the fp64 statement the kernels are held to).  Clouds, segments
+ * and status as eyoc_normals_batched; normals_dev f32 [total][3] are the caller's (eyoc_normals_batched's point to the origin; Open3D's
+ * are unoriented unless the caller orients them, and FPFH depends on the orientation).  For every row i of a cloud:
+ *   list      L_i = the first max_nn rows of the SAME cloud with d2 < radius * radius by (d2, j) ascending - eyoc_normals_batched's list,
+ *             the same fp64 arithmetic, the same cell edge, entry for entry.  N_i = L_i without row i itself, in list order, k_i = |N_i|,
+ *             0 <= k_i <= max_nn - 1.  Open3D drops "the first entry" instead: the same unless a duplicate of the point sorts ahead of
+ *             the row, where Open3D pairs the row with itself and loses the duplicate.  ONE corner departs from "L_i without row i":
+ *             max_nn or more duplicates ahead of the row push it out of L_i, and N_i is then the first max_nn - 1 entries of L_i, not
+ *             all max_nn of them.  So k_i <= max_nn - 1 holds everywhere, and in that corner alone N_i is not eyoc_normals_batched's
+ *             list without the row.
+ *   pair      (p1, n1) = row i, (p2, n2) = row j, fp64, every operation rounded on its own, dots and squared norms as (x + y) + z:
+ *             d = p2 - p1, len = |d|; len == 0 -> (0, 0, 0).  a1 = n1.d / len, a2 = n2.d / len.  acos|a1| > acos|a2| (strict): swap n1 and
+ *             n2, negate d, f2 = -a2; otherwise f2 = a1.  v = d x n1; |v| == 0 -> (0, 0, 0); v /= |v|, w = n1 x v, f1 = v.n2,
+ *             f0 = atan2(w.n2, n1.n2).  A feature of (0, 0, 0) is binned like any other (a zero normal ends there).
+ *   SPFH      b0 = clamp(floor(11 (f0 + pi) / (2 pi)), 0, 10), b1 = 11 + clamp(floor(11 (f1 + 1) / 2), 0, 10), b2 = 22 + the same of
+ *             f2; cnt_i[33] integer counts over N_i; S_i[b] = cnt_i[b] * (100 / k_i), one division and one product; k_i = 0: S_i = 0.
+ *   FPFH      W_i[b] = sum over j in N_i with d2_ij > 0 of S_j[b] / d2_ij and G_i[g] = the sum of the same terms over the 11 bins of
+ *             group g = b / 11, both added neighbour by neighbour in list order and, inside a neighbour, bin by bin ascending;
+ *             F_i[b] = W_i[b] * (G_i[g] != 0 ? 100 / G_i[g] : 0) + S_i[b]; k_i = 0: F_i = 0.
+ *   output    float32(F_i[b]); with normalize != 0 float32(F_i[b] / (sqrt(sum_b F_i[b]^2) + 1e-6)), the sum over b ascending, all fp64
+ *             (scripts/SC2_PCR/dataset.py's feature / (norm + 1e-6) on Open3D's float64 rows, rounded once).
+ * out_dev f32 [total][out_stride], out_stride 33 or 64 (columns 33..63 are zeros: eyoc_knn1 takes c = 64, and zero columns change no
+ * distance); hist_dev uint8 [total][33] = cnt_i, or NULL; count_dev int32 [total] = k_i, or NULL.  status_dev[b] = EYOC_ICP_RANGE for a
+ * cloud with a non-finite point, a non-finite normal or a cell outside [-2^17, 2^17): zero rows, zero counts, nothing of it is searched,
+ * the other clouds keep their bytes.  EYOC_ERR_INVALID for a radius that is not positive and finite, max_nn outside [2, 128] (counts fit
+ * a byte; a radius-only search is not built) or a stride other than 33 / 64.  Caller-owned 256-byte aligned workspace of
+ * eyoc_fpfh_workspace_bytes (it holds every row's list: 12 bytes x (max_nn - 1) per row), EYOC_ERR_WORKSPACE before any write when it is
+ * short; no allocation, no read-back, no host synchronisation, no floating-point atomics; every 64-cloud chunk builds its own grid.  A
+ * cloud's bytes are the same from run to run, alone, and at any place in a batch. */
+size_t eyoc_fpfh_workspace_bytes(int n_clouds, int total, int max_nn);
+int eyoc_fpfh_batched(eyoc_ctx* ctx, const float* pts_dev, const float* normals_dev, const int32_t* seg_host, int n_clouds, double radius,
+                      int max_nn, int normalize, int out_stride, float* out_dev, uint8_t* hist_dev, int32_t* count_dev,
+                      int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Point-to-plane ICP for a batch of pairs.  Added after 111 without a bump, additive only.
  * Open3D's registration_icp with TransformationEstimationPointToPlane restated (parity unpinned).  Call shape, segments, params (flags
  * 0), records, corr_dev and workspace rules are eyoc_icp_batched's; tgt_normals_dev f32 [total_tgt][3] is added (NULL only with no
