@@ -15,7 +15,11 @@
 // loss (pos_d2, and dist of the chosen candidate) are then evaluated once more with an fp64 accumulator and rounded to fp32 once:
 // an fp32 chain over 64 channels is up to 8 ulp from the exact value, and the stage tests hold these values to one ulp of fp64.
 // The triplet losses of the reference's other two trainers follow below the hardest-contrastive entry points, on the same table and search;
-// the random-negative contrastive loss of the base trainer comes last, on the same table.
+// the random-negative contrastive loss of the base trainer comes last, on the same table.  Those two share one backward (a sorted
+// contribution list and rows_kernel, between the hardest-contrastive and the triplet part); the hardest-contrastive backward stays apart: it
+// finds a row's entries without a sort and forms its products in fp32 before widening, so moving it onto the list would change its bytes.
+#include <type_traits>
+
 #include "pose_math.h"
 
 using namespace eyoc;
@@ -86,6 +90,52 @@ __device__ inline int wave_sum_i(int v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
   return v;  // valid in lane 0
+}
+
+// f(std::integral_constant<int, C>) for the feature width C = c of a call (16, 32 or 64, checked by every entry point)
+template <typename F>
+void for_width(int c, F&& f) {
+  if (c == 16) f(std::integral_constant<int, 16>());
+  else if (c == 32) f(std::integral_constant<int, 32>());
+  else f(std::integral_constant<int, 64>());
+}
+
+// The ordered sum of a final kernel (one workgroup of HC_THREADS): thread t adds the partials of the workgroups t, t + 256, ... by
+// add(b, v, c), wave_sum, lane 0 of every wave to LDS, thread 0 adds the waves in order.  True in thread 0 alone, which holds the totals.
+template <int ND, int NI, typename Add>
+__device__ inline bool block_sum_ordered(int nblk, Add add, double (&v)[ND], int (&c)[NI]) {
+  __shared__ double red_d[HC_WAVES][ND];
+  __shared__ int red_i[HC_WAVES][NI];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < ND; ++k) v[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < NI; ++k) c[k] = 0;
+  for (int b = threadIdx.x; b < nblk; b += HC_THREADS) add(b, v, c);
+#pragma unroll
+  for (int k = 0; k < ND; ++k) v[k] = wave_sum(v[k]);
+#pragma unroll
+  for (int k = 0; k < NI; ++k) c[k] = wave_sum_i(c[k]);
+  if (lane == 0) {
+    for (int k = 0; k < ND; ++k) red_d[wave][k] = v[k];
+    for (int k = 0; k < NI; ++k) red_i[wave][k] = c[k];
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return false;
+  for (int k = 0; k < ND; ++k) v[k] = 0.0;
+  for (int k = 0; k < NI; ++k) c[k] = 0;
+  for (int x = 0; x < HC_WAVES; ++x) {
+    for (int k = 0; k < ND; ++k) v[k] += red_d[x][k];
+    for (int k = 0; k < NI; ++k) c[k] += red_i[x][k];
+  }
+  return true;
+}
+
+// the opening of every backward: both gradients zeroed (an empty matrix has no buffer)
+int zero_gradients(float* dF0, int n0, float* dF1, int n1, int c, hipStream_t st) {
+  if (n0 > 0) EYOC_CHECK_HIP(hipMemsetAsync(dF0, 0, (size_t)n0 * c * sizeof(float), st));
+  if (n1 > 0) EYOC_CHECK_HIP(hipMemsetAsync(dF1, 0, (size_t)n1 * c * sizeof(float), st));
+  return EYOC_OK;
 }
 
 __device__ inline bool key_member(const HcWs& w, unsigned long long key1) {
@@ -348,33 +398,15 @@ __global__ __launch_bounds__(64) void hc_terms_kernel(const float* __restrict__ 
 
 __global__ __launch_bounds__(HC_THREADS) void hc_final_kernel(int n_used, HcWs w, eyoc_hcloss_record* __restrict__ out) {
 #pragma clang fp contract(off)
-  __shared__ double red_d[HC_WAVES][3];
-  __shared__ int red_i[HC_WAVES][2];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double v[3] = {0.0, 0.0, 0.0};
-  int c[2] = {0, 0};
-  for (int b = threadIdx.x; b < w.nwg; b += HC_THREADS) {
+  double sum[3];
+  int cnt[2];
+  const auto add = [&](int b, double (&v)[3], int (&c)[2]) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) v[k] += w.part_sum[(size_t)k * w.nwg + b];
 #pragma unroll
     for (int k = 0; k < 2; ++k) c[k] += w.part_cnt[(size_t)k * w.nwg + b];
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) v[k] = wave_sum(v[k]);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) c[k] = wave_sum_i(c[k]);
-  if (lane == 0) {
-    for (int k = 0; k < 3; ++k) red_d[wave][k] = v[k];
-    for (int k = 0; k < 2; ++k) red_i[wave][k] = c[k];
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  double sum[3] = {0.0, 0.0, 0.0};
-  int cnt[2] = {0, 0};
-  for (int x = 0; x < HC_WAVES; ++x) {
-    for (int k = 0; k < 3; ++k) sum[k] += red_d[x][k];
-    for (int k = 0; k < 2; ++k) cnt[k] += red_i[x][k];
-  }
+  };
+  if (!block_sum_ordered(w.nwg, add, sum, cnt)) return;
   eyoc_hcloss_record r;
   r.sum_pos = sum[0]; r.sum01 = sum[1]; r.sum10 = sum[2];
   r.n_used = n_used; r.k01 = cnt[0]; r.k10 = cnt[1];
@@ -544,12 +576,10 @@ int launch_prep_search(const float* F0, int n0, const float* F1, int n1, int c, 
   tiles = tiles < 1 ? 1 : tiles;
   zs = zs > tiles ? tiles : zs;
   const dim3 grid(w.nwg, 2, zs);
-#define HC_SEARCH(CC) \
-  hipLaunchKernelGGL((hc_search_kernel<CC>), grid, dim3(HC_THREADS), 0, st, F0, n0, F1, n1, P, n_pairs, U, n_used, S0, s0, S1, s1, w)
-  if (c == 16) HC_SEARCH(16);
-  else if (c == 32) HC_SEARCH(32);
-  else HC_SEARCH(64);
-#undef HC_SEARCH
+  for_width(c, [&](auto cc) {
+    hipLaunchKernelGGL((hc_search_kernel<decltype(cc)::value>), grid, dim3(HC_THREADS), 0, st, F0, n0, F1, n1, P, n_pairs, U, n_used, S0, s0,
+                       S1, s1, w);
+  });
   return EYOC_OK;
 }
 
@@ -611,13 +641,10 @@ int eyoc_hcloss_forward(eyoc_ctx* ctx, const float* F0, int n0, const float* F1,
   const long long* S1 = (const long long*)sel1;
   if (int rc = launch_prep_search(F0, n0, F1, n1, c, P, n_pairs, U, n_used, S0, s0, S1, s1, w, st)) return rc;
   const dim3 grid_terms(w.nwg, 2);
-#define HC_TERMS(CC)                                                                                                               \
-  hipLaunchKernelGGL((hc_terms_kernel<CC>), grid_terms, dim3(64), 0, st, F0, n0, F1, n1, P, n_pairs, U, n_used, S0, s0, S1, s1, pos_thresh, \
-                     neg_thresh, w)
-  if (c == 16) HC_TERMS(16);
-  else if (c == 32) HC_TERMS(32);
-  else HC_TERMS(64);
-#undef HC_TERMS
+  for_width(c, [&](auto cc) {
+    hipLaunchKernelGGL((hc_terms_kernel<decltype(cc)::value>), grid_terms, dim3(64), 0, st, F0, n0, F1, n1, P, n_pairs, U, n_used, S0, s0, S1,
+                       s1, pos_thresh, neg_thresh, w);
+  });
   hipLaunchKernelGGL(hc_final_kernel, dim3(1), dim3(HC_THREADS), 0, st, n_used, w, record_out);
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
@@ -636,18 +663,14 @@ int eyoc_hcloss_backward(eyoc_ctx* ctx, const float* F0, int n0, const float* F1
   const long long* U = (const long long*)used;
   const long long* S0 = (const long long*)sel0;
   const long long* S1 = (const long long*)sel1;
-  if (n0 > 0) EYOC_CHECK_HIP(hipMemsetAsync(dF0, 0, (size_t)n0 * c * sizeof(float), st));
-  if (n1 > 0) EYOC_CHECK_HIP(hipMemsetAsync(dF1, 0, (size_t)n1 * c * sizeof(float), st));
+  if (int rc = zero_gradients(dF0, n0, dF1, n1, c, st)) return rc;
   if (n_used == 0) return EYOC_OK;   // no positive, no contribution
   hipLaunchKernelGGL(hc_weights_kernel, dim3(cdiv(n_used, HC_THREADS)), dim3(HC_THREADS), 0, st, P, n_pairs, U, n_used, S0, s0, S1, s1, n0,
                      n1, pos_thresh, neg_thresh, g_pos, g_neg, w);
   const dim3 grid(2 * n_used, 2);
-#define HC_ROWS(CC) \
-  hipLaunchKernelGGL((hc_rows_kernel<CC>), grid, dim3(HC_THREADS), 0, st, F0, F1, P, U, S0, S1, n_used, w, dF0, dF1)
-  if (c == 16) HC_ROWS(16);
-  else if (c == 32) HC_ROWS(32);
-  else HC_ROWS(64);
-#undef HC_ROWS
+  for_width(c, [&](auto cc) {
+    hipLaunchKernelGGL((hc_rows_kernel<decltype(cc)::value>), grid, dim3(HC_THREADS), 0, st, F0, F1, P, U, S0, S1, n_used, w, dF0, dF1);
+  });
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
 }
@@ -655,12 +678,112 @@ int eyoc_hcloss_backward(eyoc_ctx* ctx, const float* F0, int n0, const float* F1
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// The backward the triplet and the contrastive losses share: a weights kernel of the loss writes one contribution entry per (term,
+// destination row), sort_and_sum_rows sorts (destination, entry number) stably and rows_kernel sums every run of equal destinations.
+namespace {
+
+// the destination of an entry as a sort key: 0 is the empty entry and sorts ahead of every row
+__host__ __device__ inline unsigned int contrib_key(unsigned int row, int matrix) { return 2u * row + (unsigned int)matrix + 1u; }
+__host__ __device__ inline int key_matrix(unsigned int key) { return (int)((key - 1u) & 1u); }
+__host__ __device__ inline size_t key_row(unsigned int key) { return (size_t)((key - 1u) >> 1); }
+
+struct Contrib {
+  int ncon;                    // entries
+  unsigned int *key, *key_s;   // contrib_key of the destination; sorted
+  int *idx, *idx_s;            // entry numbers; sorted along
+  float *w, *w2;               // the factor of an entry; its second factor (0: none), NULL in a list of one factor
+  int *r, *r2;                 // the rows of the OTHER matrix they scale the difference to
+  void* sort_tmp;
+  size_t sort_bytes;
+  const unsigned int* status;  // the status word of the loss's record (set by the loss's carve)
+};
+
+Contrib carve_contrib(Carver& cv, int ncon, bool two_factors) {
+  Contrib l;
+  const size_t nc = (size_t)ncon;
+  l.ncon = ncon;
+  l.key = cv.take<unsigned int>(nc);
+  l.key_s = cv.take<unsigned int>(nc);
+  l.idx = cv.take<int>(nc);
+  l.idx_s = cv.take<int>(nc);
+  l.w = cv.take<float>(nc);
+  l.w2 = two_factors ? cv.take<float>(nc) : nullptr;
+  l.r = cv.take<int>(nc);
+  l.r2 = two_factors ? cv.take<int>(nc) : nullptr;
+  l.sort_bytes = align_up(sort_rows_tmp_bytes(ncon, 32));
+  l.sort_tmp = cv.take<char>(l.sort_bytes);
+  l.status = nullptr;
+  return l;
+}
+
+// what follows the HcWs a loss's workspace starts with
+Carver carver_behind(const HcWs& hc, void* base, size_t bytes) {
+  return Carver(base ? (char*)base + hc.total : nullptr, bytes > hc.total ? bytes - hc.total : 0);
+}
+
+// One workgroup per position of the sorted list.  The first position of a run of equal destinations does the row: C lanes take one entry
+// (lane = channel), 256 / C entries side by side, entry k of the run goes to slot k mod (256 / C), fp64 accumulators, the slots are added
+// in order and rounded once.  Every other position leaves after two loads, so the list is read a bounded number of times however long a
+// run is.  TWO: the entries carry a second factor and row.  (The loop bound is q < ncon - k, not k + q < ncon: with the latter the compiler
+// indexes key_s from k + q in every step instead of stepping a pointer, +1.2 % on the kernel at 3.2 M entries.)
+template <int C, bool TWO>
+__global__ __launch_bounds__(HC_THREADS) void rows_kernel(const float* __restrict__ F0, const float* __restrict__ F1, Contrib l,
+                                                          float* __restrict__ dF0, float* __restrict__ dF1) {
+#pragma clang fp contract(off)
+  constexpr int G = HC_THREADS / C;
+  __shared__ double slot_acc[HC_THREADS];
+  const int k = blockIdx.x;
+  const unsigned int key = l.key_s[k];
+  if (key == 0u) return;
+  if (k > 0 && l.key_s[k - 1] == key) return;
+  const int m = key_matrix(key);
+  const size_t row = key_row(key);
+  const int slot = threadIdx.x / C, ch = threadIdx.x % C;
+  const float* __restrict__ FO = m ? F0 : F1;   // the other matrix
+  const double own = (double)(m ? F1 : F0)[row * C + ch];
+  double acc = 0.0;
+  for (int q = slot; q < l.ncon - k && l.key_s[k + q] == key; q += G) {
+    const int e = l.idx_s[k + q];
+    acc += (double)l.w[e] * (own - (double)FO[(size_t)l.r[e] * C + ch]);
+    if constexpr (TWO) {
+      const float wn = l.w2[e];
+      if (wn != 0.0f) acc += (double)wn * (own - (double)FO[(size_t)l.r2[e] * C + ch]);
+    }
+  }
+  slot_acc[threadIdx.x] = acc;
+  __syncthreads();
+  if (threadIdx.x >= C) return;
+  double total = 0.0;
+#pragma unroll
+  for (int g = 0; g < G; ++g) total += slot_acc[g * C + threadIdx.x];
+  float* __restrict__ dF = m ? dF1 : dF0;
+  dF[row * C + threadIdx.x] = *l.status ? __builtin_nanf("") : (float)total;
+}
+
+// the end of a backward, after the loss's weights kernel: the sort and the row sums
+template <bool TWO>
+int sort_and_sum_rows(const Contrib& l, const float* F0, int n0, const float* F1, int n1, int c, float* dF0, float* dF1, hipStream_t st) {
+  // as many bits as the greatest key has; equal keys keep their entry order (a radix sort is stable)
+  const unsigned long long top = contrib_key((unsigned int)(n0 > n1 ? n0 : n1) - 1u, 1);
+  int bits = 1;
+  while ((1ull << bits) <= top) ++bits;
+  if (int rc = sort_rows_by_key(l.sort_tmp, l.sort_bytes, l.key, l.key_s, l.idx, l.idx_s, l.ncon, bits, st)) return rc;
+  for_width(c, [&](auto cc) {
+    hipLaunchKernelGGL((rows_kernel<decltype(cc)::value, TWO>), dim3(l.ncon), dim3(HC_THREADS), 0, st, F0, F1, l, dF0, dF1);
+  });
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // Triplet and hardest-triplet loss (lib/trainer.py:567-621, :701-782; include/eyoc_hip.h has the contract).  The workspace starts with
 // an HcWs of the same (n_pairs, n_used): hc_prep_kernel and hc_search_kernel run on it unchanged (key table, index check, t*).
 // Forward, 5 launches: the fill, hc_prep_kernel, hc_search_kernel, tr_terms_kernel (grid.y = direction 01, direction 10, random triplets;
 // lane = term), tr_final_kernel.  Backward: two fills, tr_weights_kernel (three contribution entries per term, entry number = sequence
-// number), one stable sort of (destination, entry number) by rocPRIM's radix_sort_pairs, tr_rows_kernel (one workgroup per sorted position; the first position
-// of a run of equal destinations adds the run in order, every other one leaves after two loads: linear in the list).
+// number), one stable sort of (destination, entry number) by rocPRIM's radix_sort_pairs, rows_kernel with two factors per entry (linear
+// in the list).
 namespace {
 
 static_assert(sizeof(eyoc_triplet_record) == 96, "eyoc_triplet_record is 96 bytes");
@@ -676,20 +799,14 @@ struct TrWs {
   int nblk;                    // workgroups of the terms kernel per part (>= 1)
   double* part_sum;            // [3][nblk][3]
   int* part_cnt;               // [3][nblk]
-  int ncon;                    // 3 (n_rand + 2 n_used) contribution entries
-  unsigned int *ckey, *ckey_s; // destination 2 row + matrix + 1, 0 = empty; sorted
-  int *cidx, *cidx_s;          // entry numbers; sorted along
-  float *cwq, *cwn;            // the two factors of an entry
-  int *crq, *crn;              // the rows of the OTHER matrix they scale the difference to
-  void* sort_tmp;
-  size_t sort_bytes;
+  Contrib list;                // 3 (n_rand + 2 n_used) entries of two factors
   size_t total;
 };
 
 TrWs tr_carve(void* base, size_t bytes, int n_pairs, int n_used, int n_rand) {
   TrWs w;
   w.hc = carve(base, bytes, n_pairs, n_used);
-  Carver cv(base ? (char*)base + w.hc.total : nullptr, bytes > w.hc.total ? bytes - w.hc.total : 0);
+  Carver cv = carver_behind(w.hc, base, bytes);
   const size_t n = (size_t)n_used, nr = (size_t)n_rand;
   w.rec = (eyoc_triplet_record*)cv.take<char>(256);
   w.pos_dist = cv.take<float>(n);
@@ -702,18 +819,8 @@ TrWs tr_carve(void* base, size_t bytes, int n_pairs, int n_used, int n_rand) {
   w.nblk = most > 0 ? cdiv(most, HC_A) : 1;
   w.part_sum = cv.take<double>(9 * (size_t)w.nblk);
   w.part_cnt = cv.take<int>(3 * (size_t)w.nblk);
-  w.ncon = 3 * (n_rand + 2 * n_used);
-  const size_t nc = (size_t)w.ncon;
-  w.ckey = cv.take<unsigned int>(nc);
-  w.ckey_s = cv.take<unsigned int>(nc);
-  w.cidx = cv.take<int>(nc);
-  w.cidx_s = cv.take<int>(nc);
-  w.cwq = cv.take<float>(nc);
-  w.cwn = cv.take<float>(nc);
-  w.crq = cv.take<int>(nc);
-  w.crn = cv.take<int>(nc);
-  w.sort_bytes = align_up(sort_rows_tmp_bytes(w.ncon, 32));
-  w.sort_tmp = cv.take<char>(w.sort_bytes);
+  w.list = carve_contrib(cv, 3 * (n_rand + 2 * n_used), true);
+  w.list.status = w.rec ? &w.rec->status : nullptr;
   w.total = w.hc.total + align_up(cv.off);
   return w;
 }
@@ -839,38 +946,17 @@ __global__ __launch_bounds__(64) void tr_terms_kernel(const float* __restrict__ 
 __global__ __launch_bounds__(HC_THREADS) void tr_final_kernel(int n_pairs, int n_used, int n_rand, int hardest, TrWs w,
                                                               eyoc_triplet_record* __restrict__ out) {
 #pragma clang fp contract(off)
-  __shared__ double red_d[HC_WAVES][9];
-  __shared__ int red_i[HC_WAVES][3];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double v[9];
-  int c[3] = {0, 0, 0};
-#pragma unroll
-  for (int k = 0; k < 9; ++k) v[k] = 0.0;
-  for (int b = threadIdx.x; b < w.nblk; b += HC_THREADS) {
+  double sum[9];
+  int cnt[3];
+  const auto add = [&](int b, double (&v)[9], int (&c)[3]) {
 #pragma unroll
     for (int part = 0; part < 3; ++part) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) v[3 * part + k] += w.part_sum[((size_t)part * w.nblk + b) * 3 + k];
       c[part] += w.part_cnt[(size_t)part * w.nblk + b];
     }
-  }
-#pragma unroll
-  for (int k = 0; k < 9; ++k) v[k] = wave_sum(v[k]);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) c[k] = wave_sum_i(c[k]);
-  if (lane == 0) {
-    for (int k = 0; k < 9; ++k) red_d[wave][k] = v[k];
-    for (int k = 0; k < 3; ++k) red_i[wave][k] = c[k];
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  double sum[9];
-  int cnt[3] = {0, 0, 0};
-  for (int k = 0; k < 9; ++k) sum[k] = 0.0;
-  for (int x = 0; x < HC_WAVES; ++x) {
-    for (int k = 0; k < 9; ++k) sum[k] += red_d[x][k];
-    for (int k = 0; k < 3; ++k) cnt[k] += red_i[x][k];
-  }
+  };
+  if (!block_sum_ordered(w.nblk, add, sum, cnt)) return;
   eyoc_triplet_record r;
   r.sum01 = sum[0]; r.sum_pos_dist = sum[1]; r.sum_d01 = sum[2];
   r.sum10 = sum[3]; r.sum_d10 = sum[5];
@@ -949,54 +1035,20 @@ __global__ __launch_bounds__(HC_THREADS) void tr_weights_kernel(const long long*
     const double gk = (double)*g / (double)K;
     wq = (float)(gk / (double)pos);
     wn = (float)(-gk / (double)neg);
-    key[0] = 2u * (unsigned int)ra + (unsigned int)mA + 1u;
-    key[1] = 2u * (unsigned int)rq + (unsigned int)(1 - mA) + 1u;
-    key[2] = 2u * (unsigned int)rn + (unsigned int)(1 - mA) + 1u;
+    key[0] = contrib_key((unsigned int)ra, mA);
+    key[1] = contrib_key((unsigned int)rq, 1 - mA);
+    key[2] = contrib_key((unsigned int)rn, 1 - mA);
   }
+  const Contrib& l = w.list;
   const size_t e = 3 * (size_t)t;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    w.ckey[e + k] = key[k];
-    w.cidx[e + k] = (int)(e + k);
+    l.key[e + k] = key[k];
+    l.idx[e + k] = (int)(e + k);
   }
-  w.cwq[e] = wq;     w.cwn[e] = wn;       w.crq[e] = (int)rq;     w.crn[e] = (int)rn;
-  w.cwq[e + 1] = wq; w.cwn[e + 1] = 0.0f; w.crq[e + 1] = (int)ra; w.crn[e + 1] = 0;
-  w.cwq[e + 2] = wn; w.cwn[e + 2] = 0.0f; w.crq[e + 2] = (int)ra; w.crn[e + 2] = 0;
-}
-
-// One workgroup per position of the sorted list.  The first position of a run of equal destinations does the row: C lanes take one entry
-// (lane = channel), 256 / C entries side by side, entry k of the run goes to slot k mod (256 / C), the slots are added in order.  Every
-// other position leaves after two loads, so the list is read a bounded number of times however long a run is.
-template <int C>
-__global__ __launch_bounds__(HC_THREADS) void tr_rows_kernel(const float* __restrict__ F0, const float* __restrict__ F1, TrWs w,
-                                                             float* __restrict__ dF0, float* __restrict__ dF1) {
-#pragma clang fp contract(off)
-  constexpr int G = HC_THREADS / C;
-  __shared__ double slot_acc[HC_THREADS];
-  const int k = blockIdx.x;
-  const unsigned int key = w.ckey_s[k];
-  if (key == 0u) return;
-  if (k > 0 && w.ckey_s[k - 1] == key) return;
-  const int m = (int)((key - 1u) & 1u);
-  const size_t row = (size_t)((key - 1u) >> 1);
-  const int slot = threadIdx.x / C, ch = threadIdx.x % C;
-  const float* __restrict__ FO = m ? F0 : F1;   // the other matrix
-  const double own = (double)(m ? F1 : F0)[row * C + ch];
-  double acc = 0.0;
-  for (int q = slot; k + q < w.ncon && w.ckey_s[k + q] == key; q += G) {
-    const int e = w.cidx_s[k + q];
-    acc += (double)w.cwq[e] * (own - (double)FO[(size_t)w.crq[e] * C + ch]);
-    const float wn = w.cwn[e];
-    if (wn != 0.0f) acc += (double)wn * (own - (double)FO[(size_t)w.crn[e] * C + ch]);
-  }
-  slot_acc[threadIdx.x] = acc;
-  __syncthreads();
-  if (threadIdx.x >= C) return;
-  double total = 0.0;
-#pragma unroll
-  for (int g = 0; g < G; ++g) total += slot_acc[g * C + threadIdx.x];
-  float* __restrict__ dF = m ? dF1 : dF0;
-  dF[row * C + threadIdx.x] = w.rec->status ? __builtin_nanf("") : (float)total;
+  l.w[e] = wq;     l.w2[e] = wn;       l.r[e] = (int)rq;     l.r2[e] = (int)rn;
+  l.w[e + 1] = wq; l.w2[e + 1] = 0.0f; l.r[e + 1] = (int)ra; l.r2[e + 1] = 0;
+  l.w[e + 2] = wn; l.w2[e + 2] = 0.0f; l.r[e + 2] = (int)ra; l.r2[e + 2] = 0;
 }
 
 int tr_check_args(const char* what, const eyoc_ctx* ctx, const void* F0, int n0, const void* F1, int n1, int c, const void* pairs,
@@ -1042,7 +1094,7 @@ int eyoc_triplet_workspace_layout(int n_pairs, int n_used, int s0, int s1, int n
   out->n_used = n_used;
   out->n_rand = n_rand;
   out->table_slots = (int32_t)(w.hc.mask + 1);
-  out->n_contrib = w.ncon;
+  out->n_contrib = w.list.ncon;
   out->total = w.total;
   out->off_record = (uint64_t)((char*)w.rec - base);
   out->off_tstar = (uint64_t)((char*)w.hc.tstar - base);
@@ -1054,7 +1106,7 @@ int eyoc_triplet_workspace_layout(int n_pairs, int n_used, int s0, int s1, int n
   out->off_rand_neg = (uint64_t)((char*)w.rneg - base);
   out->off_rand_term = (uint64_t)((char*)w.rterm - base);
   out->off_rand_flags = (uint64_t)((char*)w.rflags - base);
-  out->off_contrib_key = (uint64_t)((char*)w.ckey - base);
+  out->off_contrib_key = (uint64_t)((char*)w.list.key - base);
   return EYOC_OK;
 }
 
@@ -1077,13 +1129,10 @@ int eyoc_triplet_forward(eyoc_ctx* ctx, const float* F0, int n0, const float* F1
   // (rand_idx and negatives are checked by the terms kernel, the only reader of both)
   if (int rc = launch_prep_search(F0, n0, F1, n1, c, P, n_pairs, U, n_used, S0, s0, S1, s1, w.hc, st)) return rc;
   const dim3 grid_terms(w.nblk, 3);
-#define TR_TERMS(CC)                                                                                                                   \
-  hipLaunchKernelGGL((tr_terms_kernel<CC>), grid_terms, dim3(64), 0, st, F0, n0, F1, n1, P, n_pairs, U, n_used, S0, s0, S1, s1, RI, NG, n_rand, \
-                     margin, w)
-  if (c == 16) TR_TERMS(16);
-  else if (c == 32) TR_TERMS(32);
-  else TR_TERMS(64);
-#undef TR_TERMS
+  for_width(c, [&](auto cc) {
+    hipLaunchKernelGGL((tr_terms_kernel<decltype(cc)::value>), grid_terms, dim3(64), 0, st, F0, n0, F1, n1, P, n_pairs, U, n_used, S0, s0, S1,
+                       s1, RI, NG, n_rand, margin, w);
+  });
   hipLaunchKernelGGL(tr_final_kernel, dim3(1), dim3(HC_THREADS), 0, st, n_pairs, n_used, n_rand, s1 > 0 ? 1 : 0, w, record_out);
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
@@ -1100,24 +1149,12 @@ int eyoc_triplet_backward(eyoc_ctx* ctx, const float* F0, int n0, const float* F
   EYOC_REQUIRE(g && (dF0 || n0 == 0) && (dF1 || n1 == 0), EYOC_ERR_INVALID, "eyoc_triplet_backward: NULL argument");
   hipStream_t st = (hipStream_t)stream;
   const TrWs w = tr_carve(ws, ws_bytes, n_pairs, n_used, n_rand);
-  if (n0 > 0) EYOC_CHECK_HIP(hipMemsetAsync(dF0, 0, (size_t)n0 * c * sizeof(float), st));
-  if (n1 > 0) EYOC_CHECK_HIP(hipMemsetAsync(dF1, 0, (size_t)n1 * c * sizeof(float), st));
+  if (int rc = zero_gradients(dF0, n0, dF1, n1, c, st)) return rc;
   if (n_used == 0 || n_pairs == 0) return EYOC_OK;   // no term, no contribution
   hipLaunchKernelGGL(tr_weights_kernel, dim3(cdiv(n_rand + 2 * n_used, HC_THREADS)), dim3(HC_THREADS), 0, st, (const long long*)pairs,
                      n_pairs, (const long long*)used, n_used, (const long long*)sel0, s0, (const long long*)sel1, s1,
                      (const long long*)rand_idx, (const long long*)negatives, n_rand, n0, n1, g, w);
-  // keys are 2 row + matrix + 1 <= 2 max(n0, n1): that many bits; equal keys keep their entry order (a radix sort is stable)
-  const unsigned long long top = 2ull * (unsigned long long)(n0 > n1 ? n0 : n1);
-  int bits = 1;
-  while ((1ull << bits) <= top) ++bits;
-  if (int rc = sort_rows_by_key(w.sort_tmp, w.sort_bytes, w.ckey, w.ckey_s, w.cidx, w.cidx_s, w.ncon, bits, st)) return rc;
-#define TR_ROWS(CC) hipLaunchKernelGGL((tr_rows_kernel<CC>), dim3(w.ncon), dim3(HC_THREADS), 0, st, F0, F1, w, dF0, dF1)
-  if (c == 16) TR_ROWS(16);
-  else if (c == 32) TR_ROWS(32);
-  else TR_ROWS(64);
-#undef TR_ROWS
-  EYOC_CHECK_HIP(hipGetLastError());
-  return EYOC_OK;
+  return sort_and_sum_rows<true>(w.list, F0, n0, F1, n1, c, dF0, dF1, st);
 }
 
 }  // extern "C"
@@ -1127,9 +1164,8 @@ int eyoc_triplet_backward(eyoc_ctx* ctx, const float* F0, int n0, const float* F
 // contract).  The workspace starts with an HcWs of (n_pairs, 0 used positives): hc_prep_kernel runs on it unchanged (key table, index check
 // of the positives).  Forward, 4 launches: the fill (control block + key table), hc_prep_kernel, cl_terms_kernel (grid.y = positives,
 // candidate negatives; lane = term), cl_final_kernel.  Backward: two fills, cl_weights_kernel (two contribution entries per term, entry
-// number = sequence number), one stable sort of (destination, entry number) by rocPRIM's radix_sort_pairs, cl_rows_kernel (tr_rows_kernel's
-// scheme with one factor per entry: the first position of a run of equal destinations adds the run in order, every other one leaves after
-// two loads).
+// number = sequence number), one stable sort of (destination, entry number) by rocPRIM's radix_sort_pairs, rows_kernel with one factor
+// per entry.
 namespace {
 
 static_assert(sizeof(eyoc_closs_record) == 48, "eyoc_closs_record is 48 bytes");
@@ -1144,20 +1180,14 @@ struct ClWs {
   int nblk;                    // workgroups of the terms kernel per part (>= 1)
   double* part_sum;            // [2][nblk]: positives, kept candidates
   int* part_cnt;               // [2][nblk]: kept, active
-  int ncon;                    // 2 (n_pairs + n_neg) contribution entries
-  unsigned int *ckey, *ckey_s; // destination 2 row + matrix + 1, 0 = empty; sorted
-  int *cidx, *cidx_s;          // entry numbers; sorted along
-  float* cw;                   // the factor of an entry
-  int* cr;                     // the row of the OTHER matrix it scales the difference to
-  void* sort_tmp;
-  size_t sort_bytes;
+  Contrib list;                // 2 (n_pairs + n_neg) entries of one factor
   size_t total;
 };
 
 ClWs cl_carve(void* base, size_t bytes, int n_pairs, int n_neg) {
   ClWs w;
   w.hc = carve(base, bytes, n_pairs, 0);
-  Carver cv(base ? (char*)base + w.hc.total : nullptr, bytes > w.hc.total ? bytes - w.hc.total : 0);
+  Carver cv = carver_behind(w.hc, base, bytes);
   const size_t np = (size_t)n_pairs, nn = (size_t)n_neg;
   w.rec = (eyoc_closs_record*)cv.take<char>(256);
   w.pos_d2 = cv.take<float>(np);
@@ -1168,16 +1198,8 @@ ClWs cl_carve(void* base, size_t bytes, int n_pairs, int n_neg) {
   w.nblk = most > 0 ? cdiv(most, HC_A) : 1;
   w.part_sum = cv.take<double>(2 * (size_t)w.nblk);
   w.part_cnt = cv.take<int>(2 * (size_t)w.nblk);
-  w.ncon = 2 * (n_pairs + n_neg);
-  const size_t nc = (size_t)w.ncon;
-  w.ckey = cv.take<unsigned int>(nc);
-  w.ckey_s = cv.take<unsigned int>(nc);
-  w.cidx = cv.take<int>(nc);
-  w.cidx_s = cv.take<int>(nc);
-  w.cw = cv.take<float>(nc);
-  w.cr = cv.take<int>(nc);
-  w.sort_bytes = align_up(sort_rows_tmp_bytes(w.ncon, 32));
-  w.sort_tmp = cv.take<char>(w.sort_bytes);
+  w.list = carve_contrib(cv, 2 * (n_pairs + n_neg), false);
+  w.list.status = w.rec ? &w.rec->status : nullptr;
   w.total = w.hc.total + align_up(cv.off);
   return w;
 }
@@ -1258,38 +1280,15 @@ __global__ __launch_bounds__(64) void cl_terms_kernel(const float* __restrict__ 
 
 __global__ __launch_bounds__(HC_THREADS) void cl_final_kernel(int n_pairs, int n_neg, ClWs w, eyoc_closs_record* __restrict__ out) {
 #pragma clang fp contract(off)
-  __shared__ double red_d[HC_WAVES][2];
-  __shared__ int red_i[HC_WAVES][2];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double v[2] = {0.0, 0.0};
-  int c[2] = {0, 0};
-  for (int b = threadIdx.x; b < w.nblk; b += HC_THREADS) {   // (a workgroup past the end of its part wrote zeros)
+  double sum[2];
+  int cnt[2];
+  const auto add = [&](int b, double (&v)[2], int (&c)[2]) {   // (a workgroup past the end of its part wrote zeros)
     v[0] += w.part_sum[b];
     v[1] += w.part_sum[(size_t)w.nblk + b];
     c[0] += w.part_cnt[b];
     c[1] += w.part_cnt[(size_t)w.nblk + b];
-  }
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    v[k] = wave_sum(v[k]);
-    c[k] = wave_sum_i(c[k]);
-  }
-  if (lane == 0) {
-    for (int k = 0; k < 2; ++k) {
-      red_d[wave][k] = v[k];
-      red_i[wave][k] = c[k];
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  double sum[2] = {0.0, 0.0};
-  int cnt[2] = {0, 0};
-  for (int x = 0; x < HC_WAVES; ++x) {
-    for (int k = 0; k < 2; ++k) {
-      sum[k] += red_d[x][k];
-      cnt[k] += red_i[x][k];
-    }
-  }
+  };
+  if (!block_sum_ordered(w.nblk, add, sum, cnt)) return;
   eyoc_closs_record r;
   r.sum_pos = sum[0]; r.sum_neg = sum[1];
   r.n_pairs = n_pairs; r.n_neg = n_neg; r.k_neg = cnt[0]; r.n_active = cnt[1];
@@ -1333,48 +1332,16 @@ __global__ __launch_bounds__(HC_THREADS) void cl_weights_kernel(const long long*
     }
   }
   emit = emit && i >= 0 && i < n0 && j >= 0 && j < n1;
+  const Contrib& l = w.list;
   const size_t e = 2 * (size_t)t;
-  w.ckey[e] = emit ? 2u * (unsigned int)i + 1u : 0u;
-  w.ckey[e + 1] = emit ? 2u * (unsigned int)j + 2u : 0u;
-  w.cidx[e] = (int)e;
-  w.cidx[e + 1] = (int)(e + 1);
-  w.cw[e] = emit ? f : 0.0f;
-  w.cw[e + 1] = emit ? f : 0.0f;
-  w.cr[e] = emit ? (int)j : 0;
-  w.cr[e + 1] = emit ? (int)i : 0;
-}
-
-// One workgroup per position of the sorted list; tr_rows_kernel's scheme: the first position of a run of equal destinations does the row,
-// C lanes take one entry (lane = channel), 256 / C entries side by side, entry k of the run goes to slot k mod (256 / C), fp64
-// accumulators, the slots added in order, rounded once.
-template <int C>
-__global__ __launch_bounds__(HC_THREADS) void cl_rows_kernel(const float* __restrict__ F0, const float* __restrict__ F1, ClWs w,
-                                                             float* __restrict__ dF0, float* __restrict__ dF1) {
-#pragma clang fp contract(off)
-  constexpr int G = HC_THREADS / C;
-  __shared__ double slot_acc[HC_THREADS];
-  const int k = blockIdx.x;
-  const unsigned int key = w.ckey_s[k];
-  if (key == 0u) return;
-  if (k > 0 && w.ckey_s[k - 1] == key) return;
-  const int m = (int)((key - 1u) & 1u);
-  const size_t row = (size_t)((key - 1u) >> 1);
-  const int slot = threadIdx.x / C, ch = threadIdx.x % C;
-  const float* __restrict__ FO = m ? F0 : F1;   // the other matrix
-  const double own = (double)(m ? F1 : F0)[row * C + ch];
-  double acc = 0.0;
-  for (int q = slot; q < w.ncon - k && w.ckey_s[k + q] == key; q += G) {
-    const int e = w.cidx_s[k + q];
-    acc += (double)w.cw[e] * (own - (double)FO[(size_t)w.cr[e] * C + ch]);
-  }
-  slot_acc[threadIdx.x] = acc;
-  __syncthreads();
-  if (threadIdx.x >= C) return;
-  double total = 0.0;
-#pragma unroll
-  for (int g = 0; g < G; ++g) total += slot_acc[g * C + threadIdx.x];
-  float* __restrict__ dF = m ? dF1 : dF0;
-  dF[row * C + threadIdx.x] = w.rec->status ? __builtin_nanf("") : (float)total;
+  l.key[e] = emit ? contrib_key((unsigned int)i, 0) : 0u;
+  l.key[e + 1] = emit ? contrib_key((unsigned int)j, 1) : 0u;
+  l.idx[e] = (int)e;
+  l.idx[e + 1] = (int)(e + 1);
+  l.w[e] = emit ? f : 0.0f;
+  l.w[e + 1] = emit ? f : 0.0f;
+  l.r[e] = emit ? (int)j : 0;
+  l.r[e + 1] = emit ? (int)i : 0;
 }
 
 int cl_check_args(const char* what, const eyoc_ctx* ctx, const void* F0, int n0, const void* F1, int n1, int c, const void* pairs,
@@ -1410,7 +1377,7 @@ int eyoc_closs_workspace_layout(int n_pairs, int n_neg, int c, eyoc_closs_layout
   out->n_pairs = n_pairs;
   out->n_neg = n_neg;
   out->table_slots = (int32_t)(w.hc.mask + 1);
-  out->n_contrib = w.ncon;
+  out->n_contrib = w.list.ncon;
   out->reserved = 0;
   out->total = w.total;
   out->off_record = (uint64_t)((char*)w.rec - base);
@@ -1418,7 +1385,7 @@ int eyoc_closs_workspace_layout(int n_pairs, int n_neg, int c, eyoc_closs_layout
   out->off_dist = (uint64_t)((char*)w.dist - base);
   out->off_term = (uint64_t)((char*)w.term - base);
   out->off_flags = (uint64_t)((char*)w.flags - base);
-  out->off_contrib_key = (uint64_t)((char*)w.ckey - base);
+  out->off_contrib_key = (uint64_t)((char*)w.list.key - base);
   return EYOC_OK;
 }
 
@@ -1437,11 +1404,9 @@ int eyoc_closs_forward(eyoc_ctx* ctx, const float* F0, int n0, const float* F1, 
   hipLaunchKernelGGL(hc_prep_kernel, dim3(pg), dim3(HC_THREADS), 0, st, P, n_pairs, (const long long*)nullptr, 0, (const long long*)nullptr, 0,
                      (const long long*)nullptr, 0, n0, n1, n_pairs, w.hc);
   const dim3 grid_terms(w.nblk, 2);
-#define CL_TERMS(CC) hipLaunchKernelGGL((cl_terms_kernel<CC>), grid_terms, dim3(64), 0, st, F0, n0, F1, n1, P, n_pairs, N, n_neg, neg_thresh, w)
-  if (c == 16) CL_TERMS(16);
-  else if (c == 32) CL_TERMS(32);
-  else CL_TERMS(64);
-#undef CL_TERMS
+  for_width(c, [&](auto cc) {
+    hipLaunchKernelGGL((cl_terms_kernel<decltype(cc)::value>), grid_terms, dim3(64), 0, st, F0, n0, F1, n1, P, n_pairs, N, n_neg, neg_thresh, w);
+  });
   hipLaunchKernelGGL(cl_final_kernel, dim3(1), dim3(HC_THREADS), 0, st, n_pairs, n_neg, w, record_out);
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
@@ -1454,23 +1419,11 @@ int eyoc_closs_backward(eyoc_ctx* ctx, const float* F0, int n0, const float* F1,
   EYOC_REQUIRE(g_pos && g_neg && (dF0 || n0 == 0) && (dF1 || n1 == 0), EYOC_ERR_INVALID, "eyoc_closs_backward: NULL argument");
   hipStream_t st = (hipStream_t)stream;
   const ClWs w = cl_carve(ws, ws_bytes, n_pairs, n_neg);
-  if (n0 > 0) EYOC_CHECK_HIP(hipMemsetAsync(dF0, 0, (size_t)n0 * c * sizeof(float), st));
-  if (n1 > 0) EYOC_CHECK_HIP(hipMemsetAsync(dF1, 0, (size_t)n1 * c * sizeof(float), st));
+  if (int rc = zero_gradients(dF0, n0, dF1, n1, c, st)) return rc;
   if (n_pairs == 0) return EYOC_OK;   // both values are NaN by definition: no contribution
   hipLaunchKernelGGL(cl_weights_kernel, dim3(cdiv(n_pairs + n_neg, HC_THREADS)), dim3(HC_THREADS), 0, st, (const long long*)pairs, n_pairs,
                      (const long long*)neg, n_neg, n0, n1, neg_thresh, g_pos, g_neg, w);
-  // keys are 2 row + matrix + 1 <= 2 max(n0, n1): that many bits; equal keys keep their entry order (a radix sort is stable)
-  const unsigned long long top = 2ull * (unsigned long long)(n0 > n1 ? n0 : n1);
-  int bits = 1;
-  while ((1ull << bits) <= top) ++bits;
-  if (int rc = sort_rows_by_key(w.sort_tmp, w.sort_bytes, w.ckey, w.ckey_s, w.cidx, w.cidx_s, w.ncon, bits, st)) return rc;
-#define CL_ROWS(CC) hipLaunchKernelGGL((cl_rows_kernel<CC>), dim3(w.ncon), dim3(HC_THREADS), 0, st, F0, F1, w, dF0, dF1)
-  if (c == 16) CL_ROWS(16);
-  else if (c == 32) CL_ROWS(32);
-  else CL_ROWS(64);
-#undef CL_ROWS
-  EYOC_CHECK_HIP(hipGetLastError());
-  return EYOC_OK;
+  return sort_and_sum_rows<false>(w.list, F0, n0, F1, n1, c, dF0, dF1, st);
 }
 
 }  // extern "C"

@@ -31,10 +31,75 @@ BAD_INDEX, MASKED, VALID = 1, 1, 2        # record status bit; per-direction fla
 _RECORD_FLOATS = C.sizeof(_lib.HclossRecord) // 4
 
 
-def layout(n_pairs, n_used, s0, s1, c):
-    out = _lib.HclossLayout()
-    _lib.check(_lib.load().eyoc_hcloss_workspace_layout(n_pairs, n_used, s0, s1, c, C.byref(out)), "eyoc_hcloss_workspace_layout")
+# The call plumbing of the three losses; ``name`` is the prefix of a loss's C symbols (``eyoc_hcloss``, ``eyoc_triplet``, ``eyoc_closs``).
+def _layout(name, struct, *shape):
+    out = struct()
+    _lib.check(getattr(_lib.load(), name + "_workspace_layout")(*shape, C.byref(out)), name + "_workspace_layout")
     return out
+
+
+def _forward(name, record_floats, shape, args, F0):
+    """``<name>_forward`` with a workspace of ``<name>_workspace_bytes(*shape)`` -> ``(record, workspace)``; ``args``: the C arguments up
+    to the record."""
+    lib = _lib.load()
+    with _lib.on_device(F0.device):
+        ws = _lib.workspace(getattr(lib, name + "_workspace_bytes")(*shape), F0.device)
+        rec = torch.empty(record_floats, dtype=torch.float32, device=F0.device)
+        _lib.check(getattr(lib, name + "_forward")(*args, _lib.ptr(rec), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), name + "_forward")
+    return rec, ws
+
+
+def _backward(name, args, F0, F1, grads, ws):
+    """``<name>_backward`` -> ``(dF0, dF1)``; ``args``: the C arguments up to the upstream gradients ``grads``."""
+    lib = _lib.load()
+    dF0, dF1 = torch.empty_like(F0), torch.empty_like(F1)
+    with _lib.on_device(F0.device):
+        _lib.check(getattr(lib, name + "_backward")(*args, *[_lib.ptr(g) for g in grads], _lib.ptr(dF0), _lib.ptr(dF1), _lib.ptr(ws),
+                                                    ws.numel(), _lib.stream_ptr()), name + "_backward")
+    return dF0, dF1
+
+
+def _read(rec, struct):
+    return struct.from_buffer_copy(rec.detach().cpu().numpy().tobytes())
+
+
+def _view(ws, off, count, dtype):
+    return ws[off:off + 4 * count].view(dtype)
+
+
+def _scalar(g, device):
+    """An upstream gradient as a float32 device scalar; a missing one is zero."""
+    if g is None:
+        return torch.zeros((), dtype=torch.float32, device=device)
+    return g.to(torch.float32).contiguous()
+
+
+def _upload_draws(parts, dev):
+    """The host draws of a loss call: one pinned staging buffer, one asynchronous copy -> the parts as slices of the device copy."""
+    stage = torch.empty(sum(len(p) for p in parts), dtype=torch.int64, pin_memory=True)
+    host, bounds, at = stage.numpy(), [], 0
+    for p in parts:
+        host[at:at + len(p)] = p
+        bounds.append((at, at + len(p)))
+        at += len(p)
+    draws = stage.to(dev, non_blocking=True)
+    return [draws[a:b] for a, b in bounds]
+
+
+class _Node(torch.autograd.Function):
+    """The backward of the three nodes.  A subclass's forward saves ``(F0, F1)`` and leaves in ``ctx.call`` its raw backward, that
+    function's arguments between the features and the gradients (the node's other inputs) and the number of gradients it takes."""
+
+    @staticmethod
+    def backward(ctx, *grads):
+        F0, F1 = ctx.saved_tensors
+        raw_backward, rest, n_grads = ctx.call
+        dF0, dF1 = raw_backward(F0, F1, *rest, *[_scalar(g, F0.device) for g in grads[:n_grads]], ctx.ws)
+        return (dF0, dF1) + (None,) * len(rest)
+
+
+def layout(n_pairs, n_used, s0, s1, c):
+    return _layout("eyoc_hcloss", _lib.HclossLayout, n_pairs, n_used, s0, s1, c)
 
 
 def _args(F0, F1, pairs, used, sel0, sel1, pos_thresh, neg_thresh):
@@ -62,63 +127,38 @@ def forward_raw(F0, F1, pairs, used, sel0, sel1, pos_thresh=0.1, neg_thresh=1.4)
     ``eyoc_hcloss_record`` (``record[10]`` = pos_loss, ``record[11]`` = neg_loss; ``read_record`` decodes all of it), ``workspace`` what
     ``backward_raw`` and ``results`` read.  ``used = None`` takes every positive."""
     _check_inputs(F0, F1, pairs, used, sel0, sel1)
-    lib = _lib.load()
     n_used = pairs.shape[0] if used is None else used.shape[0]
-    with _lib.on_device(F0.device):
-        ws = _lib.workspace(lib.eyoc_hcloss_workspace_bytes(pairs.shape[0], n_used, sel0.shape[0], sel1.shape[0], F0.shape[1]), F0.device)
-        rec = torch.empty(_RECORD_FLOATS, dtype=torch.float32, device=F0.device)
-        _lib.check(lib.eyoc_hcloss_forward(*_args(F0, F1, pairs, used, sel0, sel1, pos_thresh, neg_thresh), _lib.ptr(rec), _lib.ptr(ws),
-                                           ws.numel(), _lib.stream_ptr()), "eyoc_hcloss_forward")
-    return rec, ws
+    return _forward("eyoc_hcloss", _RECORD_FLOATS, (pairs.shape[0], n_used, sel0.shape[0], sel1.shape[0], F0.shape[1]),
+                    _args(F0, F1, pairs, used, sel0, sel1, pos_thresh, neg_thresh), F0)
 
 
 def backward_raw(F0, F1, pairs, used, sel0, sel1, pos_thresh, neg_thresh, g_pos, g_neg, ws):
     """``eyoc_hcloss_backward`` -> ``(dF0, dF1)``; ``g_pos`` / ``g_neg`` float32 device scalars, ``ws`` from ``forward_raw`` on the same arguments."""
-    lib = _lib.load()
-    dF0, dF1 = torch.empty_like(F0), torch.empty_like(F1)
-    with _lib.on_device(F0.device):
-        _lib.check(lib.eyoc_hcloss_backward(*_args(F0, F1, pairs, used, sel0, sel1, pos_thresh, neg_thresh), _lib.ptr(g_pos), _lib.ptr(g_neg),
-                                            _lib.ptr(dF0), _lib.ptr(dF1), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
-                   "eyoc_hcloss_backward")
-    return dF0, dF1
+    return _backward("eyoc_hcloss", _args(F0, F1, pairs, used, sel0, sel1, pos_thresh, neg_thresh), F0, F1, (g_pos, g_neg), ws)
 
 
 def read_record(rec) -> _lib.HclossRecord:
     """The record on the host (tests, logging): this READS BACK, the loss itself never does."""
-    return _lib.HclossRecord.from_buffer_copy(rec.detach().cpu().numpy().tobytes())
+    return _read(rec, _lib.HclossRecord)
 
 
 def results(ws, n_pairs, n_used, s0, s1, c):
     """The per-positive results the forward left in its workspace, as device views: ``tstar`` int32 [2, n_used] (-1: none), ``dist``
     float32 [2, n_used], ``pos_d2`` float32 [n_used], ``flags`` int32 [2, n_used] (``MASKED`` / ``VALID``); row 0 is direction 01."""
     lay = layout(n_pairs, n_used, s0, s1, c)
-
-    def view(off, count, dtype):
-        return ws[off:off + 4 * count].view(dtype)
-    return {"tstar": view(lay.off_tstar, 2 * n_used, torch.int32).view(2, n_used),
-            "dist": view(lay.off_dist, 2 * n_used, torch.float32).view(2, n_used),
-            "pos_d2": view(lay.off_pos_d2, n_used, torch.float32),
-            "flags": view(lay.off_flags, 2 * n_used, torch.int32).view(2, n_used)}
+    return {"tstar": _view(ws, lay.off_tstar, 2 * n_used, torch.int32).view(2, n_used),
+            "dist": _view(ws, lay.off_dist, 2 * n_used, torch.float32).view(2, n_used),
+            "pos_d2": _view(ws, lay.off_pos_d2, n_used, torch.float32),
+            "flags": _view(ws, lay.off_flags, 2 * n_used, torch.int32).view(2, n_used)}
 
 
-class _HardestContrastive(torch.autograd.Function):
+class _HardestContrastive(_Node):
     @staticmethod
     def forward(ctx, F0, F1, pairs, used, sel0, sel1, pos_thresh, neg_thresh):
         rec, ws = forward_raw(F0, F1, pairs, used, sel0, sel1, pos_thresh, neg_thresh)
         ctx.save_for_backward(F0, F1)
-        ctx.idx, ctx.thresh, ctx.ws = (pairs, used, sel0, sel1), (pos_thresh, neg_thresh), ws
+        ctx.call, ctx.ws = (backward_raw, (pairs, used, sel0, sel1, pos_thresh, neg_thresh), 2), ws
         return rec[_RECORD_FLOATS - 2], rec[_RECORD_FLOATS - 1]
-
-    @staticmethod
-    def backward(ctx, g_pos, g_neg):
-        F0, F1 = ctx.saved_tensors
-
-        def scalar(g):                                  # a missing gradient is zero
-            if g is None:
-                return torch.zeros((), dtype=torch.float32, device=F0.device)
-            return g.to(torch.float32).contiguous()
-        dF0, dF1 = backward_raw(F0, F1, *ctx.idx, *ctx.thresh, scalar(g_pos), scalar(g_neg), ctx.ws)
-        return dF0, dF1, None, None, None, None, None, None
 
 
 def hardest_contrastive_loss(F0, F1, positive_pairs, num_pos=5192, num_hn_samples=2048, pos_thresh=0.1, neg_thresh=1.4, rng=None):
@@ -128,11 +168,7 @@ def hardest_contrastive_loss(F0, F1, positive_pairs, num_pos=5192, num_hn_sample
     ``positive_pairs``: a DEVICE int64 ``[n, 2]`` tensor stays on the device; a host tensor or ndarray costs one upload.  No double
     backward; ``c`` in {16, 32, 64}."""
     dev = F0.device
-    if isinstance(positive_pairs, torch.Tensor):
-        pairs = positive_pairs
-    else:
-        pairs = torch.from_numpy(np.ascontiguousarray(np.asarray(positive_pairs), dtype=np.int64))
-    pairs = pairs.reshape(-1, 2).to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
+    pairs = _device_pairs(positive_pairs, dev)
     n0, n1, n_pairs = F0.shape[0], F1.shape[0], pairs.shape[0]
     if isinstance(rng, DeviceDraws):
         # slots in the reference's order: candidates of cloud 0, of cloud 1, the positive sub-sample (an empty slot when all are kept)
@@ -141,16 +177,8 @@ def hardest_contrastive_loss(F0, F1, positive_pairs, num_pos=5192, num_hn_sample
         return _HardestContrastive.apply(F0.contiguous(), F1.contiguous(), pairs, used if n_pairs > num_pos else None, sel0, sel1,
                                          float(pos_thresh), float(neg_thresh))
     cand0, cand1, keep = _draw_loss_samples(np.random if rng is None else rng, n0, n1, n_pairs, num_hn_samples, num_pos)
-    s0, s1, n_keep = len(cand0), len(cand1), 0 if keep is None else len(keep)
-    # the draws: one pinned staging buffer, one asynchronous copy
-    stage = torch.empty(s0 + s1 + n_keep, dtype=torch.int64, pin_memory=True)
-    host = stage.numpy()
-    host[:s0], host[s0:s0 + s1] = cand0, cand1
-    if keep is not None:
-        host[s0 + s1:] = keep
-    draws = stage.to(dev, non_blocking=True)
-    used = None if keep is None else draws[s0 + s1:]
-    return _HardestContrastive.apply(F0.contiguous(), F1.contiguous(), pairs, used, draws[:s0], draws[s0:s0 + s1], float(pos_thresh),
+    sel0, sel1, *used = _upload_draws([cand0, cand1] + ([] if keep is None else [keep]), dev)
+    return _HardestContrastive.apply(F0.contiguous(), F1.contiguous(), pairs, used[0] if used else None, sel0, sel1, float(pos_thresh),
                                      float(neg_thresh))
 
 
@@ -164,9 +192,7 @@ _TRIPLET_LOSS = _lib.TripletRecord.loss.offset // 4          # loss, pos_dist_me
 
 
 def triplet_layout(n_pairs, n_used, s0, s1, n_rand, c):
-    out = _lib.TripletLayout()
-    _lib.check(_lib.load().eyoc_triplet_workspace_layout(n_pairs, n_used, s0, s1, n_rand, c, C.byref(out)), "eyoc_triplet_workspace_layout")
-    return out
+    return _layout("eyoc_triplet", _lib.TripletLayout, n_pairs, n_used, s0, s1, n_rand, c)
 
 
 def _triplet_args(F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, margin):
@@ -209,31 +235,19 @@ def triplet_raw_forward(F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, ma
     _check_inputs(F0, F1, pairs, None, rand_idx, negatives)
     if rand_idx.shape[0] != negatives.shape[0]:
         raise ValueError(f"triplet loss: {rand_idx.shape[0]} random pairs, {negatives.shape[0]} random negatives")
-    lib = _lib.load()
     n_used = pairs.shape[0] if used is None else used.shape[0]
-    with _lib.on_device(F0.device):
-        ws = _lib.workspace(lib.eyoc_triplet_workspace_bytes(pairs.shape[0], n_used, sel0.shape[0], sel1.shape[0], rand_idx.shape[0],
-                                                             F0.shape[1]), F0.device)
-        rec = torch.empty(_TRIPLET_FLOATS, dtype=torch.float32, device=F0.device)
-        _lib.check(lib.eyoc_triplet_forward(*_triplet_args(F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, margin), _lib.ptr(rec),
-                                            _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "eyoc_triplet_forward")
-    return rec, ws
+    return _forward("eyoc_triplet", _TRIPLET_FLOATS, (pairs.shape[0], n_used, sel0.shape[0], sel1.shape[0], rand_idx.shape[0], F0.shape[1]),
+                    _triplet_args(F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, margin), F0)
 
 
 def triplet_raw_backward(F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, margin, g, ws):
     """``eyoc_triplet_backward`` -> ``(dF0, dF1)``; ``g`` a float32 device scalar, ``ws`` from ``triplet_raw_forward`` on the same arguments."""
-    lib = _lib.load()
-    dF0, dF1 = torch.empty_like(F0), torch.empty_like(F1)
-    with _lib.on_device(F0.device):
-        _lib.check(lib.eyoc_triplet_backward(*_triplet_args(F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, margin), _lib.ptr(g),
-                                             _lib.ptr(dF0), _lib.ptr(dF1), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
-                   "eyoc_triplet_backward")
-    return dF0, dF1
+    return _backward("eyoc_triplet", _triplet_args(F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, margin), F0, F1, (g,), ws)
 
 
 def read_triplet_record(rec) -> _lib.TripletRecord:
     """The record on the host (tests, logging): this READS BACK, the loss itself never does."""
-    return _lib.TripletRecord.from_buffer_copy(rec.detach().cpu().numpy().tobytes())
+    return _read(rec, _lib.TripletRecord)
 
 
 def triplet_results(ws, n_pairs, n_used, s0, s1, n_rand, c):
@@ -242,47 +256,32 @@ def triplet_results(ws, n_pairs, n_used, s0, s1, n_rand, c):
     ``_ACTIVE``; row 0 is direction 01); ``rand_pos``, ``rand_neg``, ``rand_term`` float32 [n_rand], ``rand_flags`` int32 [n_rand];
     ``contrib_key`` int32 [3 (n_rand + 2 n_used)], written by the backward (2 row + matrix + 1, 0 = empty)."""
     lay = triplet_layout(n_pairs, n_used, s0, s1, n_rand, c)
-
-    def view(off, count, dtype):
-        return ws[off:off + 4 * count].view(dtype)
-    out = {"tstar": view(lay.off_tstar, 2 * n_used, torch.int32).view(2, n_used),
-           "dist": view(lay.off_dist, 2 * n_used, torch.float32).view(2, n_used),
-           "term": view(lay.off_term, 2 * n_used, torch.float32).view(2, n_used),
-           "pos_dist": view(lay.off_pos_dist, n_used, torch.float32),
-           "flags": view(lay.off_flags, 2 * n_used, torch.int32).view(2, n_used),
-           "rand_flags": view(lay.off_rand_flags, n_rand, torch.int32),
-           "contrib_key": view(lay.off_contrib_key, lay.n_contrib, torch.int32)}
+    out = {"tstar": _view(ws, lay.off_tstar, 2 * n_used, torch.int32).view(2, n_used),
+           "dist": _view(ws, lay.off_dist, 2 * n_used, torch.float32).view(2, n_used),
+           "term": _view(ws, lay.off_term, 2 * n_used, torch.float32).view(2, n_used),
+           "pos_dist": _view(ws, lay.off_pos_dist, n_used, torch.float32),
+           "flags": _view(ws, lay.off_flags, 2 * n_used, torch.int32).view(2, n_used),
+           "rand_flags": _view(ws, lay.off_rand_flags, n_rand, torch.int32),
+           "contrib_key": _view(ws, lay.off_contrib_key, lay.n_contrib, torch.int32)}
     for k in ("pos", "neg", "term"):
-        out["rand_" + k] = view(getattr(lay, "off_rand_" + k), n_rand, torch.float32)
+        out["rand_" + k] = _view(ws, getattr(lay, "off_rand_" + k), n_rand, torch.float32)
     return out
 
 
-class _Triplet(torch.autograd.Function):
+class _Triplet(_Node):
     @staticmethod
     def forward(ctx, F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, margin):
         rec, ws = triplet_raw_forward(F0, F1, pairs, used, sel0, sel1, rand_idx, negatives, margin)
         ctx.save_for_backward(F0, F1)
-        ctx.idx, ctx.margin, ctx.ws = (pairs, used, sel0, sel1, rand_idx, negatives), margin, ws
+        ctx.call, ctx.ws = (triplet_raw_backward, (pairs, used, sel0, sel1, rand_idx, negatives, margin), 1), ws
         loss, pos, neg = rec[_TRIPLET_LOSS], rec[_TRIPLET_LOSS + 1], rec[_TRIPLET_LOSS + 2]
         ctx.mark_non_differentiable(pos, neg)
         return loss, pos, neg
 
-    @staticmethod
-    def backward(ctx, g, _g_pos, _g_neg):
-        F0, F1 = ctx.saved_tensors
-        if g is None:                                   # a missing gradient is zero
-            g = torch.zeros((), dtype=torch.float32, device=F0.device)
-        dF0, dF1 = triplet_raw_backward(F0, F1, *ctx.idx, ctx.margin, g.to(torch.float32).contiguous(), ctx.ws)
-        return dF0, dF1, None, None, None, None, None, None, None
-
 
 def _triplet(F0, F1, positive_pairs, num_pos, num_hn_samples, num_rand_triplet, neg_thresh, rng):
     dev = F0.device
-    if isinstance(positive_pairs, torch.Tensor):
-        pairs = positive_pairs
-    else:
-        pairs = torch.from_numpy(np.ascontiguousarray(np.asarray(positive_pairs), dtype=np.int64))
-    pairs = pairs.reshape(-1, 2).to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
+    pairs = _device_pairs(positive_pairs, dev)
     n0, n1, n_pairs = F0.shape[0], F1.shape[0], pairs.shape[0]
     if isinstance(rng, DeviceDraws):
         check_triplet_lengths(n_pairs, n1, num_rand_triplet)           # before anything is drawn or enqueued, as on the host route
@@ -296,16 +295,7 @@ def _triplet(F0, F1, positive_pairs, num_pos, num_hn_samples, num_rand_triplet, 
                               float(neg_thresh))
     sel0, sel1, used, rand_idx, negatives = draw_triplet_samples(np.random if rng is None else rng, n0, n1, n_pairs, num_hn_samples,
                                                                  num_pos, num_rand_triplet)
-    parts = [sel0, sel1, rand_idx, negatives] + ([] if used is None else [used])
-    # the draws: one pinned staging buffer, one asynchronous copy
-    stage = torch.empty(sum(len(p) for p in parts), dtype=torch.int64, pin_memory=True)
-    host, bounds, at = stage.numpy(), [], 0
-    for p in parts:
-        host[at:at + len(p)] = p
-        bounds.append((at, at + len(p)))
-        at += len(p)
-    draws = stage.to(dev, non_blocking=True)
-    d = [draws[a:b] for a, b in bounds]
+    d = _upload_draws([sel0, sel1, rand_idx, negatives] + ([] if used is None else [used]), dev)
     return _Triplet.apply(F0.contiguous(), F1.contiguous(), pairs, None if used is None else d[4], d[0], d[1], d[2], d[3], float(neg_thresh))
 
 
@@ -336,9 +326,7 @@ _CLOSS_POS = _lib.ClossRecord.pos_loss.offset // 4            # pos_loss, neg_lo
 
 
 def contrastive_layout(n_pairs, n_neg, c):
-    out = _lib.ClossLayout()
-    _lib.check(_lib.load().eyoc_closs_workspace_layout(n_pairs, n_neg, c, C.byref(out)), "eyoc_closs_workspace_layout")
-    return out
+    return _layout("eyoc_closs", _lib.ClossLayout, n_pairs, n_neg, c)
 
 
 def draw_negative_pairs(rng, n_pairs, n0, n1, n_neg=0):
@@ -359,30 +347,19 @@ def contrastive_raw_forward(F0, F1, pairs, neg, neg_thresh=1.4):
     ``contrastive_results`` read.  ``pairs`` int64 ``[n_pairs, 2]``: all positives; ``neg`` int64 ``[n_neg, 2]``: the raw candidates."""
     _check_inputs(F0, F1, pairs, None, None, None)
     _check_inputs(F0, F1, neg, None, None, None)
-    lib = _lib.load()
-    with _lib.on_device(F0.device):
-        ws = _lib.workspace(lib.eyoc_closs_workspace_bytes(pairs.shape[0], neg.shape[0], F0.shape[1]), F0.device)
-        rec = torch.empty(_CLOSS_FLOATS, dtype=torch.float32, device=F0.device)
-        _lib.check(lib.eyoc_closs_forward(*_contrastive_args(F0, F1, pairs, neg, neg_thresh), _lib.ptr(rec), _lib.ptr(ws), ws.numel(),
-                                          _lib.stream_ptr()), "eyoc_closs_forward")
-    return rec, ws
+    return _forward("eyoc_closs", _CLOSS_FLOATS, (pairs.shape[0], neg.shape[0], F0.shape[1]),
+                    _contrastive_args(F0, F1, pairs, neg, neg_thresh), F0)
 
 
 def contrastive_raw_backward(F0, F1, pairs, neg, neg_thresh, g_pos, g_neg, ws):
     """``eyoc_closs_backward`` -> ``(dF0, dF1)``; ``g_pos`` / ``g_neg`` float32 device scalars, ``ws`` from ``contrastive_raw_forward``
     on the same arguments."""
-    lib = _lib.load()
-    dF0, dF1 = torch.empty_like(F0), torch.empty_like(F1)
-    with _lib.on_device(F0.device):
-        _lib.check(lib.eyoc_closs_backward(*_contrastive_args(F0, F1, pairs, neg, neg_thresh), _lib.ptr(g_pos), _lib.ptr(g_neg),
-                                           _lib.ptr(dF0), _lib.ptr(dF1), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
-                   "eyoc_closs_backward")
-    return dF0, dF1
+    return _backward("eyoc_closs", _contrastive_args(F0, F1, pairs, neg, neg_thresh), F0, F1, (g_pos, g_neg), ws)
 
 
 def read_contrastive_record(rec) -> _lib.ClossRecord:
     """The record on the host (tests, logging): this READS BACK, the loss itself never does."""
-    return _lib.ClossRecord.from_buffer_copy(rec.detach().cpu().numpy().tobytes())
+    return _read(rec, _lib.ClossRecord)
 
 
 def contrastive_results(ws, n_pairs, n_neg, c):
@@ -390,32 +367,18 @@ def contrastive_results(ws, n_pairs, n_neg, c):
     [n_neg], ``flags`` int32 [n_neg] (``CLOSS_MASKED`` / ``_VALID`` / ``_ACTIVE``); ``contrib_key`` int32 [2 (n_pairs + n_neg)], written
     by the backward (2 row + matrix + 1, 0 = empty)."""
     lay = contrastive_layout(n_pairs, n_neg, c)
-
-    def view(off, count, dtype):
-        return ws[off:off + 4 * count].view(dtype)
-    return {"pos_d2": view(lay.off_pos_d2, n_pairs, torch.float32), "dist": view(lay.off_dist, n_neg, torch.float32),
-            "term": view(lay.off_term, n_neg, torch.float32), "flags": view(lay.off_flags, n_neg, torch.int32),
-            "contrib_key": view(lay.off_contrib_key, lay.n_contrib, torch.int32)}
+    return {"pos_d2": _view(ws, lay.off_pos_d2, n_pairs, torch.float32), "dist": _view(ws, lay.off_dist, n_neg, torch.float32),
+            "term": _view(ws, lay.off_term, n_neg, torch.float32), "flags": _view(ws, lay.off_flags, n_neg, torch.int32),
+            "contrib_key": _view(ws, lay.off_contrib_key, lay.n_contrib, torch.int32)}
 
 
-class _Contrastive(torch.autograd.Function):
+class _Contrastive(_Node):
     @staticmethod
     def forward(ctx, F0, F1, pairs, neg, neg_thresh):
         rec, ws = contrastive_raw_forward(F0, F1, pairs, neg, neg_thresh)
         ctx.save_for_backward(F0, F1)
-        ctx.idx, ctx.thresh, ctx.ws = (pairs, neg), neg_thresh, ws
+        ctx.call, ctx.ws = (contrastive_raw_backward, (pairs, neg, neg_thresh), 2), ws
         return rec[_CLOSS_POS], rec[_CLOSS_POS + 1]
-
-    @staticmethod
-    def backward(ctx, g_pos, g_neg):
-        F0, F1 = ctx.saved_tensors
-
-        def scalar(g):                                  # a missing gradient is zero
-            if g is None:
-                return torch.zeros((), dtype=torch.float32, device=F0.device)
-            return g.to(torch.float32).contiguous()
-        dF0, dF1 = contrastive_raw_backward(F0, F1, *ctx.idx, ctx.thresh, scalar(g_pos), scalar(g_neg), ctx.ws)
-        return dF0, dF1, None, None, None
 
 
 def _device_pairs(positive_pairs, dev):
