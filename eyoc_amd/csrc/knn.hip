@@ -7,7 +7,13 @@
 // index" independently of how the work was split.
 //
 // Arithmetic contract (bit-exact with oracle/matching.py): d = a - b; s = d * d; acc = acc + s in
-// fp32, channels in order, no FMA contraction.
+// fp32, channels in order, no FMA contraction.  It is written down ONCE - knn_load_query, knn_group_distances, knn_candidate, knn_key -
+// and both lane-per-query kernels (knn1_kernel, knn1_mutual_kernel) call that text.
+//
+// Host side: every entry point reads its segment lists through seg_plan, the ctx's scratch is laid out by knn_layout (one function for
+// the byte count and for the pointers), and only the public entry points ever grow the scratch - see knn_run.
+#include <type_traits>
+
 #include "scan.h"
 
 namespace {
@@ -39,9 +45,21 @@ __global__ void knn_transpose_targets(const float* __restrict__ B, SegArgs seg, 
   dst[0] = v.x; dst[ld] = v.y; dst[2 * (size_t)ld] = v.z; dst[3 * (size_t)ld] = v.w;
 }
 
+// the lane's query `row` (C floats) as packed operands: a[c] = {row[c], row[c]}, the feature in both halves
+template <int C>
+__device__ __forceinline__ void knn_load_query(const float* row, f32x2 (&a)[C]) {
+  const float4* src = reinterpret_cast<const float4*>(row);
+#pragma unroll
+  for (int i = 0; i < C / 4; ++i) {
+    const float4 v = src[i];
+    a[4 * i] = f32x2{v.x, v.x}; a[4 * i + 1] = f32x2{v.y, v.y}; a[4 * i + 2] = f32x2{v.z, v.z}; a[4 * i + 3] = f32x2{v.w, v.w};
+  }
+}
+
 // acc[k] = the contract's value for targets 2 k, 2 k + 1 of the group of TGROUP whose channel-major rows start at `col` (wave-uniform,
-// row length ld) against the lane's query `a`: the squared distance, or with DOT -<a, b>.  This is knn1_kernel's own group body, word for word: that kernel keeps its text (and with it the code it
-// was measured with - sharing the function changes its register allocation), knn1_mutual_kernel calls this copy.
+// row length ld) against the lane's query `a`: the squared distance, or with DOT -<a, b>.  The one group body of this file: knn1_kernel
+// and knn1_mutual_kernel both call it, so the order of operations, the batching of the scalar loads and the sched_barrier placement are
+// the same in both (EXPERIMENTS.md "kNN: one group body" has knn1_kernel's registers and times before and after it shared this text).
 template <int C, bool DOT>
 __device__ __forceinline__ void knn_group_distances(const f32x2 (&a)[C], const float* col, int ld, f32x2 (&acc)[TGROUP / 2]) {
 #pragma clang fp contract(off)
@@ -156,85 +174,22 @@ __global__ __launch_bounds__(256) void knn1_kernel(const float* __restrict__ A, 
   } else if (q0 >= na) {
     return;
   }
-  f32x2 a[C];   // {a_c, a_c}: the query's feature in both halves of a packed operand
-  {
-    const float4* src = reinterpret_cast<const float4*>(A + (size_t)(a0 + (q_ok ? q : 0)) * C);
-#pragma unroll
-    for (int i = 0; i < C / 4; ++i) {
-      const float4 v = src[i];
-      a[4 * i] = f32x2{v.x, v.x}; a[4 * i + 1] = f32x2{v.y, v.y}; a[4 * i + 2] = f32x2{v.z, v.z}; a[4 * i + 3] = f32x2{v.w, v.w};
-    }
-  }
+  f32x2 a[C];
+  knn_load_query<C>(A + (size_t)(a0 + (q_ok ? q : 0)) * C, a);
   float best_d = __builtin_inff(), second_d = __builtin_inff();
   int best_j = 0x7FFFFFFF;
   bool any = false;
   // the four waves of the block take interleaved groups of TGROUP targets
   const float* bt = Bt + seg.bt_off[s];
   for (int t = t_begin + wave * TGROUP; t < t_end; t += 4 * TGROUP) {
-    // (the group body below has a word-for-word COPY, knn_group_distances, which knn1_mutual_kernel calls: a change of the arithmetic
-    // contract here must be made there too - tests/test_gpu_mutual.py compares the two kernels' indices)
     f32x2 acc[TGROUP / 2];
-#pragma unroll
-    for (int k = 0; k < TGROUP / 2; ++k) acc[k] = f32x2{0.0f, 0.0f};
-    const float* col = bt + t;   // wave-uniform address
-    // Channels in batches of CB (eight SGPRs per channel).  Scalar loads return out of order, so a wait is always
-    // "all of them": the next batch is therefore issued right AFTER the wait for the current one (behind the first
-    // packed op that needs it) and its latency hides behind the rest of the current batch.
-    constexpr int CB = C >= 8 ? 4 : C / 2;
-    auto load_batch = [&](int cb, f32x2 (&b)[CB][TGROUP / 2]) {
-#pragma unroll
-      for (int c = 0; c < CB; ++c) {
-        const float4 lo = *reinterpret_cast<const float4*>(col + (size_t)(cb + c) * ld);
-        const float4 hi = *reinterpret_cast<const float4*>(col + (size_t)(cb + c) * ld + 4);
-        b[c][0] = f32x2{lo.x, lo.y}; b[c][1] = f32x2{lo.z, lo.w}; b[c][2] = f32x2{hi.x, hi.y}; b[c][3] = f32x2{hi.z, hi.w};
-      }
-    };
-    // the four target pairs side by side, so that dependent packed ops are never back to back (a wait state each)
-    auto channel = [&](int c, const f32x2 (&b)[TGROUP / 2]) {
-      if (DOT) {
-#pragma unroll
-        for (int k = 0; k < TGROUP / 2; ++k) acc[k] = __builtin_elementwise_fma(a[c], -b[k], acc[k]);
-        return;
-      }
-      f32x2 d[TGROUP / 2];
-#pragma unroll
-      for (int k = 0; k < TGROUP / 2; ++k) d[k] = a[c] - b[k];
-#pragma unroll
-      for (int k = 0; k < TGROUP / 2; ++k) d[k] = d[k] * d[k];
-#pragma unroll
-      for (int k = 0; k < TGROUP / 2; ++k) acc[k] = acc[k] + d[k];
-    };
-    f32x2 b0[CB][TGROUP / 2], b1[CB][TGROUP / 2];
-    load_batch(0, b0);
-#pragma unroll
-    for (int cb = 0; cb < C; cb += 2 * CB) {
-      __builtin_amdgcn_sched_barrier(0);
-      channel(cb, b0[0]);                               // forces the wait for batch b0
-      __builtin_amdgcn_sched_barrier(0);
-      load_batch(cb + CB, b1);                          // C is a multiple of 2 CB
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int c = 1; c < CB; ++c) channel(cb + c, b0[c]);
-      __builtin_amdgcn_sched_barrier(0);
-      channel(cb + CB, b1[0]);
-      __builtin_amdgcn_sched_barrier(0);
-      if (cb + 2 * CB < C) load_batch(cb + 2 * CB, b0);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int c = 1; c < CB; ++c) channel(cb + CB + c, b1[c]);
-    }
+    knn_group_distances<C, DOT>(a, bt + t, ld, acc);   // (bt + t: a wave-uniform address)
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int e = 0; e < TGROUP; ++e) {
       // branch-free on purpose: with branches here LLVM sinks the arithmetic of targets 2..7 below the first
       // compare and keeps every scalar-loaded operand alive until then (SGPR spills)
-      float v = (e & 1) ? acc[e / 2].y : acc[e / 2].x;
-      v = dist_type == 1 ? sqrtf(v + 1e-7f) : v;
-      if (MODE == 2) {          // acc = -S exactly (the negated chain rounds symmetrically)
-        const float w = (2.0f - 2.0f * (-v)) + 1e-6f;
-        const float d = sqrtf(w);
-        v = d != d ? -1.0f : d;                                        // NaN first: below every distance
-      }
+      const float v = knn_candidate<MODE>((e & 1) ? acc[e / 2].y : acc[e / 2].x, dist_type);
       const bool valid = t + e < t_end;
       const bool better = valid & (v < best_d);
       if (TOP2) {   // the displaced best, or a value between the two, becomes the runner-up (NaNs never enter)
@@ -270,12 +225,7 @@ __global__ __launch_bounds__(256) void knn1_kernel(const float* __restrict__ A, 
     }
     return;
   }
-  if (q_ok && any) {
-    unsigned int bits = __float_as_uint(best_d);
-    if (DOT) bits = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);   // negative values too: order-preserving key
-    unsigned long long packed = ((unsigned long long)bits << 32) | (unsigned)best_j;
-    atomicMin(&best[a0 + q], packed);
-  }
+  if (q_ok && any) atomicMin(&best[a0 + q], ((unsigned long long)knn_key<DOT>(best_d) << 32) | (unsigned)best_j);
   if (!only) return;
   }
 }
@@ -318,15 +268,8 @@ __global__ __launch_bounds__(256) void knn1_mutual_kernel(const float* __restric
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int q = q0 + lane;
   const bool q_ok = q < na;
-  f32x2 a[C];   // {a_c, a_c}: the query's feature in both halves of a packed operand
-  {
-    const float4* src = reinterpret_cast<const float4*>(A + (size_t)(a0 + (q_ok ? q : 0)) * C);
-#pragma unroll
-    for (int i = 0; i < C / 4; ++i) {
-      const float4 v = src[i];
-      a[4 * i] = f32x2{v.x, v.x}; a[4 * i + 1] = f32x2{v.y, v.y}; a[4 * i + 2] = f32x2{v.z, v.z}; a[4 * i + 3] = f32x2{v.w, v.w};
-    }
-  }
+  f32x2 a[C];
+  knn_load_query<C>(A + (size_t)(a0 + (q_ok ? q : 0)) * C, a);
   float best_d = __builtin_inff();
   int best_j = 0x7FFFFFFF;
   bool any = false;
@@ -786,23 +729,220 @@ __global__ void pdist_kernel(const float* __restrict__ A, int n, const float* __
   out[idx] = acc;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Host side.
+
+// floats of the packed targets of a segment of `nb` rows: 3 x 64 float4 per tile of 16 targets
+long long packed_target_floats(int nb) { return (long long)eyoc::cdiv(nb, 16) * 3 * 64 * 4; }
+
+// What the segment lists of a call come to.  seg_plan is the one pass every entry point makes over its lists, and the only place that
+// fills a SegArgs; everything about the targets (ld, bt_off, bm_off, bt_floats, bm_floats) describes the b side.
+struct SegPlan {
+  SegArgs seg;
+  SegMfma sm;
+  int n_a, n_b;                      // rows in all
+  int max_na, max_nb, max_ld;
+  long long bt_floats, bm_floats;    // the transposed / the packed targets of all segments
+  long long waves_a, waves_b;        // waves of MF_ROWS rows
+};
+
+// seg_a / seg_b: nseg + 1 offsets each; a caller with one list passes NULL for the other side, whose segments are then empty.  c: the
+// width of the rows (it only sizes the transposed targets).  Refuses nseg outside [1, MAX_SEG] and a decreasing list; whether a list
+// must start at 0 is the entry point's own rule.
+int seg_plan(const char* who, const int32_t* seg_a, const int32_t* seg_b, int nseg, int c, SegPlan* p) {
+  EYOC_REQUIRE(nseg >= 1 && nseg <= MAX_SEG, EYOC_ERR_INVALID, "%s: nseg %d not in [1,%d]", who, nseg, MAX_SEG);
+  *p = SegPlan{};
+  for (int s = 0; s <= nseg; ++s) {
+    p->seg.a[s] = seg_a ? seg_a[s] : 0;
+    p->seg.b[s] = seg_b ? seg_b[s] : 0;
+  }
+  for (int s = 0; s < nseg; ++s) {
+    const int na = p->seg.a[s + 1] - p->seg.a[s], nb = p->seg.b[s + 1] - p->seg.b[s];
+    EYOC_REQUIRE(na >= 0 && nb >= 0, EYOC_ERR_INVALID, "%s: negative segment length", who);
+    p->max_na = na > p->max_na ? na : p->max_na;
+    p->max_nb = nb > p->max_nb ? nb : p->max_nb;
+    p->seg.ld[s] = eyoc::cdiv(nb, TGROUP) * TGROUP;
+    p->max_ld = p->seg.ld[s] > p->max_ld ? p->seg.ld[s] : p->max_ld;
+    p->seg.bt_off[s] = p->bt_floats;
+    p->bt_floats += (long long)p->seg.ld[s] * c;
+    p->sm.bm_off[s] = p->bm_floats;
+    p->bm_floats += packed_target_floats(nb);
+    p->waves_a += eyoc::cdiv(na, MF_ROWS);
+    p->waves_b += eyoc::cdiv(nb, MF_ROWS);
+  }
+  p->n_a = p->seg.a[nseg] - p->seg.a[0];
+  p->n_b = p->seg.b[nseg] - p->seg.b[0];
+  return EYOC_OK;
+}
+
+bool knn_width_ok(int c) { return c == 4 || c == 16 || c == 32 || c == 64 || c == 128; }
+
+// f(std::integral_constant<int, C>) for the width c (one that knn_width_ok accepts)
+template <typename F>
+void dispatch_width(int c, F&& f) {
+  switch (c) {
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    case 64: f(std::integral_constant<int, 64>{}); break;
+    default: f(std::integral_constant<int, 128>{}); break;
+  }
+}
+
+// grid.y: the targets of the longest segment in nsplit pieces of split_len, a multiple of `align`, so that about 4096 blocks fly
+// (`blocks` of them before splitting); !may_split: one piece
+struct SplitPlan { int nsplit, split_len; };
+SplitPlan split_plan(int blocks, int max_nb, int align, bool may_split) {
+  const int max_splits = eyoc::cdiv(max_nb, align);
+  int nsplit = may_split ? 4096 / (blocks > 0 ? blocks : 1) : 1;
+  nsplit = nsplit < 1 ? 1 : nsplit > max_splits ? max_splits : nsplit;
+  const int split_len = eyoc::cdiv(eyoc::cdiv(max_nb, nsplit), align) * align;
+  return {eyoc::cdiv(max_nb, split_len), split_len};
+}
+
 template <int C>
-void launch_knn(const float* A, const float* Bt, const SegArgs& seg, int nseg, int max_na, int max_nb, int dist_type,
-                unsigned long long* best, float* second, bool dot, hipStream_t st, const int* only = nullptr,
-                const int* only_cnt = nullptr) {
-  int qtiles = only ? 2 : eyoc::cdiv(max_na, 64);   // second pass of the pre-filter: two blocks per (segment, split) walk the list
-  int total = qtiles * nseg;
-  int max_splits = eyoc::cdiv(max_nb, SPLIT_ALIGN);
-  int nsplit = 4096 / (total > 0 ? total : 1);
-  if (nsplit < 1 || second) nsplit = 1;
-  if (nsplit > max_splits) nsplit = max_splits;
-  int split_len = eyoc::cdiv(eyoc::cdiv(max_nb, nsplit), SPLIT_ALIGN) * SPLIT_ALIGN;
-  nsplit = eyoc::cdiv(max_nb, split_len);
-  dim3 grid(qtiles, nsplit, nseg);
-  if (second) hipLaunchKernelGGL((knn1_kernel<C, true, 0>), grid, dim3(256), 0, st, A, Bt, seg, split_len, dist_type, best, second, (const int*)nullptr, (const int*)nullptr);
-  else if (dot) hipLaunchKernelGGL((knn1_kernel<C, false, 1>), grid, dim3(256), 0, st, A, Bt, seg, split_len, 0, best, second, (const int*)nullptr, (const int*)nullptr);
-  else if (dist_type == 2) hipLaunchKernelGGL((knn1_kernel<C, false, 2>), grid, dim3(256), 0, st, A, Bt, seg, split_len, 0, best, second, only, only_cnt);
-  else hipLaunchKernelGGL((knn1_kernel<C, false, 0>), grid, dim3(256), 0, st, A, Bt, seg, split_len, dist_type, best, second, only, only_cnt);
+void launch_knn(const float* A, const float* Bt, const SegPlan& p, int nseg, int dist_type, unsigned long long* best, float* second,
+                bool dot, hipStream_t st, const int* only, const int* only_cnt) {
+  const int qtiles = only ? 2 : eyoc::cdiv(p.max_na, 64);   // second pass of the pre-filter: two blocks per (segment, split) walk the list
+  const SplitPlan sp = split_plan(qtiles * nseg, p.max_nb, SPLIT_ALIGN, !second);   // (a runner-up cannot be merged over blocks)
+  const dim3 grid(qtiles, sp.nsplit, nseg);
+  if (second) hipLaunchKernelGGL((knn1_kernel<C, true, 0>), grid, dim3(256), 0, st, A, Bt, p.seg, sp.split_len, dist_type, best, second, (const int*)nullptr, (const int*)nullptr);
+  else if (dot) hipLaunchKernelGGL((knn1_kernel<C, false, 1>), grid, dim3(256), 0, st, A, Bt, p.seg, sp.split_len, 0, best, second, (const int*)nullptr, (const int*)nullptr);
+  else if (dist_type == 2) hipLaunchKernelGGL((knn1_kernel<C, false, 2>), grid, dim3(256), 0, st, A, Bt, p.seg, sp.split_len, 0, best, second, only, only_cnt);
+  else hipLaunchKernelGGL((knn1_kernel<C, false, 0>), grid, dim3(256), 0, st, A, Bt, p.seg, sp.split_len, dist_type, best, second, only, only_cnt);
+}
+
+template <int C>
+void launch_knn_mutual(const float* A, const float* Bt, const SegPlan& p, int nseg, int dist_type, unsigned long long* best,
+                       unsigned long long* colbest, hipStream_t st) {
+  const int qtiles = eyoc::cdiv(p.max_na, 64);
+  const SplitPlan sp = split_plan(qtiles * nseg, p.max_nb, MUT_SPLIT_ALIGN, true);
+  const dim3 grid(qtiles, sp.nsplit, nseg);
+  if (dist_type == 2) hipLaunchKernelGGL((knn1_mutual_kernel<C, 2>), grid, dim3(256), 0, st, A, Bt, p.seg, sp.split_len, 0, best, colbest);
+  else hipLaunchKernelGGL((knn1_mutual_kernel<C, 0>), grid, dim3(256), 0, st, A, Bt, p.seg, sp.split_len, dist_type, best, colbest);
+}
+
+void launch_transpose(const float* B_dev, const SegPlan& p, int nseg, int c, float* Bt, hipStream_t st) {
+  hipLaunchKernelGGL(knn_transpose_targets, dim3(eyoc::cdiv((long long)p.max_ld * (c / 4), 256), 1, nseg), dim3(256), 0, st, B_dev, p.seg, c, Bt);
+}
+
+// bmax (one word per segment) must be zero when this runs
+void launch_pack_targets(const float* B_dev, const SegPlan& p, int nseg, float* Bm, int* bmax, int zero_norm, hipStream_t st) {
+  hipLaunchKernelGGL(knn_pack_targets_mfma<32>, dim3(eyoc::cdiv(eyoc::cdiv(p.max_nb, 16), 4 * PK_TILES), 1, nseg), dim3(256), 0, st, B_dev, p.seg,
+                     p.sm, Bm, bmax, zero_norm);
+}
+
+// MFMA pre-filter (see knn_mfma_kernel): `plain` index queries - no distances, no runner-up, no inner product - that fill the chip
+// (a single pair - 79 waves, each walking all 5000 targets - takes 0.15 ms there against 0.10 in the exact kernel)
+bool knn_prefilter_on(const eyoc_ctx* ctx, const SegPlan& p, int c, int dist_type, bool plain) {
+  const int knob = ctx->knobs.knn_prefilter;
+  return knob != 0 && plain && dist_type != 1 && c == 32 && p.max_nb > 0 && (p.waves_a >= 512 || knob == 2);
+}
+
+// The arrays of one one-way query, carved in ONE place: on a null base every pointer is null and `bytes` is what the query needs, on a
+// workspace they are the arrays.  The byte count and the carving are the same code, so they cannot drift apart.
+struct KnnWs {
+  unsigned long long* best;   // [n_a] packed minima
+  float* Bt;                  // the transposed targets, 64 bytes of slack behind them
+  float *Bm, *anorm;          // pre-filter: the packed targets, |a|^2 per row
+  int *flags, *bmax, *fcnt;   // pre-filter: the undecided rows per segment; bmax[MAX_SEG] and fcnt[MAX_SEG] are one array (one memset), 64 bytes of slack behind it
+  size_t bytes;
+};
+KnnWs knn_layout(void* base, const SegPlan& p, bool prefilter) {
+  eyoc::Carver cv(base, 0);
+  KnnWs w = {};
+  w.best = cv.take<unsigned long long>(p.n_a);
+  w.Bt = cv.take<float>(p.bt_floats + 16);
+  if (prefilter) {
+    w.Bm = cv.take<float>(p.bm_floats);
+    w.anorm = cv.take<float>(p.n_a);
+    w.flags = cv.take<int>(p.n_a);
+    w.bmax = cv.take<int>(2 * MAX_SEG + 16);
+    w.fcnt = base ? w.bmax + MAX_SEG : nullptr;
+  }
+  w.bytes = eyoc::align_up(cv.off);
+  return w;
+}
+
+// One one-way query of p.n_a > 0 rows on a workspace of the caller's (256-byte aligned).  It carves, it never allocates: no path from
+// here reaches eyoc_ctx::ensure_scratch, whose growth frees the old buffer.  That is what lets eyoc_knn1_mutual keep arrays of its own in
+// the same scratch across two of these runs - a workspace too small for the layout is EYOC_ERR_WORKSPACE here, not a buffer freed under
+// queued kernels.  The guarantee is this structure; no test can see it (the scratch only grows, in a test process it has grown before).
+// has_dev: see knn1_unpack.
+int knn_run(const eyoc_ctx* ctx, void* ws, size_t ws_bytes, const SegPlan& p, int nseg, const float* A_dev, const float* B_dev, int c,
+            int dist_type, bool dot, int64_t* idx_dev, float* dist_dev, float* second_dev, unsigned char* has_dev, hipStream_t st) {
+  const bool prefilter = knn_prefilter_on(ctx, p, c, dist_type, !dot && !second_dev && !dist_dev);
+  const KnnWs w = knn_layout(ws, p, prefilter);
+  EYOC_REQUIRE(w.bytes <= ws_bytes, EYOC_ERR_WORKSPACE, "kNN query: workspace %zu < %zu bytes", ws_bytes, w.bytes);
+  EYOC_CHECK_HIP(hipMemsetAsync(w.best, 0xFF, (size_t)p.n_a * sizeof(unsigned long long), st));
+  if (prefilter) {
+    EYOC_CHECK_HIP(hipMemsetAsync(w.bmax, 0, 2 * MAX_SEG * sizeof(int), st));
+    launch_pack_targets(B_dev, p, nseg, w.Bm, w.bmax, dist_type == 2 ? 1 : 0, st);
+    hipLaunchKernelGGL(knn_row_norms, dim3(eyoc::cdiv(p.n_a, 256)), dim3(256), 0, st, A_dev, p.n_a, c, w.anorm);
+    const dim3 grid(eyoc::cdiv(p.max_na, 4 * MF_ROWS), 1, nseg);
+    if (dist_type == 2)
+      hipLaunchKernelGGL((knn_mfma_kernel<32, 2>), grid, dim3(256), 0, st, A_dev, w.Bm, p.seg, p.sm, w.anorm, w.bmax, w.best, w.flags, w.fcnt);
+    else
+      hipLaunchKernelGGL((knn_mfma_kernel<32, 0>), grid, dim3(256), 0, st, A_dev, w.Bm, p.seg, p.sm, w.anorm, w.bmax, w.best, w.flags, w.fcnt);
+  }
+  if (prefilter && dist_type == 0) {
+    // the undecided rows, lane = target (no transposed copy of the targets needed)
+    hipLaunchKernelGGL(knn1_list_kernel<32>, dim3(eyoc::cdiv(p.max_nb, 256), 1, nseg), dim3(256), 0, st, A_dev, B_dev, p.seg, w.best,
+                       (const int*)w.flags, (const int*)w.fcnt);
+  } else if (p.max_nb > 0) {
+    launch_transpose(B_dev, p, nseg, c, w.Bt, st);
+    dispatch_width(c, [&](auto width) {
+      launch_knn<decltype(width)::value>(A_dev, w.Bt, p, nseg, dist_type, w.best, second_dev, dot, st, w.flags, w.fcnt);   // (null without the pre-filter)
+    });
+  }
+  hipLaunchKernelGGL(knn1_unpack, dim3(eyoc::cdiv(p.n_a, 256)), dim3(256), 0, st, w.best, p.n_a, (long long*)idx_dev, dist_dev,
+                     dot ? 1 : dist_type == 2 ? 2 : 0, has_dev);
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
+// eyoc_knn1 / eyoc_knn2 / eyoc_dotmax: the checks, ONE growth of the scratch to the layout's size, the run
+int knn_query(const char* who, eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c, const int32_t* seg_a, const int32_t* seg_b,
+              int nseg, int dist_type, bool dot, int64_t* idx_dev, float* dist_dev, float* second_dev, void* stream) {
+  EYOC_REQUIRE(ctx && A_dev && B_dev && seg_a && seg_b, EYOC_ERR_INVALID, "%s: NULL argument", who);
+  EYOC_REQUIRE(dist_type >= 0 && dist_type <= 2, EYOC_ERR_INVALID, "%s: dist_type %d", who, dist_type);
+  EYOC_REQUIRE(!(dist_type == 2 && (dot || second_dev)), EYOC_ERR_INVALID, "%s: dist_type 2 is a 1-NN mode", who);
+  EYOC_REQUIRE(knn_width_ok(c), EYOC_ERR_INVALID, "%s: feature dimension %d not supported (4/16/32/64/128)", who, c);
+  SegPlan p;
+  if (int rc = seg_plan(who, seg_a, seg_b, nseg, c, &p)) return rc;
+  if (p.n_a == 0) return EYOC_OK;
+  EYOC_REQUIRE(seg_a[0] == 0, EYOC_ERR_INVALID, "%s: seg_a[0] must be 0", who);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t need = knn_layout(nullptr, p, knn_prefilter_on(ctx, p, c, dist_type, !dot && !second_dev && !dist_dev)).bytes;
+  if (int rc = ctx->ensure_scratch(need, st)) return rc;
+  return knn_run(ctx, ctx->scratch, need, p, nseg, A_dev, B_dev, c, dist_type, dot, idx_dev, dist_dev, second_dev, nullptr, st);
+}
+
+// eyoc_knn1_mutual's share of the scratch: [has_a | has_b | idx_ba when the caller wants none] in front, then the fused route's three
+// arrays or `dir`, dir_bytes for the two one-way runs (one after the other in the same bytes).  Null base: the byte count, like knn_layout.
+struct MutualWs {
+  unsigned char *has_a, *has_b;
+  long long* idx_ba;
+  unsigned long long *best, *colbest;
+  float* Bt;
+  char* dir;
+  size_t bytes;
+};
+MutualWs mutual_layout(void* base, const SegPlan& p, bool own_idx_ba, bool fused, size_t dir_bytes) {
+  eyoc::Carver cv(base, 0);
+  MutualWs w = {};
+  w.has_a = cv.take<unsigned char>(p.n_a);
+  w.has_b = cv.take<unsigned char>(p.n_b);
+  if (own_idx_ba) w.idx_ba = cv.take<long long>(p.n_b);
+  if (fused) {
+    w.best = cv.take<unsigned long long>(p.n_a);
+    w.colbest = cv.take<unsigned long long>(p.n_b);
+    w.Bt = cv.take<float>(p.bt_floats + 16);
+  } else {
+    w.dir = cv.take<char>(dir_bytes);
+  }
+  w.bytes = eyoc::align_up(cv.off);
+  return w;
 }
 
 }  // namespace
@@ -814,128 +954,15 @@ extern "C" int eyoc_knn_prefilter(eyoc_ctx* ctx, int mode) {
   return prev;
 }
 
-// bmax (one word per segment) must be zero when this runs
-static void launch_pack_targets(const float* B_dev, const SegArgs& seg, const SegMfma& sm, int nseg, int max_nb, float* Bm, int* bmax,
-                                int zero_norm, hipStream_t st) {
-  hipLaunchKernelGGL(knn_pack_targets_mfma<32>, dim3(eyoc::cdiv(eyoc::cdiv(max_nb, 16), 4 * PK_TILES), 1, nseg), dim3(256), 0, st, B_dev, seg,
-                     sm, Bm, bmax, zero_norm);
-}
-
-// floats of the packed targets of segments of `nb` rows: 3 x 64 float4 per tile of 16 targets
-static long long packed_target_floats(int nb) { return (long long)eyoc::cdiv(nb, 16) * 3 * 64 * 4; }
-
 extern "C" int eyoc_knn_pack_targets(eyoc_ctx* ctx, const float* B_dev, const int32_t* seg_b, int nseg, int zero_norm, float* packed_dev,
                                      size_t packed_floats, int32_t* bmax_dev, void* stream) {
   EYOC_REQUIRE(ctx && B_dev && seg_b && packed_dev && bmax_dev, EYOC_ERR_INVALID, "eyoc_knn_pack_targets: NULL argument");
-  EYOC_REQUIRE(nseg >= 1 && nseg <= MAX_SEG, EYOC_ERR_INVALID, "eyoc_knn_pack_targets: nseg %d not in [1,%d]", nseg, MAX_SEG);
+  SegPlan p;
+  if (int rc = seg_plan("eyoc_knn_pack_targets", nullptr, seg_b, nseg, 32, &p)) return rc;
+  EYOC_REQUIRE((size_t)p.bm_floats <= packed_floats, EYOC_ERR_INVALID, "eyoc_knn_pack_targets: %lld floats needed, %zu given", p.bm_floats, packed_floats);
   hipStream_t st = (hipStream_t)stream;
-  SegArgs seg = {};
-  SegMfma sm;
-  long long floats = 0;
-  int max_nb = 0;
-  for (int s = 0; s <= nseg; ++s) seg.b[s] = seg_b[s];
-  for (int s = 0; s < nseg; ++s) {
-    const int nb = seg_b[s + 1] - seg_b[s];
-    EYOC_REQUIRE(nb >= 0, EYOC_ERR_INVALID, "eyoc_knn_pack_targets: negative segment length");
-    max_nb = nb > max_nb ? nb : max_nb;
-    sm.bm_off[s] = floats;
-    floats += packed_target_floats(nb);
-  }
-  EYOC_REQUIRE((size_t)floats <= packed_floats, EYOC_ERR_INVALID, "eyoc_knn_pack_targets: %lld floats needed, %zu given", floats, packed_floats);
   EYOC_CHECK_HIP(hipMemsetAsync(bmax_dev, 0, (size_t)nseg * sizeof(int32_t), st));
-  if (max_nb > 0) launch_pack_targets(B_dev, seg, sm, nseg, max_nb, packed_dev, bmax_dev, zero_norm ? 1 : 0, st);
-  EYOC_CHECK_HIP(hipGetLastError());
-  return EYOC_OK;
-}
-
-static int knn_run(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c, const int32_t* seg_a,
-                   const int32_t* seg_b, int nseg, int dist_type, int64_t* idx_dev, float* dist_dev, float* second_dev,
-                   void* stream, bool dot = false, size_t base = 0, unsigned char* has_dev = nullptr) {
-  // base (a multiple of 256): the first bytes of the ctx's scratch belong to the caller (eyoc_knn1_mutual); has_dev: see knn1_unpack
-  EYOC_REQUIRE(ctx && A_dev && B_dev && seg_a && seg_b, EYOC_ERR_INVALID, "eyoc_knn1: NULL argument");
-  EYOC_REQUIRE(nseg >= 1 && nseg <= MAX_SEG, EYOC_ERR_INVALID, "eyoc_knn1: nseg %d not in [1,%d]", nseg, MAX_SEG);
-  EYOC_REQUIRE(dist_type >= 0 && dist_type <= 2, EYOC_ERR_INVALID, "eyoc_knn1: dist_type %d", dist_type);
-  EYOC_REQUIRE(!(dist_type == 2 && (dot || second_dev)), EYOC_ERR_INVALID, "eyoc_knn1: dist_type 2 is a 1-NN mode");
-  EYOC_REQUIRE(c == 4 || c == 16 || c == 32 || c == 64 || c == 128, EYOC_ERR_INVALID,
-               "eyoc_knn1: feature dimension %d not supported (4/16/32/64/128)", c);
-  hipStream_t st = (hipStream_t)stream;
-  SegArgs seg;
-  int max_na = 0, max_nb = 0;
-  for (int s = 0; s <= nseg; ++s) { seg.a[s] = seg_a[s]; seg.b[s] = seg_b[s]; }
-  for (int s = 0; s < nseg; ++s) {
-    int na = seg_a[s + 1] - seg_a[s], nb = seg_b[s + 1] - seg_b[s];
-    EYOC_REQUIRE(na >= 0 && nb >= 0, EYOC_ERR_INVALID, "eyoc_knn1: negative segment length");
-    max_na = na > max_na ? na : max_na;
-    max_nb = nb > max_nb ? nb : max_nb;
-  }
-  const int n_total = seg_a[nseg] - seg_a[0];
-  if (n_total == 0) return EYOC_OK;
-  EYOC_REQUIRE(seg_a[0] == 0, EYOC_ERR_INVALID, "eyoc_knn1: seg_a[0] must be 0");
-  long long bt_floats = 0;
-  int max_ld = 0;
-  for (int s = 0; s < nseg; ++s) {
-    const int nb = seg_b[s + 1] - seg_b[s];
-    seg.ld[s] = (nb + TGROUP - 1) / TGROUP * TGROUP;
-    seg.bt_off[s] = bt_floats;
-    bt_floats += (long long)seg.ld[s] * c;
-    max_ld = seg.ld[s] > max_ld ? seg.ld[s] : max_ld;
-  }
-  // MFMA pre-filter (see knn_mfma_kernel): plain index queries that fill the chip
-  const int prefilter_env = ctx->knobs.knn_prefilter;
-  long long waves = 0, bm_floats = 0;
-  SegMfma sm;
-  for (int s = 0; s < nseg; ++s) {
-    waves += eyoc::cdiv(seg_a[s + 1] - seg_a[s], MF_ROWS);
-    sm.bm_off[s] = bm_floats;
-    bm_floats += packed_target_floats(seg_b[s + 1] - seg_b[s]);
-  }
-  const bool prefilter = prefilter_env != 0 && !dot && !second_dev && !dist_dev && dist_type != 1 && c == 32 && max_nb > 0 &&
-                         (waves >= 512 || prefilter_env == 2);   // (round 5: a single pair - 79 waves, each walking all 5000 targets - takes 0.15 ms here against 0.10 in the exact kernel)
-  const size_t off_bt = eyoc::align_up(base + (size_t)n_total * sizeof(unsigned long long));
-  const size_t off_bm = eyoc::align_up(off_bt + (size_t)bt_floats * sizeof(float) + 64);
-  const size_t off_an = eyoc::align_up(off_bm + (prefilter ? (size_t)bm_floats * sizeof(float) : 0));
-  const size_t off_fl = eyoc::align_up(off_an + (prefilter ? (size_t)n_total * sizeof(float) : 0));
-  const size_t off_bx = eyoc::align_up(off_fl + (prefilter ? (size_t)n_total * sizeof(int) : 0));
-  int rc = ctx->ensure_scratch(off_bx + 2 * MAX_SEG * sizeof(int) + 64, st);
-  if (rc) return rc;
-  unsigned long long* best = (unsigned long long*)((char*)ctx->scratch + base);
-  float* Bt = (float*)((char*)ctx->scratch + off_bt);
-  EYOC_CHECK_HIP(hipMemsetAsync(best, 0xFF, (size_t)n_total * sizeof(unsigned long long), st));
-  const int *only = nullptr, *only_cnt = nullptr;
-  if (prefilter) {
-    float* Bm = (float*)((char*)ctx->scratch + off_bm);
-    float* anorm = (float*)((char*)ctx->scratch + off_an);
-    int* flags = (int*)((char*)ctx->scratch + off_fl);
-    int* bmax = (int*)((char*)ctx->scratch + off_bx);
-    int* fcnt = bmax + MAX_SEG;
-    EYOC_CHECK_HIP(hipMemsetAsync(bmax, 0, 2 * MAX_SEG * sizeof(int), st));
-    launch_pack_targets(B_dev, seg, sm, nseg, max_nb, Bm, bmax, dist_type == 2 ? 1 : 0, st);
-    hipLaunchKernelGGL(knn_row_norms, dim3(eyoc::cdiv(n_total, 256)), dim3(256), 0, st, A_dev, n_total, c, anorm);
-    if (dist_type == 2)
-      hipLaunchKernelGGL((knn_mfma_kernel<32, 2>), dim3(eyoc::cdiv(max_na, 4 * MF_ROWS), 1, nseg), dim3(256), 0, st, A_dev, Bm, seg,
-                         sm, anorm, bmax, best, flags, fcnt);
-    else
-      hipLaunchKernelGGL((knn_mfma_kernel<32, 0>), dim3(eyoc::cdiv(max_na, 4 * MF_ROWS), 1, nseg), dim3(256), 0, st, A_dev, Bm, seg,
-                         sm, anorm, bmax, best, flags, fcnt);
-    only = flags;
-    only_cnt = fcnt;
-  }
-  if (prefilter && dist_type == 0 && max_nb > 0) {
-    // the undecided rows, lane = target (no transposed copy of the targets needed)
-    hipLaunchKernelGGL(knn1_list_kernel<32>, dim3(eyoc::cdiv(max_nb, 256), 1, nseg), dim3(256), 0, st, A_dev, B_dev, seg, best, only, only_cnt);
-  } else if (max_nb > 0) {
-    hipLaunchKernelGGL(knn_transpose_targets, dim3(eyoc::cdiv((long long)max_ld * (c / 4), 256), 1, nseg), dim3(256), 0, st, B_dev,
-                       seg, c, Bt);
-    switch (c) {
-      case 4: launch_knn<4>(A_dev, Bt, seg, nseg, max_na, max_nb, dist_type, best, second_dev, dot, st); break;
-      case 16: launch_knn<16>(A_dev, Bt, seg, nseg, max_na, max_nb, dist_type, best, second_dev, dot, st); break;
-      case 32: launch_knn<32>(A_dev, Bt, seg, nseg, max_na, max_nb, dist_type, best, second_dev, dot, st, only, only_cnt); break;
-      case 64: launch_knn<64>(A_dev, Bt, seg, nseg, max_na, max_nb, dist_type, best, second_dev, dot, st); break;
-      default: launch_knn<128>(A_dev, Bt, seg, nseg, max_na, max_nb, dist_type, best, second_dev, dot, st); break;
-    }
-  }
-  hipLaunchKernelGGL(knn1_unpack, dim3(eyoc::cdiv(n_total, 256)), dim3(256), 0, st, best, n_total,
-                     (long long*)idx_dev, dist_dev, dot ? 1 : dist_type == 2 ? 2 : 0, has_dev);
+  if (p.max_nb > 0) launch_pack_targets(B_dev, p, nseg, packed_dev, bmax_dev, zero_norm ? 1 : 0, st);
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
 }
@@ -943,7 +970,18 @@ static int knn_run(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c,
 extern "C" int eyoc_knn1(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c, const int32_t* seg_a,
                          const int32_t* seg_b, int nseg, int dist_type, int64_t* idx_dev, float* dist_dev,
                          void* stream) {
-  return knn_run(ctx, A_dev, B_dev, c, seg_a, seg_b, nseg, dist_type, idx_dev, dist_dev, nullptr, stream);
+  return knn_query("eyoc_knn1", ctx, A_dev, B_dev, c, seg_a, seg_b, nseg, dist_type, false, idx_dev, dist_dev, nullptr, stream);
+}
+
+extern "C" int eyoc_dotmax(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c, const int32_t* seg_a,
+                           const int32_t* seg_b, int nseg, int64_t* idx_dev, float* weight_dev, void* stream) {
+  return knn_query("eyoc_dotmax", ctx, A_dev, B_dev, c, seg_a, seg_b, nseg, 0, true, idx_dev, weight_dev, nullptr, stream);
+}
+
+extern "C" int eyoc_knn2(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c, const int32_t* seg_a,
+                         const int32_t* seg_b, int nseg, int64_t* idx_dev, float* d1_dev, float* d2_dev, void* stream) {
+  EYOC_REQUIRE(d2_dev != nullptr, EYOC_ERR_INVALID, "eyoc_knn2: d2_dev is NULL");
+  return knn_query("eyoc_knn2", ctx, A_dev, B_dev, c, seg_a, seg_b, nseg, 0, false, idx_dev, d1_dev, d2_dev, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -955,103 +993,51 @@ extern "C" int eyoc_knn_mutual_select(eyoc_ctx* ctx, int mode) {
   return prev + 2;
 }
 
-// what knn_run carves behind `base` for n query rows against the targets seg_b, at most (pre-filter buffers included)
-static size_t knn_scratch_bound(int n, const int32_t* seg_b, int nseg, int c) {
-  long long bt = 0, bm = 0;
-  for (int s = 0; s < nseg; ++s) {
-    const int nb = seg_b[s + 1] - seg_b[s];
-    bt += (long long)((nb + TGROUP - 1) / TGROUP * TGROUP) * c;
-    bm += packed_target_floats(nb);
-  }
-  return eyoc::align_up((size_t)n * 8) + eyoc::align_up((size_t)bt * 4 + 64) + eyoc::align_up((size_t)bm * 4) + 2 * eyoc::align_up((size_t)n * 4) +
-         2 * MAX_SEG * sizeof(int) + 64 + 256;
-}
-
-template <int C>
-static void launch_knn_mutual(const float* A, const float* Bt, const SegArgs& seg, int nseg, int max_na, int max_nb, int dist_type,
-                              unsigned long long* best, unsigned long long* colbest, hipStream_t st) {
-  const int qtiles = eyoc::cdiv(max_na, 64);
-  int nsplit = 4096 / (qtiles * nseg);
-  const int max_splits = eyoc::cdiv(max_nb, MUT_SPLIT_ALIGN);
-  nsplit = nsplit < 1 ? 1 : nsplit > max_splits ? max_splits : nsplit;
-  const int split_len = eyoc::cdiv(eyoc::cdiv(max_nb, nsplit), MUT_SPLIT_ALIGN) * MUT_SPLIT_ALIGN;
-  const dim3 grid(qtiles, eyoc::cdiv(max_nb, split_len), nseg);
-  if (dist_type == 2) hipLaunchKernelGGL((knn1_mutual_kernel<C, 2>), grid, dim3(256), 0, st, A, Bt, seg, split_len, 0, best, colbest);
-  else hipLaunchKernelGGL((knn1_mutual_kernel<C, 0>), grid, dim3(256), 0, st, A, Bt, seg, split_len, dist_type, best, colbest);
-}
-
 extern "C" int eyoc_knn1_mutual(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c, const int32_t* seg_a, const int32_t* seg_b,
                                 int nseg, int dist_type, int64_t* idx_ab_dev, int64_t* idx_ba_dev, uint8_t* mutual_dev, void* stream) {
-  EYOC_REQUIRE(ctx && A_dev && B_dev && seg_a && seg_b, EYOC_ERR_INVALID, "eyoc_knn1_mutual: NULL argument");
-  EYOC_REQUIRE(nseg >= 1 && nseg <= MAX_SEG, EYOC_ERR_INVALID, "eyoc_knn1_mutual: nseg %d not in [1,%d]", nseg, MAX_SEG);
-  EYOC_REQUIRE(dist_type >= 0 && dist_type <= 2, EYOC_ERR_INVALID, "eyoc_knn1_mutual: dist_type %d", dist_type);
-  EYOC_REQUIRE(c == 4 || c == 16 || c == 32 || c == 64 || c == 128, EYOC_ERR_INVALID,
-               "eyoc_knn1_mutual: feature dimension %d not supported (4/16/32/64/128)", c);
-  EYOC_REQUIRE(seg_a[0] == 0 && seg_b[0] == 0, EYOC_ERR_INVALID, "eyoc_knn1_mutual: seg_a[0] and seg_b[0] must be 0");
+  const char* who = "eyoc_knn1_mutual";
+  EYOC_REQUIRE(ctx && A_dev && B_dev && seg_a && seg_b, EYOC_ERR_INVALID, "%s: NULL argument", who);
+  EYOC_REQUIRE(dist_type >= 0 && dist_type <= 2, EYOC_ERR_INVALID, "%s: dist_type %d", who, dist_type);
+  EYOC_REQUIRE(knn_width_ok(c), EYOC_ERR_INVALID, "%s: feature dimension %d not supported (4/16/32/64/128)", who, c);
+  SegPlan ab, ba;   // A's rows against the targets B, and the reverse query
+  if (int rc = seg_plan(who, seg_a, seg_b, nseg, c, &ab)) return rc;
+  if (int rc = seg_plan(who, seg_b, seg_a, nseg, c, &ba)) return rc;
+  EYOC_REQUIRE(seg_a[0] == 0 && seg_b[0] == 0, EYOC_ERR_INVALID, "%s: seg_a[0] and seg_b[0] must be 0", who);
   hipStream_t st = (hipStream_t)stream;
-  SegArgs seg;
-  int max_na = 0, max_nb = 0, max_ld = 0;
-  long long bt_floats = 0;
-  for (int s = 0; s <= nseg; ++s) { seg.a[s] = seg_a[s]; seg.b[s] = seg_b[s]; }
-  for (int s = 0; s < nseg; ++s) {
-    const int na = seg_a[s + 1] - seg_a[s], nb = seg_b[s + 1] - seg_b[s];
-    EYOC_REQUIRE(na >= 0 && nb >= 0, EYOC_ERR_INVALID, "eyoc_knn1_mutual: negative segment length");
-    max_na = na > max_na ? na : max_na;
-    max_nb = nb > max_nb ? nb : max_nb;
-    seg.ld[s] = (nb + TGROUP - 1) / TGROUP * TGROUP;
-    seg.bt_off[s] = bt_floats;
-    bt_floats += (long long)seg.ld[s] * c;
-    max_ld = seg.ld[s] > max_ld ? seg.ld[s] : max_ld;
-  }
-  const int n_a = seg_a[nseg], n_b = seg_b[nseg];
+  const int n_a = ab.n_a, n_b = ab.n_b;
   if (n_a == 0 && (n_b == 0 || !idx_ba_dev)) return EYOC_OK;
-  EYOC_REQUIRE((n_a == 0 || (idx_ab_dev && mutual_dev)), EYOC_ERR_INVALID, "eyoc_knn1_mutual: NULL output");
-  // the ctx's scratch: [has_a | has_b | idx_ba when the caller wants none] in front, then either route's own buffers
-  const size_t off_hb = eyoc::align_up((size_t)n_a);
-  const size_t off_ba = eyoc::align_up(off_hb + (size_t)n_b);
-  const size_t base = eyoc::align_up(off_ba + (idx_ba_dev ? 0 : (size_t)n_b * sizeof(int64_t)));
-  const size_t need0 = knn_scratch_bound(n_a, seg_b, nseg, c), need1 = knn_scratch_bound(n_b, seg_a, nseg, c);
-  int rc = ctx->ensure_scratch(base + (need0 > need1 ? need0 : need1) + eyoc::align_up((size_t)n_b * 8), st);   // (no call below grows it: the front survives)
-  if (rc) return rc;
-  unsigned char* has_a = (unsigned char*)ctx->scratch;
-  unsigned char* has_b = has_a + off_hb;
-  long long* idx_ba = idx_ba_dev ? (long long*)idx_ba_dev : (long long*)((char*)ctx->scratch + off_ba);
+  EYOC_REQUIRE((n_a == 0 || (idx_ab_dev && mutual_dev)), EYOC_ERR_INVALID, "%s: NULL output", who);
   // auto, as measured (EXPERIMENTS.md "Mutual nearest-neighbour filter"): the fused sweep for c = 32 queries that do not fill the chip in
   // either direction (< 512 waves of MF_ROWS rows: eyoc_knn1 runs its exact kernel there, twice; a single 5000 x 5000 pair: 0.19 against
   // 0.30 ms), two one-way queries where the MFMA pre-filter carries them (64 pairs: 1.4 against 4.6 ms) and for every shape class that
   // was not measured (other widths, whose fused kernel spills)
-  long long waves_a = 0, waves_b = 0;
-  for (int s = 0; s < nseg; ++s) {
-    waves_a += eyoc::cdiv(seg_a[s + 1] - seg_a[s], MF_ROWS);
-    waves_b += eyoc::cdiv(seg_b[s + 1] - seg_b[s], MF_ROWS);
-  }
-  const int route = ctx->knobs.knn_mutual >= 0 ? ctx->knobs.knn_mutual : (c == 32 && waves_a < 512 && waves_b < 512) ? 1 : 0;
-  if (route == 0 || max_na == 0 || max_nb == 0) {
+  const int route = ctx->knobs.knn_mutual >= 0 ? ctx->knobs.knn_mutual : (c == 32 && ab.waves_a < 512 && ab.waves_b < 512) ? 1 : 0;
+  const bool fused = route != 0 && ab.max_na > 0 && ab.max_nb > 0;
+  // the scratch grows HERE, once, to the front plus the larger of the two directions' layouts; knn_run below gets its slice and cannot grow it
+  const size_t need_ab = knn_layout(nullptr, ab, knn_prefilter_on(ctx, ab, c, dist_type, true)).bytes;
+  const size_t need_ba = knn_layout(nullptr, ba, knn_prefilter_on(ctx, ba, c, dist_type, true)).bytes;
+  const size_t dir_bytes = need_ab > need_ba ? need_ab : need_ba;
+  if (int rc = ctx->ensure_scratch(mutual_layout(nullptr, ab, !idx_ba_dev, fused, dir_bytes).bytes, st)) return rc;
+  const MutualWs w = mutual_layout(ctx->scratch, ab, !idx_ba_dev, fused, dir_bytes);
+  long long* idx_ba = idx_ba_dev ? (long long*)idx_ba_dev : w.idx_ba;
+  if (!fused) {
     // both one-way queries as eyoc_knn1 runs them (a side without rows has nothing to write)
-    if (n_a) rc = knn_run(ctx, A_dev, B_dev, c, seg_a, seg_b, nseg, dist_type, idx_ab_dev, nullptr, nullptr, stream, false, base, has_a);
+    int rc = EYOC_OK;
+    if (n_a) rc = knn_run(ctx, w.dir, dir_bytes, ab, nseg, A_dev, B_dev, c, dist_type, false, idx_ab_dev, nullptr, nullptr, w.has_a, st);
     if (rc) return rc;
-    if (n_b) rc = knn_run(ctx, B_dev, A_dev, c, seg_b, seg_a, nseg, dist_type, (int64_t*)idx_ba, nullptr, nullptr, stream, false, base, has_b);
+    if (n_b) rc = knn_run(ctx, w.dir, dir_bytes, ba, nseg, B_dev, A_dev, c, dist_type, false, (int64_t*)idx_ba, nullptr, nullptr, w.has_b, st);
     if (rc) return rc;
   } else {
-    unsigned long long* best = (unsigned long long*)((char*)ctx->scratch + base);
-    unsigned long long* colbest = (unsigned long long*)((char*)ctx->scratch + eyoc::align_up(base + (size_t)n_a * 8));
-    float* Bt = (float*)((char*)ctx->scratch + eyoc::align_up(eyoc::align_up(base + (size_t)n_a * 8) + (size_t)n_b * 8));
-    EYOC_CHECK_HIP(hipMemsetAsync(best, 0xFF, (size_t)n_a * 8, st));
-    EYOC_CHECK_HIP(hipMemsetAsync(colbest, 0xFF, (size_t)n_b * 8, st));
-    hipLaunchKernelGGL(knn_transpose_targets, dim3(eyoc::cdiv((long long)max_ld * (c / 4), 256), 1, nseg), dim3(256), 0, st, B_dev, seg, c, Bt);
-    switch (c) {
-      case 4: launch_knn_mutual<4>(A_dev, Bt, seg, nseg, max_na, max_nb, dist_type, best, colbest, st); break;
-      case 16: launch_knn_mutual<16>(A_dev, Bt, seg, nseg, max_na, max_nb, dist_type, best, colbest, st); break;
-      case 32: launch_knn_mutual<32>(A_dev, Bt, seg, nseg, max_na, max_nb, dist_type, best, colbest, st); break;
-      case 64: launch_knn_mutual<64>(A_dev, Bt, seg, nseg, max_na, max_nb, dist_type, best, colbest, st); break;
-      default: launch_knn_mutual<128>(A_dev, Bt, seg, nseg, max_na, max_nb, dist_type, best, colbest, st); break;
-    }
-    hipLaunchKernelGGL(knn1_unpack, dim3(eyoc::cdiv(n_a, 256)), dim3(256), 0, st, best, n_a, (long long*)idx_ab_dev, (float*)nullptr, 0, has_a);
-    hipLaunchKernelGGL(knn1_unpack, dim3(eyoc::cdiv(n_b, 256)), dim3(256), 0, st, colbest, n_b, idx_ba, (float*)nullptr, 0, has_b);
+    EYOC_CHECK_HIP(hipMemsetAsync(w.best, 0xFF, (size_t)n_a * 8, st));
+    EYOC_CHECK_HIP(hipMemsetAsync(w.colbest, 0xFF, (size_t)n_b * 8, st));
+    launch_transpose(B_dev, ab, nseg, c, w.Bt, st);
+    dispatch_width(c, [&](auto width) { launch_knn_mutual<decltype(width)::value>(A_dev, w.Bt, ab, nseg, dist_type, w.best, w.colbest, st); });
+    hipLaunchKernelGGL(knn1_unpack, dim3(eyoc::cdiv(n_a, 256)), dim3(256), 0, st, w.best, n_a, (long long*)idx_ab_dev, (float*)nullptr, 0, w.has_a);
+    hipLaunchKernelGGL(knn1_unpack, dim3(eyoc::cdiv(n_b, 256)), dim3(256), 0, st, w.colbest, n_b, idx_ba, (float*)nullptr, 0, w.has_b);
   }
   if (n_a)
-    hipLaunchKernelGGL(knn_mutual_flags, dim3(eyoc::cdiv(max_na, 256), 1, nseg), dim3(256), 0, st, seg, (const long long*)idx_ab_dev,
-                       (const long long*)idx_ba, (const unsigned char*)has_a, (const unsigned char*)has_b, (unsigned char*)mutual_dev);
+    hipLaunchKernelGGL(knn_mutual_flags, dim3(eyoc::cdiv(ab.max_na, 256), 1, nseg), dim3(256), 0, st, ab.seg, (const long long*)idx_ab_dev,
+                       (const long long*)idx_ba, (const unsigned char*)w.has_a, (const unsigned char*)w.has_b, (unsigned char*)mutual_dev);
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
 }
@@ -1059,36 +1045,31 @@ extern "C" int eyoc_knn1_mutual(eyoc_ctx* ctx, const float* A_dev, const float* 
 extern "C" int eyoc_mutual_compact(eyoc_ctx* ctx, const int64_t* idx_ab_dev, const uint8_t* mutual_dev, const int32_t* seg_a, int nseg,
                                    int min_keep, int64_t* rows_dev, int64_t* corr_dev, int32_t* seg_out_dev, void* stream) {
   EYOC_REQUIRE(ctx && seg_a && seg_out_dev, EYOC_ERR_INVALID, "eyoc_mutual_compact: NULL argument");
-  EYOC_REQUIRE(nseg >= 1 && nseg <= MAX_SEG, EYOC_ERR_INVALID, "eyoc_mutual_compact: nseg %d not in [1,%d]", nseg, MAX_SEG);
+  SegPlan p;
+  if (int rc = seg_plan("eyoc_mutual_compact", seg_a, nullptr, nseg, 0, &p)) return rc;
   EYOC_REQUIRE(min_keep >= 0 && seg_a[0] == 0, EYOC_ERR_INVALID, "eyoc_mutual_compact: min_keep %d, seg_a[0] %d", min_keep, seg_a[0]);
   hipStream_t st = (hipStream_t)stream;
-  SegArgs seg = {};
-  int max_na = 0;
-  for (int s = 0; s <= nseg; ++s) seg.a[s] = seg_a[s];
-  for (int s = 0; s < nseg; ++s) {
-    const int na = seg_a[s + 1] - seg_a[s];
-    EYOC_REQUIRE(na >= 0, EYOC_ERR_INVALID, "eyoc_mutual_compact: negative segment length");
-    max_na = na > max_na ? na : max_na;
-  }
-  const int n = seg_a[nseg];
+  const int n = p.n_a;
   if (n == 0) {
     EYOC_CHECK_HIP(hipMemsetAsync(seg_out_dev, 0, (size_t)(nseg + 1) * sizeof(int32_t), st));
     return EYOC_OK;
   }
   EYOC_REQUIRE(idx_ab_dev && mutual_dev && rows_dev && corr_dev, EYOC_ERR_INVALID, "eyoc_mutual_compact: NULL argument");
   const int tiles = eyoc::cdiv(n, SCAN_TILE);
-  const size_t off_keep = eyoc::align_up(2 * MAX_SEG * sizeof(int));
-  const size_t off_loc = eyoc::align_up(off_keep + (size_t)n * sizeof(int));
-  const size_t off_part = eyoc::align_up(off_loc + (size_t)n * sizeof(int));
-  int rc = ctx->ensure_scratch(off_part + (size_t)(tiles + 2) * sizeof(int), st);
-  if (rc) return rc;
-  int* cnt = (int*)ctx->scratch;
+  int *cnt = nullptr, *keep = nullptr, *loc = nullptr, *partial = nullptr;
+  auto carve = [&](void* base) {
+    eyoc::Carver cv(base, 0);
+    cnt = cv.take<int>(2 * MAX_SEG);      // + fallback[MAX_SEG]
+    keep = cv.take<int>(n);
+    loc = cv.take<int>(n);
+    partial = cv.take<int>(tiles + 2);    // [tiles] + the total behind them
+    return eyoc::align_up(cv.off);
+  };
+  if (int rc = ctx->ensure_scratch(carve(nullptr), st)) return rc;
+  carve(ctx->scratch);
   int* fallback = cnt + MAX_SEG;
-  int* keep = (int*)((char*)ctx->scratch + off_keep);
-  int* loc = (int*)((char*)ctx->scratch + off_loc);
-  int* partial = (int*)((char*)ctx->scratch + off_part);     // [tiles] + the total behind them
-  hipLaunchKernelGGL(k_mutual_count, dim3(nseg), dim3(SCAN_BLOCK), 0, st, seg, (const unsigned char*)mutual_dev, min_keep, cnt, fallback);
-  hipLaunchKernelGGL(k_mutual_keep, dim3(eyoc::cdiv(max_na, 256), 1, nseg), dim3(256), 0, st, seg, nseg, (const unsigned char*)mutual_dev,
+  hipLaunchKernelGGL(k_mutual_count, dim3(nseg), dim3(SCAN_BLOCK), 0, st, p.seg, (const unsigned char*)mutual_dev, min_keep, cnt, fallback);
+  hipLaunchKernelGGL(k_mutual_keep, dim3(eyoc::cdiv(p.max_na, 256), 1, nseg), dim3(256), 0, st, p.seg, nseg, (const unsigned char*)mutual_dev,
                      (const int*)cnt, (const int*)fallback, keep, loc, seg_out_dev);
   hipLaunchKernelGGL(k_scan_partials, dim3(tiles), dim3(SCAN_BLOCK), 0, st, (const int*)keep, n, partial);
   hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(SCAN_BLOCK), 0, st, partial, tiles, partial + tiles);
@@ -1096,17 +1077,6 @@ extern "C" int eyoc_mutual_compact(eyoc_ctx* ctx, const int64_t* idx_ab_dev, con
                      (const long long*)idx_ab_dev, n, (long long*)rows_dev, (long long*)corr_dev);
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
-}
-
-extern "C" int eyoc_dotmax(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c, const int32_t* seg_a,
-                           const int32_t* seg_b, int nseg, int64_t* idx_dev, float* weight_dev, void* stream) {
-  return knn_run(ctx, A_dev, B_dev, c, seg_a, seg_b, nseg, 0, idx_dev, weight_dev, nullptr, stream, true);
-}
-
-extern "C" int eyoc_knn2(eyoc_ctx* ctx, const float* A_dev, const float* B_dev, int c, const int32_t* seg_a,
-                         const int32_t* seg_b, int nseg, int64_t* idx_dev, float* d1_dev, float* d2_dev, void* stream) {
-  EYOC_REQUIRE(d2_dev != nullptr, EYOC_ERR_INVALID, "eyoc_knn2: d2_dev is NULL");
-  return knn_run(ctx, A_dev, B_dev, c, seg_a, seg_b, nseg, 0, idx_dev, d1_dev, d2_dev, stream);
 }
 
 extern "C" int eyoc_pdist(eyoc_ctx* ctx, const float* A_dev, int n, const float* B_dev, int m, int c, int dist_type,

@@ -224,6 +224,21 @@ __global__ __launch_bounds__(1024) void k_pair_filter_batched(FilterSegs s, int 
   if (threadIdx.x == 0) n_out[pb] = base_s;
 }
 
+// the ctx-scratch arrays of a top-k call over n rows with sort keys of type K; on a null base `bytes` alone means anything
+template <typename K>
+struct TopkWs { float* w; K *k0, *k1; int *r0, *r1; void* tmp; size_t bytes; };
+template <typename K>
+TopkWs<K> topk_layout(void* base, int n, size_t tmp_bytes) {
+  Carver c(base, 0);
+  TopkWs<K> t;
+  t.w = c.take<float>(n);
+  t.k0 = c.take<K>(n); t.k1 = c.take<K>(n);
+  t.r0 = c.take<int>(n); t.r1 = c.take<int>(n);
+  t.tmp = c.take<char>(tmp_bytes);
+  t.bytes = align_up(c.off);
+  return t;
+}
+
 }  // namespace
 
 extern "C" {
@@ -237,20 +252,13 @@ int eyoc_lowe_topk(eyoc_ctx* ctx, const float* d1_dev, const float* d2_dev, int 
   if (k == 0) return EYOC_OK;
   hipStream_t st = (hipStream_t)stream;
   const size_t tmp = align_up(sort_rows_tmp_bytes(n, 32));
-  const size_t off_w = 0, off_k0 = align_up((size_t)n * 4), off_k1 = off_k0 + align_up((size_t)n * 4);
-  const size_t off_r0 = off_k1 + align_up((size_t)n * 4), off_r1 = off_r0 + align_up((size_t)n * 4), off_tmp = off_r1 + align_up((size_t)n * 4);
-  int rc = ctx->ensure_scratch(off_tmp + tmp, st);
+  int rc = ctx->ensure_scratch(topk_layout<unsigned int>(nullptr, n, tmp).bytes, st);
   if (rc) return rc;
-  char* sc = (char*)ctx->scratch;
-  float* w = (float*)(sc + off_w);
-  unsigned int* k0 = (unsigned int*)(sc + off_k0);
-  unsigned int* k1 = (unsigned int*)(sc + off_k1);
-  int* r0 = (int*)(sc + off_r0);
-  int* r1 = (int*)(sc + off_r1);
-  hipLaunchKernelGGL(k_lowe_weight, dim3(cdiv(n, 256)), dim3(256), 0, st, d1_dev, d2_dev, n, w, k0, r0);
-  rc = sort_rows_by_key(sc + off_tmp, tmp, k0, k1, r0, r1, n, 32, st);
+  const TopkWs<unsigned int> t = topk_layout<unsigned int>(ctx->scratch, n, tmp);
+  hipLaunchKernelGGL(k_lowe_weight, dim3(cdiv(n, 256)), dim3(256), 0, st, d1_dev, d2_dev, n, t.w, t.k0, t.r0);
+  rc = sort_rows_by_key(t.tmp, tmp, t.k0, t.k1, t.r0, t.r1, n, 32, st);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_take_topk, dim3(cdiv(k, 256)), dim3(256), 0, st, r1, w, k, (long long*)idx_out_dev, w_out_dev);
+  hipLaunchKernelGGL(k_take_topk, dim3(cdiv(k, 256)), dim3(256), 0, st, t.r1, t.w, k, (long long*)idx_out_dev, w_out_dev);
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
 }
@@ -301,19 +309,10 @@ int eyoc_lowe_topk_segmented(eyoc_ctx* ctx, const float* d1_dev, const float* d2
   if (k == 0) return EYOC_OK;
   const int n = seg_host[nseg];
   hipStream_t st = (hipStream_t)stream;
-  Carver c(nullptr, 0);
-  (void)c.take<float>(n);
-  (void)c.take<unsigned long long>(n); (void)c.take<unsigned long long>(n);
-  (void)c.take<int>(n); (void)c.take<int>(n);
   const size_t tmp = sort_rows64_tmp_bytes(n);
-  (void)c.take<char>(tmp);
-  int rc = ctx->ensure_scratch(align_up(c.off), st);
+  int rc = ctx->ensure_scratch(topk_layout<unsigned long long>(nullptr, n, tmp).bytes, st);
   if (rc) return rc;
-  Carver d(ctx->scratch, c.off);
-  float* w = d.take<float>(n);
-  unsigned long long *k0 = d.take<unsigned long long>(n), *k1 = d.take<unsigned long long>(n);
-  int *r0 = d.take<int>(n), *r1 = d.take<int>(n);
-  void* sort_tmp = d.take<char>(tmp);
+  const TopkWs<unsigned long long> t = topk_layout<unsigned long long>(ctx->scratch, n, tmp);
   int seg_bits = 1;
   while ((1 << seg_bits) < nseg) ++seg_bits;
   TopkSegs ts;
@@ -321,15 +320,15 @@ int eyoc_lowe_topk_segmented(eyoc_ctx* ctx, const float* d1_dev, const float* d2
     ts.n_seg = nseg - s0 < LBL_CHUNK ? nseg - s0 : LBL_CHUNK;
     ts.first_seg = s0;
     for (int b = 0; b <= ts.n_seg; ++b) ts.seg[b] = seg_host[s0 + b];
-    hipLaunchKernelGGL(k_lowe_weight_seg, dim3(cdiv(max_len, 256), ts.n_seg), dim3(256), 0, st, ts, mode, d1_dev, d2_dev, w, k0, r0);
+    hipLaunchKernelGGL(k_lowe_weight_seg, dim3(cdiv(max_len, 256), ts.n_seg), dim3(256), 0, st, ts, mode, d1_dev, d2_dev, t.w, t.k0, t.r0);
   }
-  rc = sort_rows_by_key64(sort_tmp, tmp, k0, k1, r0, r1, n, 32 + seg_bits, st);
+  rc = sort_rows_by_key64(t.tmp, tmp, t.k0, t.k1, t.r0, t.r1, n, 32 + seg_bits, st);
   if (rc) return rc;
   for (int s0 = 0; s0 < nseg; s0 += LBL_CHUNK) {
     ts.n_seg = nseg - s0 < LBL_CHUNK ? nseg - s0 : LBL_CHUNK;
     ts.first_seg = s0;
     for (int b = 0; b <= ts.n_seg; ++b) ts.seg[b] = seg_host[s0 + b];
-    hipLaunchKernelGGL(k_take_topk_seg, dim3(cdiv(k, 256), ts.n_seg), dim3(256), 0, st, ts, r1, w, k, (long long*)idx_out_dev, w_out_dev);
+    hipLaunchKernelGGL(k_take_topk_seg, dim3(cdiv(k, 256), ts.n_seg), dim3(256), 0, st, ts, t.r1, t.w, k, (long long*)idx_out_dev, w_out_dev);
   }
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;

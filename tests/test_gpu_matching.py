@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import _inputs as gi
+import mutual_restatement as M
 
 pytestmark = pytest.mark.gpu
 
@@ -366,3 +367,64 @@ def test_matcher_match_pair_vs_reference_golden_and_oracle():
             cand = np.nonzero(t_sel == ref[row])[0][:1]
             d = om.match_pair_distance(A[row:row + 1], B[[want[row], cand[0]]])[0]
             assert np.isnan(d).any() or abs(float(d[0]) - float(d[1])) <= 2e-4 * max(1.0, float(d[0]))
+
+
+# ----------------------------------------------------------------------------- every instantiation of knn1_kernel
+_EXACT_REF = {}          # (query, c, na, nb) -> the restatement's outputs, computed once
+
+
+def _exact_reference(query, c, na, nb):
+    """What the exact kernel must return for ``M.pair_inputs(na, nb, c)``: the three distance forms from tests/mutual_restatement.py
+    (index and the winner's entry of its distance matrix), the runner-up and the inner product from oracle.matching's contract
+    (``sqdist_rows`` with the winner struck out; ``dot_rows``, first maximum)."""
+    from oracle import matching as om
+    key = (query, c, na, nb)
+    if key not in _EXACT_REF:
+        A, B = M.pair_inputs(na, nb, c)
+        rows = np.arange(na)
+        if query in M.DIST:
+            idx = M.search(A, B, [0, na], [0, nb], M.DIST[query])[0]
+            out = (idx, M.distance_matrix(A, B, M.DIST[query])[rows, idx])
+        elif query == "knn2":
+            D = om.sqdist_rows(A, B)
+            idx = np.argmin(D, axis=1).astype(np.int64)
+            d1 = D[rows, idx].copy()
+            D[rows, idx] = np.inf
+            out = (idx, d1, D.min(axis=1))
+        else:
+            S = om.dot_rows(A, B)
+            idx = np.argmax(S, axis=1).astype(np.int64)
+            out = (idx, S[rows, idx])
+        assert not any(np.isnan(o).any() for o in out[1:])              # unit rows: every value is a number, so bits can be compared
+        _EXACT_REF[key] = out
+    return _EXACT_REF[key]
+
+
+@pytest.mark.parametrize("query", ["SquareL2", "L2", "GemmL2", "knn2", "dotmax"])
+@pytest.mark.parametrize("c", M.WIDTHS)
+def test_exact_kernel_every_width_and_query_bit_exact(c, query):
+    """knn1_kernel<C, TOP2, MODE> has 5 widths x {distance (SquareL2 and L2 share one), GemmL2, runner-up, inner product} = 20
+    instantiations; with the pre-filter off every query below runs exactly one of them.  Index bytes and the bits of every float the
+    call returns, at 65 x 33 (a query tile boundary at 64, a target count that is no multiple of the group of 8, a split boundary at 32)
+    and 257 x 255 (several tiles and splits, all four waves busy)."""
+    import eyoc_amd
+    from eyoc_amd import _lib
+    from eyoc_amd.eval import dotmax_segmented
+    prev = _lib.knob("eyoc_knn_prefilter", 0)
+    try:
+        for na, nb in M.WIDE_SHAPES:
+            A, B = (torch.from_numpy(x).cuda() for x in M.pair_inputs(na, nb, c))
+            if query in M.DIST:
+                got = eyoc_amd.knn1_segmented(A, B, [0, na], [0, nb], query)
+            elif query == "knn2":
+                got = eyoc_amd.knn2_segmented(A, B, [0, na], [0, nb])
+            else:
+                w, idx = dotmax_segmented(A, B, [0, na], [0, nb])
+                got = (idx, w)
+            want = _exact_reference(query, c, na, nb)
+            assert len(got) == len(want)
+            for k, (g, w) in enumerate(zip(got, want)):
+                g = g.cpu().numpy()
+                assert g.dtype == w.dtype and g.tobytes() == w.tobytes(), f"output {k} of {query}, c = {c}, {na} x {nb} differs"
+    finally:
+        _lib.knob("eyoc_knn_prefilter", prev)
