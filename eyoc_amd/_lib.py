@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("EYOC_HIP_LIB") or os.path.join(_HERE, "lib", "libeyoc
 
 MAX_LEVELS = 4
 MAP_S1, MAP_DOWN, MAP_UP = 0, 1, 2
+RECORDS_S1, RECORDS_S1W, RECORDS_DOWN, RECORDS_UP, RECORDS_UPC = range(5)   # eyoc_records_family
 
 
 class MapsInfo(C.Structure):
@@ -129,6 +130,7 @@ PROTOTYPES = {
     "eyoc_maps_row_order": (_vp, [_vp]),
     "eyoc_maps_copy_row_order": (_i, [_vp, _vp, _vp]),
     "eyoc_maps_rows": (_i, [_vp, _i]),
+    "eyoc_maps_records": (_i, [_vp, _i, _i]),
     "eyoc_maps_coords": (_vp, [_vp, _i]),
     "eyoc_maps_table": (_vp, [_vp, _i, _i]),
     "eyoc_maps_copy_coords": (_i, [_vp, _i, _vp, _vp]),

@@ -1251,7 +1251,10 @@ struct MapBuild {
       EYOC_REQUIRE(host->late.scan_total[l] == m->rows[l], EYOC_ERR_INVALID,
                    "eyoc_maps_build: internal error - level %d has %d rows by its scan, %d by the up-front count", l, host->late.scan_total[l], m->rows[l]);
     const Counters::Overflow& ovf = host->overflow;
-    if (ovf.s1 != 0) {   // a tile with more distinct input rows than two passes stage (does not happen for Z-ordered rows): no staged kernel
+    // a 256-row tile of some level with more distinct input rows than two passes stage (1278): no staged stride-1 kernel at any level.
+    // Z-order does not rule it out - a few hundred voxels that each touch 3 x 3 cells of a dense plane next to them do it (192 such rows
+    // in one tile read 2002 rows, 256 fill the builder's hash: tests/record_overflow_cases.py) - lidar scans just stay far below
+    if (ovf.s1 != 0) {
       for (int l = 0; l < EYOC_MAX_LEVELS; ++l) m->local_s1[l] = nullptr;
       MAPS_TRY(maps_ensure_table(m.get(), EYOC_MAP_S1, 0, st));   // the gathering kernels read the table
     }
@@ -1559,6 +1562,20 @@ int eyoc_maps_free(eyoc_maps* maps) {
 int eyoc_maps_rows(const eyoc_maps* maps, int level) {
   if (!maps || level < 0 || level >= maps->n_levels) return -1;
   return maps->rows[level];
+}
+
+int eyoc_maps_records(const eyoc_maps* maps, int family, int level) {   // host fields only: what read_back_records left of the build's records
+  EYOC_REQUIRE(maps && level >= 0 && level < maps->n_levels, EYOC_ERR_INVALID, "eyoc_maps_records: NULL maps or level %d", level);
+  switch (family) {
+    case EYOC_RECORDS_S1: return maps->local_s1[level] != nullptr;
+    case EYOC_RECORDS_S1W: return maps->local_s1w[level] != nullptr;
+    case EYOC_RECORDS_DOWN: return maps->local_down[level] != nullptr;
+    case EYOC_RECORDS_UP: return maps->local_up[level] != nullptr;
+    case EYOC_RECORDS_UPC: return maps->local_upc[level] != nullptr;
+    default: break;
+  }
+  eyoc::set_error("eyoc_maps_records: family %d", family);
+  return EYOC_ERR_INVALID;
 }
 
 const int32_t* eyoc_maps_coords(const eyoc_maps* maps, int level) {

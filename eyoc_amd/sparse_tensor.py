@@ -151,6 +151,17 @@ class CoordinateManager:
             _lib.check(_lib.load().eyoc_maps_copy_up_order(m, level, _lib.ptr(out), _lib.stream_ptr()), "eyoc_maps_copy_up_order")
         return out
 
+    def records(self, internal: bool = False) -> list[list[int]]:
+        """What the build kept of its tile records, ``[family][level]`` with the families in the order of ``_lib.RECORDS_*``: 1 = the
+        maps hold records, 0 = never asked for or dropped because a tile overflowed (``eyoc_maps_records``).  The caller-order maps
+        by default (they have none), ``internal=True``: the forward's own.  Host fields only."""
+        m = self.maps() if internal else self._caller_maps()
+        lib = _lib.load()
+        out = [[lib.eyoc_maps_records(m, f, l) for l in range(_lib.MAX_LEVELS)] for f in range(5)]
+        if min(min(r) for r in out) < 0:
+            _lib.check(min(min(r) for r in out), "eyoc_maps_records")
+        return out
+
     def info(self, conv1_kernel_size: int = 0) -> dict:
         info = _lib.MapsInfo()
         m = self.maps()

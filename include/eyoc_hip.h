@@ -48,6 +48,7 @@ typedef enum {
  *     eyoc_voxelize_batched_isolating(_workspace_bytes), again found by symbol; nothing that existed changes.
  *     Training batches from raw scans add eyoc_cloud_centroids(_workspace_bytes), eyoc_augment_poses and
  *     eyoc_voxelize_batched_posed(_workspace_bytes) the same way.
+ *     eyoc_maps_records (what a build kept of its tile records) comes the same way: a read-only accessor, found by symbol.
  *     A fix without a new number: eyoc_voxelize and eyoc_voxelize_batched refuse a point with a NaN coordinate (EYOC_ERR_RANGE), which
  *     earlier libraries of 111 took for cell 0 on that axis; no signature and no output for valid input changes.
  * 110 (round 6): the kernel-selection setters and eyoc_ransac_workspace_bytes take the ctx first (round 5), eyoc_maps_gather_window
@@ -151,7 +152,19 @@ const int32_t* eyoc_maps_row_order(const eyoc_maps* maps);
 /* stream-ordered copy of the same array (the identity when the caller's order was kept); out_dev: int32 [rows[0]] */
 int eyoc_maps_copy_row_order(const eyoc_maps* maps, int32_t* out_dev, void* stream);
 int eyoc_maps_rows(const eyoc_maps* maps, int level);
-/* Streams.  A maps object may be read on any stream, not only the one it was built on: everything the build writes is complete when
+/* What a build kept of its tile records (Z-ordered builds; DESIGN.md "Records that overflow"): 1 when the maps hold records of that
+ * family and level, 0 when the build never asked for them or dropped them because a tile did not fit its stage - the layers of that
+ * family and level then run on the gathering kernels.  Reads host fields only: no device work, no synchronisation.  EYOC_ERR_INVALID
+ * for NULL maps, a family outside the enum or a level outside [0, n_levels).  For tests and diagnostics. */
+typedef enum {
+  EYOC_RECORDS_S1 = 0,    /* stride-1 table, 256-row tiles                                    */
+  EYOC_RECORDS_S1W = 1,   /* stride-1 table, 128-row tiles (the coarsest level)               */
+  EYOC_RECORDS_DOWN = 2,  /* strided table level -> level + 1, 128-row tiles                  */
+  EYOC_RECORDS_UP = 3,    /* transposed table level + 1 -> level, Morton tiles                */
+  EYOC_RECORDS_UPC = 4    /* transposed table level + 1 -> level, class-major tiles           */
+} eyoc_records_family;
+int eyoc_maps_records(const eyoc_maps* maps, int family, int level);
+/* Streams. A maps object may be read on any stream, not only the one it was built on: everything the build writes is complete when
  * eyoc_maps_build returns, and what is filled later on demand (lazy tables, the level-0 hash table) is filled on the stream of the
  * first call that needs it, which records an event; every later reader - eyoc_maps_table / _copy_table / _info, a forward, a window
  * gather - waits for that event, on the host (eyoc_maps_table) or on its own stream (everything else).  The maps' workspace is the

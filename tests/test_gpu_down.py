@@ -49,17 +49,27 @@ def test_staged_strided_layers_equal_the_gathering_kernel_and_the_oracle(batches
 
 
 def test_a_cloud_in_no_spatial_order_falls_back(batches_take_the_batch_kernels):
-    """Rows in random positions: a 128-row coarse tile then reads more distinct fine rows than two stage passes hold (or its hash
-    fills up) - the table keeps the gathering kernel, and the forward still matches the oracle."""
+    """A FULL 30^3 box, its rows handed over in no spatial order (the build sorts them: the order does not matter, the density does).  A
+    128-row tile of level-1 rows is a block of about 8 x 4 x 4 cells whose 3^3 windows cover 17 x 9 x 9 fine voxels: 18 of the 27 tiles
+    of the strided table 0 -> 1 name more than the 1278 distinct rows two stage passes hold (1505 at most, counted on the CPU with
+    tests/record_overflow_cases.py).  The build drops the strided records of level 0 - and only them -, that table keeps the gathering
+    kernel, and the forward still matches the oracle.  (The box used to be 59 % full: 908 rows at most, nothing fell back.)"""
+    import eyoc_amd
+    from eyoc_amd import _lib
     from test_gpu_round2 import _model
     from oracle import resunet as orr
     rng = np.random.default_rng(0)
-    c = np.unique(rng.integers(0, 30, size=(24000, 3)), axis=0).astype(np.int32)       # a dense 30^3 box: every coarse row has ~27 fine neighbours
+    c = np.stack(np.meshgrid(*[np.arange(30)] * 3, indexing="ij"), -1).reshape(-1, 3).astype(np.int32)
+    c = c[rng.permutation(len(c))]
     from eyoc_amd import synthetic as syn
     coords = syn.batch_coords([c])
     feats = rng.uniform(0.5, 1.5, size=(len(coords), 1)).astype(np.float32)
     model, sd = _model()
-    f = _forward(model, coords, feats).cpu().numpy()
+    x = eyoc_amd.SparseTensor(torch.from_numpy(feats).cuda(), coordinates=torch.from_numpy(coords).cuda())
+    f = model(x).F.cpu().numpy()
+    kept = x.coordinate_manager.records(internal=True)
+    assert kept[_lib.RECORDS_DOWN] == [0, 1, 1, 0], "the strided records of level 0 must be dropped, those of levels 1 and 2 kept"
+    assert kept[_lib.RECORDS_S1] == [1, 1, 1, 1] and kept[_lib.RECORDS_UPC] == [1, 1, 1, 0]
     want = np.asarray(orr.resunet_forward(sd, coords, feats))
     assert np.abs(f - want).max() <= 1e-4 * np.abs(want).max()
 
