@@ -202,6 +202,7 @@ PROTOTYPES = {
     "eyoc_model_workspace_bytes_rows": (_sz, [_vp, _vp, _i]),
     "eyoc_model_forward_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "eyoc_model_sampled_tail": (_i, [_vp, _i]),
+    "eyoc_model_forward_steps": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "eyoc_model_num_layers": (_i, [_vp]),
     "eyoc_model_layer_work": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_char_p), C.POINTER(C.c_int64),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -55,18 +55,18 @@ struct eyoc_model {
   float* blob = nullptr;
   size_t blob_floats = 0;
   int math = -1;           // -1 automatic, 0 fp32 MFMA, 1 SPLIT16 (eyoc_model_set_math)
-  int last_math = 0;       // what the last forward used
   int timing = 0;
   std::vector<hipEvent_t> events;     // two sets of layers + 1 events (eyoc_model_timing_slot)
   int slot = 0;
-  int events_valid[2] = {0, 0};
   hipEvent_t progress_event = nullptr;   // eyoc_model_set_progress_event: recorded in front of layer `progress_layer` of every forward
   int progress_layer = -1;
   unsigned int* range = nullptr;      // device: {overflow flag of the forward in flight, max |activation| bits (probe), probe switch, sticky overflow flag} - split16_guard in spconv.h
   int probe = 0;
-  // eyoc_model_forward_rows: the most recent forward computed its last 3^3 layer (index sampled_layer) and the 1x1 tail for
-  // sampled_rows listed rows only (-1: it was a full forward); range word 6 holds the (row, offset) pairs that layer multiplied
-  int sampled_layer = -1, sampled_rows = 0;
+  // What a forward leaves behind in its (const) model - forward_impl is the one writer.  math: what the last forward used;
+  // eyoc_model_forward_rows: it computed its last 3^3 layer (index sampled_layer) and the 1x1 tail for sampled_rows listed rows only
+  // (-1: it was a full forward), range word 6 holds the (row, offset) pairs that layer multiplied; events_valid: a timed forward
+  // has recorded into that event set
+  struct Last { int math = 0, sampled_layer = -1, sampled_rows = 0, events_valid[2] = {0, 0}; } last;
 };
 
 namespace {
@@ -789,12 +789,12 @@ int eyoc_model_set_math(eyoc_model* m, int mode) {
   return prev + 1 ? prev + 2 : 1;   // previous mode + 2 (so that every valid answer is positive): 1 = auto, 2 = fp32, 3 = split16
 }
 
-int eyoc_model_last_math(const eyoc_model* m) { return m ? m->last_math : -1; }
+int eyoc_model_last_math(const eyoc_model* m) { return m ? m->last.math : -1; }
 
 int eyoc_model_set_timing(eyoc_model* m, int on) {
   EYOC_REQUIRE(m, EYOC_ERR_INVALID, "eyoc_model_set_timing: NULL model");
   m->timing = on ? 1 : 0;
-  m->events_valid[0] = m->events_valid[1] = 0;
+  m->last.events_valid[0] = m->last.events_valid[1] = 0;
   if (on && m->events.empty()) {
     m->events.resize(2 * (m->layers.size() + 1));
     for (auto& e : m->events) EYOC_CHECK_HIP(hipEventCreate(&e));
@@ -810,7 +810,7 @@ int eyoc_model_timing_slot(eyoc_model* m, int slot) {
 
 int eyoc_model_layer_ms(eyoc_model* m, float* ms) {
   EYOC_REQUIRE(m && ms, EYOC_ERR_INVALID, "eyoc_model_layer_ms: NULL argument");
-  EYOC_REQUIRE(m->timing && m->events_valid[m->slot], EYOC_ERR_INVALID, "eyoc_model_layer_ms: no timed forward recorded in slot %d", m->slot);
+  EYOC_REQUIRE(m->timing && m->last.events_valid[m->slot], EYOC_ERR_INVALID, "eyoc_model_layer_ms: no timed forward recorded in slot %d", m->slot);
   const hipEvent_t* ev = m->events.data() + (size_t)m->slot * (m->layers.size() + 1);
   EYOC_CHECK_HIP(hipEventSynchronize(ev[m->layers.size()]));
   for (size_t i = 0; i < m->layers.size(); ++i) EYOC_CHECK_HIP(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
@@ -819,199 +819,276 @@ int eyoc_model_layer_ms(eyoc_model* m, float* ms) {
 
 }  // extern "C"
 
-// eyoc_model_forward (rows_dev == NULL: out_dev is [N, out_channels]) and eyoc_model_forward_rows (out_dev is [n_rows, out_channels],
-// row i = the network's output row rows_dev[i]): one schedule.  With rows, the last 3^3 layer and the 1x1 tail run on the listed rows
-// only where the full forward would fuse them (spconv_rows.hip); otherwise the full output goes to the workspace and its rows are taken.
-static int forward_impl(eyoc_ctx* ctx, const eyoc_model* mc, const eyoc_maps* maps, const float* feats_dev, float* out_dev, void* ws,
-                        size_t ws_bytes, void* stream, const int64_t* rows_dev, int n_rows) {
-  eyoc_model* m = const_cast<eyoc_model*>(mc);
-  hipStream_t st = (hipStream_t)stream;
-  float* buf[B_COUNT];
+// ---- The forward: carve the workspace, RESOLVE the launch schedule (host decisions only: which launch every layer becomes and what
+// must be ready in front of it - eyoc_model_forward_steps returns them as data), then RUN it.  eyoc_model_forward (rows_dev == NULL:
+// out_dev is [N, out_channels]) and eyoc_model_forward_rows (out_dev is [n_rows, out_channels], row i = the network's output row
+// rows_dev[i]) are one schedule.  With rows, the last 3^3 layer and the 1x1 tail run on the listed rows only where the full forward
+// would fuse them (spconv_rows.hip); otherwise the full output goes to the workspace and its rows are taken.
+namespace {
+
+struct Bufs {                          // the carved workspace of one forward
+  float* buf[B_COUNT];                 // B_OUT of a forward with a row list: rows_region (the full output, whose rows are taken at the end)
+  float* ks_part = nullptr;            // split-K scratch of the staged kernel (ks_part_bytes)
+  void* in_ws = nullptr;               // the instance-norm layers' scratch (in_ws_bytes)
+  float* rows_region = nullptr;        // a row list: the compact rows [n_rows, 96] (sampled tail) or the full output (fallback)
+  void* rows_scratch = nullptr;        // ... and the rows kernel's scratch
+  float* out = nullptr;                // the caller's out_dev
+};
+
+Bufs carve(const eyoc_model* m, const eyoc_maps* maps, const float* feats_dev, float* out_dev, void* ws, size_t ws_bytes,
+           const int64_t* rows_dev, int n_rows) {
+  Bufs b;
   Carver cv(ws, ws_bytes);
-  buf[B_IN] = const_cast<float*>(feats_dev);
-  buf[B_OUT] = out_dev;
-  for (int i = B_X1; i < B_OUT; ++i) buf[i] = cv.take<float>((size_t)maps->rows[m->bufs[i].level] * m->bufs[i].width);
-  const size_t ks_bytes = ks_part_bytes(m, maps);
-  float* ks_part = ks_bytes ? cv.take<float>(ks_bytes / 4) : nullptr;
-  const size_t in_bytes = in_ws_bytes(m, maps);
-  void* in_ws = in_bytes ? cv.take<unsigned char>(in_bytes) : nullptr;
-  float* rows_region = nullptr;        // the compact rows / the full output of a forward with a row list
-  void* rows_scratch = nullptr;
+  b.buf[B_IN] = const_cast<float*>(feats_dev);
+  b.buf[B_OUT] = b.out = out_dev;
+  for (int i = B_X1; i < B_OUT; ++i) b.buf[i] = cv.take<float>((size_t)maps->rows[m->bufs[i].level] * m->bufs[i].width);
+  if (const size_t ks_bytes = ks_part_bytes(m, maps)) b.ks_part = cv.take<float>(ks_bytes / 4);
+  if (const size_t in_bytes = in_ws_bytes(m, maps)) b.in_ws = cv.take<unsigned char>(in_bytes);
   if (rows_dev) {
     const size_t extra = rows_extra_floats(m, maps, n_rows);
-    rows_region = extra ? cv.take<float>(extra) : buf[B_X1];
-    rows_scratch = cv.take<unsigned char>(spconv_rows_scratch_bytes(maps->rows[0], n_rows));
-    buf[B_OUT] = rows_region;          // until the sampled tail takes over: the full output, whose rows are taken at the end
+    b.rows_region = extra ? cv.take<float>(extra) : b.buf[B_X1];
+    b.rows_scratch = cv.take<unsigned char>(spconv_rows_scratch_bytes(maps->rows[0], n_rows));
+    b.buf[B_OUT] = b.rows_region;
   }
-  m->sampled_layer = -1;
-  m->sampled_rows = 0;
-  // arithmetic of the sparse convolutions: SPLIT16 needs the wave-private kernel for EVERY layer (only it reads and
-  // writes the format), which round 1 measured to pay off once the finest level alone fills the chip (>= 4096 wave tiles ~ 4 KITTI
-  // pairs); small batches stay on fp32, where the launcher picks the workgroup-tiled kernel per layer
+  return b;
+}
+
+// arithmetic of the sparse convolutions: SPLIT16 needs the wave-private kernel for EVERY layer (only it reads and
+// writes the format), which round 1 measured to pay off once the finest level alone fills the chip (>= 4096 wave tiles ~ 4 KITTI
+// pairs); small batches stay on fp32, where the launcher picks the workgroup-tiled kernel per layer
+int forward_math(const eyoc_ctx* ctx, const eyoc_model* m, const eyoc_maps* maps, bool* split) {
   const int want = m->math;
   const bool split_ok = ctx->knobs.spconv_kernel != 0 && !(m->desc.normalize_feature && m->desc.out_channels > 64) &&
                         m->desc.channels[1] % 32 == 0;
-  const bool split = split_ok && (want == 1 || (want < 0 && maps->rows[0] >= 8192));   // = the Z-order threshold of eyoc_maps_build
-  EYOC_REQUIRE(want != 1 || split, EYOC_ERR_INVALID,
+  *split = split_ok && (want == 1 || (want < 0 && maps->rows[0] >= 8192));   // = the Z-order threshold of eyoc_maps_build
+  EYOC_REQUIRE(want != 1 || *split, EYOC_ERR_INVALID,
                "eyoc_model_forward: split16 arithmetic is not available for this model / kernel selection");
-  m->last_math = split ? 1 : 0;
+  return EYOC_OK;
+}
+
+enum StepKind { S_INORM, S_AFFINE, S_CONV1, S_SPCONV, S_TAIL, S_SPCONV_TAIL, S_ROWS_TAIL, S_TAKE_ROWS };   // eyoc_hip.h lists them
+
+struct Step {
+  StepKind kind;
+  int first, count = 1;                // the layers [first, first + count) it covers; the time of a step is booked on its first layer
+  int path = -1;                       // S_SPCONV, S_SPCONV_TAIL, S_ROWS_TAIL: spconv_record_path of `a`
+  SpconvArgs a;                        // ... the layer (S_SPCONV_TAIL: with a.tail, the 1x1 pair in its epilogue)
+  Conv1Args c1;                        // S_CONV1
+  // made ready in front of the launch, in this order
+  int in_plan_level = -1;              // maps_ensure_in_plan
+  int table_kind = -1, table_level = 0;   // maps_ensure_table: a lazily skipped [27][n] table that a gathering kernel reads
+  const float* permute_src = nullptr;  // S_CONV1 on Z-ordered maps: the caller's features, copied in internal order to c1.in
+  bool table0 = false;                 // maps_build_table0: the first convolution probes the hash table
+};
+constexpr int MAX_STEPS = RP_MAXL + 1;   // one per layer and the row gather
+
+// layers li, li + 1 are the 1x1 pair the tail kernels take (spconv_tail.hip): conv1_tr -> [ReLU] -> final (+ bias) -> [row normalisation]
+bool is_tail_pair(const eyoc_model* m, size_t li) {
+  if (li + 2 > m->layers.size()) return false;
+  const LayerPlan &q1 = m->layers[li], &q2 = m->layers[li + 1];
+  return q1.map == M_IDENT && q1.K == 1 && q1.res_buf < 0 && q2.map == M_IDENT && q2.K == 1 && q2.in_buf == q1.out_buf && q2.res_buf < 0 &&
+         !q2.relu && q2.out_buf == B_OUT && q1.out_col == 0 && tail_fusable(q1.cin, q1.cout, q2.cout);
+}
+
+int launch_tail(const eyoc_model* m, size_t li, const float* in, int ld_in, int n, float* out, int ld_out, const int32_t* out_perm,
+                hipStream_t st) {
+  const LayerPlan &q1 = m->layers[li], &q2 = m->layers[li + 1];
+  return launch_tail_fused(in, ld_in, n, m->blob + q1.w16_off, m->blob + q1.s_off, m->blob + q1.b_off, q1.relu, m->blob + q2.w16_off,
+                           m->blob + q2.s_off, m->blob + q2.b_off, q2.l2norm, out, ld_out, out_perm, m->range, st);
+}
+
+// a sparse-convolution layer's arguments.  A split16 layer is handed every tile-record family its table kind and widths admit - one
+// rule per family; which of them takes the layer is spconv_record_path's decision
+SpconvArgs fill_spconv(eyoc_ctx* ctx, const eyoc_model* m, const eyoc_maps* maps, const Bufs& b, bool split, const LayerPlan& p) {
+  SpconvArgs a;
+  a.nbr = p.map == M_S1 ? maps->nbr_s1[p.level] : p.map == M_DOWN ? maps->nbr_down[p.level]
+          : p.map == M_UP ? maps->nbr_up[p.level] : nullptr;
+  a.K = p.K; a.n_out = maps->rows[p.out_level];
+  a.n_in = maps->rows[m->bufs[p.in_buf].level];
+  a.in = b.buf[p.in_buf] + p.in_col; a.ld_in = m->bufs[p.in_buf].width; a.cin = p.cin;
+  a.w = m->blob + p.w_off; a.cout = p.cout; a.bias = m->blob + p.b_off;
+  a.res = p.res_buf >= 0 ? b.buf[p.res_buf] : nullptr; a.ld_res = p.res_buf >= 0 ? m->bufs[p.res_buf].width : 0;
+  a.relu = p.relu; a.l2norm = p.l2norm;
+  a.out = b.buf[p.out_buf] + p.out_col; a.ld_out = m->bufs[p.out_buf].width;
+  a.ctx = ctx;
+  if (split) {
+    a.math = 1;
+    a.w = m->blob + p.w16_off;
+    a.out_scale = m->blob + p.s_off;
+    a.out_split = p.out_buf != B_OUT;
+    a.range = m->range;
+    const bool blocks = p.cin % 32 == 0;
+    if (p.map == M_S1 && blocks && p.cin >= 32) { a.local = maps->local_s1[p.level]; a.ks_part = b.ks_part; }   // spconv_st.hip, Z-ordered rows
+    if (p.map == M_S1 && blocks && p.cout % 128 == 0 && ctx->knobs.s1_wide) a.local128 = maps->local_s1w[p.level];
+    if (p.map == M_DOWN && blocks && p.cout % 64 == 0) a.local_down = maps->local_down[p.level];                 // spconv_st.hip on 128-row tiles
+    if (p.map == M_UP && blocks && p.cout % 64 == 0) { a.local_up = maps->local_up[p.level]; a.local_upc = maps->local_upc[p.level]; }   // spconv_up.hip; spconv_upc.hip (class-major tiles)
+  }
+  if (p.out_buf == B_OUT) a.out_perm = maps->row_perm;   // the network output goes back to the caller's row order
+  a.perm = p.map == M_UP ? maps->perm_up[p.level] : p.map == M_S1 ? maps->perm_s1[p.level]
+           : p.map == M_DOWN ? maps->perm_down[p.level] : nullptr;
+  return a;
+}
+
+void fill_conv1(eyoc_ctx* ctx, const eyoc_model* m, const eyoc_maps* maps, const Bufs& b, bool split, const LayerPlan& p, Step& s) {
+  Conv1Args& a = s.c1;
+  a.coords = maps->coords[0]; a.n = maps->rows[p.out_level]; a.table = maps->table[0]; a.ks = m->desc.conv1_kernel_size;
+  a.in = b.buf[p.in_buf]; a.cin = p.cin; a.w = m->blob + p.w_off; a.bias = m->blob + p.b_off; a.cout = p.cout;
+  a.out = b.buf[p.out_buf] + p.out_col; a.ld_out = m->bufs[p.out_buf].width;
+  a.out_split = split ? 1 : 0;
+  a.ctx = ctx;
+  a.range = split ? m->range : nullptr;
+  a.wscale = m->blob + p.s_off;
+  a.in_perm = maps->row_perm;                        // Z-ordered maps: the caller's features are read through the permutation
+  if (a.in_perm) {
+    // ... once: a copy in internal order in a buffer nothing uses yet (an indirection per probed neighbour cost the
+    // 5^3 first convolution 0.4 of its 2.0 ms on the 64-pair batch)
+    int best = -1;
+    size_t best_sz = 0;
+    for (int i = B_X1; i < B_OUT; ++i) {
+      const size_t sz = (size_t)maps->rows[m->bufs[i].level] * m->bufs[i].width;
+      if (i != p.out_buf && sz > best_sz) { best = i; best_sz = sz; }
+    }
+    if (best >= 0 && best_sz >= (size_t)a.n * p.cin) {
+      s.permute_src = a.in;
+      a.in = b.buf[best];
+      a.in_perm = nullptr;
+    }
+  }
+  a.parent = maps->parent[0]; a.children = maps->children[0]; a.s1c = maps->nbr_s1[1]; a.nc = maps->rows[1];
+  a.local1 = maps->row_perm ? maps->local_s1[1] : nullptr;          // Z-ordered maps: the level-1 tile rulebooks (256-parent tiles)
+  s.table0 = !conv1_walks_octree(a);
+}
+
+// -> the number of steps.  Reads the plan, the maps' host fields and the ctx's knobs; launches and writes nothing
+int resolve_schedule(eyoc_ctx* ctx, const eyoc_model* m, const eyoc_maps* maps, const Bufs& b, bool split, const int64_t* rows_dev,
+                     Step* steps) {
+  const size_t nl = m->layers.size();
+  EYOC_REQUIRE(nl >= 1 && nl < MAX_STEPS, EYOC_ERR_INVALID, "eyoc_model_forward: a plan of %zu layers", nl);
+  const bool want_rows = rows_dev && ctx->knobs.sampled_tail;
+  int ns = 0;
+  for (size_t li = 0; li < nl; li += steps[ns].count, ++ns) {
+    const LayerPlan& p = m->layers[li];
+    Step& s = steps[ns];
+    s.first = (int)li;
+    if (p.map == M_INORM) {
+      s.kind = S_INORM; s.in_plan_level = p.out_level;   // built on the first instance-norm forward over these maps, without a read-back
+    } else if (p.map == M_AFFINE) {
+      s.kind = S_AFFINE;
+    } else if (p.map == M_CONV1) {
+      s.kind = S_CONV1; fill_conv1(ctx, m, maps, b, split, p, s);
+    } else if (split && ctx->knobs.fuse_tail != 0 && li + 2 == nl && is_tail_pair(m, li)) {
+      s.kind = S_TAIL; s.count = 2;   // conv1_tr -> ReLU -> final (+ bias) -> row normalisation in one kernel: the [N, 64] intermediate stays in registers
+    } else {
+      s.kind = S_SPCONV;
+      s.a = fill_spconv(ctx, m, maps, b, split, p);
+      s.path = spconv_record_path(s.a);
+      // lazy tables (common.h eyoc_maps): a layer that no tile-record kernel takes reads its [27][n] table - filled on first use
+      if ((p.map == M_S1 || p.map == M_UP) && s.path == 0) { s.table_kind = p.map == M_S1 ? EYOC_MAP_S1 : EYOC_MAP_UP; s.table_level = p.level; }
+      // the 1x1 tail behind the last staged layer (eyoc_model_fuse_tail 2, the default): block2_tr.conv2 writes the 64 decoder channels
+      // the tail reads next to the 32 skip channels.  (A row list does not ask for the 256-row kernel: small inputs, whose full forward
+      // runs the tail as a kernel of its own - the same bits -, take the sampled path too)
+      if (split && ctx->knobs.fuse_tail == 2 && li + 3 == nl && p.map == M_S1 && p.cout == 64 && is_tail_pair(m, li + 1)) {
+        const LayerPlan &q1 = m->layers[li + 1], &q2 = m->layers[li + 2];
+        if (q1.in_buf == p.out_buf && q1.in_col == p.out_col && q1.cin == p.cout + 32 && s.path == 1 &&
+            (spconv_st_can_fuse_tail(s.a) || want_rows)) {
+          if (want_rows && maps->row_perm && spconv_rows_supported(s.a)) {
+            // this layer for the listed rows only (compact [n_rows, 96] split16 rows: its 64 channels + the 32 skip channels), then the
+            // tail as a kernel of its own on them - the bits of the fused epilogue
+            s.kind = S_ROWS_TAIL; s.count = 3;
+          } else if (spconv_st_can_fuse_tail(s.a)) {
+            // in the layer's epilogue: with the tail riding there the 64 channels never reach memory
+            s.kind = S_SPCONV_TAIL; s.count = 3;
+            TailFuse& t = s.a.tail;
+            t.skip = b.buf[q1.in_buf] + q1.in_col + p.cout; t.ld_skip = m->bufs[q1.in_buf].width;
+            t.w1 = m->blob + q1.w16_off; t.s1 = m->blob + q1.s_off; t.b1 = m->blob + q1.b_off; t.relu1 = q1.relu;
+            t.w2 = m->blob + q2.w16_off; t.s2 = m->blob + q2.s_off; t.b2 = m->blob + q2.b_off; t.l2norm = q2.l2norm;
+            t.out = b.buf[q2.out_buf] + q2.out_col; t.ld_out = m->bufs[q2.out_buf].width; t.out_perm = maps->row_perm;
+          }
+        }
+      }
+    }
+  }
+  if (rows_dev && steps[ns - 1].kind != S_ROWS_TAIL) steps[ns++] = Step{S_TAKE_ROWS, (int)nl, 0};   // the fallback: the rows of the full output
+  return ns;
+}
+
+int run_schedule(const eyoc_model* m, const eyoc_maps* maps_c, const Bufs& b, bool split, const int64_t* rows_dev, int n_rows,
+                 const Step* steps, int ns, hipStream_t st) {
+  eyoc_maps* maps = const_cast<eyoc_maps*>(maps_c);                      // what a step needs ready is filled on first use (common.h eyoc_maps)
+  const hipEvent_t* ev = m->timing ? m->events.data() + (size_t)m->slot * (m->layers.size() + 1) : nullptr;
+  if (ev) EYOC_CHECK_HIP(hipEventRecord(ev[0], st));
+  bool progress_recorded = m->progress_event == nullptr;
+  for (int si = 0; si < ns; ++si) {
+    const Step& s = steps[si];
+    const LayerPlan* p = m->layers.data() + s.first;                     // p[0 .. count): the covered layers
+    // in front of the first step that begins at or behind the layer: a layer inside a multi-layer step has no launch of its own
+    if (!progress_recorded && s.first >= m->progress_layer) { EYOC_CHECK_HIP(hipEventRecord(m->progress_event, st)); progress_recorded = true; }
+    int rc = EYOC_OK;
+    if (s.in_plan_level >= 0) rc = maps_ensure_in_plan(maps, s.in_plan_level, st);
+    if (!rc && s.table_kind >= 0) rc = maps_ensure_table(maps, s.table_kind, s.table_level, st);
+    if (!rc && s.permute_src) rc = launch_permute_rows(s.permute_src, maps->row_perm, s.c1.n, s.c1.cin, const_cast<float*>(s.c1.in), st);
+    if (!rc && s.table0) rc = maps_build_table0(maps, st);
+    if (rc) return rc;
+    const int n_out = s.count ? maps->rows[p->out_level] : 0;
+    switch (s.kind) {
+      case S_INORM:
+        if (n_out)
+          rc = launch_in_layer(b.buf[p->in_buf] + p->in_col, m->bufs[p->in_buf].width, n_out, p->cout, maps->in_plan[p->out_level],
+                               m->blob + p->w_off, m->blob + p->b_off, IN_EPS, p->relu, p->res_buf >= 0 ? b.buf[p->res_buf] : nullptr,
+                               p->res_buf >= 0 ? m->bufs[p->res_buf].width : 0, b.buf[p->out_buf] + p->out_col, m->bufs[p->out_buf].width,
+                               split, split ? m->range : nullptr, b.in_ws, st);
+        break;
+      case S_AFFINE:
+        rc = launch_affine(b.buf[p->in_buf] + p->in_col, m->bufs[p->in_buf].width, n_out, p->cout, m->blob + p->w_off, m->blob + p->b_off,
+                           b.buf[p->out_buf] + p->out_col, m->bufs[p->out_buf].width, split, split ? m->range : nullptr, st);
+        break;
+      case S_CONV1: rc = launch_conv1(s.c1, st); break;
+      case S_SPCONV:
+      case S_SPCONV_TAIL: rc = launch_spconv(s.a, s.path, st); break;
+      case S_TAIL:
+        rc = launch_tail(m, s.first, b.buf[p->in_buf] + p->in_col, m->bufs[p->in_buf].width, n_out, b.buf[p[1].out_buf] + p[1].out_col,
+                         m->bufs[p[1].out_buf].width, maps->row_perm, st);
+        break;
+      case S_ROWS_TAIL:
+        EYOC_CHECK_HIP(hipMemsetAsync(m->range + 6, 0, 4, st));          // word 6: the (row, offset) pairs the rows kernel multiplies
+        rc = launch_spconv_rows(s.a, s.a.local, maps->row_perm, rows_dev, n_rows, b.buf[p[1].in_buf] + p[1].in_col + p->cout,
+                                m->bufs[p[1].in_buf].width, b.rows_region, b.rows_scratch, m->range + 6, st);
+        if (!rc) rc = launch_tail(m, s.first + 1, b.rows_region, 96, n_rows, b.out, m->desc.out_channels, nullptr, st);
+        break;
+      case S_TAKE_ROWS: rc = launch_take_rows(b.rows_region, maps->rows[0], m->desc.out_channels, rows_dev, n_rows, b.out, st); break;
+    }
+    if (rc) return rc;
+    for (int e = 1; ev && e <= s.count; ++e) EYOC_CHECK_HIP(hipEventRecord(ev[s.first + e], st));   // the other covered layers read 0
+  }
+  if (!progress_recorded) EYOC_CHECK_HIP(hipEventRecord(m->progress_event, st));
+  return EYOC_OK;
+}
+
+int forward_impl(eyoc_ctx* ctx, const eyoc_model* m, const eyoc_maps* maps, const float* feats_dev, float* out_dev, void* ws,
+                 size_t ws_bytes, void* stream, const int64_t* rows_dev, int n_rows) {
+  hipStream_t st = (hipStream_t)stream;
+  bool split;
+  if (int rc = forward_math(ctx, m, maps, &split)) return rc;
+  const Bufs b = carve(m, maps, feats_dev, out_dev, ws, ws_bytes, rows_dev, n_rows);
+  Step steps[MAX_STEPS];
+  const int ns = resolve_schedule(ctx, m, maps, b, split, rows_dev, steps);
+  if (ns < 0) return ns;
+  eyoc_model::Last& last = const_cast<eyoc_model*>(m)->last;             // the one thing a forward writes to its model: what it was
+  const bool sampled = steps[ns - 1].kind == S_ROWS_TAIL;                // (it covers the last three layers, so it is the last step)
+  last.math = split ? 1 : 0;
+  last.sampled_layer = sampled ? steps[ns - 1].first : -1;
+  last.sampled_rows = sampled ? n_rows : 0;
   // the overflow flag of THIS forward (the sticky copy is word 3).  Cleared by every forward, fp32 ones included: after an
   // overflow switched a model to fp32 MFMAs, eyoc_model_range_snapshot must not keep reporting the old verdict for forwards
   // that cannot overflow
   EYOC_CHECK_HIP(hipMemsetAsync(m->range, 0, 4, st));
   EYOC_CHECK_HIP(hipMemsetAsync(m->range + 4, 0, 8, st));             // words 4, 5: the fused tail's own verdicts (spconv_st.hip TAILF)
-  hipEvent_t* ev = m->timing ? m->events.data() + (size_t)m->slot * (m->layers.size() + 1) : nullptr;
-  if (m->timing) EYOC_CHECK_HIP(hipEventRecord(ev[0], st));
-  bool progress_recorded = m->progress_event == nullptr;
-  for (size_t li = 0; li < m->layers.size(); ++li) {
-    const LayerPlan& p = m->layers[li];
-    const int n_out = maps->rows[p.out_level];
-    int rc;
-    if (!progress_recorded && (int)li >= m->progress_layer) {            // (>=: a layer fused into its predecessor has no iteration of its own)
-      EYOC_CHECK_HIP(hipEventRecord(m->progress_event, st));
-      progress_recorded = true;
-    }
-    if (p.map == M_INORM) {
-      // the level's instance plan: built on the first instance-norm forward over these maps, without a read-back (maps_ensure_in_plan)
-      if ((rc = maps_ensure_in_plan(const_cast<eyoc_maps*>(maps), p.out_level, st))) return rc;
-      rc = n_out ? launch_in_layer(buf[p.in_buf] + p.in_col, m->bufs[p.in_buf].width, n_out, p.cout, maps->in_plan[p.out_level], m->blob + p.w_off,
-                                   m->blob + p.b_off, IN_EPS, p.relu, p.res_buf >= 0 ? buf[p.res_buf] : nullptr,
-                                   p.res_buf >= 0 ? m->bufs[p.res_buf].width : 0, buf[p.out_buf] + p.out_col, m->bufs[p.out_buf].width, split,
-                                   split ? m->range : nullptr, in_ws, st)
-                 : EYOC_OK;
-    } else if (p.map == M_AFFINE) {
-      rc = launch_affine(buf[p.in_buf] + p.in_col, m->bufs[p.in_buf].width, n_out, p.cout, m->blob + p.w_off, m->blob + p.b_off,
-                         buf[p.out_buf] + p.out_col, m->bufs[p.out_buf].width, split, split ? m->range : nullptr, st);
-    } else if (p.map == M_CONV1) {
-      Conv1Args a;
-      a.coords = maps->coords[0]; a.n = n_out; a.table = maps->table[0]; a.ks = m->desc.conv1_kernel_size;
-      a.in = buf[p.in_buf]; a.cin = p.cin; a.w = m->blob + p.w_off; a.bias = m->blob + p.b_off; a.cout = p.cout;
-      a.out = buf[p.out_buf] + p.out_col; a.ld_out = m->bufs[p.out_buf].width;
-      a.out_split = split ? 1 : 0;
-      a.ctx = ctx;
-      a.range = split ? m->range : nullptr;
-      a.wscale = m->blob + p.s_off;
-      a.in_perm = maps->row_perm;                        // Z-ordered maps: the caller's features are read through the permutation
-      if (a.in_perm) {
-        // ... once: a copy in internal order in a buffer nothing uses yet (an indirection per probed neighbour cost the
-        // 5^3 first convolution 0.4 of its 2.0 ms on the 64-pair batch)
-        int best = -1;
-        size_t best_sz = 0;
-        for (int i = B_X1; i < B_OUT; ++i) {
-          const size_t sz = (size_t)maps->rows[m->bufs[i].level] * m->bufs[i].width;
-          if (i != p.out_buf && sz > best_sz) { best = i; best_sz = sz; }
-        }
-        if (best >= 0 && best_sz >= (size_t)n_out * p.cin) {
-          rc = launch_permute_rows(a.in, a.in_perm, n_out, p.cin, buf[best], st);
-          if (rc) return rc;
-          a.in = buf[best];
-          a.in_perm = nullptr;
-        }
-      }
-      a.parent = maps->parent[0]; a.children = maps->children[0]; a.s1c = maps->nbr_s1[1]; a.nc = maps->rows[1];
-      a.local1 = maps->row_perm ? maps->local_s1[1] : nullptr;          // Z-ordered maps: the level-1 tile rulebooks (256-parent tiles)
-      rc = conv1_walks_octree(a) ? EYOC_OK : maps_build_table0(const_cast<eyoc_maps*>(maps), st);
-      if (!rc) rc = launch_conv1(a, st);
-    } else if (split && ctx->knobs.fuse_tail != 0 && li + 2 == m->layers.size() && p.map == M_IDENT && p.K == 1 && p.res_buf < 0 &&
-               m->layers[li + 1].map == M_IDENT && m->layers[li + 1].K == 1 && m->layers[li + 1].in_buf == p.out_buf &&
-               m->layers[li + 1].res_buf < 0 && !m->layers[li + 1].relu && m->layers[li + 1].out_buf == B_OUT && p.out_col == 0 &&
-               tail_fusable(p.cin, p.cout, m->layers[li + 1].cout)) {
-      // conv1_tr -> ReLU -> final (+ bias) -> row normalisation in one kernel: the [N, 64] intermediate stays in registers
-      const LayerPlan& q = m->layers[li + 1];
-      rc = launch_tail_fused(buf[p.in_buf] + p.in_col, m->bufs[p.in_buf].width, n_out, m->blob + p.w16_off, m->blob + p.s_off,
-                             m->blob + p.b_off, p.relu, m->blob + q.w16_off, m->blob + q.s_off, m->blob + q.b_off, q.l2norm,
-                             buf[q.out_buf] + q.out_col, m->bufs[q.out_buf].width, maps->row_perm, m->range, st);
-      if (rc) return rc;
-      if (m->timing) {                                  // the pair's time is booked on the first layer, the second reads 0
-        EYOC_CHECK_HIP(hipEventRecord(ev[li + 1], st));
-        EYOC_CHECK_HIP(hipEventRecord(ev[li + 2], st));
-      }
-      ++li;
-      continue;
-    } else {
-      SpconvArgs a;
-      a.nbr = p.map == M_S1 ? maps->nbr_s1[p.level] : p.map == M_DOWN ? maps->nbr_down[p.level]
-              : p.map == M_UP ? maps->nbr_up[p.level] : nullptr;
-      a.K = p.K; a.n_out = n_out;
-      a.n_in = maps->rows[m->bufs[p.in_buf].level];
-      a.in = buf[p.in_buf] + p.in_col; a.ld_in = m->bufs[p.in_buf].width; a.cin = p.cin;
-      a.w = m->blob + p.w_off; a.cout = p.cout; a.bias = m->blob + p.b_off;
-      a.res = p.res_buf >= 0 ? buf[p.res_buf] : nullptr; a.ld_res = p.res_buf >= 0 ? m->bufs[p.res_buf].width : 0;
-      a.relu = p.relu; a.l2norm = p.l2norm;
-      a.out = buf[p.out_buf] + p.out_col; a.ld_out = m->bufs[p.out_buf].width;
-      a.ctx = ctx;
-      if (split) {
-        a.math = 1;
-        a.w = m->blob + p.w16_off;
-        a.out_scale = m->blob + p.s_off;
-        a.out_split = p.out_buf != B_OUT;
-        a.range = m->range;
-        // stride-1 layers on Z-ordered rows: tile-local input stage (spconv_st.hip)
-        if (p.map == M_S1 && p.cin >= 32 && p.cin % 32 == 0) { a.local = maps->local_s1[p.level]; a.ks_part = ks_part; }
-        if (p.map == M_S1 && p.cin % 32 == 0 && p.cout % 128 == 0 && ctx->knobs.s1_wide) a.local128 = maps->local_s1w[p.level];
-        if (p.map == M_DOWN && p.cin % 32 == 0 && p.cout % 64 == 0) a.local_down = maps->local_down[p.level];   // spconv_st.hip on 128-row tiles
-        if (p.map == M_UP && p.cin % 32 == 0 && p.cout % 64 == 0) a.local_up = maps->local_up[p.level];   // spconv_up.hip
-        if (p.map == M_UP && p.cin % 32 == 0 && p.cout % 64 == 0) a.local_upc = maps->local_upc[p.level]; // spconv_upc.hip (class-major tiles)
-      }
-      if (p.out_buf == B_OUT) a.out_perm = maps->row_perm;   // the network output goes back to the caller's row order
-      // lazy tables (common.h eyoc_maps): a layer that no tile-record kernel takes reads its [27][n] table - filled here on first use
-      if ((p.map == M_S1 || p.map == M_UP) && spconv_record_path(a) == 0)
-        if ((rc = maps_ensure_table(const_cast<eyoc_maps*>(maps), p.map == M_S1 ? EYOC_MAP_S1 : EYOC_MAP_UP, p.level, st))) return rc;
-      a.perm = p.map == M_UP ? maps->perm_up[p.level] : p.map == M_S1 ? maps->perm_s1[p.level]
-               : p.map == M_DOWN ? maps->perm_down[p.level] : nullptr;
-      // the 1x1 tail in the epilogue of the last staged layer (eyoc_model_fuse_tail 2, the default): block2_tr.conv2 writes the 64
-      // decoder channels the tail reads next to the 32 skip channels - with the tail riding in its epilogue they never reach memory
-      if (split && ctx->knobs.fuse_tail == 2 && li + 3 == m->layers.size() && p.map == M_S1 && p.cout == 64) {
-        const LayerPlan &q1 = m->layers[li + 1], &q2 = m->layers[li + 2];
-        if (q1.map == M_IDENT && q1.K == 1 && q1.res_buf < 0 && q2.map == M_IDENT && q2.K == 1 && q2.in_buf == q1.out_buf && q2.res_buf < 0 &&
-            !q2.relu && q2.out_buf == B_OUT && q1.out_col == 0 && tail_fusable(q1.cin, q1.cout, q2.cout) && q1.in_buf == p.out_buf &&
-            q1.in_col == p.out_col && q1.cin == p.cout + 32 && spconv_record_path(a) == 1 &&
-            (spconv_st_can_fuse_tail(a) || (rows_dev && ctx->knobs.sampled_tail))) {
-          // (a row list does not ask for the 256-row kernel: small inputs, whose full forward runs the tail as a kernel of its own - the
-          // same bits -, take the sampled path too)
-          if (rows_dev && ctx->knobs.sampled_tail && maps->row_perm && spconv_rows_supported(a)) {
-            // the caller reads n_rows rows: this layer for those rows only (compact [n_rows, 96] split16 rows: its 64 channels + the
-            // 32 skip channels), then the tail as a kernel of its own on them - the bits of the fused epilogue
-            EYOC_CHECK_HIP(hipMemsetAsync(m->range + 6, 0, 4, st));
-            rc = launch_spconv_rows(a, a.local, maps->row_perm, rows_dev, n_rows, buf[q1.in_buf] + q1.in_col + p.cout,
-                                    m->bufs[q1.in_buf].width, rows_region, rows_scratch, m->range + 6, st);
-            if (!rc)
-              rc = launch_tail_fused(rows_region, 96, n_rows, m->blob + q1.w16_off, m->blob + q1.s_off, m->blob + q1.b_off, q1.relu,
-                                     m->blob + q2.w16_off, m->blob + q2.s_off, m->blob + q2.b_off, q2.l2norm, out_dev,
-                                     m->desc.out_channels, nullptr, m->range, st);
-            if (rc) return rc;
-            m->sampled_layer = (int)li;
-            m->sampled_rows = n_rows;
-            if (m->timing)
-              for (int e = 1; e <= 3; ++e) EYOC_CHECK_HIP(hipEventRecord(ev[li + e], st));
-            li += 2;
-            continue;
-          }
-          if (!spconv_st_can_fuse_tail(a)) goto unfused;
-          a.tail.skip = buf[q1.in_buf] + q1.in_col + p.cout; a.tail.ld_skip = m->bufs[q1.in_buf].width;
-          a.tail.w1 = m->blob + q1.w16_off; a.tail.s1 = m->blob + q1.s_off; a.tail.b1 = m->blob + q1.b_off; a.tail.relu1 = q1.relu;
-          a.tail.w2 = m->blob + q2.w16_off; a.tail.s2 = m->blob + q2.s_off; a.tail.b2 = m->blob + q2.b_off; a.tail.l2norm = q2.l2norm;
-          a.tail.out = buf[q2.out_buf] + q2.out_col; a.tail.ld_out = m->bufs[q2.out_buf].width; a.tail.out_perm = maps->row_perm;
-          rc = launch_spconv(a, st);
-          if (rc) return rc;
-          if (m->timing)                                                  // the three layers' time is booked on the first one
-            for (int e = 1; e <= 3; ++e) EYOC_CHECK_HIP(hipEventRecord(ev[li + e], st));
-          li += 2;
-          continue;
-        }
-      }
-    unfused:
-      rc = launch_spconv(a, st);
-    }
-    if (rc) return rc;
-    if (m->timing) EYOC_CHECK_HIP(hipEventRecord(ev[li + 1], st));
-  }
-  if (!progress_recorded) EYOC_CHECK_HIP(hipEventRecord(m->progress_event, st));
-  if (rows_dev && m->sampled_layer < 0)                                  // the fallback: the rows of the full output
-    if (int rc = launch_take_rows(rows_region, maps->rows[0], m->desc.out_channels, rows_dev, n_rows, out_dev, st)) return rc;
-  if (m->timing) m->events_valid[m->slot] = 1;
+  if (int rc = run_schedule(m, maps, b, split, rows_dev, n_rows, steps, ns, st)) return rc;
+  if (m->timing) last.events_valid[m->slot] = 1;
   return EYOC_OK;
 }
+
+}  // namespace
 
 extern "C" {
 
@@ -1036,6 +1113,24 @@ int eyoc_model_forward_rows(eyoc_ctx* ctx, const eyoc_model* mc, const eyoc_maps
   return forward_impl(ctx, mc, maps, feats_dev, out_dev, ws, ws_bytes, stream, rows_dev, n_rows);
 }
 
+int eyoc_model_forward_steps(eyoc_ctx* ctx, const eyoc_model* m, const eyoc_maps* maps, const int64_t* rows_dev, int n_rows, void* ws,
+                             size_t ws_bytes, int32_t* step_of_layer, int32_t* kind_of_layer, int32_t* path_of_layer) {
+  EYOC_REQUIRE(ctx && m && maps && ws && step_of_layer && kind_of_layer && path_of_layer && (!rows_dev || n_rows >= 1), EYOC_ERR_INVALID,
+               "eyoc_model_forward_steps: NULL argument");
+  const size_t need = rows_dev ? eyoc_model_workspace_bytes_rows(m, maps, n_rows) : eyoc_model_workspace_bytes(m, maps);
+  EYOC_REQUIRE(ws_bytes >= need, EYOC_ERR_WORKSPACE, "eyoc_model_forward_steps: workspace %zu < required %zu bytes", ws_bytes, need);
+  EYOC_REQUIRE(((uintptr_t)ws & 255) == 0, EYOC_ERR_INVALID, "eyoc_model_forward_steps: workspace must be 256-byte aligned");
+  bool split;
+  if (int rc = forward_math(ctx, m, maps, &split)) return rc;
+  // the caller's features and output take no part in any decision: a residual or an output permutation does, hence the real carve
+  const Bufs b = carve(m, maps, nullptr, nullptr, ws, ws_bytes, rows_dev, n_rows);
+  Step steps[MAX_STEPS];
+  const int ns = resolve_schedule(ctx, m, maps, b, split, rows_dev, steps);
+  for (int si = 0; si < ns; ++si)
+    for (int l = steps[si].first; l < steps[si].first + steps[si].count; ++l) { step_of_layer[l] = si; kind_of_layer[l] = steps[si].kind; path_of_layer[l] = steps[si].path; }
+  return ns;
+}
+
 int eyoc_model_set_progress_event(eyoc_model* m, int layer, void* hip_event) {
   EYOC_REQUIRE(m, EYOC_ERR_INVALID, "eyoc_model_set_progress_event: NULL model");
   const int n = (int)m->layers.size();
@@ -1055,17 +1150,17 @@ int eyoc_model_layer_work(eyoc_ctx* ctx, const eyoc_model* m, const eyoc_maps* m
   // the handle's most recent forward computed its last three layers for a row list (eyoc_model_forward_rows): their work is what
   // that forward multiplied - the pairs its rows kernel counted (range word 6), the listed rows for the two 1x1 layers
   unsigned int sampled_pairs = 0;
-  if (m->sampled_layer >= 0) {
+  if (m->last.sampled_layer >= 0) {
     EYOC_CHECK_HIP(hipMemcpyAsync(&sampled_pairs, m->range + 6, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
     EYOC_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
   }
   for (size_t li = 0; li < m->layers.size(); ++li) {
     const LayerPlan& p = m->layers[li];
-    const bool sampled = m->sampled_layer >= 0 && (int)li >= m->sampled_layer && (int)li <= m->sampled_layer + 2;
-    const double n_out = sampled ? m->sampled_rows : maps->rows[p.out_level];
+    const bool sampled = m->last.sampled_layer >= 0 && (int)li >= m->last.sampled_layer && (int)li <= m->last.sampled_layer + 2;
+    const double n_out = sampled ? m->last.sampled_rows : maps->rows[p.out_level];
     double n_in = n_out, pr = 0;
     if (sampled) {
-      pr = (int)li == m->sampled_layer ? (double)sampled_pairs : n_out;
+      pr = (int)li == m->last.sampled_layer ? (double)sampled_pairs : n_out;
     } else
     switch (p.map) {
       case M_CONV1: pr = (double)info.pairs_conv1; break;

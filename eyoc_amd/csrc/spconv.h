@@ -164,12 +164,13 @@ __device__ inline int canonical_slot_id(const int* hk, const unsigned short* hpo
 }
 
 int launch_spconv(const SpconvArgs& a, hipStream_t st);
+int launch_spconv(const SpconvArgs& a, int record_path, hipStream_t st);   // record_path: spconv_record_path(a), computed by the caller
 int launch_permute_rows(const float* in, const int32_t* perm, int n, int c, float* out, hipStream_t st);
 int launch_spconv_st(const SpconvArgs& a, const unsigned char* local_dev, hipStream_t st);   // tile-local input stage (spconv_st.hip)
 int launch_spconv_up(const SpconvArgs& a, const unsigned char* local_dev, hipStream_t st);   // transposed 3^3 / stride 2 (spconv_up.hip)
 size_t local_rulebook_up_bytes(int n_out);
 bool spconv_st_can_fuse_tail(const SpconvArgs& a);   // spconv_st.hip: would launch_spconv_st run the 256-row NH = 2 assembly kernel on this (64-channel) layer
-int spconv_record_path(const SpconvArgs& a);   // spconv.hip: 1 / 2 / 3 = a tile-record kernel takes the layer (a.nbr is not read), 0 = a gathering kernel
+int spconv_record_path(const SpconvArgs& a);   // spconv.hip: 1 .. 5 = a tile-record kernel takes the layer (a.nbr is not read), 0 = a gathering kernel
 int build_local_rulebook_up(const int32_t* nbr_dev, int K, int n_out, unsigned char* out_dev, int* overflow_dev, hipStream_t st);
 // class-major transposed kernel (spconv_upc.hip): `ws` = upc_kept_bytes of header + tile order + records, built by build_upc
 // (which also needs upc_scratch_bytes of scratch it does not keep)

@@ -758,7 +758,8 @@ namespace eyoc {
 
 // Which tile-record kernel takes a split16 layer: 1 the staged stride-1 kernel (spconv_st.hip), 2 class-major transposed tiles
 // (spconv_upc.hip), 3 Morton transposed tiles (spconv_up.hip), 4 the staged kernel on 128-row tiles of a strided table, 5 ... of a stride-1 table (>= 128 output channels), 0 none - a gathering kernel, which reads a.nbr.  ONE predicate for the
-// launcher below and for eyoc_model_forward, which fills a lazily skipped table only when a layer really reads it (common.h eyoc_maps).
+// launcher below and for eyoc_model_forward, which fills a lazily skipped table only when a layer really reads it (common.h eyoc_maps)
+// and hands the launcher the path it resolved.
 int spconv_record_path(const SpconvArgs& a) {
   if (a.math != 1 || a.K != 27 || a.l2norm) return 0;
   const int use_rs = knobs_of(a.ctx).split16_kernel;
@@ -775,7 +776,9 @@ int spconv_record_path(const SpconvArgs& a) {
   return 0;
 }
 
-int launch_spconv(const SpconvArgs& a, hipStream_t st) {
+int launch_spconv(const SpconvArgs& a, hipStream_t st) { return launch_spconv(a, spconv_record_path(a), st); }
+
+int launch_spconv(const SpconvArgs& a, int record_path, hipStream_t st) {
   EYOC_REQUIRE(a.in && a.w && a.out, EYOC_ERR_INVALID, "spconv: NULL tensor");
   EYOC_REQUIRE(a.n_out >= 0, EYOC_ERR_INVALID, "spconv: n_out %d", a.n_out);
   EYOC_REQUIRE(a.cin > 0 && a.cin % 32 == 0, EYOC_ERR_INVALID, "spconv: C_in %d must be a multiple of 32", a.cin);
@@ -810,9 +813,7 @@ int launch_spconv(const SpconvArgs& a, hipStream_t st) {
     // measured per layer of the 64-pair bench: the row-stationary kernel wins on the stride-1, transposed and 1x1 layers
     // with C_in >= 64 (-5 .. -15 %); the 32-channel layers and the strided convolutions (few, scattered pairs per
     // output row: 2.9x more zero MFMAs buy nothing there) stay on the wave-private kernel
-    // stride-1 table with local rulebooks: staged kernel (its workgroups cover 64 - or 32 - output channels each and
-    // 1, 2, 4 or 8 of them share a tile; other widths stay on the gathering kernels)
-    switch (spconv_record_path(a)) {
+    switch (record_path) {
       case 1: { SpconvArgs b = a; b.perm = nullptr; return launch_spconv_st(b, a.local, st); }
       case 2: { SpconvArgs b = a; b.perm = nullptr; return launch_spconv_upc(b, a.local_upc, st); }     // transposed table, class-major tiles
       case 3: { SpconvArgs b = a; b.perm = nullptr; return launch_spconv_up(b, a.local_up, st); }       // transposed table with tile rulebooks

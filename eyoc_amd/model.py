@@ -444,6 +444,30 @@ class ResUNet2(nn.Module):
             return out
         return SparseTensor(out, coordinate_map_key=x.coordinate_map_key, coordinate_manager=cm)
 
+    STEP_KINDS = ("inorm", "affine", "conv1", "spconv", "tail", "spconv+tail", "rows+tail", "take_rows")
+
+    def forward_steps(self, x: SparseTensor, rows: torch.Tensor | None = None):
+        """The launch schedule ``model(x)`` / ``model(x, rows=rows)`` would run now, as data (``eyoc_model_forward_steps``; nothing is
+        launched): one ``(layer name, step index, step kind, tile-record path or -1)`` per layer of the packed plan, the kinds named as
+        in ``STEP_KINDS``.  A row gather that ends the schedule covers no layer: it comes last, under the name ``""``."""
+        lib = _lib.load()
+        names = [w["name"] for w in self.layer_work(x)]                    # (packs the model where it has no handle yet)
+        n, dev = len(names), x.device
+        maps = x.coordinate_manager.maps(-1)
+        step, kind, path = (C.c_int32 * n)(), (C.c_int32 * n)(), (C.c_int32 * n)()
+        with torch.cuda.device(dev):
+            if rows is None:
+                ws = _lib.workspace(lib.eyoc_model_workspace_bytes(self._handle, maps), dev)
+            else:
+                rows = rows.to(dev, torch.int64).contiguous().reshape(-1)
+                ws = _lib.workspace(lib.eyoc_model_workspace_bytes_rows(self._handle, maps, rows.numel()), dev)
+            ns = lib.eyoc_model_forward_steps(_lib.ctx(dev.index), self._handle, maps, _lib.ptr(rows), 0 if rows is None else rows.numel(),
+                                              _lib.ptr(ws), ws.numel(), step, kind, path)
+        if ns < 0:
+            _lib.check(ns, "eyoc_model_forward_steps")
+        out = [(names[i], int(step[i]), self.STEP_KINDS[kind[i]], int(path[i])) for i in range(n)]
+        return out + [("", ns - 1, "take_rows", -1)] * (ns - 1 > step[n - 1])
+
     def check_range(self):
         """Raise ``EyocError`` (``code == EYOC_ERR_RANGE``) if ANY split16 forward since the last check stored an
         activation of magnitude >= 6e4; synchronises the current stream.  The forwards that overflowed are the ones whose

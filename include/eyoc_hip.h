@@ -485,6 +485,19 @@ int eyoc_model_forward_rows(eyoc_ctx* ctx, const eyoc_model* model, const eyoc_m
                             const int64_t* rows_dev, int n_rows, float* out_dev, void* workspace_dev, size_t workspace_bytes,
                             void* stream);
 int eyoc_model_sampled_tail(eyoc_ctx* ctx, int on);
+/* The launch schedule of ResUNet2.forward (model/resunet.py:143-193) as data: what eyoc_model_forward (rows_dev == NULL) or
+ * eyoc_model_forward_rows (rows_dev and n_rows >= 1) WOULD launch for this model, these maps, this workspace and the ctx's switches
+ * now.  Same workspace arguments and checks as those two; nothing is launched, no device memory is touched, model and maps stay as
+ * they are.  A step is one launch (with what it needs ready in front of it) and covers 1, 2 or 3 consecutive layers; per layer
+ * (arrays of eyoc_model_num_layers() entries): step_of_layer the index of its step, kind_of_layer that step's kind - 0 instance norm,
+ * 1 stand-alone affine norm, 2 first convolution, 3 sparse convolution, 4 the 1x1 tail as one kernel (2 layers), 5 the last staged
+ * layer with the tail in its epilogue (3 layers), 6 that layer for the listed rows + the tail on the compact rows (3 layers) -,
+ * path_of_layer the tile-record kernel of a step of kind 3, 5 or 6 (1 staged stride-1, 2 class-major transposed, 3 Morton transposed,
+ * 4 strided 128-row tiles, 5 stride-1 128-row tiles, 0 none: a gathering kernel), -1 for the other kinds.  Returns the number of
+ * steps - one more than the last layer's step index when a row gather (kind 7, no layer) ends the schedule - or a negative status. */
+int eyoc_model_forward_steps(eyoc_ctx* ctx, const eyoc_model* model, const eyoc_maps* maps, const int64_t* rows_dev, int n_rows,
+                             void* workspace_dev, size_t workspace_bytes, int32_t* step_of_layer, int32_t* kind_of_layer,
+                             int32_t* path_of_layer);
 /* per-layer algorithmic work of the last forward geometry (SURVEY.md 8d formulas); arrays of
  * eyoc_model_num_layers() entries, any may be NULL */
 /* When the handle's most recent forward was an eyoc_model_forward_rows that computed listed rows only, the entries of the last 3^3

@@ -319,7 +319,7 @@ def test_listed_rows(batch_kernels_from_8192_rows, name):
 # ------------------------------------------------------------------------------------------------ refusals
 def test_a_normalised_128_channel_output_has_no_split16_forward(batch_kernels_from_8192_rows):
     """``normalize_feature=True, out_channels=128``: the row normalisation needs the whole row in one tile, which only the fp32
-    workgroup-tiled kernel has (``split_ok`` in forward_impl).  Asking for split16 raises; automatic mode runs fp32 on cloud M and
+    workgroup-tiled kernel has (``split_ok`` in forward_math, model.hip).  Asking for split16 raises; automatic mode runs fp32 on cloud M and
     meets the bar."""
     import eyoc_amd
     from eyoc_amd import _lib, synthetic as syn

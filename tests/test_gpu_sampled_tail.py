@@ -42,12 +42,10 @@ def cloud():
     from eyoc_amd import synthetic as syn
     from oracle import coords as oc
     from oracle import resunet as orr
+    from forward_matrix import large_batch
     L, lib = _lib()
-    g = np.stack(np.meshgrid(np.arange(20), np.arange(20), np.arange(20), indexing="ij"), -1).reshape(-1, 3) + 5
-    p = syn.make_pair(2, beams=32, azimuths=1000, band=None)
-    coords = syn.batch_coords([g, p["coords0"], p["coords1"]])
+    coords, feats, sizes = large_batch()                         # (shared with tests/test_gpu_forward_steps.py)
     n = len(coords)
-    feats = np.random.default_rng(5).uniform(0.5, 2.0, size=(n, 1)).astype(np.float32)
     sd = syn.make_weights()
     maps = oc.build_maps(coords, 5)
     want, inter, _ = orr.resunet_forward(sd, coords, feats, maps=maps, return_intermediate=True)
@@ -75,7 +73,7 @@ def cloud():
     assert int(ovf.item()) == 0 and n_u.min() >= 1 and n_u.max() <= 1278
     assert (n_u > 639).any() and (n_u <= 639).any(), "the fixture needs two-pass and one-pass tiles: move the dense block"
     c.update(perm=perm, inv=inv, n_u=n_u)
-    starts = np.concatenate([[0], np.cumsum([len(g), len(p["coords0"]), len(p["coords1"])])])
+    starts = np.concatenate([[0], np.cumsum(sizes)])
     rng = np.random.default_rng(17)
     lists = {f"n{k}": rng.permutation(n)[:k] for k in (1, 15, 16, 17, 5000)}
     t2 = int(np.flatnonzero(n_u > 639)[0])
