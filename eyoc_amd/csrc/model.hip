@@ -956,7 +956,7 @@ void fill_conv1(eyoc_ctx* ctx, const eyoc_model* m, const eyoc_maps* maps, const
   }
   a.parent = maps->parent[0]; a.children = maps->children[0]; a.s1c = maps->nbr_s1[1]; a.nc = maps->rows[1];
   a.local1 = maps->row_perm ? maps->local_s1[1] : nullptr;          // Z-ordered maps: the level-1 tile rulebooks (256-parent tiles)
-  s.table0 = !conv1_walks_octree(a);
+  s.table0 = conv1_path(a) == Conv1Path::Probe;
 }
 
 // -> the number of steps.  Reads the plan, the maps' host fields and the ctx's knobs; launches and writes nothing

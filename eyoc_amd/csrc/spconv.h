@@ -165,7 +165,7 @@ __device__ inline int canonical_slot_id(const int* hk, const unsigned short* hpo
 
 int launch_spconv(const SpconvArgs& a, hipStream_t st);
 int launch_spconv(const SpconvArgs& a, int record_path, hipStream_t st);   // record_path: spconv_record_path(a), computed by the caller
-int launch_permute_rows(const float* in, const int32_t* perm, int n, int c, float* out, hipStream_t st);
+int launch_permute_rows(const float* in, const int32_t* perm, int n, int c, float* out, hipStream_t st);   // spconv_conv1.hip: the first layer's input copy
 int launch_spconv_st(const SpconvArgs& a, const unsigned char* local_dev, hipStream_t st);   // tile-local input stage (spconv_st.hip)
 int launch_spconv_up(const SpconvArgs& a, const unsigned char* local_dev, hipStream_t st);   // transposed 3^3 / stride 2 (spconv_up.hip)
 size_t local_rulebook_up_bytes(int n_out);
@@ -248,7 +248,7 @@ struct Conv1Args {
   const unsigned char* local1 = nullptr;
   const eyoc_ctx* ctx = nullptr;      // whose switches decide the kernel (eyoc_spconv_select_conv1_kernel); NULL: the defaults
 };
-// layout of a local rulebook record (spconv_st.hip owns it; conv1_bf_kernel in spconv.hip reads the row list and the entries)
+// layout of a local rulebook record (spconv_st.hip owns it; conv1_bf_kernel in spconv_conv1.hip reads the row list and the entries)
 constexpr int ST_TILE = 256, ST_UMAX = 639, ST_UCAP = 1280, ST_NPASS = 2, ST_LOC_OFF = 16 + ST_UCAP * 4, ST_INV_OFF = 33152, ST_LR_BYTES = 33408;
 // Instance norm as a layer of the packed plan (inorm.hip): y = [relu]((x - mean_b) / sqrt(var_b + eps) * weight + bias [+ res]) on fp32 or
 // SPLIT16 rows, in place allowed, over the level's instance plan (maps_ensure_in_plan: built for the maps' batch limit, never read back);
@@ -258,7 +258,10 @@ int in_plan_build_nosync(const int32_t* coords_dev, int n, void* plan_dev, hipSt
 size_t in_layer_workspace_bytes(int n, int c);
 int launch_in_layer(const float* x, int ld_x, int n, int c, const void* plan, const float* weight, const float* bias, float eps, int relu,
                     const float* res, int ld_res, float* y, int ld_y, bool split, unsigned int* range, void* ws, hipStream_t st);
+// spconv_conv1.hip.  Which kernel launch_conv1 runs - a pure host function of the arguments and the ctx's switches (no HIP call):
+// Probe reads a.table (it must be built), Tree walks the octree links in exact fp32, Mfma / Bf / Bfp are the split16 formulations
+enum class Conv1Path { Probe, Tree, Mfma, Bf, Bfp };
+Conv1Path conv1_path(const Conv1Args& a);
 int launch_conv1(const Conv1Args& a, hipStream_t st);
-bool conv1_walks_octree(const Conv1Args& a);   // false: launch_conv1 will probe a.table (it must be built)
 
 }  // namespace eyoc

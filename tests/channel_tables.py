@@ -1,6 +1,6 @@
 """The ResUNet channel tables the forward is checked on (tests/test_gpu_channel_tables.py, tests/test_oracle_channel_tables.py):
 class name, constructor arguments, and which kernel of the split16 forward takes which layer - worked out from the dispatch
-conditions in eyoc_amd/csrc (``resolve_schedule`` in model.hip, ``spconv_record_path`` / ``launch_conv1`` in spconv.hip,
+conditions in eyoc_amd/csrc (``resolve_schedule`` in model.hip, ``spconv_record_path`` in spconv.hip, ``conv1_path`` in spconv_conv1.hip,
 ``spconv_st_can_fuse_tail``, ``spconv_rows_supported``, ``tail_fusable``), one line per model."""
 import functools
 
