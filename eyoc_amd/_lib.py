@@ -117,6 +117,7 @@ PROTOTYPES = {
     "eyoc_last_error": (C.c_char_p, []),
     "eyoc_create": (_i, [_i, C.POINTER(_vp)]),
     "eyoc_destroy": (_i, [_vp]),
+    "eyoc_debug_scratch_fill": (C.c_longlong, [_vp, _i, _vp]),
     "eyoc_maps_workspace_bytes": (_sz, [_i]),
     "eyoc_maps_build": (_i, [_vp, _vp, _i, _vp, _sz, _vp, C.POINTER(_vp)]),
     "eyoc_maps_build_ordered": (_i, [_vp, _vp, _i, _vp, _sz, _vp, _i, C.POINTER(_vp)]),

@@ -85,4 +85,14 @@ int eyoc_destroy(eyoc_ctx* ctx) {
   return EYOC_OK;
 }
 
+long long eyoc_debug_scratch_fill(eyoc_ctx* ctx, int byte, void* stream) {
+  EYOC_REQUIRE(ctx != nullptr, EYOC_ERR_INVALID, "eyoc_debug_scratch_fill: ctx is NULL");
+  EYOC_REQUIRE(byte >= 0 && byte <= 255, EYOC_ERR_INVALID, "eyoc_debug_scratch_fill: byte %d outside [0, 255]", byte);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = ctx->ensure_scratch(0, st)) return rc;   // a consumer's hand-over, nothing grown
+  if (!ctx->scratch_bytes) return 0;
+  EYOC_CHECK_HIP(hipMemsetAsync(ctx->scratch, byte, ctx->scratch_bytes, st));
+  return (long long)ctx->scratch_bytes;
+}
+
 }  // extern "C"

@@ -165,6 +165,7 @@ static int bn_train_forward(eyoc_ctx* ctx, const float* x_dev, int n, int c, int
   EYOC_REQUIRE(ctx && x_dev && gamma_dev && beta_dev && y_dev && mean_var_dev && ws_dev, EYOC_ERR_INVALID, "eyoc_bn_train_forward: NULL argument");
   EYOC_REQUIRE(bn_shape_ok(n, c) && ld_x % 4 == 0 && ld_y % 4 == 0 && ld_x >= c && ld_y >= c, EYOC_ERR_INVALID,
                "eyoc_bn_train_forward: n %d, c %d (a divisor of 256, >= 4), leading dimensions %d / %d (multiples of 4)", n, c, ld_x, ld_y);
+  EYOC_REQUIRE(((uintptr_t)ws_dev & 255) == 0, EYOC_ERR_INVALID, "eyoc_bn_train_forward: workspace must be 256-byte aligned");
   EYOC_REQUIRE(ws_bytes >= eyoc_bn_workspace_bytes(n, c), EYOC_ERR_WORKSPACE, "eyoc_bn_train_forward: workspace %zu < %zu bytes", ws_bytes,
                eyoc_bn_workspace_bytes(n, c));
   hipStream_t st = (hipStream_t)stream;
@@ -200,6 +201,7 @@ int eyoc_bn_train_backward(eyoc_ctx* ctx, const float* x_dev, int ld_x, const fl
                "eyoc_bn_train_backward: NULL argument");
   EYOC_REQUIRE(bn_shape_ok(n, c) && ld_x >= c && ld_dy >= c && ld_dx >= c && (!y_dev || ld_y >= c), EYOC_ERR_INVALID,
                "eyoc_bn_train_backward: n %d, c %d (a divisor of 256, >= 4)", n, c);
+  EYOC_REQUIRE(((uintptr_t)ws_dev & 255) == 0, EYOC_ERR_INVALID, "eyoc_bn_train_backward: workspace must be 256-byte aligned");
   EYOC_REQUIRE(ws_bytes >= eyoc_bn_workspace_bytes(n, c), EYOC_ERR_WORKSPACE, "eyoc_bn_train_backward: workspace %zu < %zu bytes", ws_bytes,
                eyoc_bn_workspace_bytes(n, c));
   hipStream_t st = (hipStream_t)stream;

@@ -136,6 +136,7 @@ int eyoc_draw_subsets(eyoc_ctx* ctx, uint64_t seed, uint64_t call, int n_slots, 
   s.k_off[DRAW_SLOTS] = (int)total_k;
   if (total_k == 0) return EYOC_OK;
   EYOC_REQUIRE(out_idx && ws, EYOC_ERR_INVALID, "eyoc_draw_subsets: NULL output or workspace");
+  EYOC_REQUIRE(((uintptr_t)ws & 255) == 0, EYOC_ERR_INVALID, "eyoc_draw_subsets: workspace must be 256-byte aligned");
   const DrawWs w = draw_carve(ws, ws_bytes, (int)total_n);
   EYOC_REQUIRE(w.total <= ws_bytes, EYOC_ERR_WORKSPACE, "eyoc_draw_subsets: workspace %zu < %zu bytes", ws_bytes, w.total);
   hipStream_t st = (hipStream_t)stream;

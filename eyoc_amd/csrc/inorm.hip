@@ -451,6 +451,7 @@ static int in_forward_checked(const char* who, bool split, eyoc_ctx* ctx, const 
                EYOC_ERR_INVALID, "%s: leading dimensions %d / %d / %d (multiples of %d, >= c = %d)", who, ld_x, ld_y, ld_res, q, c);
   EYOC_REQUIRE(aligned16(x_dev) && aligned16(y_dev) && aligned16(residual_dev) && aligned16(stats_dev) && aligned16(weight_dev) && aligned16(bias_dev),
                EYOC_ERR_INVALID, "%s: tensors must be 16-byte aligned", who);
+  EYOC_REQUIRE(((uintptr_t)ws_dev & 255) == 0, EYOC_ERR_INVALID, "%s: workspace must be 256-byte aligned", who);
   EYOC_REQUIRE(ws_bytes >= eyoc_in_workspace_bytes(n, c, n_inst), EYOC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes,
                eyoc_in_workspace_bytes(n, c, n_inst));
   hipStream_t st = (hipStream_t)stream;
@@ -491,6 +492,7 @@ int eyoc_in_backward(eyoc_ctx* ctx, const float* x_dev, int ld_x, const float* y
   EYOC_REQUIRE(aligned16(x_dev) && aligned16(y_dev) && aligned16(dy_dev) && aligned16(dx_dev) && aligned16(dres_dev) && aligned16(stats_dev) &&
                    aligned16(weight_dev),
                EYOC_ERR_INVALID, "eyoc_in_backward: tensors must be 16-byte aligned");
+  EYOC_REQUIRE(((uintptr_t)ws_dev & 255) == 0, EYOC_ERR_INVALID, "eyoc_in_backward: workspace must be 256-byte aligned");
   EYOC_REQUIRE(ws_bytes >= eyoc_in_workspace_bytes(n, c, n_inst), EYOC_ERR_WORKSPACE, "eyoc_in_backward: workspace %zu < %zu bytes", ws_bytes,
                eyoc_in_workspace_bytes(n, c, n_inst));
   hipStream_t st = (hipStream_t)stream;

@@ -67,6 +67,11 @@ int eyoc_destroy(eyoc_ctx* ctx);
  * eyoc_ransac_transform_store) are state of the ctx they are given: every entry point reads them from ITS ctx (file-scope statics until
  * round 4).  They exist for parity tests and profiling; production code never calls them.  Each returns the previous value (-1 for a
  * NULL ctx) and only queries when the argument is out of range. */
+/* Tests only (no production path calls it): fills the whole scratch the ctx currently owns with `byte` on `stream`, ordered on the
+ * scratch exactly as a consumer is (the same hand-over between streams).  Returns the scratch size in bytes, 0 when the ctx owns
+ * none yet, a negative eyoc_status on error.  The workspace contract tests use it to show that no consumer of the ctx scratch reads
+ * what an earlier call - its own or another consumer's - left there. */
+long long eyoc_debug_scratch_fill(eyoc_ctx* ctx, int byte, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * coordinate maps + rulebooks
@@ -740,7 +745,8 @@ int eyoc_valid_metrics_batched(eyoc_ctx* ctx, const float* p0_dev, const float* 
  * and BIASED variance of x f32 [n, c] (rows ld_x floats apart) -> mean_var_dev f32 [2 c] = {mean, variance};
  * y = (x - mean) / sqrt(var + eps) * gamma + beta, then ReLU if `relu`.  c must divide 256 (32 ... 256 in this model family).
  * The statistics are summed in fp64 in a fixed order (bit-reproducible).  The running-statistics update (momentum, unbiased
- * variance) is host glue on the returned 2 c floats.  Workspace: eyoc_bn_workspace_bytes(n, c), caller-owned. */
+ * variance) is host glue on the returned 2 c floats.  Workspace: eyoc_bn_workspace_bytes(n, c), caller-owned, 256-byte aligned (a
+ * misaligned one is EYOC_ERR_INVALID, a smaller one EYOC_ERR_WORKSPACE, forward and backward alike, before any launch). */
 size_t eyoc_bn_workspace_bytes(int n, int c);
 int eyoc_bn_train_forward(eyoc_ctx* ctx, const float* x_dev, int n, int c, int ld_x, const float* gamma_dev, const float* beta_dev,
                           float eps, int relu, float* y_dev, int ld_y, float* mean_var_dev, void* workspace_dev, size_t workspace_bytes,
@@ -773,8 +779,9 @@ int eyoc_bn_train_backward(eyoc_ctx* ctx, const float* x_dev, int ld_x, const fl
  * tail of a residual block in one pass.  eyoc_in_backward: g = dy where y > 0 (y = the forward's output when a ReLU was fused, else
  * NULL); dx = weight invstd[b] (g - mean_b(g) - xhat mean_b(g xhat)); dres (or NULL) = g, the residual's gradient; dweight = sum g xhat
  * and dbias = sum g over ALL rows.  c must divide 256 (as eyoc_bn_*); every leading dimension a multiple of 4 and >= c, tensors 16-byte
- * aligned; workspace eyoc_in_workspace_bytes(n, c, n_inst), caller-owned.  Three launches forward, four backward, whatever n_inst; no
- * host synchronisation, no floating-point atomics.
+ * aligned; workspace eyoc_in_workspace_bytes(n, c, n_inst), caller-owned, 256-byte aligned (a misaligned one is EYOC_ERR_INVALID, a
+ * smaller one EYOC_ERR_WORKSPACE, before any launch).  Three launches forward, four backward, whatever n_inst; no host synchronisation,
+ * no floating-point atomics.
  *
  * Batch invariance: sums are fp64 about the instance's first row (plan order), over chunks of eyoc_in_chunk_rows() rows of the
  * instance, added in an order that depends on the instance's row count alone.  The bytes of an instance's stats, y and dx rows do not
@@ -1430,7 +1437,8 @@ int eyoc_closs_backward(eyoc_ctx* ctx, const float* F0_dev, int n0, const float*
  *   EYOC_ERR_INVALID before any launch, nothing written.  A slot with k == 0 or n == 0 is legal, puts no keys into the sort and writes
  *   nothing; a call whose slots are all empty launches nothing (out_idx and the workspace may be NULL then).
  * Workspace: eyoc_draw_workspace_bytes(total_n), total_n = the sum of n[s] over the slots with k[s] > 0 (0 for total_n <= 0); caller-owned,
- * 256-byte aligned, needed until the call's kernels have run; a smaller one is EYOC_ERR_WORKSPACE before any launch.
+ * 256-byte aligned, needed until the call's kernels have run; a smaller one is EYOC_ERR_WORKSPACE, a misaligned one EYOC_ERR_INVALID,
+ * both before any launch.
  * Launches: one that writes keys, the rocPRIM sort (which chooses its passes by the length), one that writes out_idx.
  *
  * eyoc_draw_pairs: floor(rand(N, 2) * [n0, n1]) as a distribution (lib/trainer.py:212-218): out int64 [n_rows][2], row-major, in one

@@ -56,10 +56,11 @@ def all_plus_zero(a):
     return not a.view(np.uint32).any()
 
 
-def check_stages(golden_dir, name, what=None):
-    """The device's results on a named input set against its restatement; returns the realised (value, distance, gradient) errors."""
+def check_stages(golden_dir, name, what=None, dev=None):
+    """The device's results on a named input set against its restatement; returns the realised (value, distance, gradient) errors.
+    ``dev``: the results of a ``run`` of that set made by the caller (default: run it here)."""
     args = cc.input_sets(golden_dir)[name]
-    dev, r = run(args), cc.restated(golden_dir, name)
+    dev, r = run(args) if dev is None else dev, cc.restated(golden_dir, name)
     F0, F1, pairs, neg = args
     n_pairs, n_neg = len(pairs), len(neg)
     rec = dev["record"]

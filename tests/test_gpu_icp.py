@@ -93,17 +93,13 @@ def test_one_evaluation_row_for_row(seed, kind, gate):
 
 # ---- 2. whole runs
 
-@pytest.mark.parametrize("seed,kind,gate", CASES + [(3, "samples", 0.6)])
-def test_whole_run_matches_the_restatement(seed, kind, gate):
+def check_whole_run(got, want, src, tgt, gate, what=""):
+    """A decoded device run (with its correspondence set) against the restated run of the same inputs, under the module's bounds."""
     from eyoc_amd import icp
-    src, tgt, T0 = _case(seed, kind)
-    want = _restated(seed, kind, gate)
-    res, corr = icp.icp_batched(src, tgt, [0, len(src)], [0, len(tgt)], gate, T0[None], 30, return_correspondences=True)
-    got = icp.decode_icp_result(res[0], corr)
     # best d2 of every row up to just beyond the gate (a wider gate keeps the rows right above it too)
     near_gate = int((np.abs(R.evaluate(src, tgt, want.T, np.sqrt(gate * gate + 2 * GATE_BAND)).d2 - gate * gate) < GATE_BAND).sum())
     dT = np.abs(got.transformation - want.T).max()
-    print(f"seed {seed} {kind} gate {gate}: iterations {got.iterations} / {want.iterations}, status {got.status} / {want.status}, max |dT| "
+    print(f"{what}: iterations {got.iterations} / {want.iterations}, status {got.status} / {want.status}, max |dT| "
           f"{dT:.3e}, d rmse {abs(got.inlier_rmse - want.inlier_rmse):.3e}, correspondences {got.inliers} / {want.correspondences} "
           f"({near_gate} rows within {GATE_BAND} m^2 of the gate)")
     assert got.iterations == want.iterations
@@ -115,6 +111,16 @@ def test_whole_run_matches_the_restatement(seed, kind, gate):
     assert got.correspondence_set.shape == (got.inliers, 2)
     if near_gate == 0:
         np.testing.assert_array_equal(got.correspondence_set[:, 0], np.flatnonzero(want.last.corr >= 0))
+
+
+@pytest.mark.parametrize("seed,kind,gate", CASES + [(3, "samples", 0.6)])
+def test_whole_run_matches_the_restatement(seed, kind, gate):
+    from eyoc_amd import icp
+    src, tgt, T0 = _case(seed, kind)
+    want = _restated(seed, kind, gate)
+    res, corr = icp.icp_batched(src, tgt, [0, len(src)], [0, len(tgt)], gate, T0[None], 30, return_correspondences=True)
+    got = icp.decode_icp_result(res[0], corr)
+    check_whole_run(got, want, src, tgt, gate, f"seed {seed} {kind} gate {gate}")
     if (seed, kind, gate) == (3, "samples", 0.6):
         assert want.status & R.CONVERGED and want.iterations < 30        # the case the issue names: it stops early
 

@@ -172,17 +172,11 @@ def within_one_ulp(got, want64):
     return np.abs(got.astype(np.float64) - w.astype(np.float64)) <= np.spacing(np.abs(w)).astype(np.float64)
 
 
-def in_check(sizes, order, c, relu, with_res, pad, constant_column, seed):
-    """One forward + backward against the restatement under the bars of the module docstring; returns the worst err / bound."""
-    rng = np.random.default_rng([c, int(relu), int(with_res), seed, len(sizes)])
-    n_inst = len(sizes)
-    ids = make_ids(sizes, order, rng)
-    n = len(ids)
-    x, w, b, dy, res = in_input(rng, n, c, constant_column)
-    if not with_res:
-        res = None
-    plan, hdr, seg, perm = build_plan(ids, n_inst)
-    y, stats, yd = forward_gpu(x, plan, n_inst, w, b, relu, res, pad)
+def in_compare(x, w, b, dy, res, ids, sizes, relu, constant_column, y, stats, dx, dres, dweight, dbias, what=""):
+    """The results of one forward (``stats [n_inst, 2, c]``) and one backward against the restatement under the bars of the module
+    docstring; ``res``: the residual or None (``dres`` is then not looked at).  Returns the worst err / bound."""
+    n_inst, n, c = len(sizes), len(ids), x.shape[1]
+    with_res = res is not None
     y64, mean, var = IR.in_forward(x, ids, n_inst, w, b, EPS, False, res)
     w64, b64 = w.astype(np.float64), b.astype(np.float64)
     present = np.array(sizes) > 0
@@ -199,7 +193,7 @@ def in_check(sizes, order, c, relu, with_res, pad, constant_column, seed):
         bound = bound + U * np.abs(y64)
     err = np.abs(y - (np.maximum(y64, 0.0) if relu else y64))
     r_y = float((err / bound).max())
-    assert np.isfinite(y).all() and (err <= bound).all(), ("y", sizes, order, c, relu, with_res, r_y)
+    assert np.isfinite(y).all() and (err <= bound).all(), ("y", sizes, what, c, relu, with_res, r_y)
     for i in np.flatnonzero(np.array(sizes) == 1):                      # one row: y = bias (+ residual), exactly
         rows = ids == i
         want = b[None, :] + (res[rows] if with_res else 0.0)
@@ -207,10 +201,6 @@ def in_check(sizes, order, c, relu, with_res, pad, constant_column, seed):
     if relu:
         flipped = (y > 0) != (y64 > 0)
         assert (np.abs(y64[flipped]) <= bound[flipped]).all()
-    y2, stats2, _ = forward_gpu(x, plan, n_inst, w, b, relu, res, pad)
-    assert y.tobytes() == y2.tobytes() and stats.tobytes() == stats2.tobytes()
-
-    dx, dres, dweight, dbias = backward_gpu(x, yd if relu else None, dy, plan, n_inst, w, stats, pad, with_res)
     dx64, g, dw64, db64 = IR.in_backward(x, y if relu else None, dy, ids, n_inst, w, mean, var, EPS)
     if with_res:
         np.testing.assert_array_equal(dres, g.astype(np.float32))
@@ -232,13 +222,29 @@ def in_check(sizes, order, c, relu, with_res, pad, constant_column, seed):
     ratios = {}
     for name, got, want, E in (("dbias", dbias, db64, E_b), ("dweight", dweight, dw64, E_g), ("dx", dx, dx64, E_dx)):
         e = np.abs(got - want)
-        assert np.isfinite(got).all() and (e <= E).all(), (name, sizes, order, c, relu, with_res, float(np.max(e / np.maximum(E, 1e-300))))
+        assert np.isfinite(got).all() and (e <= E).all(), (name, sizes, what, c, relu, with_res, float(np.max(e / np.maximum(E, 1e-300))))
         ratios[name] = float(np.max(np.divide(e, E, out=np.zeros_like(e), where=E > 0), initial=0.0))
-    dx2, dres2, dweight2, dbias2 = backward_gpu(x, yd if relu else None, dy, plan, n_inst, w, stats, pad, with_res)
-    assert dx.tobytes() == dx2.tobytes() and dweight.tobytes() == dweight2.tobytes() and dbias.tobytes() == dbias2.tobytes()
-    print(f"in sizes={sizes} {order} c={c} relu={int(relu)} res={int(with_res)} pad={pad}: max err / bound  y {r_y:.3g}  "
+    print(f"in sizes={sizes} {what} c={c} relu={int(relu)} res={int(with_res)}: max err / bound  y {r_y:.3g}  "
           f"dbias {ratios['dbias']:.3g}  dweight {ratios['dweight']:.3g}  dx {ratios['dx']:.3g}")
     return max(r_y, *ratios.values())
+
+
+def in_check(sizes, order, c, relu, with_res, pad, constant_column, seed):
+    """One forward + backward through the raw entry points, each twice (the same bits), under ``in_compare``."""
+    rng = np.random.default_rng([c, int(relu), int(with_res), seed, len(sizes)])
+    n_inst = len(sizes)
+    ids = make_ids(sizes, order, rng)
+    x, w, b, dy, res = in_input(rng, len(ids), c, constant_column)
+    if not with_res:
+        res = None
+    plan, hdr, seg, perm = build_plan(ids, n_inst)
+    y, stats, yd = forward_gpu(x, plan, n_inst, w, b, relu, res, pad)
+    y2, stats2, _ = forward_gpu(x, plan, n_inst, w, b, relu, res, pad)
+    assert y.tobytes() == y2.tobytes() and stats.tobytes() == stats2.tobytes()
+    dx, dres, dweight, dbias = backward_gpu(x, yd if relu else None, dy, plan, n_inst, w, stats, pad, with_res)
+    dx2, dres2, dweight2, dbias2 = backward_gpu(x, yd if relu else None, dy, plan, n_inst, w, stats, pad, with_res)
+    assert dx.tobytes() == dx2.tobytes() and dweight.tobytes() == dweight2.tobytes() and dbias.tobytes() == dbias2.tobytes()
+    return in_compare(x, w, b, dy, res, ids, sizes, relu, constant_column, y, stats, dx, dres, dweight, dbias, what=f"{order} pad={pad}")
 
 
 def batches():

@@ -119,6 +119,21 @@ def test_normals_row_for_row(name):
 
 # ---- 2. whole runs
 
+def check_whole_run(got, want, src, tgt, gate, what=""):
+    """A decoded device run (with its correspondence set) against the restated run of the same inputs, under the module's bounds."""
+    near_gate = int((np.abs(R.evaluate(src, tgt, want.T, np.sqrt(gate * gate + 2 * GATE_BAND)).d2 - gate * gate) < GATE_BAND).sum())
+    dT = np.abs(got.transformation - want.T).max()
+    print(f"{what}: iterations {got.iterations} / {want.iterations}, status {got.status} / {want.status}, max |dT| {dT:.3e}, d rmse "
+          f"{abs(got.inlier_rmse - want.inlier_rmse):.3e}, correspondences {got.inliers} / {want.correspondences} ({near_gate} rows within "
+          f"{GATE_BAND} m^2 of the gate)")
+    assert got.iterations == want.iterations
+    assert got.status == want.status
+    assert dT < 1e-4
+    assert abs(got.inlier_rmse - want.inlier_rmse) < 1e-4
+    assert abs(got.inliers - want.correspondences) <= near_gate
+    assert got.correspondence_set.shape == (got.inliers, 2)
+
+
 @pytest.mark.parametrize("seed", [0, 1, 2, 3])
 def test_whole_run_matches_the_restatement(seed):
     from eyoc_amd import icp
@@ -127,17 +142,7 @@ def test_whole_run_matches_the_restatement(seed):
     assert closest > 1e-9, "this case's iteration count hangs on rounding: use another seed"
     res, corr = icp.icp_plane_batched(src, tgt, _normals32(seed), [0, len(src)], [0, len(tgt)], GATE, T0[None], 30, return_correspondences=True)
     got = icp.decode_icp_result(res[0], corr)
-    near_gate = int((np.abs(R.evaluate(src, tgt, want.T, np.sqrt(GATE * GATE + 2 * GATE_BAND)).d2 - GATE * GATE) < GATE_BAND).sum())
-    dT = np.abs(got.transformation - want.T).max()
-    print(f"seed {seed}: iterations {got.iterations} / {want.iterations}, status {got.status} / {want.status}, max |dT| {dT:.3e}, d rmse "
-          f"{abs(got.inlier_rmse - want.inlier_rmse):.3e}, correspondences {got.inliers} / {want.correspondences} ({near_gate} rows within "
-          f"{GATE_BAND} m^2 of the gate), closest approach to a threshold {closest:.3e}")
-    assert got.iterations == want.iterations
-    assert got.status == want.status
-    assert dT < 1e-4
-    assert abs(got.inlier_rmse - want.inlier_rmse) < 1e-4
-    assert abs(got.inliers - want.correspondences) <= near_gate
-    assert got.correspondence_set.shape == (got.inliers, 2)
+    check_whole_run(got, want, src, tgt, GATE, f"seed {seed} (closest approach to a threshold {closest:.3e})")
 
 
 # ---- 3. kernel-shape edges: byte-identical from run to run and to the pair / cloud alone

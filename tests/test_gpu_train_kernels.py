@@ -365,8 +365,9 @@ def within_one_ulp(got, want64):
     return np.abs(got.astype(np.float64) - w.astype(np.float64)) <= np.spacing(np.abs(w)).astype(np.float64)
 
 
-def bn_check(n, c, relu, pad, constant_column, seed):
-    """One forward (with running statistics) + backward against the restatement.  Bars, u = 2^-24, all quantities on the right from the
+def bn_compare(x, gamma, beta, dy, relu, constant_column, y, stats, dx, dgamma, dbeta, run0=None, run=None, what=""):
+    """The results of one forward (``run0`` / ``run``: the running statistics before and after it, or None for the plain entry point) and one
+    backward against the restatement; ``what``: a label for messages.  Returns the worst err / bound.  Bars, u = 2^-24, all quantities on the right from the
     float64 restatement (invstd = 1 / sqrt(var + eps), xhat = (x - mean) invstd):
 
     forward   |y - y64| <= 8u (|xhat gamma| + |beta|) + 2u |mean| invstd |gamma|: the seven fp32 roundings of k_bn_apply (x - mean, var + eps,
@@ -381,10 +382,7 @@ def bn_check(n, c, relu, pad, constant_column, seed):
               E_B = E_b / n + 2u |dbeta| / n + (e_xhat |dgamma| + |xhat| E_g) / n + 3u |xhat dgamma| / n + u (|g| + |dbeta| / n) + u |B|
               E_dx = |gamma| invstd E_B + 6u |dx|        (gamma invstd: 4u + u, the last product u)
     The backward restatement is given the GPU's own y for the ReLU mask (the forward's decisions are checked above)."""
-    rng = np.random.default_rng([n, c, int(relu), seed])
-    x, gamma, beta, dy = bn_input(rng, n, c, constant_column)
-    run0 = (rng.normal(size=c).astype(np.float32), rng.uniform(0.5, 1.5, c).astype(np.float32))
-    y, stats, run, yd = bn_forward_gpu(x, gamma, beta, relu, pad, running=run0)
+    n, c = x.shape
     y64, mean, var = R.bn_forward(x, gamma, beta, EPS, False)
     g64, b64 = gamma.astype(np.float64), beta.astype(np.float64)
     invstd = 1.0 / np.sqrt(var + EPS)
@@ -402,15 +400,11 @@ def bn_check(n, c, relu, pad, constant_column, seed):
     if relu:
         flipped = (y > 0) != (y64 > 0)
         assert (np.abs(y64[flipped]) <= bound[flipped]).all() and int(flipped.sum()) <= int((np.abs(y64) <= bound).sum())
-    # running statistics: (1 - m) (u), the two products (u each), the sum (u), the statistic itself (2u), the unbiasing factor (2u)
-    want_rm, want_rv = R.bn_running(run0[0], run0[1], mean, var, n, MOMENTUM)
-    for got, want, old, stat in ((run[0], want_rm, run0[0], mean), (run[1], want_rv, run0[1], var * (n / max(n - 1, 1)))):
-        assert (np.abs(got - want) <= 8 * U * ((1 - MOMENTUM) * np.abs(old) + MOMENTUM * np.abs(stat))).all(), ("running", n, c)
-    # the plain entry point and a second call: the same bits
-    y2, stats2, _, _ = bn_forward_gpu(x, gamma, beta, relu, pad)
-    assert y.tobytes() == y2.tobytes() and stats.tobytes() == stats2.tobytes()
-
-    dx, dgamma, dbeta = bn_backward_gpu(x, yd if relu else None, dy, gamma, stats, pad)
+    if run is not None:
+        # running statistics: (1 - m) (u), the two products (u each), the sum (u), the statistic itself (2u), the unbiasing factor (2u)
+        want_rm, want_rv = R.bn_running(run0[0], run0[1], mean, var, n, MOMENTUM)
+        for got, want, old, stat in ((run[0], want_rm, run0[0], mean), (run[1], want_rv, run0[1], var * (n / max(n - 1, 1)))):
+            assert (np.abs(got - want) <= 8 * U * ((1 - MOMENTUM) * np.abs(old) + MOMENTUM * np.abs(stat))).all(), ("running", n, c)
     dx64, dg64, db64 = R.bn_backward(x, y if relu else None, dy, gamma, mean, var, EPS)
     g = np.where(y > 0, dy, 0.0).astype(np.float64) if relu else dy.astype(np.float64)
     e_xhat = 6 * U * np.abs(xhat) + 2 * U * np.abs(mean) * invstd
@@ -425,10 +419,23 @@ def bn_check(n, c, relu, pad, constant_column, seed):
         e = np.abs(got - want)
         assert np.isfinite(got).all() and (e <= E).all(), (name, n, c, relu, float(np.max(e / np.maximum(E, 1e-300))))
         ratios[name] = float(np.max(np.divide(e, E, out=np.zeros_like(e), where=E > 0), initial=0.0))
+    print(f"bn n={n} c={c} relu={int(relu)} {what}: max err / bound  y {r_y:.3g}  dbeta {ratios['dbeta']:.3g}  dgamma {ratios['dgamma']:.3g}  dx {ratios['dx']:.3g}")
+    return max(r_y, *ratios.values())
+
+
+def bn_check(n, c, relu, pad, constant_column, seed):
+    """One forward (with running statistics) + backward through the raw entry points, each twice (the same bits), under ``bn_compare``."""
+    rng = np.random.default_rng([n, c, int(relu), seed])
+    x, gamma, beta, dy = bn_input(rng, n, c, constant_column)
+    run0 = (rng.normal(size=c).astype(np.float32), rng.uniform(0.5, 1.5, c).astype(np.float32))
+    y, stats, run, yd = bn_forward_gpu(x, gamma, beta, relu, pad, running=run0)
+    # the plain entry point and a second call: the same bits
+    y2, stats2, _, _ = bn_forward_gpu(x, gamma, beta, relu, pad)
+    assert y.tobytes() == y2.tobytes() and stats.tobytes() == stats2.tobytes()
+    dx, dgamma, dbeta = bn_backward_gpu(x, yd if relu else None, dy, gamma, stats, pad)
     dx2, dgamma2, dbeta2 = bn_backward_gpu(x, yd if relu else None, dy, gamma, stats, pad)
     assert dx.tobytes() == dx2.tobytes() and dgamma.tobytes() == dgamma2.tobytes() and dbeta.tobytes() == dbeta2.tobytes()
-    print(f"bn n={n} c={c} relu={int(relu)} pad={pad}: max err / bound  y {r_y:.3g}  dbeta {ratios['dbeta']:.3g}  dgamma {ratios['dgamma']:.3g}  dx {ratios['dx']:.3g}")
-    return max(r_y, *ratios.values())
+    return bn_compare(x, gamma, beta, dy, relu, constant_column, y, stats, dx, dgamma, dbeta, run0, run, what=f"pad={pad}")
 
 
 def _constant_columns(c):
