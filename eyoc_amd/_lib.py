@@ -256,6 +256,9 @@ PROTOTYPES = {
                                     C.POINTER(RansacParams), _vp, _vp, _sz, _vp]),
     "eyoc_ransac_batched": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
                                  C.POINTER(RansacParams), _vp, _vp]),
+    "eyoc_ransac_converging_workspace_bytes": (_sz, [_vp, _i, _i, _i, C.c_int32, _sz]),
+    "eyoc_ransac_converging_batched_ws": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
+                                               C.POINTER(RansacParams), C.c_float, C.c_int32, _vp, _vp, _vp, _sz, _vp]),
     "eyoc_sc2pcr_workspace_bytes": (_sz, [_i, C.POINTER(Sc2pcrParams)]),
     "eyoc_sc2pcr": (_i, [_vp, _vp, _vp, _i, C.POINTER(Sc2pcrParams), _vp, _vp, _vp, _sz, _vp]),
     "eyoc_sc2pcr_batched_workspace_bytes": (_sz, [_i, C.POINTER(Sc2pcrParams)]),

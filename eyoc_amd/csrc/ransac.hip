@@ -58,6 +58,30 @@ struct PairArgs {          // a chunk of pairs; segment bounds travel as kernel 
   int count_bound;         // k_count: survivors that cannot reach the pair's best count any more stop counting (eyoc_ransac_select_pruning 2)
 };
 
+// ---- rounds (eyoc_ransac_converging_batched_ws).  The sampler is a counter hash of base + 2 h (+ 1): hypotheses [h_lo, h_hi) of a pair are
+// hypotheses [0, h_hi - h_lo) under base + 2 h_lo.  A round therefore is the whole pipeline below on PairArgs with H = h_hi - h_lo - the
+// survivor lists hold h - h_lo, which orders like h.  Every phase kernel ends in a parameter pack `rd...`: empty in the one-pass call (the
+// instantiation has the signature and the code it always had), a Round in a round, which adds the shift and returns at once for a pair
+// that is finished.
+struct PairState {             // what a pair carries from round to round; NOT in the counter block, which every round clears
+  unsigned long long key;      // best record so far: (inliers << 32) | ~bits(rmse), as in k_select
+  int h;                       // its hypothesis (0x7FFFFFFF: none yet)
+  int survivors;               // survivors of all rounds so far
+  int done;                    // written by Decide::merge, read by the next round's kernels (same stream: the kernel boundary orders them)
+  int pad[3];
+};
+struct Round {
+  unsigned long long shift2;   // 2 h_lo
+  const PairState* st;         // [chunk]
+  __device__ unsigned long long shift() const { return shift2; }
+  __device__ bool finished(int c) const { return st[c].done != 0; }
+};
+// what a kernel does with its trailing `rd...`: nothing for the empty pack of the one-pass call (both fold away)
+template <class... RD>
+__device__ __forceinline__ unsigned long long round_shift(const RD&... rd) { return (0ull + ... + rd.shift()); }
+template <class... RD>
+__device__ __forceinline__ bool round_finished(int c, const RD&... rd) { return (false || ... || rd.finished(c)); }
+
 __global__ void k_gather_targets(const float* __restrict__ src, const float* __restrict__ tgt,
                                  const long long* __restrict__ corr, PairArgs a) {
   const int c = blockIdx.y;
@@ -272,9 +296,9 @@ struct CompactRecords {        // two planes in LDS: (x, y | z, qx) as 8 bytes a
 };
 
 template <class Records>
-__device__ __forceinline__ void generate_loop(const PairArgs& a, int c, const Records recs, int (*queue)[128], int (*queue1)[128]) {
+__device__ __forceinline__ void generate_loop(const PairArgs& a, const unsigned long long shift, int c, const Records recs, int (*queue)[128], int (*queue1)[128]) {
   const int b = a.pair0 + c, n = a.n[c];
-  const unsigned long long base = pair_base(a.seed, b);
+  const unsigned long long base = pair_base(a.seed, b) + shift;
   int* ncand = a.n_surv + c * CNT_STRIDE + 2;              // the pair's candidate counter ([0] survivors, [1] largest count)
   int* cand = a.cnts + (size_t)c * a.H;                    // candidates wait in the pair's count array (k_count writes it after k_fit)
   const int lane = threadIdx.x & 63;
@@ -325,11 +349,12 @@ __device__ __forceinline__ void generate_loop(const PairArgs& a, int c, const Re
 }
 
 // the exact form (eyoc_ransac_select_generate 0, and launches with a pair larger than LDS_RECORDS_Q)
-template <bool IN_LDS>
-__global__ __launch_bounds__(GEN_THREADS) void k_generate(PairArgs a) {
+template <bool IN_LDS, class... RD>
+__global__ __launch_bounds__(GEN_THREADS) void k_generate(PairArgs a, RD... rd) {
   extern __shared__ __attribute__((aligned(16))) float lrec[];
   __shared__ int queue[GEN_THREADS / 64][128], queue1[GEN_THREADS / 64][128];
   const int c = blockIdx.y;
+  if (round_finished(c, rd...)) return;
   const int s0 = a.s0[c], n = a.n[c];
   const float* rec = a.rec + (size_t)s0 * 6;
   if (IN_LDS) {
@@ -338,14 +363,16 @@ __global__ __launch_bounds__(GEN_THREADS) void k_generate(PairArgs a) {
     __syncthreads();
     rec = lrec;
   }
-  generate_loop(a, c, ExactRecords{rec, (double)a.edge_sim}, queue, queue1);
+  generate_loop(a, round_shift(rd...), c, ExactRecords{rec, (double)a.edge_sim}, queue, queue1);
 }
 
 // the compact form: 12 bytes per record, 76 KB of LDS at 5000 records with the queues, at most 64 registers - two workgroups per CU
-__global__ __launch_bounds__(GEN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_generate_q(PairArgs a) {
+template <class... RD>
+__global__ __launch_bounds__(GEN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_generate_q(PairArgs a, RD... rd) {
   extern __shared__ __attribute__((aligned(16))) float lrec[];
   __shared__ int queue[GEN_THREADS / 64][128], queue1[GEN_THREADS / 64][128];
   const int c = blockIdx.y;
+  if (round_finished(c, rd...)) return;
   const int s0 = a.s0[c], n = a.n[c];
   float inv_step;
   if (!pair_is_compact(a, c, inv_step)) {                                // workgroup-uniform: no usable scale - k_fit walks ALL hypotheses of this pair
@@ -367,17 +394,19 @@ __global__ __launch_bounds__(GEN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
   const double e2 = (double)a.edge_sim * (double)a.edge_sim;
   const float c_up = __double2float_ru((1.0 + 0x1p-8) * (1.0 + 0x1p-20));
   const float c_dn = __double2float_rd(e2 * (1.0 - 0x1p-8) * (1.0 - 0x1p-20));
-  generate_loop(a, c, CompactRecords{xyzq, qyz, c_up, c_dn}, queue, queue1);
+  generate_loop(a, round_shift(rd...), c, CompactRecords{xyzq, qyz, c_up, c_dn}, queue, queue1);
 }
 
 // 4-point fit + distance checker of the queued candidates: one lane per candidate, 256-thread workgroups (the whole register
 // file: no scratch), records from global memory (a pair's 120 KB stay in L2).  Survivors append their hypothesis number and
 // transform exactly as the fused kernel did; which slot a survivor gets depends on atomics, the results do not.
-__global__ __launch_bounds__(256) void k_fit(PairArgs a) {
+template <class... RD>
+__global__ __launch_bounds__(256) void k_fit(PairArgs a, RD... rd) {
   const int c = blockIdx.y;
+  if (round_finished(c, rd...)) return;
   const float* __restrict__ rec = a.rec + (size_t)a.s0[c] * 6;
   const int n = a.n[c];
-  const unsigned long long base = pair_base(a.seed, a.pair0 + c);
+  const unsigned long long base = pair_base(a.seed, a.pair0 + c) + round_shift(rd...);
   int* cnt = a.n_surv + c * CNT_STRIDE;
   const bool all = cnt[2] < 0;                              // k_generate_q made no list for this pair (no usable scale): every hypothesis is a candidate
   const int ncand = all ? a.H : cnt[2];
@@ -418,9 +447,12 @@ __device__ inline double thr2_of(float max_dist) { return (double)max_dist * (do
 // skipped work depends on it.
 constexpr int NBUCKET = 64;
 
-__global__ __launch_bounds__(256) void k_bucket(PairArgs a) {
+// (`rd`: nothing in the one-pass call, the Round in a round - see k_count)
+template <class... RD>
+__global__ __launch_bounds__(256) void k_bucket(PairArgs a, RD... rd) {
   __shared__ int hist[NBUCKET], start[NBUCKET];
   __shared__ double red[4];
+  if (round_finished(blockIdx.x, rd...)) return;
   const int c = blockIdx.x;
   const int s0 = a.s0[c], n = a.n[c];
   const float* __restrict__ rec = a.rec + (size_t)s0 * 6;
@@ -499,7 +531,9 @@ __global__ __launch_bounds__(256) void k_bucket(PairArgs a) {
 // the blocks past its prefix (reference pruning above).
 constexpr int PPL = 4;
 
-__global__ __launch_bounds__(256) void k_count_fp64(PairArgs a, const double* __restrict__ xf_all, int pruned) {
+template <class... RD>
+__global__ __launch_bounds__(256) void k_count_fp64(PairArgs a, const double* __restrict__ xf_all, int pruned, RD... rd) {
+  if (round_finished(blockIdx.y, rd...)) return;
   const int c = blockIdx.y;
   const int s0 = a.s0[c], n = a.n[c];
   const float* __restrict__ rec = (pruned ? a.rec_sorted : a.rec) + (size_t)s0 * 6;
@@ -615,8 +649,13 @@ __device__ inline bool inlier_fp64(const float* __restrict__ rec, int i, const d
 }
 
 // five waves per SIMD (96 VGPRs; the spills this costs are in the block prologue and the fp64 recount, not in the sweep): 1.92 -> 1.72 ms
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_count(PairArgs a, const double* __restrict__ xf_all) {
+// (`rd`: nothing in the one-pass call - the kernel is then what it was without the parameter -, the Round in a round, whose finished
+// pairs return here.  A round starts the pair's largest count at the count of its best record so far, k_round_begin: the bound's test
+// is strict, so a survivor that ties with it is still counted in full)
+template <class... RD>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_count(PairArgs a, const double* __restrict__ xf_all, RD... rd) {
   __shared__ float4 deltas[4][64][3];    // per wave: fp32( T_s - T_ref ) of its group's survivors - dR row-major, dt
+  if (round_finished(blockIdx.y, rd...)) return;
   const int c = blockIdx.y;
   const int s0 = a.s0[c], n = a.n[c];
   const float* __restrict__ rec = a.rec_sorted + (size_t)s0 * 6;
@@ -817,11 +856,13 @@ __device__ inline void sweep(const float* __restrict__ rec, int n, const double 
 }
 
 // survivors beyond the transform store (more than cap_t per pair): one wave per survivor re-derives the transform
-__global__ __launch_bounds__(256) void k_count_overflow(PairArgs a) {
+template <class... RD>
+__global__ __launch_bounds__(256) void k_count_overflow(PairArgs a, RD... rd) {
   const int c = blockIdx.y, b = a.pair0 + c;
+  if (round_finished(c, rd...)) return;
   const int s0 = a.s0[c], n = a.n[c];
   const float* rec = a.rec + (size_t)s0 * 6;
-  const unsigned long long base = pair_base(a.seed, b);
+  const unsigned long long base = pair_base(a.seed, b) + round_shift(rd...);
   const int lane = threadIdx.x & 63;
   const int ns = a.n_surv[c * CNT_STRIDE];
   const int* surv = a.surv + (size_t)c * a.H;
@@ -841,11 +882,13 @@ __global__ __launch_bounds__(256) void k_count_overflow(PairArgs a) {
 }
 
 // inlier RMSE (fp32 bits) of the survivors that reach the largest count
-__global__ __launch_bounds__(256) void k_rmse(PairArgs a) {
+template <class... RD>
+__global__ __launch_bounds__(256) void k_rmse(PairArgs a, RD... rd) {
   const int c = blockIdx.y, b = a.pair0 + c;
+  if (round_finished(c, rd...)) return;
   const int s0 = a.s0[c], n = a.n[c];
   const float* rec = a.rec + (size_t)s0 * 6;
-  const unsigned long long base = pair_base(a.seed, b);
+  const unsigned long long base = pair_base(a.seed, b) + round_shift(rd...);
   const int lane = threadIdx.x & 63;
   const int ns = a.n_surv[c * CNT_STRIDE], best = a.n_surv[c * CNT_STRIDE + 1];
   const int* surv = a.surv + (size_t)c * a.H;
@@ -873,14 +916,76 @@ __global__ __launch_bounds__(256) void k_rmse(PairArgs a) {
   }
 }
 
+// ---- the round driver's own pieces.
+// start of a round: the pair's counters (survivors, candidates) are cleared, the largest count starts at the count of the pair's best
+// record so far (word [3], the pair's magnitude from k_gather_targets, stays); the first round of a chunk also resets the carried state
+__global__ void k_round_begin(PairArgs a, PairState* __restrict__ st, int nc, int first) {
+  const int c = threadIdx.x;
+  if (c >= nc) return;
+  if (first) {
+    PairState s;
+    s.key = 0; s.h = 0x7FFFFFFF; s.survivors = 0; s.done = 0; s.pad[0] = s.pad[1] = s.pad[2] = 0;
+    st[c] = s;
+  }
+  int* cnt = a.n_surv + c * CNT_STRIDE;
+  cnt[0] = 0;
+  cnt[1] = first || st[c].done ? 0 : (int)(st[c].key >> 32);
+  cnt[2] = 0;
+}
+
+// end of a round whose hypotheses are [h_lo, E) (k_select with this as `rd`): the round's best record is merged into the pair's (a later
+// round's hypotheses are all higher, so the carried record wins a tie on the key), the convergence criterion is evaluated in fp64 on the
+// best record over all h < E, and a pair that is finished - criterion met, or E = max_iteration (`last`) - gets its iterations and,
+// from k_select's own code, its result record
+struct Decide {
+  PairState* st;               // [chunk]
+  int h_lo, E, last;
+  float confidence;
+  int32_t* iterations;         // [n_pairs]
+  __device__ bool finished(int c) const { return st[c].done != 0; }
+  // one thread: (ns, key, h) arrive as the round's survivors and best (h inside the round) and leave as the pair's over all h < E;
+  // -> whether the pair is finished now
+  __device__ bool merge(int c, int b, int n, int& ns, unsigned long long& key, int& h) const {
+    PairState* ps = st + c;
+    unsigned long long ck = ps->key;
+    int ch = ps->h;
+    if (ns > 0 && h != 0x7FFFFFFF) {
+      const int gh = h_lo + h;
+      if (key > ck || (key == ck && gh < ch)) { ck = key; ch = gh; }
+    }
+    ns += ps->survivors;
+    key = ck;
+    h = ch;
+    bool fin = last != 0;
+    const int inliers = (int)(ck >> 32);
+    if (!fin && confidence < 1.0f && ch != 0x7FFFFFFF && inliers > 0) {
+      const double f = (double)inliers / (double)n;
+      const double q = (f * f) * (f * f);
+      fin = q >= 1.0 || (double)E >= log(1.0 - (double)confidence) / log(1.0 - q);
+    }
+    ps->key = ck; ps->h = ch; ps->survivors = ns;
+    if (fin) {
+      ps->done = 1;
+      iterations[b] = E;
+    }
+    return fin;
+  }
+};
+template <class T>
+__device__ __forceinline__ const T& only(const T& t) { return t; }
+
 // key: (inliers << 32) | ~bits(rmse_f32): larger is better; ties on the key are broken by lower h
-__global__ __launch_bounds__(1024) void k_select(PairArgs a, eyoc_ransac_result* __restrict__ results) {
+// (`rd`: nothing in the one-pass call, a Decide at the end of a round)
+template <class... RD>
+__global__ __launch_bounds__(1024) void k_select(PairArgs a, eyoc_ransac_result* __restrict__ results, RD... rd) {
   __shared__ unsigned long long bk[16];
   __shared__ int bh[16];
   const int c = blockIdx.x, b = a.pair0 + c;
+  if (round_finished(c, rd...)) return;                                // workgroup-uniform
   const int s0 = a.s0[c], n = a.n[c];
   const float* rec = a.rec + (size_t)s0 * 6;
-  const int ns = a.n_surv[c * CNT_STRIDE], best = a.n_surv[c * CNT_STRIDE + 1];
+  int ns = a.n_surv[c * CNT_STRIDE];
+  const int best = a.n_surv[c * CNT_STRIDE + 1];
   const int* surv = a.surv + (size_t)c * a.H;
   const int* cnts = a.cnts + (size_t)c * a.H;
   const unsigned int* rmse = a.rmse + (size_t)c * a.H;
@@ -904,6 +1009,9 @@ __global__ __launch_bounds__(1024) void k_select(PairArgs a, eyoc_ransac_result*
   if (threadIdx.x == 0) {
     for (int w = 1; w < 16; ++w)
       if (bk[w] > best_k || (bk[w] == best_k && bh[w] < best_h)) { best_k = bk[w]; best_h = bh[w]; }
+    if constexpr (sizeof...(RD) > 0) {
+      if (!only(rd...).merge(c, b, n, ns, best_k, best_h)) return;      // not finished: no record yet
+    }
     double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, t[3] = {0, 0, 0};
     out->survivors = ns;
     if (ns > 0 && best_h != 0x7FFFFFFF) {
@@ -957,18 +1065,44 @@ int ransac_pick_chunk(int n_pairs, int total, int H, size_t budget, int store) {
   return chunk;
 }
 
+// the kernels' view of a scratch laid out for H hypotheses per pair
+PairArgs ransac_args(const RansacLayout& l, char* sc, const eyoc_ransac_params* p, int H, int store) {
+  PairArgs a;
+  a.rec = (float*)(sc + l.off_rec); a.seed = p->seed; a.H = H; a.edge_sim = p->edge_similarity; a.max_dist = p->max_distance;
+  a.n_surv = (int*)(sc + l.off_cnt); a.surv = (int*)(sc + l.off_surv); a.cnts = (int*)(sc + l.off_cnts);
+  a.rmse = (unsigned int*)(sc + l.off_rmse); a.xf = (double*)(sc + l.off_xf); a.cap_t = ransac_cap_t(H, store);
+  a.rec_sorted = (float*)(sc + l.off_rs); a.rr_sorted = (float*)(sc + l.off_rr); a.bucket_end = (int*)(sc + l.off_be); a.pmax = (double*)(sc + l.off_pm);
+  a.pair0 = 0; a.count_bound = 0;
+  return a;
+}
+// the segment bounds of the chunk's nc pairs from pair p0 on (the unused slots repeat the first pair); -> its largest pair
+int ransac_chunk_pairs(PairArgs& a, const int32_t* seg_src_host, const int32_t* seg_tgt_host, int p0, int nc) {
+  int chunk_max = 0;
+  a.pair0 = p0;
+  for (int c = 0; c < CHUNK; ++c) {
+    const int b = p0 + (c < nc ? c : 0);
+    a.s0[c] = seg_src_host[b]; a.n[c] = seg_src_host[b + 1] - seg_src_host[b]; a.t0[c] = seg_tgt_host[b];
+    chunk_max = a.n[c] > chunk_max ? a.n[c] : chunk_max;
+  }
+  return chunk_max;
+}
+int ransac_set_attributes(eyoc_ctx* ctx) {
+  if (ctx->ransac_attr_set) return EYOC_OK;
+  EYOC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_generate<true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_RECORDS * 24));
+  EYOC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_generate_q<>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_RECORDS_Q * 12));
+  EYOC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_generate<true, Round>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_RECORDS * 24));
+  EYOC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_generate_q<Round>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_RECORDS_Q * 12));
+  ctx->ransac_attr_set = true;
+  return EYOC_OK;
+}
+
 int ransac_run(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int64_t* corr_tgt_dev, const int32_t* seg_src_host,
                const int32_t* seg_tgt_host, int n_pairs, const eyoc_ransac_params* p, eyoc_ransac_result* results_dev, char* sc,
                int chunk, int max_n, int store, hipStream_t st) {
   const int H = p->max_iteration;
   const int total = seg_src_host[n_pairs];
   const int cap_t = ransac_cap_t(H, store);
-  const RansacLayout l = ransac_layout(chunk, total, H, store);
-  PairArgs a;
-  a.rec = (float*)(sc + l.off_rec); a.seed = p->seed; a.H = H; a.edge_sim = p->edge_similarity; a.max_dist = p->max_distance;
-  a.n_surv = (int*)(sc + l.off_cnt); a.surv = (int*)(sc + l.off_surv); a.cnts = (int*)(sc + l.off_cnts);
-  a.rmse = (unsigned int*)(sc + l.off_rmse); a.xf = (double*)(sc + l.off_xf); a.cap_t = cap_t;
-  a.rec_sorted = (float*)(sc + l.off_rs); a.rr_sorted = (float*)(sc + l.off_rr); a.bucket_end = (int*)(sc + l.off_be); a.pmax = (double*)(sc + l.off_pm);
+  PairArgs a = ransac_args(ransac_layout(chunk, total, H, store), sc, p, H, store);
   const int pruned = ctx->knobs.ransac_prune && max_n <= 8192 ? 1 : 0;
   const int want_bound = ctx->knobs.ransac_prune >= 2 ? 1 : 0;
   // eyoc_ransac_select_generate 1: the compact records, where a launch's pairs fit the LDS in that form and the band's derivation holds
@@ -976,43 +1110,111 @@ int ransac_run(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const 
   const bool compact = ctx->knobs.ransac_generate == 1 && max_n <= LDS_RECORDS_Q && p->edge_similarity > 0.0f && p->edge_similarity <= 1.0f;
   const bool in_lds = max_n <= LDS_RECORDS;
   const size_t lds_bytes = compact ? (size_t)max_n * 12 : in_lds ? (size_t)max_n * 24 : 0;
-  if (!ctx->ransac_attr_set) {
-    EYOC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_generate<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       LDS_RECORDS * 24));
-    EYOC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_generate_q), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       LDS_RECORDS_Q * 12));
-    ctx->ransac_attr_set = true;
-  }
+  if (int rc = ransac_set_attributes(ctx)) return rc;
   for (int p0 = 0; p0 < n_pairs; p0 += chunk) {
     const int nc = n_pairs - p0 < chunk ? n_pairs - p0 : chunk;
-    a.pair0 = p0;
     // the count bound polls ONE word per pair from every wave and block: 100 k agent-scope loads per launch whatever the number of pairs
     // (the groups shrink as the pairs get fewer), and loads of one address are served one after the other - spread over 64 words they
     // cost nothing that shows, on the 8 words of an 8-pair chunk they cost 0.55 ms (k_count 0.36 -> 0.93 ms): small chunks count like round 5
     a.count_bound = want_bound && nc >= 32 ? 1 : 0;                       // (measured: 16 pairs 0.87 -> 1.03 ms with the bound, 32 pairs 1.50 -> 1.32, 64 pairs 3.1 -> 2.5)
-    int chunk_max = 0;
-    for (int c = 0; c < CHUNK; ++c) {
-      const int b = p0 + (c < nc ? c : 0);
-      a.s0[c] = seg_src_host[b]; a.n[c] = seg_src_host[b + 1] - seg_src_host[b]; a.t0[c] = seg_tgt_host[b];
-      chunk_max = a.n[c] > chunk_max ? a.n[c] : chunk_max;
-    }
+    const int chunk_max = ransac_chunk_pairs(a, seg_src_host, seg_tgt_host, p0, nc);
     EYOC_CHECK_HIP(hipMemsetAsync(a.n_surv, 0, (size_t)nc * CNT_STRIDE * 4, st));
     hipLaunchKernelGGL(k_gather_targets, dim3(cdiv(chunk_max, 256), nc), dim3(256), 0, st, src_dev, tgt_dev,
                        (const long long*)corr_tgt_dev, a);
     const int gen_blocks = GEN_BLOCKS_TOTAL / nc > GEN_BLOCKS_MIN ? GEN_BLOCKS_TOTAL / nc : GEN_BLOCKS_MIN;
     if (compact) {
       const int total = max_n <= GEN_Q_PAIRED ? GEN_Q_BLOCKS_TOTAL : GEN_BLOCKS_TOTAL;
-      hipLaunchKernelGGL(k_generate_q, dim3(total / nc > GEN_BLOCKS_MIN ? total / nc : GEN_BLOCKS_MIN, nc), dim3(GEN_THREADS), lds_bytes, st, a);
+      hipLaunchKernelGGL(k_generate_q<>, dim3(total / nc > GEN_BLOCKS_MIN ? total / nc : GEN_BLOCKS_MIN, nc), dim3(GEN_THREADS), lds_bytes, st, a);
     } else if (in_lds) hipLaunchKernelGGL(k_generate<true>, dim3(gen_blocks, nc), dim3(GEN_THREADS), lds_bytes, st, a);
     else hipLaunchKernelGGL(k_generate<false>, dim3(gen_blocks, nc), dim3(GEN_THREADS), 0, st, a);
-    hipLaunchKernelGGL(k_fit, dim3(2048 / nc > 8 ? 2048 / nc : 8, nc), dim3(256), 0, st, a);
-    if (pruned) hipLaunchKernelGGL(k_bucket, dim3(nc), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_fit<>, dim3(2048 / nc > 8 ? 2048 / nc : 8, nc), dim3(256), 0, st, a);
+    if (pruned) hipLaunchKernelGGL(k_bucket<>, dim3(nc), dim3(256), 0, st, a);
     constexpr int KC_BLOCKS = 4096;   // workgroups of the count over the pairs of a launch (2048: 1.6 rounds of the 1280 the chip holds - measured 3.5 vs 3.3 ms in round 4; with the round-6 count bound 1.22 vs 1.19 ms, 8192: 1.59)
-    if (pruned) hipLaunchKernelGGL(k_count, dim3(KC_BLOCKS / nc, nc), dim3(256), 0, st, a, (const double*)a.xf);
-    else hipLaunchKernelGGL(k_count_fp64, dim3(KC_BLOCKS / nc, nc), dim3(256), 0, st, a, (const double*)a.xf, pruned);
-    if (H > cap_t) hipLaunchKernelGGL(k_count_overflow, dim3(256, nc), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_rmse, dim3(64, nc), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_select, dim3(nc), dim3(1024), 0, st, a, results_dev);
+    if (pruned) hipLaunchKernelGGL(k_count<>, dim3(KC_BLOCKS / nc, nc), dim3(256), 0, st, a, (const double*)a.xf);
+    else hipLaunchKernelGGL(k_count_fp64<>, dim3(KC_BLOCKS / nc, nc), dim3(256), 0, st, a, (const double*)a.xf, pruned);
+    if (H > cap_t) hipLaunchKernelGGL(k_count_overflow<>, dim3(256, nc), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_rmse<>, dim3(64, nc), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_select<>, dim3(nc), dim3(1024), 0, st, a, results_dev);
+  }
+  EYOC_CHECK_HIP(hipGetLastError());
+  return EYOC_OK;
+}
+
+// ---- rounds between checkpoints E_0 = min(first_check, H), E_{j+1} = min(2 E_j, H) (include/eyoc_hip.h).  The per-round scratch is the
+// one-pass layout for the LONGEST round instead of H, and behind it the pairs' carried state
+inline int next_checkpoint(int E, int H) { return (long long)2 * E < (long long)H ? 2 * E : H; }
+inline int first_checkpoint(int H, int first_check) { return first_check < H ? first_check : H; }
+int longest_round(int H, int first_check) {
+  int E = first_checkpoint(H, first_check), longest = E;
+  while (E < H) {
+    const int next = next_checkpoint(E, H);
+    longest = next - E > longest ? next - E : longest;
+    E = next;
+  }
+  return longest;
+}
+struct RoundsLayout {
+  RansacLayout round;
+  size_t off_state, bytes;
+};
+RoundsLayout rounds_layout(int chunk, int total, int longest, int store) {
+  RoundsLayout l;
+  l.round = ransac_layout(chunk, total, longest, store);
+  l.off_state = l.round.bytes;
+  l.bytes = align_up(l.off_state + (size_t)chunk * sizeof(PairState));
+  return l;
+}
+int rounds_pick_chunk(int n_pairs, int total, int longest, size_t budget, int store) {
+  int chunk = n_pairs < CHUNK ? n_pairs : CHUNK;
+  while (chunk > 1 && rounds_layout(chunk, total, longest, store).bytes > budget) chunk >>= 1;
+  return chunk;
+}
+
+// ransac_run in rounds: every round's launches are enqueued whatever the pairs decide (the host never waits); the workgroups of a
+// finished pair return on their first test.  A chunk runs all its rounds before the next chunk starts.
+int ransac_run_rounds(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int64_t* corr_tgt_dev, const int32_t* seg_src_host,
+                      const int32_t* seg_tgt_host, int n_pairs, const eyoc_ransac_params* p, float confidence, int first_check,
+                      eyoc_ransac_result* results_dev, int32_t* iterations_dev, char* sc, int chunk, int max_n, int store, hipStream_t st) {
+  const int H = p->max_iteration;
+  const int total = seg_src_host[n_pairs];
+  const int longest = longest_round(H, first_check);
+  const RoundsLayout l = rounds_layout(chunk, total, longest, store);
+  PairArgs a = ransac_args(l.round, sc, p, longest, store);
+  const int cap_t = a.cap_t;
+  PairState* state = (PairState*)(sc + l.off_state);
+  const int pruned = ctx->knobs.ransac_prune && max_n <= 8192 ? 1 : 0;
+  const int want_bound = ctx->knobs.ransac_prune >= 2 ? 1 : 0;
+  const bool compact = ctx->knobs.ransac_generate == 1 && max_n <= LDS_RECORDS_Q && p->edge_similarity > 0.0f && p->edge_similarity <= 1.0f;
+  const bool in_lds = max_n <= LDS_RECORDS;
+  const size_t lds_bytes = compact ? (size_t)max_n * 12 : in_lds ? (size_t)max_n * 24 : 0;
+  if (int rc = ransac_set_attributes(ctx)) return rc;
+  for (int p0 = 0; p0 < n_pairs; p0 += chunk) {
+    const int nc = n_pairs - p0 < chunk ? n_pairs - p0 : chunk;
+    a.count_bound = want_bound && nc >= 32 ? 1 : 0;                       // as in ransac_run
+    const int chunk_max = ransac_chunk_pairs(a, seg_src_host, seg_tgt_host, p0, nc);
+    EYOC_CHECK_HIP(hipMemsetAsync(a.n_surv, 0, (size_t)nc * CNT_STRIDE * 4, st));
+    hipLaunchKernelGGL(k_gather_targets, dim3(cdiv(chunk_max, 256), nc), dim3(256), 0, st, src_dev, tgt_dev,
+                       (const long long*)corr_tgt_dev, a);
+    const int gen_blocks = GEN_BLOCKS_TOTAL / nc > GEN_BLOCKS_MIN ? GEN_BLOCKS_TOTAL / nc : GEN_BLOCKS_MIN;
+    const int gen_q_total = max_n <= GEN_Q_PAIRED ? GEN_Q_BLOCKS_TOTAL : GEN_BLOCKS_TOTAL;
+    const int gen_q_blocks = gen_q_total / nc > GEN_BLOCKS_MIN ? gen_q_total / nc : GEN_BLOCKS_MIN;
+    constexpr int KC_BLOCKS = 4096;
+    for (int h_lo = 0, E = first_checkpoint(H, first_check);; h_lo = E, E = next_checkpoint(E, H)) {
+      a.H = E - h_lo;                                                     // the round's hypotheses, and the stride of its lists (<= longest)
+      const Round rd{2ull * (unsigned long long)h_lo, state};
+      hipLaunchKernelGGL(k_round_begin, dim3(1), dim3(CHUNK), 0, st, a, state, nc, h_lo == 0 ? 1 : 0);
+      if (compact) hipLaunchKernelGGL(k_generate_q<Round>, dim3(gen_q_blocks, nc), dim3(GEN_THREADS), lds_bytes, st, a, rd);
+      else if (in_lds) hipLaunchKernelGGL((k_generate<true, Round>), dim3(gen_blocks, nc), dim3(GEN_THREADS), lds_bytes, st, a, rd);
+      else hipLaunchKernelGGL((k_generate<false, Round>), dim3(gen_blocks, nc), dim3(GEN_THREADS), 0, st, a, rd);
+      hipLaunchKernelGGL(k_fit<Round>, dim3(2048 / nc > 8 ? 2048 / nc : 8, nc), dim3(256), 0, st, a, rd);
+      if (pruned) hipLaunchKernelGGL(k_bucket<Round>, dim3(nc), dim3(256), 0, st, a, rd);
+      if (pruned) hipLaunchKernelGGL(k_count<Round>, dim3(KC_BLOCKS / nc, nc), dim3(256), 0, st, a, (const double*)a.xf, rd);
+      else hipLaunchKernelGGL(k_count_fp64<Round>, dim3(KC_BLOCKS / nc, nc), dim3(256), 0, st, a, (const double*)a.xf, pruned, rd);
+      if (a.H > cap_t) hipLaunchKernelGGL(k_count_overflow<Round>, dim3(256, nc), dim3(256), 0, st, a, rd);
+      hipLaunchKernelGGL(k_rmse<Round>, dim3(64, nc), dim3(256), 0, st, a, rd);
+      hipLaunchKernelGGL(k_select<Decide>, dim3(nc), dim3(1024), 0, st, a, results_dev, Decide{state, h_lo, E, E == H ? 1 : 0, confidence, iterations_dev});
+      if (E == H) break;
+    }
   }
   EYOC_CHECK_HIP(hipGetLastError());
   return EYOC_OK;
@@ -1188,6 +1390,65 @@ extern "C" int eyoc_ransac_batched(eyoc_ctx* ctx, const float* src_dev, const fl
   }
   return ransac_run(ctx, src_dev, tgt_dev, corr_tgt_dev, seg_src_host, seg_tgt_host, n_pairs, p, results_dev, (char*)ctx->scratch, chunk,
                     max_n, store, st);
+}
+
+// ---- the convergence criterion (include/eyoc_hip.h: checkpoints, when a pair is finished, what the call returns)
+__global__ void k_zero_iterations(int32_t* __restrict__ iterations, FailedPairs f) {
+  if ((int)threadIdx.x < f.n) iterations[f.idx[threadIdx.x]] = 0;
+}
+
+extern "C" size_t eyoc_ransac_converging_workspace_bytes(const eyoc_ctx* ctx, int n_pairs, int total_corr, int max_iteration,
+                                                         int32_t first_check, size_t budget_bytes) {
+  if (n_pairs < 1 || total_corr < 0 || max_iteration < 1 || first_check < 1) return 0;
+  const int store = knobs_of(ctx).ransac_store;
+  const int longest = longest_round(max_iteration, first_check);
+  const int chunk = rounds_pick_chunk(n_pairs, total_corr, longest, budget_bytes ? budget_bytes : ~(size_t)0, store);
+  return rounds_layout(chunk, total_corr, longest, store).bytes;
+}
+
+extern "C" int eyoc_ransac_converging_batched_ws(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int64_t* corr_tgt_dev,
+                                                 const int32_t* seg_src_host, const int32_t* seg_tgt_host, int n_pairs,
+                                                 const eyoc_ransac_params* p, float confidence, int32_t first_check,
+                                                 eyoc_ransac_result* results_dev, int32_t* iterations_dev, void* workspace_dev,
+                                                 size_t workspace_bytes, void* stream) {
+  EYOC_REQUIRE(ctx && workspace_dev && iterations_dev, EYOC_ERR_INVALID, "eyoc_ransac_converging_batched_ws: NULL argument");
+  EYOC_REQUIRE(((uintptr_t)workspace_dev & 255) == 0, EYOC_ERR_INVALID, "eyoc_ransac_converging_batched_ws: workspace must be 256-byte aligned");
+  EYOC_REQUIRE(confidence > 0.0f, EYOC_ERR_INVALID, "eyoc_ransac_converging_batched_ws: confidence %g (must be above 0)", (double)confidence);   // false for a NaN
+  EYOC_REQUIRE(first_check >= 1, EYOC_ERR_INVALID, "eyoc_ransac_converging_batched_ws: first_check %d", (int)first_check);
+  hipStream_t st = (hipStream_t)stream;
+  int rc = ransac_split(ctx, seg_src_host, seg_tgt_host, n_pairs, p, results_dev, st,
+                        [&](const int32_t* ss, const int32_t* stt, int np, const eyoc_ransac_params* q, eyoc_ransac_result* r) {
+                          return eyoc_ransac_converging_batched_ws(ctx, src_dev, tgt_dev, corr_tgt_dev, ss, stt, np, q, confidence, first_check,
+                                                                   r, iterations_dev + (r - results_dev), workspace_dev, workspace_bytes, stream);
+                        });
+  if (rc < 0) return rc;
+  if (rc == 0) {                                                          // the degenerate pairs have their failed record: iterations 0
+    FailedPairs f;
+    f.n = 0;
+    for (int b = 0; b < n_pairs; ++b) {
+      const int n = seg_src_host[b + 1] - seg_src_host[b];
+      if (n >= 0 && n < 4) f.idx[f.n++] = b;
+      if (f.n == 64 || (b == n_pairs - 1 && f.n)) {
+        hipLaunchKernelGGL(k_zero_iterations, dim3(1), dim3(64), 0, st, iterations_dev, f);
+        f.n = 0;
+      }
+    }
+    EYOC_CHECK_HIP(hipGetLastError());
+    return EYOC_OK;
+  }
+  int max_n = 0;
+  rc = ransac_validate(src_dev, tgt_dev, corr_tgt_dev, seg_src_host, seg_tgt_host, n_pairs, p, results_dev, &max_n);
+  if (rc) return rc;
+  const int total = seg_src_host[n_pairs];
+  const int store = ctx->knobs.ransac_store;
+  const int longest = longest_round(p->max_iteration, first_check);
+  const int chunk = rounds_pick_chunk(n_pairs, total, longest, workspace_bytes, store);
+  const size_t need = rounds_layout(chunk, total, longest, store).bytes;
+  EYOC_REQUIRE(need <= workspace_bytes, EYOC_ERR_WORKSPACE,
+               "eyoc_ransac_converging_batched_ws: workspace %zu < %zu bytes (one pair per launch; eyoc_ransac_converging_workspace_bytes)",
+               workspace_bytes, need);
+  return ransac_run_rounds(ctx, src_dev, tgt_dev, corr_tgt_dev, seg_src_host, seg_tgt_host, n_pairs, p, confidence, first_check, results_dev,
+                           iterations_dev, (char*)workspace_dev, chunk, max_n, store, st);
 }
 
 extern "C" int eyoc_ransac(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int64_t* corr_tgt_dev, int n,

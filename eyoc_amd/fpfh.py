@@ -92,13 +92,14 @@ def fpfh_descriptors(pts, seg, voxel_size, normal_radius=None, normal_max_nn=30,
 
 
 def register_fpfh_batched(src, tgt, seg_src, seg_tgt, voxel_size, distance_threshold, backend="ransac", mutual=False, seed=0,
-                          max_iteration=4000000, matcher=None, **descriptor_args):
+                          max_iteration=4000000, matcher=None, confidence=1.0, first_check=_reg.RANSAC_FIRST_CHECK, **descriptor_args):
     """Raw points to poses for a batch of pairs, without a network: ``fpfh_descriptors`` on both sides, the feature-space nearest
     neighbour of every source row (``eval.knn1_segmented``; ``mutual``: only the reciprocal matches, ``eval.mutual_correspondences``),
     then ``backend``:
 
     ``"ransac"``  ``registration.ransac_batched_from_correspondences`` with ``distance_threshold`` and ``max_iteration``; pair ``b`` draws
                   with ``seed + b``.  With ``mutual`` a pair with fewer than 4 reciprocal matches keeps all its matches, like Open3D.
+                  ``confidence`` below 1 (and ``first_check``) switch that call's convergence criterion on; the results then carry ``iterations``.
     ``"sc2pcr"``  ``registration.Matcher.SC2_PCR_packed`` on the matched points (the first ``max_points`` of a pair); ``matcher``: the
                   ``Matcher`` to use, default ``Matcher(inlier_threshold=distance_threshold, num_node='all', nms_radius=distance_threshold,
                   num_iterations=20)``.  ``fitness`` is the share of matches within ``inlier_threshold`` under the pose.
@@ -150,9 +151,15 @@ def register_fpfh_batched(src, tgt, seg_src, seg_tgt, voxel_size, distance_thres
             sl = slice(seg_m[b0], seg_m[b1])
             res = _reg.ransac_batched_from_correspondences(ms[sl], t[seg_t[b0]:seg_t[b1]], corr[sl], [v - seg_m[b0] for v in seg_m[b0:b1 + 1]],
                                                            [v - seg_t[b0] for v in seg_t[b0:b1 + 1]], float(distance_threshold),
-                                                           int(max_iteration), int(seed) + b0)
+                                                           int(max_iteration), int(seed) + b0, confidence=confidence,
+                                                           first_check=first_check, return_iterations=float(confidence) < 1.0)
+            its = None
+            if float(confidence) < 1.0:
+                res, its = res[0], res[1].cpu().numpy()
             for b in range(b0, b1):
                 out[b] = _reg.decode_ransac_result(res[b - b0], int(ns[b]))
+                if its is not None:
+                    out[b].iterations = int(its[b - b0])
         return out
     m = matcher if matcher is not None else _reg.Matcher(inlier_threshold=float(distance_threshold), num_node='all',
                                                          nms_radius=float(distance_threshold), num_iterations=20)

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import contextlib
 import copy
+import ctypes as C
 import json
 import logging
 from dataclasses import dataclass, field
@@ -43,6 +44,11 @@ class RegistrationConfig:
     n_points: int = 5000                 # scripts/test_kitti.py:156
     use_RANSAC: bool = True
     ransac_max_iteration: int = 4000000  # scripts/test_kitti.py:176
+    # RANSAC route only: RANSACConvergenceCriteria's confidence.  1.0 (the reference's 10000, clamped) runs every iteration; below 1 a pair
+    # stops at the first checkpoint (ransac_first_check, then doubling) at which its best fitness meets the criterion, decided on the
+    # device (registration.ransac_batched_from_correspondences), and the results carry ``iterations``.  ``load_config`` leaves both alone
+    ransac_confidence: float = 1.0
+    ransac_first_check: int = reg.RANSAC_FIRST_CHECK
     rte_thresh: float = 2.0
     rre_thresh: float = 5.0
     sc2pcr: dict = field(default_factory=lambda: dict(
@@ -79,6 +85,8 @@ class RegistrationConfig:
             raise ValueError(f"icp_method = {self.icp_method!r}: \"point\" or \"plane\"")
         if self.mutual_filter and not self.use_RANSAC:
             raise ValueError("mutual_filter is implemented for the RANSAC route only (use_RANSAC=True)")
+        if not self.ransac_confidence > 0.0 or self.ransac_first_check < 1:
+            raise ValueError(f"ransac_confidence = {self.ransac_confidence!r} must be above 0, ransac_first_check = {self.ransac_first_check!r} at least 1")
 
 
 # ``RegistrationResult.status`` / ``PendingStep.status`` bit: the pair's step overflowed split16 and was registered again in fp32
@@ -373,8 +381,8 @@ class MapsHandle(NamedTuple):
 class _Step:
     """What ONE enqueued step produced (``RegistrationPipeline._step``).  Nothing of it is on the pipeline: ``_publish`` makes a step
     "the last step", a retry hands its step to whoever asked for it."""
-    __slots__ = ("slot", "timers", "batch", "F", "featured", "matched", "nn_idx", "kept_rows", "kept_seg", "result", "icp", "words", "host",
-                 "icp_host", "done")
+    __slots__ = ("slot", "timers", "batch", "F", "featured", "matched", "nn_idx", "kept_rows", "kept_seg", "result", "packed", "icp", "words",
+                 "host", "icp_host", "done")
 
     def __init__(self, slot, timers):
         self.slot, self.timers = slot, timers      # the buffer set the step uses; its four stage-timer events (None: not timed)
@@ -383,14 +391,20 @@ class _Step:
         self.nn_idx = None                         # RANSAC path: the feature correspondences on the device
         self.kept_rows = self.kept_seg = None      # mutual_filter: the source rows RANSAC ran on (device, row inside its pair) and their segments (host, [P + 1])
         self.result = self.icp = None              # the back-end's records on the device; icp_refine: the ``eyoc_icp_result`` records
+        self.packed = None                         # ransac_confidence < 1: ONE device buffer, the records (= ``result``, a view) in front and the
+                                                   # pairs' int32 iterations behind - what the step's one read-back copies
         self.words = self.host = self.icp_host = self.done = None    # the read-back, when it was enqueued with the step
 
 
 class PendingStep:
     """A step whose read-back was enqueued with it (``RegistrationPipeline.enqueue``)."""
 
-    def __init__(self, host, words, done, device_result, keep=None, retry=None, dropped=None, icp=None):
+    def __init__(self, host, words, done, device_result, keep=None, retry=None, dropped=None, icp=None, packed=False):
         self.host, self.words, self.done, self.device_result = host, words, done, device_result
+        self.iterations = None    # ransac_confidence < 1: int32 [P] in the same pinned buffer, behind the records (valid like ``host``)
+        self._packed = None
+        if packed:                # the read-back was the step's packed buffer: records in front, iterations behind
+            self._packed, (self.host, self.iterations) = host, split_packed(host)
         self.icp = icp            # icp_refine: the step's ``eyoc_icp_result`` records, ``uint8 [P, 160]`` in pinned host memory (valid like ``host``)
         self.dropped = dropped    # isolate_failures: the step's DROPPED_* bits per pair (their records are the back-end's failed ones)
         self.keep = keep          # tensors another stream still reads (the features under ``tail_stream``): released by ``wait``
@@ -408,12 +422,25 @@ class PendingStep:
         if overflow and self.retry is not None:
             pipe, batch, seed, maps, slot = self.retry
             again = pipe._retry_fp32(batch, seed, maps, slot, pipelined=True)
-            self.host.copy_(again.result.cpu())
+            if self._packed is not None:
+                self._packed.copy_(again.packed.cpu())
+            else:
+                self.host.copy_(again.result.cpu())
             if self.icp is not None:
                 self.icp.copy_(again.icp.cpu())
             self.status |= RETRIED_FP32
         self.retry = None
         return self.host, overflow
+
+
+RECORD_BYTES = C.sizeof(_lib.RansacResult)
+
+
+def split_packed(buf):
+    """A step's packed buffer (``uint8 [P * (RECORD_BYTES + 4)]``, device or host) -> views ``(records uint8 [P, RECORD_BYTES],
+    iterations int32 [P])``."""
+    P = buf.numel() // (RECORD_BYTES + 4)
+    return buf[:P * RECORD_BYTES].view(P, RECORD_BYTES), buf[P * RECORD_BYTES:].view(torch.int32)
 
 
 _CALLERS_STREAM = contextlib.nullcontext()      # the tail of a step that stays on the stream of its forward
@@ -554,8 +581,9 @@ class RegistrationPipeline:
             step.result = (self._match_and_register if self.cfg.use_RANSAC else self._match_and_register_sc2)(step, seed)
             self._mark(step, 3)
             if read_back:
-                step.host = self._pinned_set(slot, step.result)
-                step.host.copy_(step.result, non_blocking=True)
+                dev = step.result if step.packed is None else step.packed      # records and iterations come back in the one copy
+                step.host = self._pinned_set(slot, dev)
+                step.host.copy_(dev, non_blocking=True)
                 if self.cfg.icp_refine:
                     step.icp_host = self._pinned_set(slot, step.icp)
                     step.icp_host.copy_(step.icp, non_blocking=True)
@@ -637,7 +665,8 @@ class RegistrationPipeline:
             retry = (self, step.batch, seed, None if self.cfg.isolate_failures else maps, slot)
         # under ``tail_stream`` F was allocated on the caller's stream and is read on the tail stream: it stays referenced until wait()
         return PendingStep(step.host, step.words, step.done, step.result, keep=(step.F,) if tail_stream else None, retry=retry,
-                           dropped=step.batch.dropped.copy() if self.cfg.isolate_failures else None, icp=step.icp_host)
+                           dropped=step.batch.dropped.copy() if self.cfg.isolate_failures else None, icp=step.icp_host,
+                           packed=step.packed is not None)
 
     def _icp_refine(self, step, T):
         """icp_refine: one batched ICP over the pairs' sample sets on the CURRENT stream, started from the back-end's poses ``T f32 [P, 16]``
@@ -726,11 +755,17 @@ class RegistrationPipeline:
         # size gives the same records)
         if self._ransac_budget is None:
             self._ransac_budget = reg._ransac_budget(F.device)
+        out, more = None, {}
+        if self.cfg.ransac_confidence < 1.0:
+            # records and iterations in one buffer, so that the step's one read-back brings both
+            step.packed = torch.empty(batch.P * (RECORD_BYTES + 4), dtype=torch.uint8, device=F.device)
+            out = split_packed(step.packed)
+            more = dict(confidence=self.cfg.ransac_confidence, first_check=self.cfg.ransac_first_check, _out=out)
         with self._accept_degenerate(F.device):
             res = reg.ransac_batched_from_correspondences(
                 src, batch.xyz1.reshape(-1, 3), corr, seg_src, batch.seg,
                 self.cfg.voxel_size * 1.0, self.cfg.ransac_max_iteration, seed=seed,
-                workspace_budget=self._ransac_budget)                                  # [P, 84] bytes on the device
+                workspace_budget=self._ransac_budget, **more)                          # [P, 84] bytes on the device
         if self.cfg.icp_refine:
             res.view(torch.float32)[:, :16] = self._icp_refine(step, res.view(torch.float32)[:, :16])
         return res
@@ -754,7 +789,10 @@ class RegistrationPipeline:
         """``register``: the records of ``step`` on the host, decoded (``status`` or-ed in) - or, after a split16 overflow in automatic
         mode, those of the step run again: that step alone in fp32 (``fp32_retry_per_step``), or with the model switched to fp32 MFMAs for good."""
         words = self._range_snapshot()
-        host = step.result.cpu()
+        if step.packed is None:
+            host, its = step.result.cpu(), None
+        else:                         # still one copy: the iterations lie behind the records
+            host, its = split_packed(step.packed.cpu())
         if self.cfg.icp_refine:     # the ICP records follow the results to the host (the stream is drained by then)
             icp_host = step.icp.cpu()
             self.last_icp = [icp.decode_icp_result(icp_host[p]) for p in range(icp_host.shape[0])]
@@ -777,6 +815,9 @@ class RegistrationPipeline:
         if self.cfg.use_RANSAC:
             used = np.full(batch.P, batch.n_points) if step.kept_seg is None else np.diff(step.kept_seg)      # mutual_filter: fitness over the kept rows
             results = [reg.decode_ransac_result(host[p], int(used[p])) for p in range(batch.P)]
+            if its is not None:
+                for p in range(batch.P):
+                    results[p].iterations = int(its[p])
         else:
             Th = host.numpy().astype(np.float64)
             results = [reg.RegistrationResult(Th[p], 0.0, 0.0) for p in range(batch.P)]

@@ -131,7 +131,8 @@ class CorrespondenceCheckerBasedOnDistance:
 
 class RANSACConvergenceCriteria:
     """``confidence`` is clamped to [0, 1] like Open3D >= 0.12 does; at 1 (the reference passes 10000) there is no early
-    exit and every one of ``max_iteration`` hypotheses is evaluated - which is the only mode the library implements."""
+    exit and every one of ``max_iteration`` hypotheses is evaluated; below 1 a pair stops at the first checkpoint at which its best
+    fitness meets the criterion (``eyoc_amd.registration.ransac_batched_from_correspondences``; 0 is refused by the call)."""
 
     def __init__(self, max_iteration=100000, confidence=0.999):
         self.max_iteration = int(max_iteration)
@@ -182,8 +183,8 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
     if not isinstance(estimation_method, TransformationEstimationPointToPoint) or estimation_method.with_scaling:
         raise NotImplementedError("only TransformationEstimationPointToPoint(False) is implemented (scripts/test_kitti.py:173)")
     criteria = RANSACConvergenceCriteria() if criteria is None else criteria
-    if criteria.confidence < 1.0:
-        raise NotImplementedError("early termination (confidence < 1) is not implemented: the reference runs all iterations")
+    if not criteria.confidence > 0.0:
+        raise ValueError(f"RANSACConvergenceCriteria.confidence = {criteria.confidence!r}: must be above 0")
     edge, dist = None, None
     for c in checkers or ():
         if isinstance(c, CorrespondenceCheckerBasedOnEdgeLength):
@@ -202,7 +203,7 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
         np.asarray(source.points, np.float32), np.asarray(target.points, np.float32),
         _knn_rows(source_feature), _knn_rows(target_feature),
         mutual_filter, float(max_correspondence_distance), None, ransac_n, None, (criteria.max_iteration, criteria.confidence),
-        seed=seed, edge_similarity=edge)
+        seed=seed, edge_similarity=edge, confidence=min(float(criteria.confidence), 1.0))     # Open3D clamps the confidence to 1
 
 
 def registration_icp(source, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None):

@@ -34,30 +34,60 @@ class RegistrationResult:
                                     # harness.DROPPED_* when the pair was dropped from its batch (isolate_failures);
                                     # icp.CONVERGED / BAD_INIT / FEW / RANGE on a record of eyoc_amd.icp
     correspondence_set: np.ndarray | None = None   # ICP only: int [m, 2] (source row, target row) under ``transformation``
-    iterations: int = 0             # ICP only: pose updates done
+    iterations: int = 0             # ICP: pose updates done; RANSAC with a confidence below 1: the checkpoint at which the pair stopped
+
+
+# first checkpoint of the convergence criterion (``confidence`` below 1; include/eyoc_hip.h: E_0 = min(first_check, H), then doubling).
+# Picked from scripts/bench_ransac_confidence.py on an MI355X (64 pairs x 5000 correspondences, 4 000 000 hypotheses, confidence 0.999;
+# ms per call for first_check 4096 / 16384 / 65536; EXPERIMENTS.md "RANSAC convergence criterion" has the full table): the candidate
+# with the lowest time at inlier ratio 0.3 - 0.49 / 0.42 / 0.38 ms, no other within the run-to-run spread (65536: 0.38-0.38, 16384:
+# 0.41-0.43) -, which is also the fastest at ratio 0.1 (1.08 / 0.85 / 0.58 ms: fewer rounds until the pairs stop at 131072).  At ratio
+# 0.6 it is the slowest of the three (0.46 / 0.65 / 0.99 ms: every pair scores the survivors of 65536 hypotheses before its first check),
+# still 16 times faster than the 16.1 ms of running every iteration.
+RANSAC_FIRST_CHECK = 65536
 
 
 def ransac_from_correspondences(src, tgt, corr_tgt, max_correspondence_distance, max_iteration=4000000, seed=0,
-                                edge_similarity=0.9, as_device_result=False):
+                                edge_similarity=0.9, as_device_result=False, confidence=1.0, first_check=RANSAC_FIRST_CHECK,
+                                return_iterations=False):
     """``src [n,3]``, ``tgt [m,3]``, ``corr_tgt int64 [n]``: 4-point RANSAC over the correspondences
-    ``(i, corr_tgt[i])``.  Returns a ``RegistrationResult`` (one device->host copy of 84 bytes)."""
+    ``(i, corr_tgt[i])``.  Returns a ``RegistrationResult`` (one device->host copy of 84 bytes).  ``confidence``, ``first_check``,
+    ``return_iterations``: see ``ransac_batched_from_correspondences``; the result's ``iterations`` is set when a confidence below 1
+    or ``return_iterations`` asks for it (one more copy of 4 bytes), and ``as_device_result`` then returns ``(record, iterations)``."""
     s = _cuda_f32(src)
     t = _cuda_f32(tgt, s.device)
     c = corr_tgt.to(s.device, torch.int64).contiguous()
     n = s.shape[0]
+    want_it = return_iterations or float(confidence) < 1.0
     res = ransac_batched_from_correspondences(s, t, c, [0, n], [0, 0], max_correspondence_distance, max_iteration, seed,
-                                              edge_similarity)[0]
+                                              edge_similarity, confidence=confidence, first_check=first_check, return_iterations=want_it)
+    res, it = (res[0][0], res[1][0]) if want_it else (res[0], None)
     if as_device_result:
-        return res
-    return decode_ransac_result(res, n)
+        return (res, it) if want_it else res
+    out = decode_ransac_result(res, n)
+    if want_it:
+        out.iterations = int(it)
+    return out
 
 
 def ransac_batched_from_correspondences(src, tgt, corr_tgt, seg_src, seg_tgt, max_correspondence_distance,
-                                        max_iteration=4000000, seed=0, edge_similarity=0.9, workspace_budget=None):
+                                        max_iteration=4000000, seed=0, edge_similarity=0.9, workspace_budget=None, confidence=1.0,
+                                        first_check=RANSAC_FIRST_CHECK, return_iterations=False, _out=None):
     """All pairs of a batch in a few launches: ``src [N,3]`` / ``corr_tgt int64 [N]`` hold the pairs back to back
     (pair ``b`` = rows ``seg_src[b]:seg_src[b+1]``), ``tgt [M,3]`` likewise with ``seg_tgt``; ``corr_tgt`` indexes
     INSIDE the pair's target segment.  Pair ``b`` uses ``seed + b``.  Returns the ``[P, 84]`` byte tensor of
-    ``eyoc_ransac_result`` records on the device (decode with ``decode_ransac_result``)."""
+    ``eyoc_ransac_result`` records on the device (decode with ``decode_ransac_result``).
+
+    ``confidence`` below 1 (``RANSACConvergenceCriteria``'s second argument; 1, the default, runs every iteration through the entry
+    point this function always used): a pair stops at the first checkpoint ``first_check, 2 first_check, ...`` at which its best
+    fitness ``f`` gives ``checkpoint >= log(1 - confidence) / log(1 - f^4)`` (``eyoc_ransac_converging_batched_ws``, decided on the device;
+    the record is the one ``max_iteration = that checkpoint`` gives).  ``return_iterations=True`` returns ``(records, iterations int32 [P]
+    on the device)``: the checkpoint at which each pair stopped, ``max_iteration`` for a pair that ran them all, 0 for a degenerate pair.
+    ``_out``: ``(records, iterations)`` tensors to write into (the pipeline keeps both in one buffer)."""
+    if not float(confidence) > 0.0:
+        raise ValueError(f"confidence = {confidence!r}: must be above 0")
+    if int(first_check) < 1:
+        raise ValueError(f"first_check = {first_check!r}: must be at least 1")
     s = _cuda_f32(src)
     t = _cuda_f32(tgt, s.device)
     c = corr_tgt.to(s.device, torch.int64).contiguous()
@@ -65,8 +95,19 @@ def ransac_batched_from_correspondences(src, tgt, corr_tgt, seg_src, seg_tgt, ma
     ss = (C.c_int32 * (P + 1))(*[int(v) for v in seg_src])
     st = (C.c_int32 * (P + 1))(*[int(v) for v in seg_tgt])
     p = _lib.RansacParams(float(max_correspondence_distance), float(edge_similarity), int(max_iteration), int(seed))
-    res = torch.empty((P, C.sizeof(_lib.RansacResult)), dtype=torch.uint8, device=s.device)
+    res = torch.empty((P, C.sizeof(_lib.RansacResult)), dtype=torch.uint8, device=s.device) if _out is None else _out[0]
     lib = _lib.load()
+    if float(confidence) < 1.0:
+        it = torch.empty(P, dtype=torch.int32, device=s.device) if _out is None else _out[1]
+        with torch.cuda.device(s.device):
+            budget = int(workspace_budget) if workspace_budget else _ransac_budget(s.device)
+            ws = _lib.workspace(lib.eyoc_ransac_converging_workspace_bytes(_lib.ctx(s.device.index), P, int(seg_src[-1]), int(max_iteration),
+                                                                           int(first_check), budget), s.device)
+            _lib.check(lib.eyoc_ransac_converging_batched_ws(_lib.ctx(s.device.index), _lib.ptr(s), _lib.ptr(t), _lib.ptr(c), ss, st, P,
+                                                             C.byref(p), float(confidence), int(first_check), _lib.ptr(res), _lib.ptr(it),
+                                                             _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                       "eyoc_ransac_converging_batched_ws")
+        return (res, it) if return_iterations else res
     with torch.cuda.device(s.device):
         # the scratch (survivor lists: 144 MB per pair at 4 M hypotheses) is the caller's, i.e. torch's caching allocator's:
         # the largest launch chunk that fits ``workspace_budget`` bytes (default: a quarter of what the device and the
@@ -76,6 +117,13 @@ def ransac_batched_from_correspondences(src, tgt, corr_tgt, seg_src, seg_tgt, ma
         _lib.check(lib.eyoc_ransac_batched_ws(_lib.ctx(s.device.index), _lib.ptr(s), _lib.ptr(t), _lib.ptr(c), ss, st, P,
                                               C.byref(p), _lib.ptr(res), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
                    "eyoc_ransac_batched_ws")
+    if return_iterations:      # every iteration ran; a degenerate pair (eyoc_registration_accept_degenerate) ran none
+        n = np.diff(np.asarray([int(v) for v in seg_src], np.int64))
+        it = torch.from_numpy(np.where(n >= 4, int(max_iteration), 0).astype(np.int32)).to(s.device)
+        if _out is not None:
+            _out[1].copy_(it)
+            it = _out[1]
+        return res, it
     return res
 
 
@@ -95,13 +143,17 @@ def decode_ransac_result(res: torch.Tensor, n: int) -> RegistrationResult:
 def registration_ransac_based_on_feature_matching(source, target, source_feature, target_feature,
                                                   mutual_filter=False, max_correspondence_distance=0.3,
                                                   estimation_method=None, ransac_n=4, checkers=None,
-                                                  criteria=(4000000, 0.999), seed=0, edge_similarity=0.9):
+                                                  criteria=(4000000, 0.999), seed=0, edge_similarity=0.9, confidence=None):
     """Drop-in for the Open3D call of ``scripts/test_kitti.py:171-176``.
 
     ``source/target``: ``[n,3]`` points (numpy or torch); ``*_feature``: ``[n,C]`` rows (the layout of
     the model output - not Open3D's transposed ``[C,n]``).  ``criteria = (max_iteration, confidence)``:
     like Open3D >= 0.12 with the reference's ``confidence = 10000`` (clamped to 1), every iteration
-    runs.  Correspondences are the feature-space nearest neighbours of the source points.
+    runs - WHATEVER ``criteria[1]`` says: this function has always ignored it, and callers rely on the records of the full run.  The
+    keyword ``confidence`` is what switches the convergence criterion on: ``None`` (default) or a value >= 1 runs every iteration,
+    a value in (0, 1) stops a pair at the first checkpoint (``RANSAC_FIRST_CHECK``, then doubling) at which its best fitness meets Open3D's
+    ``log(1 - confidence) / log(1 - fitness^4)`` (``ransac_batched_from_correspondences``); ``iterations`` of the result says where.
+    The ``o3d`` shim passes ``criteria.confidence`` here.  Correspondences are the feature-space nearest neighbours of the source points.
 
     ``mutual_filter=True`` (the reference passes False): only the source points whose neighbour's own nearest source point is
     them keep their correspondence (``eval.mutual_correspondences``); with fewer than ``ransac_n`` of them every correspondence
@@ -118,7 +170,10 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
         source = _cuda_f32(source, F0.device)[rows]
     else:
         idx = knn1_segmented(F0, F1, [0, F0.shape[0]], [0, F1.shape[0]], "SquareL2", return_distance=False)
-    return ransac_from_correspondences(source, target, idx, max_correspondence_distance, int(criteria[0]), seed, edge_similarity)
+    if confidence is None or float(confidence) >= 1.0:
+        return ransac_from_correspondences(source, target, idx, max_correspondence_distance, int(criteria[0]), seed, edge_similarity)
+    return ransac_from_correspondences(source, target, idx, max_correspondence_distance, int(criteria[0]), seed, edge_similarity,
+                                       confidence=float(confidence))
 
 
 class Matcher:

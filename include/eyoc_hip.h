@@ -890,6 +890,46 @@ int eyoc_registration_accept_degenerate(eyoc_ctx* ctx, int on);
  * only queries; returns the previous value.  Per ctx; tests set it tiny to drive every survivor through the overflow path. */
 int eyoc_ransac_transform_store(eyoc_ctx* ctx, int survivors);
 
+/* RANSACConvergenceCriteria(max_iteration, confidence) with confidence below 1: early termination, decided on the device.
+ * (Symbols added without a change of EYOC_VERSION, like the other additions since 111.  Opt-in: eyoc_ransac_batched(_ws) is what
+ * confidence >= 1 means everywhere else and does not change.)
+ *
+ * Checkpoints.  With H = params->max_iteration the hypotheses of a pair are evaluated in rounds between checkpoints
+ * E_0 < E_1 < ... < E_last = H:  E_0 = min(first_check, H),  E_{j+1} = min(2 E_j, H);  round j covers h in [E_{j-1}, E_j), E_{-1} = 0.
+ * Doubling keeps the number of rounds at about log2(H / first_check) - 9 for first_check = 16384 and H = 4 000 000 -, so that all
+ * rounds are enqueued without the host waiting, and a pair overshoots its exact stopping point by at most a factor of two.
+ * Open3D evaluates the criterion after every iteration, under OpenMP with a sampler seeded from std::random_device, and is not
+ * reproducible against itself; here the criterion is looked at only at the checkpoints and what a pair returns is a pure function of
+ * (seed, the order of h, first_check).
+ *
+ * When a pair is finished.  After checkpoint E take the pair's best record over all h < E under the total order of eyoc_ransac (more
+ * inliers, then lower fp32 inlier RMSE, then lower h).  With inliers == 0 (nothing survived yet) the pair is not finished.  Otherwise,
+ * in fp64 with n the pair's correspondences and c = (double)confidence:  f = inliers / n,  q = (f f)(f f);  the pair is finished if
+ * q >= 1, or if (double)E >= log(1 - c) / log(1 - q).  A finished pair evaluates nothing further (the workgroups of the later rounds
+ * return on their first test); a pair that never finishes ends at H.
+ *
+ * What the call returns.  results[b] is byte for byte what eyoc_ransac_batched_ws gives for that pair with max_iteration =
+ * iterations[b] and seed params->seed + b, `survivors` included (the sampler is a counter hash that does not depend on H).
+ * iterations_dev: int32 [n_pairs] on the device, the checkpoint at which the pair stopped, or H; 0 for a degenerate pair under
+ * eyoc_registration_accept_degenerate, which keeps its failed record.  Neither depends on the launch chunk or on the other pairs of
+ * the batch.  Nothing is read back, nothing is allocated and the host never waits inside the call.  confidence >= 1 never finishes a
+ * pair early: the records are those of eyoc_ransac_batched_ws and iterations = H.
+ *
+ * Scratch: CALLER-OWNED, 256-byte aligned, as for eyoc_ransac_batched_ws, but the survivor lists are sized for the longest round
+ * instead of H (plus 32 bytes of carried state per pair of a chunk).  eyoc_ransac_converging_workspace_bytes(ctx, n_pairs,
+ * total_corr, max_iteration, first_check, budget) follows the rules of eyoc_ransac_workspace_bytes (0 for arguments the call refuses).
+ * A chunk runs all its rounds before the next chunk starts.
+ *
+ * Refused: confidence <= 0 or NaN, first_check < 1, a misaligned workspace -> EYOC_ERR_INVALID; a workspace in which not even one
+ * pair fits -> EYOC_ERR_WORKSPACE, before the first write. */
+size_t eyoc_ransac_converging_workspace_bytes(const eyoc_ctx* ctx, int n_pairs, int total_corr, int max_iteration, int32_t first_check,
+                                              size_t budget_bytes);
+int eyoc_ransac_converging_batched_ws(eyoc_ctx* ctx, const float* src_dev, const float* tgt_dev, const int64_t* corr_tgt_dev,
+                                      const int32_t* seg_src_host, const int32_t* seg_tgt_host, int n_pairs,
+                                      const eyoc_ransac_params* params, float confidence, int32_t first_check,
+                                      eyoc_ransac_result* results_dev, int32_t* iterations_dev, void* workspace_dev,
+                                      size_t workspace_bytes, void* stream);
+
 /* replaces: Matcher.SC2_PCR (scripts/SC2_PCR/SC2_PCR.py:307-384) for bs == 1.
  * src,tgt f32 [n,3] matched correspondences -> T f32 [4,4], seedwise_fitness f32 [int(ratio*n)]. */
 typedef struct {
