@@ -32,3 +32,4 @@ from .matches import (matching_indices_batched, get_matching_indices, compute_ov
 from .trainbatch import TrainBatch, draw_augmentation  # noqa: F401,E402
 from .icp import (estimate_normals, estimate_normals_batched, icp_plane_batched, registration_icp_point_to_plane)  # noqa: F401,E402
 from .fpfh import (compute_fpfh_batched, compute_fpfh_feature, fpfh_descriptors, register_fpfh_batched)  # noqa: F401,E402
+from .downsample import voxel_down_sample, voxel_down_sample_batched  # noqa: F401,E402

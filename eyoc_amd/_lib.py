@@ -313,6 +313,11 @@ PROTOTYPES = {
     "eyoc_draw_workspace_bytes": (_sz, [_i]),
     "eyoc_draw_subsets": (_i, [_vp, C.c_uint64, C.c_uint64, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _vp, _vp, _sz, _vp]),
     "eyoc_draw_pairs": (_i, [_vp, C.c_uint64, C.c_uint64, _i, _i, _i, _i, _vp, _vp]),
+    "eyoc_voxel_downsample_workspace_bytes": (_sz, [_i, _i, _i]),
+    "eyoc_voxel_downsample_batched": (_i, [_vp, _vp, _i, C.POINTER(C.c_int64), _i, _i, C.c_double, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           C.POINTER(C.c_int64), _vp, _sz, _vp]),
+    "eyoc_voxel_downsample_batched_timed": (_i, [_vp, _vp, _i, C.POINTER(C.c_int64), _i, _i, C.c_double, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                                 _vp, C.POINTER(C.c_int64), _vp, _sz, _vp, C.POINTER(C.c_float)]),
 }
 
 

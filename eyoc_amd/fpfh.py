@@ -4,7 +4,8 @@ The reference's SC2-PCR programs take two descriptor kinds, ``fcgf`` and ``fpfh`
 ``config.py:63,71``); the ``fpfh`` branch L2-normalises Open3D's 33-D rows and hands them to the same ``Matcher``.  This module is that
 branch without Open3D: ``compute_fpfh_batched`` restates ``compute_fpfh_feature(pcd, KDTreeSearchParamHybrid(radius, max_nn))`` for a
 batch of clouds (the contract is in ``include/eyoc_hip.h``), ``fpfh_descriptors`` gives the rows in the form the matcher takes and
-``register_fpfh_batched`` chains descriptor, nearest neighbour and pose for a batch of pairs.  Opt-in: nothing else calls it, and
+``register_fpfh_batched`` chains descriptor, nearest neighbour and pose for a batch of pairs (``downsample=True``: from raw scans,
+through ``eyoc_amd.downsample`` first).  Opt-in: nothing else calls it, and
 ``RegistrationPipeline`` has no FPFH route.
 
 Two differences from Open3D are by construction.  The normals of ``icp.estimate_normals_batched`` point to the origin, Open3D's are
@@ -92,7 +93,8 @@ def fpfh_descriptors(pts, seg, voxel_size, normal_radius=None, normal_max_nn=30,
 
 
 def register_fpfh_batched(src, tgt, seg_src, seg_tgt, voxel_size, distance_threshold, backend="ransac", mutual=False, seed=0,
-                          max_iteration=4000000, matcher=None, confidence=1.0, first_check=_reg.RANSAC_FIRST_CHECK, **descriptor_args):
+                          max_iteration=4000000, matcher=None, confidence=1.0, first_check=_reg.RANSAC_FIRST_CHECK, downsample=False,
+                          **descriptor_args):
     """Raw points to poses for a batch of pairs, without a network: ``fpfh_descriptors`` on both sides, the feature-space nearest
     neighbour of every source row (``eval.knn1_segmented``; ``mutual``: only the reciprocal matches, ``eval.mutual_correspondences``),
     then ``backend``:
@@ -104,6 +106,11 @@ def register_fpfh_batched(src, tgt, seg_src, seg_tgt, voxel_size, distance_thres
                   ``Matcher`` to use, default ``Matcher(inlier_threshold=distance_threshold, num_node='all', nms_radius=distance_threshold,
                   num_iterations=20)``.  ``fitness`` is the share of matches within ``inlier_threshold`` under the pose.
 
+    ``downsample=True``: ``src`` and ``tgt`` are raw scans; both sides go through ``downsample.voxel_down_sample_batched`` at
+    ``voxel_size`` first (Open3D's ``voxel_down_sample``, the first step of its global-registration recipe) and everything below runs on
+    the centroids.  The poses stay in the scans' frames; a cloud that call refuses is empty afterwards and its pair carries ``icp.RANGE``.
+    ``False`` (the default): the clouds are taken as voxelised at ``voxel_size`` already.
+
     ``descriptor_args`` go to ``fpfh_descriptors``.  -> a list of ``RegistrationResult``, one per pair; a pair whose cloud could not be
     described (``icp.RANGE``) or that has no match carries ``status = icp.RANGE`` / ``icp.FEW`` and the identity."""
     if backend not in ("ransac", "sc2pcr"):
@@ -114,9 +121,15 @@ def register_fpfh_batched(src, tgt, seg_src, seg_tgt, voxel_size, distance_thres
     P = len(seg_s) - 1
     if len(seg_t) != P + 1 or seg_s[-1] != s.shape[0] or seg_t[-1] != t.shape[0]:
         raise ValueError("register_fpfh_batched: the segments do not describe the clouds")
+    st_d = None
+    if downsample:
+        from .downsample import voxel_down_sample_batched
+        s, seg_s, st_ds = voxel_down_sample_batched(s, seg_s, voxel_size)
+        t, seg_t, st_dt = voxel_down_sample_batched(t, seg_t, voxel_size)
+        st_d = st_ds | st_dt
     Fs, st_s = fpfh_descriptors(s, seg_s, voxel_size, **descriptor_args)
     Ft, st_t = fpfh_descriptors(t, seg_t, voxel_size, **descriptor_args)
-    bad = (st_s | st_t).cpu().numpy()
+    bad = ((st_s | st_t) if st_d is None else (st_s | st_t | st_d)).cpu().numpy()
     if mutual:
         rows, corr, seg_m = mutual_correspondences(Fs, Ft, seg_s, seg_t, "SquareL2", min_keep=4 if backend == "ransac" else 0)
         seg_m = [int(v) for v in seg_m]

@@ -124,11 +124,25 @@ def _share(q):
     return (hit[seg[1:]] - hit[seg[:-1]]).double() / (seg[1:] - seg[:-1]).double()
 
 
-def overlap_ratio_batched(pcd0, pcd1, T, voxel_size, seg0=None, seg1=None):
+def _downsampled(who, pcd0, pcd1, seg0, seg1, voxel_size):
+    """Both sides of a batch through ``downsample.voxel_down_sample_batched`` -> packed clouds and their segments."""
+    from .downsample import voxel_down_sample_batched
+    s, t, _, _, _, seg0, seg1 = _packed(who, pcd0, pcd1, seg0, seg1)
+    s, seg0, _ = voxel_down_sample_batched(s, seg0, voxel_size)
+    t, seg1, _ = voxel_down_sample_batched(t, seg1, voxel_size)
+    return s, t, seg0, seg1
+
+
+def overlap_ratio_batched(pcd0, pcd1, T, voxel_size, seg0=None, seg1=None, downsample=False):
     """``compute_overlap_ratio`` for every pair of a batch -> ``f64 [P]`` on the device.  Both directions with ``K = 1``, the count pass
-    only: the share of source rows with at least one match, then the larger of the two directions.  The clouds are taken as they are:
-    they must ALREADY be voxel down-sampled (the reference down-samples inside, util/pointcloud.py:43-44).  The inverse poses are
+    only: the share of source rows with at least one match, then the larger of the two directions.  ``downsample=False`` (the default)
+    takes the clouds as they are: they must then ALREADY be voxel down-sampled.  ``downsample=True`` does what the reference's function
+    does inside (util/pointcloud.py:43-44): both clouds of every pair go through ``downsample.voxel_down_sample_batched`` at
+    ``voxel_size`` first (a cloud that call refuses is empty afterwards: its pair's ratio is nan).  The inverse poses are
     ``np.linalg.inv`` on the host, like the reference's."""
+    if downsample:
+        _need_gpu("overlap_ratio_batched")
+        pcd0, pcd1, seg0, seg1 = _downsampled("overlap_ratio_batched", pcd0, pcd1, seg0, seg1, voxel_size)
     fwd = _Search("overlap_ratio_batched", pcd0, pcd1, T, voxel_size, 1, seg0, seg1)
     a = _share(fwd)
     back = _Search("overlap_ratio_batched", fwd.t, fwd.s, None if T is None else np.linalg.inv(_host_poses(T)), voxel_size, 1, fwd.seg1,
@@ -136,8 +150,9 @@ def overlap_ratio_batched(pcd0, pcd1, T, voxel_size, seg0=None, seg1=None):
     return torch.maximum(a, _share(back))
 
 
-def compute_overlap_ratio(pcd0, pcd1, trans, voxel_size):
-    """util/pointcloud.py:42-50 on clouds that are ALREADY voxel down-sampled at ``voxel_size`` (no down-sampling happens here):
-    ``max(|matching01| / |pcd0|, |matching10| / |pcd1|)`` with ``K = 1`` and ``trans`` / its inverse."""
+def compute_overlap_ratio(pcd0, pcd1, trans, voxel_size, downsample=False):
+    """util/pointcloud.py:42-50: ``max(|matching01| / |pcd0|, |matching10| / |pcd1|)`` with ``K = 1`` and ``trans`` / its inverse.
+    ``downsample=False`` (the default): on clouds that are ALREADY voxel down-sampled at ``voxel_size``, no down-sampling happens here;
+    ``downsample=True``: both clouds are down-sampled at ``voxel_size`` first, as the reference's function does (:43-44)."""
     _need_gpu("compute_overlap_ratio")
-    return float(overlap_ratio_batched([_points(pcd0)], [_points(pcd1)], _host_poses(trans), voxel_size)[0].item())
+    return float(overlap_ratio_batched([_points(pcd0)], [_points(pcd1)], _host_poses(trans), voxel_size, downsample=downsample)[0].item())

@@ -26,6 +26,9 @@ o3d.geometry.KDTreeSearchParamHybrid(radius, max_nn))`` and ``o3d.pipelines.regi
 o3d.geometry.KDTreeSearchParamHybrid(radius, max_nn))`` (``eyoc_amd.fpfh``; the result is a ``Feature`` with ``[33, n]`` float64 ``data``).
 The normals point to the origin (Open3D leaves the sign to the eigen-solver), and FPFH depends on that sign.  Only the hybrid search
 parameter exists.
+
+``pcd.voxel_down_sample(voxel_size)``, the first call of every Open3D global-registration program and of ``util/pointcloud.py:38,43-44``,
+returns a new ``PointCloud`` of voxel centroids (``eyoc_amd.downsample``); ``voxel_down_sample_and_trace`` does not exist.
 """
 from __future__ import annotations
 
@@ -63,6 +66,32 @@ class PointCloud:
         n = _icp.estimate_normals(np.asarray(self.points, np.float32), search_param.radius, search_param.max_nn)
         self.normals = n.cpu().numpy().astype(np.float64)
         return self
+
+    def voxel_down_sample(self, voxel_size):
+        """``o3d.geometry.PointCloud.voxel_down_sample`` (util/pointcloud.py:38,43-44) -> a new ``PointCloud``: one point per occupied
+        voxel, the mean of the voxel's points (``eyoc_amd.downsample``: grid anchored half a voxel below the minimum corner, fp64 sums
+        in point order, float32 in and out), rows ordered by the voxel's lowest point index.  The shim's rule for normals: they go
+        through the same call as attributes, and every mean is then scaled to unit length; a zero mean stays zero.  Colours are not
+        carried.  Open3D is not part of any build here, so this follows its documented behaviour, not a comparison."""
+        from . import _lib, downsample as _ds
+        if not len(self.points):
+            raise RuntimeError("voxel_down_sample: the cloud has no points")
+        p = np.asarray(self.points, np.float32)
+        out = PointCloud()
+        if self.has_normals():
+            xyz, _, status, nrm = _ds.voxel_down_sample_batched(p, [0, len(p)], voxel_size, attrs=np.asarray(self.normals, np.float32))
+        else:
+            xyz, _, status = _ds.voxel_down_sample_batched(p, [0, len(p)], voxel_size)
+            nrm = None
+        if int(status[0]) != 0:
+            raise _lib.EyocError("voxel_down_sample: a point is not finite or the cloud spans more than 2^17 cells on an axis",
+                                 _lib.ERR_RANGE)
+        out.points = xyz.cpu().numpy().astype(np.float64)
+        if nrm is not None:
+            m = nrm.cpu().numpy().astype(np.float64)
+            length = np.sqrt((m * m).sum(1, keepdims=True))
+            out.normals = np.divide(m, length, out=np.zeros_like(m), where=length > 0)
+        return out
 
     def __len__(self):
         return len(self.points)

@@ -237,6 +237,48 @@ int eyoc_voxelize_batched_isolating(eyoc_ctx* ctx, const float* xyz_dev, int str
                                     void* stream, int32_t* cloud_faults);
 
 /* ------------------------------------------------------------------------------------------------
+ * centroid voxel down-sampling for a batch of clouds.  Added after 111 without a bump, additive only; opt-in, nothing else calls it.
+ *   replaces: Open3D's PointCloud::VoxelDownSample as the reference calls it (pcd.voxel_down_sample(voxel_size),
+ *             util/pointcloud.py:38,43-44), restated as a contract of this library (parity unpinned: Open3D is not part of any build
+ *             here; tests/downsample_restatement.py is the fp64 statement the kernels are held to).  NOT the voxeliser above: that one
+ *             keeps the first point of a voxel on a grid anchored at the origin, this one the mean of all its points on a grid
+ *             anchored half a voxel below the cloud's minimum corner.
+ *   xyz_dev, stride (3 or 4), point_offsets (HOST), n_clouds (1 .. 1024), n_points (<= 2^30): as eyoc_voxelize_batched.  attr_dev f32
+ *   [n_points][n_attr] (0 <= n_attr <= 8; NULL or n_attr = 0: none): per-point columns that are averaged like the coordinates.
+ *   Per cloud b with rows p_i (f32, widened exactly to f64; every operation below fp64 and rounded on its own, no fused multiply-add):
+ *     origin   vmin_k = min_i p_i[k] - 0.5 * voxel_size
+ *     cell     c_i[k] = floor((p_i[k] - vmin_k) / voxel_size)
+ *     rows     a voxel = the cloud's points with equal c.  The cloud's output rows are its voxels in ascending order of their lowest
+ *              point index (the voxeliser's "sel ascending" rule).  first = that index within the cloud, count = the voxel's points,
+ *              inverse[i] = the row, within the cloud's output range, that point i went into.
+ *     sums     per voxel and column: s = 0.0; for i in ascending point index: s += (double)p_i[k]; out = (float)(s / (double)count) -
+ *              one division, one rounding.  attr_out the same over the attribute columns.  This sequential order IS the contract.
+ *     status   status_dev[b] = EYOC_ICP_RANGE for a cloud with a NaN or +-inf in x, y or z (a fourth float and the attributes are
+ *              never tested), or whose largest cell floor((max_i p_i[k] - vmin_k) / voxel_size) is 2^17 or more on an axis: it
+ *              contributes no rows and its inverse entries are -1; every other cloud's rows are unchanged.  Else 0 (empty clouds too).
+ *   xyz_out_dev f32 [.,3], attr_out_dev f32 [.,n_attr], first_dev / count_dev int32 [.] need room for n_points rows; inverse_dev int32
+ *   [n_points]; first_dev, count_dev, inverse_dev may each be NULL.  voxel_offsets (HOST out, int64 [n_clouds+1]) = the clouds' row
+ *   ranges, back with the call's ONE stream synchronisation; rows past voxel_offsets[n_clouds] are not written.  n_points = 0 launches
+ *   nothing and writes nothing on the device (voxel_offsets = 0).  EYOC_ERR_INVALID for a voxel_size that is not positive and
+ *   finite, a stride other than 3 / 4, n_attr outside [0, 8] or offsets that do not describe n_points.  Caller-owned workspace of
+ *   eyoc_voxel_downsample_workspace_bytes, 256-byte aligned: a misaligned or smaller one is EYOC_ERR_WORKSPACE before any launch; its
+ *   previous contents do not matter.  No allocation, no floating-point atomics (the bounds use integer min / max, which commute).  A
+ *   cloud's bytes are the same from run to run, alone, and at any place in a batch.
+ *   eyoc_voxel_downsample_batched_timed (diagnostics, scripts/bench_downsample.py): the same call with events between its stages;
+ *   stage_ms (HOST out, float [7]) = bounds + status, keys, sort, run heads, flag scan, row numbers + offsets, sums, in milliseconds.
+ * --------------------------------------------------------------------------------------------- */
+size_t eyoc_voxel_downsample_workspace_bytes(int n_points_total, int n_clouds, int n_attr);
+int eyoc_voxel_downsample_batched(eyoc_ctx* ctx, const float* xyz_dev, int stride, const int64_t* point_offsets, int n_clouds, int n_points,
+                                  double voxel_size, const float* attr_dev, int n_attr, float* xyz_out_dev, float* attr_out_dev,
+                                  int32_t* first_dev, int32_t* count_dev, int32_t* inverse_dev, int32_t* status_dev,
+                                  int64_t* voxel_offsets, void* workspace_dev, size_t workspace_bytes, void* stream);
+int eyoc_voxel_downsample_batched_timed(eyoc_ctx* ctx, const float* xyz_dev, int stride, const int64_t* point_offsets, int n_clouds,
+                                        int n_points, double voxel_size, const float* attr_dev, int n_attr, float* xyz_out_dev,
+                                        float* attr_out_dev, int32_t* first_dev, int32_t* count_dev, int32_t* inverse_dev,
+                                        int32_t* status_dev, int64_t* voxel_offsets, void* workspace_dev, size_t workspace_bytes,
+                                        void* stream, float* stage_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * per-pair failure isolation: drop clouds from a collated batch
  *   coords_dev int32 [n,4] (batch, x, y, z), feats_dev f32 [n,c] or NULL, rows in any order (clouds may interleave).
  *   drop_mask (HOST, 32 words, the layout of eyoc_maps_last_fault_batches): bit b set = every row of batch index b goes; rows whose
